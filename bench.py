@@ -1,11 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the force-compute hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|c2|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|c2|...] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): particle-steps/s of the PerturbedLennardJones pair
 force at N=1,048,576, rho*=0.8, r_cut=3.0 (FP64, full neighbor list, buffer
 0.4), plus the achieved algorithmic HBM GB/s against the MI355X roofline.
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds what the headline figure does not need: the check of the timed
+states' forces against whole-row launches, the side figures (kernel time per
+cycle step and on other states and orders) and the CPU baseline with its check
+against the oracle. --dump-outputs DIR writes the forces and energies of the
+last timed step (float64, rows in particle-tag order) as DIR/forces.npy and
+DIR/energies.npy.
 
 A "step" is one pass of the force kernel(s) over the whole system on a static
 neighbor list (built once, never rebuilt in the timed region), inputs resident in
@@ -153,6 +161,26 @@ def committed_counter(kernel, workload, name):
     return None, None
 
 
+DUMP_MAX_ROWS = 1 << 20  # 32 MB of forces + energies; larger workloads write a fixed sample of the particles
+
+
+def dump_outputs(out_dir, pot, state, N):
+    """What a caller of the timed path receives from its last step: the force (N x 3) and the energy
+    (N) of every particle, FP64, rows in tag order, so that two builds that order the particles
+    differently still compare row for row. Above DUMP_MAX_ROWS particles: a seeded sample of the
+    tags (sample_tags.npy, ascending)."""
+    os.makedirs(out_dir, exist_ok=True)
+    f = pot.force_tensor[:N].cpu().numpy()
+    by_tag = np.empty_like(f)
+    by_tag[state.tag[:N].cpu().numpy().view(np.uint32).astype(np.int64)] = f
+    if N > DUMP_MAX_ROWS:
+        tags = np.sort(np.random.default_rng(2024).choice(N, DUMP_MAX_ROWS, replace=False))
+        by_tag = by_tag[tags]
+        np.save(os.path.join(out_dir, "sample_tags.npy"), tags.astype(np.float64))
+    np.save(os.path.join(out_dir, "forces.npy"), np.ascontiguousarray(by_tag[:, :3]))
+    np.save(os.path.join(out_dir, "energies.npy"), np.ascontiguousarray(by_tag[:, 3]))
+
+
 def record_md_cycle(sim, nl, kT, seed):
     """Positions of one neighbor-list rebuild cycle of a real NVE run: Maxwell velocities at
     kT on the workload's snapshot, velocity Verlet until HOOMD's distance check (a particle
@@ -184,9 +212,15 @@ def main():
     ap.add_argument("--workload", default="ns")
     ap.add_argument("--tpp", type=int, default=0, help="threads per particle (0 = library heuristic)")
     ap.add_argument("--block-size", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the check of the timed states' forces, the side "
+                         "figures and the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the forces and energies of the last timed step (float64, by particle "
+                         "tag) as DIR/forces.npy and DIR/energies.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-side-figures", action="store_true",
-                    help="only the timed region (profiler passes: every launch of the kernel belongs to the cycle)")
+                    help="with --full: only the timed region (profiler passes: every launch of the kernel belongs to the cycle)")
     ap.add_argument("--mode", default="none", choices=["none", "shift", "xplor"])
     ap.add_argument("--no-plan", action="store_true", help="generic kernel only (no LDS-staged tile plan)")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
@@ -200,7 +234,7 @@ def main():
                          "in an MD run of millions of steps) and not in the power controller's transient: from idle the first "
                          "~1 ms runs at boost clock, launches 15-50 run up to 35 %% slower, and the clock settles over ~50 ms "
                          "(profiles/r03_clock_transient.md). 0 = none")
-    ap.add_argument("--no-verify", action="store_true", help="skip the check of the timed states' forces after the timed region")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the check of the timed states' forces after the timed region")
     ap.add_argument("--kT", type=float, default=1.0, help="temperature of the Maxwell velocities that drive the recorded MD cycle")
     ap.add_argument("--bank-order", type=int, default=0,
                     help="1: bank-aware row order in the tile plan (what a list that lives >= 50 force calls gets); "
@@ -221,6 +255,11 @@ def main():
                     help="do not tell the planned kernel how far particles moved since the list was built (it then walks "
                          "whole rows, Verlet-buffer entries included)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    verify_on = args.full and not args.no_verify
+    side_on = args.full and not args.no_side_figures
+    cpu_on = args.full and not args.no_cpu_baseline
 
     import torch
 
@@ -238,6 +277,8 @@ def main():
     dev = "cuda:%d" % local_rank
 
     if world > 1 or os.environ.get("AZP_BENCH_FORCE_DD") == "1":  # the env var rehearses the N>1 code path on one GPU
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: only the one-GPU path writes its outputs")
         from azplugins_amd import decomposition
 
         return decomposition.bench_main(args, rank, world, local_rank)
@@ -359,15 +400,17 @@ def main():
     wall = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events on the launch stream
     ms_per_step = wall * 1e3 / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pot, st, N)  # before anything below launches the kernel again
 
     # ---- check of what the timed region computed (outside it): the forces the timed launches left
     # behind for the LAST cycle state, and those of every other cycle state recomputed the same way
     # (same plan, same assumed displacement bound), must be bit-identical to a launch that is told
     # nothing about displacements and walks whole rows (the kernel's cutoff test is exact either way;
-    # tests/test_gpu_full_size.py checks whole rows against the oracle at this size)
+    # tests/test_gpu_full_size.py checks whole rows against the oracle at this size). --full only.
     verified = None
     f_state0 = None
-    if not args.no_verify and pot.use_plan:
+    if verify_on and pot.use_plan:
         timed_last = pot.force_tensor.clone()
         verified = True
         for k in reversed(range(n_states)):
@@ -388,7 +431,7 @@ def main():
             raise SystemExit("bench.py: the forces of the timed states differ from the whole-row evaluation")
         step.current = -1
 
-    # ---- side figures, outside the timed region (>= 40 launches each) ----
+    # ---- side figures, outside the timed region (>= 40 launches each), --full only ----
     def timed(reps=40):
         pot.compute(0)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -400,10 +443,10 @@ def main():
         return e0.elapsed_time(e1) / reps
 
     by_step = []
-    if not args.no_side_figures:
+    if side_on:
         settle()  # the side figures too are taken at the sustained clock
     for k in range(n_states):
-        if args.no_side_figures:
+        if not side_on:
             break
         set_state(k)
         by_step.append(dict(step=k, displacement_bound=bounds[k], bound_over_half_buffer=bounds[k] / (0.5 * r_buff), kernel_ms=timed()))
@@ -411,7 +454,7 @@ def main():
     plan_info = pot.plan_info  # of the plan the timed region ran on (the side figures below recompile it)
     if plan_info and plan_info.get("valid"):
         plan_info["mean_chunks_core_sure_row"] = pot._plan.phase_chunks()
-    if n_states > 1 and not args.no_side_figures:
+    if n_states > 1 and side_on:
         # the same K launches, switching to the next cycle step at every launch (cold positions)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         step.current = -1
@@ -422,7 +465,7 @@ def main():
         torch.cuda.synchronize()
         side["cycle_mean_ms_switching_state_every_launch"] = e0.elapsed_time(e1) / args.steps
     set_state(0)
-    if pot.use_displacement_bound and not args.sort_rows and args.displace == 0.0 and not args.no_side_figures:
+    if pot.use_displacement_bound and not args.sort_rows and args.displace == 0.0 and side_on:
         side["static_list_bound_0_ms"] = timed()  # round 1's headline state
         pot.use_displacement_bound = False
         side["whole_rows_no_displacement_information_ms"] = timed()
@@ -525,7 +568,7 @@ def main():
                     "measured here, against the FP64 vector issue peak at the 2.4 GHz nominal clock; the chip holds ~1.5-1.8 GHz "
                     "under this load",
         }
-    if not args.no_cpu_baseline:
+    if cpu_on:
         out["cpu_baseline"] = cpu_baseline(args.workload, gpu_forces_by_tag=f_state0)
         out["cpu_baseline"]["gpu_over_cpu_1core"] = value / out["cpu_baseline"]["value"]
     print(json.dumps(out))

@@ -29,7 +29,7 @@ def stats(d, match=("azp::",), top=14):
 md = ["# rocprofv3 --kernel-trace --stats summaries, round 2 (one MI355X), final binary of the round", "",
       "(the tile plan is compiled straight from the cell list: `plan_cells_kernel` replaces `nlist_cell_kernel` + `plan_build_kernel` on the rebuild "
       "path; the first version of this file, with the list-based pipeline, is in the git history)", ""]
-md += ["## bench_stats: `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-side-figures --steps 80 --warmup 8`", "",
+md += ["## bench_stats: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-side-figures --steps 80 --warmup 8`", "",
        stats("bench_stats"), ""]
 md += ["## md_stats: `rocprofv3 --kernel-trace --stats -- python3 tools/md_bench.py --steps 300`", "",
        stats("md_stats", match=("azp::", "rocprim", "copyBuffer", "at::native"), top=18), ""]

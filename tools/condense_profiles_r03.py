@@ -52,7 +52,7 @@ def counters(d, kernel_substr):
 
 DRV = "--steps 20 --warmup 5"
 md = ["# rocprofv3 --kernel-trace --stats summaries, round 3 (one MI355X), final binary of the round", ""]
-md += ["## bench_stats: `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-side-figures %s` (the driver's arguments; the launches are "
+md += ["## bench_stats: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-side-figures %s` (the driver's arguments; the launches are "
        "the recorded cycle, the 80 ms run-in, warm-up, the 20 timed steps and the verification)" % DRV, "", stats("bench_stats"), ""]
 md += ["## md_stats: `rocprofv3 --kernel-trace --stats -- python3 tools/md_bench.py --steps 300` (north-star liquid, NVE)", "",
        stats("md_stats", match=("azp::", "rocprim", "copyBuffer", "at::native"), top=16), ""]
@@ -75,14 +75,14 @@ for src, dst in (("bench_driver.json", "r03_bench.json"), ("bench_default.json",
 K = "azp::pair_forces_tiled_kernel<EvalPLJ>"
 sq, n = counters("bench_sq", "pair_forces_tiled_kernel<azp::EvalPLJ")
 if sq:
-    d = {"_comment": "SQ counters per launch of the tile kernel, mean over the launches of `python3 bench.py --no-cpu-baseline --no-side-figures %s` "
+    d = {"_comment": "SQ counters per launch of the tile kernel, mean over the launches of `python3 bench.py --full --no-cpu-baseline --no-side-figures %s` "
                      "(rocprofv3 --pmc, one pass), final binary of round 3" % DRV,
          K: dict(workload="NS", launches=n, **sq)}
     json.dump(d, open(os.path.join(P, "r03_counters.json"), "w"), indent=1)
 fe, nf = counters("bench_fetch", "pair_forces_tiled_kernel<azp::EvalPLJ")
 wr, nw = counters("bench_write", "pair_forces_tiled_kernel<azp::EvalPLJ")
 if fe and wr:
-    d = {"_comment": "HBM traffic per launch of the tile kernel, mean over the launches of `python3 bench.py --no-cpu-baseline --no-side-figures %s` (recorded "
+    d = {"_comment": "HBM traffic per launch of the tile kernel, mean over the launches of `python3 bench.py --full --no-cpu-baseline --no-side-figures %s` (recorded "
                      "cycle + run-in + warm-up + timed + verification launches), separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes. Units KiB; on gfx950 "
                      "FETCH_SIZE reports half the bytes of wide coalesced streams (MI355X_MICROARCH.md, HBM section), hence fetch_correction = 2. The force array is 32 MiB "
                      "(32,768 KiB): WRITE_SIZE above that is register-spill traffic that reached HBM (the kernel keeps 116-224 B of scratch per lane around its tail path; "

@@ -7,7 +7,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 # the profiling build of the library for the phase-by-phase figures of plan_cells_kernel
 make -C azplugins_amd/csrc variant SRC=pair_plan_cells NAME=pcprof DEFS=-DAZP_PLAN_CELLS_PROFILE > $O/pcprof_build.log 2>&1
-B="python3 bench.py --no-cpu-baseline --no-side-figures --steps 80 --warmup 8"
+B="python3 bench.py --full --no-cpu-baseline --no-side-figures --steps 80 --warmup 8"
 rocprofv3 --kernel-trace --stats -d $O/bench_stats --output-format csv -- $B > $O/bench_stats.json 2> $O/bench_stats.err
 echo "bench stats pass done"
 rocprofv3 --kernel-trace --stats -d $O/md_stats --output-format csv -- python3 tools/md_bench.py --steps 300 > $O/md_bench.log 2> $O/md_bench.err
@@ -23,7 +23,7 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pc_write --output-format csv -- 
 rocprofv3 --kernel-trace --stats -d $O/c4_stats --output-format csv -- python3 tools/xtiled_probe.py c4 > $O/c4.log 2>&1
 rocprofv3 --kernel-trace --stats -d $O/c5_stats --output-format csv -- python3 tools/xtiled_probe.py c5 > $O/c5.log 2>&1
 tail -1 $O/c4.log | cut -c1-300; tail -1 $O/c5.log | cut -c1-300
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 1500 $O/bench_default.json
 python3 tools/summarize_prof.py $O $O/all > /dev/null 2>&1 || true
 echo done

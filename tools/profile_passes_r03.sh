@@ -8,11 +8,11 @@ mkdir -p $O
 export TMPDIR=/tmp
 PART=${1:-abc}
 DRV="--steps 20 --warmup 5"          # the driver's arguments
-B="python3 bench.py --no-cpu-baseline --no-side-figures $DRV"
+B="python3 bench.py --full --no-cpu-baseline --no-side-figures $DRV"
 if [[ $PART == *a* ]]; then
-python3 bench.py --gpus 1 $DRV > $O/bench_driver.json 2> $O/bench_driver.err
+python3 bench.py --gpus 1 --full $DRV > $O/bench_driver.json 2> $O/bench_driver.err
 python3 tools/show_bench.py $O/bench_driver.json
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 tools/show_bench.py $O/bench_default.json
 rocprofv3 --kernel-trace --stats -d $O/bench_stats --output-format csv -- $B > $O/bench_stats.json 2> $O/bench_stats.err
 echo "bench stats pass done"
