@@ -202,6 +202,29 @@ class NlistArgs(C.Structure):
     ]
 
 
+COORDINATES_CARTESIAN = 0
+COORDINATES_CYLINDRICAL = 1
+MAX_BINS = 2**31 - 1
+
+
+class VelocityFieldArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_vel", C.c_void_p),
+        ("N", C.c_uint32),
+        ("coordinates", C.c_uint32),
+        ("box", Box),
+        ("num_bins", C.c_uint32 * 3),
+        ("ntypes", C.c_uint32),
+        ("lower", C.c_double * 3),
+        ("upper", C.c_double * 3),
+        ("d_type_mask", C.c_void_p),
+        ("d_sums", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 # every symbol include/azp.h declares: name -> (restype, argtypes)
 _D = C.c_double
 _PD = C.POINTER(C.c_double)
@@ -267,6 +290,9 @@ SYMBOLS = {
     "azp_integrate_nve_step_two_one": (C.c_int, [C.POINTER(NVEArgs), _VP]),
     "azp_integrate_nve_rot_step_one": (C.c_int, [C.POINTER(NVERotArgs), _VP]),
     "azp_integrate_nve_rot_step_two": (C.c_int, [C.POINTER(NVERotArgs), _VP]),
+    "azp_velocity_field_scratch_size": (C.c_int, [C.POINTER(VelocityFieldArgs), C.POINTER(C.c_uint64)]),
+    "azp_velocity_field_sums": (C.c_int, [C.POINTER(VelocityFieldArgs), _VP]),
+    "azp_velocity_field_normalize": (C.c_int, [_VP, C.c_uint64, _VP, _VP]),
     "azp_version": (C.c_int, []),
     "azp_status_string": (C.c_char_p, [C.c_int]),
     "azp_last_launch": (None, [C.POINTER(C.c_uint32)] * 4),

@@ -120,6 +120,7 @@ const char* azp_status_string(int status)
     case AZP_ERROR_INVALID_ARGUMENT: return "invalid argument";
     case AZP_ERROR_TOO_MANY_TYPES: return "per-type-pair coefficient table exceeds 160 KiB of LDS";
     case AZP_ERROR_NO_DEVICE: return "no HIP device";
+    case AZP_ERROR_TOO_MANY_BINS: return "more than 2^31 - 1 bins";
     default: return status > 0 ? "HIP runtime error (value is hipError_t)" : "unknown status";
         }
     }

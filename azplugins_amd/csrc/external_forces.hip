@@ -22,30 +22,6 @@ struct BarrierKArgs
     uint32_t ntypes;
     };
 
-// HOOMD BoxDim::wrap restated for one shift per axis (particles drift by much
-// less than a box length between wraps)
-__device__ __forceinline__ void wrap_into_box(const BoxDev& b, double& x, double& y, double& z)
-    {
-    if (b.pz)
-        {
-        const double h = 0.5 * b.Lz;
-        if (z >= h) { z -= b.Lz; y -= b.Lz * b.yz; x -= b.Lz * b.xz; }
-        else if (z < -h) { z += b.Lz; y += b.Lz * b.yz; x += b.Lz * b.xz; }
-        }
-    if (b.py)
-        {
-        const double h = 0.5 * b.Ly, s = z * b.yz;
-        if (y >= h + s) { y -= b.Ly; x -= b.Ly * b.xy; }
-        else if (y < -h + s) { y += b.Ly; x += b.Ly * b.xy; }
-        }
-    if (b.px)
-        {
-        const double h = 0.5 * b.Lx, s = y * b.xy + z * (b.xz - b.xy * b.yz);
-        if (x >= h + s) x -= b.Lx;
-        else if (x < -h + s) x += b.Lx;
-        }
-    }
-
 template<bool SPHERICAL> __global__ void __launch_bounds__(256) barrier_kernel(const BarrierKArgs a)
     {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];

@@ -23,6 +23,34 @@ class All:
         return hash("All")
 
 
+class Type:
+    """``hoomd.filter.Type``: the particles of the named types. ``types`` is one type name or an iterable of type
+    names. Computes accept it; integration methods keep integrating all particles (``All`` only)."""
+
+    def __init__(self, types):
+        if isinstance(types, str):
+            types = [types]
+        self.types = tuple(types)
+        if not all(isinstance(t, str) for t in self.types):
+            raise _lib.AzpError("Type: type names must be strings, got %r" % (types,))
+
+    def mask(self, type_names):
+        """One byte per type of ``type_names`` (the state's types): 1 if the type is selected."""
+        missing = [t for t in self.types if t not in type_names]
+        if missing:
+            raise _lib.AzpError("Type filter names %s, which the state does not have (types %s)" % (missing, list(type_names)))
+        return np.array([1 if t in self.types else 0 for t in type_names], dtype=np.uint8)
+
+    def __eq__(self, other):
+        return isinstance(other, Type) and set(self.types) == set(other.types)
+
+    def __hash__(self):
+        return hash(("Type", frozenset(self.types)))
+
+    def __repr__(self):
+        return "Type(%r)" % (list(self.types),)
+
+
 class ConstantVolume:
     """NVE integration method (velocity Verlet) on all particles
     (``hoomd.md.methods.ConstantVolume(filter=hoomd.filter.All())`` without a
@@ -48,14 +76,66 @@ class Integrator:
         self.integrate_rotational_dof = bool(integrate_rotational_dof)
 
 
+class _Computes(list):
+    """``sim.operations.computes``: a list whose members know their simulation (HOOMD attaches an operation when it
+    joins the simulation's operations)."""
+
+    def __init__(self, sim):
+        super().__init__()
+        self._sim = sim
+
+    def _claim(self, op):
+        from .compute import _Compute
+
+        if not isinstance(op, _Compute):
+            raise _lib.AzpError("sim.operations.computes holds computes (azplugins_amd.compute), got %r" % (op,))
+        if op._sim is not None and op._sim is not self._sim and any(c is op for c in op._sim.operations.computes):
+            raise _lib.AzpError("%s is already in the operations of another simulation" % type(op).__name__)
+        op._sim = self._sim
+        return op
+
+    def append(self, op):
+        if not any(c is op for c in self):
+            super().append(self._claim(op))
+
+    def insert(self, i, op):
+        if not any(c is op for c in self):
+            super().insert(i, self._claim(op))
+
+    def extend(self, ops):
+        for op in ops:
+            self.append(op)
+
+    def __iadd__(self, ops):
+        self.extend(ops)
+        return self
+
+    def remove(self, op):
+        for i, c in enumerate(self):
+            if c is op:
+                del self[i]
+                op._sim = None
+                return
+        raise ValueError("%r is not in sim.operations.computes" % (op,))
+
+
 class _Operations:
-    def __init__(self):
+    def __init__(self, sim=None):
         self.integrator = None
+        self.computes = _Computes(sim)
         # HOOMD puts a ParticleSorter into sim.operations.tuners by default; so does this
         # (remove it from the list, or set trigger_period = 0, to keep the initial order)
         from .sorter import ParticleSorter
 
         self.tuners = [ParticleSorter(trigger_period=200)]
+
+    def add(self, op):
+        """Add a compute (``hoomd.Operations.add``); it is attached while the simulation has a state."""
+        self.computes.append(op)
+
+    def remove(self, op):
+        """Remove a compute; reading its results raises ``compute.DataAccessError`` afterwards."""
+        self.computes.remove(op)
 
 
 class Simulation:
@@ -64,7 +144,7 @@ class Simulation:
         self.seed = seed
         self.state = None
         self.timestep = 0
-        self.operations = _Operations()
+        self.operations = _Operations(self)
         self._attached = []
         self.domain = None  # azplugins_amd.domain.DeviceDomain of a decomposed run (attach_domain)
 

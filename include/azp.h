@@ -56,7 +56,8 @@ typedef enum azp_status
     AZP_SUCCESS = 0,
     AZP_ERROR_INVALID_ARGUMENT = -1,
     AZP_ERROR_TOO_MANY_TYPES = -2, /* per-type-pair table does not fit in LDS */
-    AZP_ERROR_NO_DEVICE = -3
+    AZP_ERROR_NO_DEVICE = -3,
+    AZP_ERROR_TOO_MANY_BINS = -4   /* velocity field: more than 2^31 - 1 bins */
     } azp_status;
 
 typedef enum azp_shift_mode
@@ -584,6 +585,51 @@ typedef struct azp_nve_rot_args
 
 int azp_integrate_nve_rot_step_one(const azp_nve_rot_args* args, void* stream);
 int azp_integrate_nve_rot_step_two(const azp_nve_rot_args* args, void* stream);
+
+/* ---- velocity / velocity-field computes ----
+ * Replaces the reference's GPU drivers of hoomd.azplugins.compute: the per-particle loop of
+ * src/VelocityFieldComputeGPU.cuh:35-71 (CartesianVelocityFieldCompute, CylindricalVelocityFieldCompute) and
+ * src/VelocityComputeGPU.cu:48-65 (VelocityCompute = the Cartesian case with num_bins = (0, 0, 0): one bin), with
+ * the bins of src/BinningOperation.h, src/CartesianBinningOperation.h and src/CylindricalBinningOperation.h.
+ * Rows [0, N) only. A particle is counted if d_type_mask[type] != 0 (d_type_mask NULL: every particle); its
+ * position is wrapped into the (global) box, binned as floor(((x - lower) / (upper - lower)) * n) in each
+ * dimension with n = num_bins[d] > 0 (outside [0, n) in any: dropped; n = 0: not binned, index 0) and raveled as
+ * z + nz (y + ny x) with a dimension that is not binned counting as size 1. Cartesian: (x, y, z) and the momentum
+ * m v as it is. Cylindrical: (r, theta, z), theta = atan2(y, x) in [0, 2 pi), the momentum rotated by
+ * (cos theta, sin theta) = (x / r, y / r), (1, 0) at r = 0.
+ * azp_velocity_field_sums OVERWRITES d_sums (bins x 4: mass, px, py, pz). Deterministic: no floating-point
+ * atomics, two calls on the same input give bit-identical sums. It needs a device scratch buffer of at least
+ * azp_velocity_field_scratch_size bytes (depends on N and the bin count only).
+ * azp_velocity_field_normalize: d_velocity[b] (bins x 3) = momentum / mass, or 0 where the mass is 0
+ * (src/VelocityFieldCompute.h:262-278); a decomposed run sums d_sums over its ranks first.
+ * Both are asynchronous on `stream`; more than 2^31 - 1 bins: AZP_ERROR_TOO_MANY_BINS; upper <= lower in a
+ * binned dimension: AZP_ERROR_INVALID_ARGUMENT. */
+typedef enum azp_coordinates
+    {
+    AZP_COORDINATES_CARTESIAN = 0,
+    AZP_COORDINATES_CYLINDRICAL = 1
+    } azp_coordinates;
+
+typedef struct azp_velocity_field_args
+    {
+    const double* d_pos;       /* N x 4 (x, y, z, type bits) */
+    const double* d_vel;       /* N x 4 (vx, vy, vz, mass) */
+    uint32_t N;
+    uint32_t coordinates;      /* azp_coordinates */
+    azp_box box;               /* global box */
+    uint32_t num_bins[3];      /* Cartesian (x, y, z) or cylindrical (r, theta, z); 0: not binned */
+    uint32_t ntypes;           /* entries of d_type_mask */
+    double lower[3];
+    double upper[3];
+    const uint8_t* d_type_mask; /* ntypes bytes, may be NULL */
+    double* d_sums;            /* bins x 4, overwritten */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_velocity_field_args;
+
+int azp_velocity_field_scratch_size(const azp_velocity_field_args* args, uint64_t* bytes);
+int azp_velocity_field_sums(const azp_velocity_field_args* args, void* stream);
+int azp_velocity_field_normalize(const double* d_sums, uint64_t n_bins, double* d_velocity, void* stream);
 
 /* ---- misc ---- */
 int azp_version(void);                    /* major * 1000 + minor       */
