@@ -225,6 +225,38 @@ class VelocityFieldArgs(C.Structure):
     ]
 
 
+FLOW_CONSTANT = 0
+FLOW_PARABOLIC = 1
+
+
+class Flow(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("_pad", C.c_uint32), ("p", C.c_double * 3)]
+
+
+class FlowMethodArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_vel", C.c_void_p),
+        ("d_accel", C.c_void_p),
+        ("d_net_force", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("d_gamma", C.c_void_p),
+        ("d_type_mask", C.c_void_p),
+        ("box", Box),
+        ("dt", C.c_double),
+        ("kT", C.c_double),
+        ("timestep", C.c_uint64),
+        ("seed", C.c_uint32),
+        ("noiseless", C.c_uint32),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("flow", Flow),
+        ("block_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 # every symbol include/azp.h declares: name -> (restype, argtypes)
 _D = C.c_double
 _PD = C.POINTER(C.c_double)
@@ -290,6 +322,10 @@ SYMBOLS = {
     "azp_integrate_nve_step_two_one": (C.c_int, [C.POINTER(NVEArgs), _VP]),
     "azp_integrate_nve_rot_step_one": (C.c_int, [C.POINTER(NVERotArgs), _VP]),
     "azp_integrate_nve_rot_step_two": (C.c_int, [C.POINTER(NVERotArgs), _VP]),
+    "azp_integrate_langevin_flow_step_one": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
+    "azp_integrate_langevin_flow_step_two": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
+    "azp_integrate_langevin_flow_step_two_one": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
+    "azp_integrate_brownian_flow_step": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
     "azp_velocity_field_scratch_size": (C.c_int, [C.POINTER(VelocityFieldArgs), C.POINTER(C.c_uint64)]),
     "azp_velocity_field_sums": (C.c_int, [C.POINTER(VelocityFieldArgs), _VP]),
     "azp_velocity_field_normalize": (C.c_int, [_VP, C.c_uint64, _VP, _VP]),

@@ -87,6 +87,25 @@ __device__ __forceinline__ void wrap_into_box(const BoxDev& b, double& x, double
         }
     }
 
+// wrap_into_box plus the image counters of row idx (NULL: none): which way each axis was wrapped (the
+// orthorhombic shortcut is exact; for triclinic boxes the z shift is read off z, the y shift off y after removing
+// z's tilt). Shared by every integration kernel.
+__device__ __forceinline__ void wrap_with_image(const BoxDev& b, double& x, double& y, double& z, int32_t* image,
+                                                uint32_t idx)
+    {
+    const double x0 = x, y0 = y, z0 = z;
+    wrap_into_box(b, x, y, z);
+    if (image)
+        {
+        const int iz = (z < z0) - (z > z0);
+        const double y1 = y0 - iz * b.Lz * b.yz;
+        const int iy = (y < y1) - (y > y1);
+        const double x1 = x0 - iz * b.Lz * b.xz - iy * b.Ly * b.xy;
+        const int ix = (x < x1) - (x > x1);
+        image[3 * idx + 0] += ix; image[3 * idx + 1] += iy; image[3 * idx + 2] += iz;
+        }
+    }
+
 // true if a particle at (x,y,z) is farther than `margin` from every periodic
 // face of an orthorhombic box, so that no listed neighbor can need wrapping.
 __device__ __forceinline__ bool is_interior(const BoxDev& b, double x, double y, double z, double margin)

@@ -136,20 +136,8 @@ template<int MODE> __global__ void __launch_bounds__(256) nve_kernel(const NVEKA
         {
         const double4 p = load_scalar4(a.pos, idx);
         double x = p.x + a.dt * v.x, y = p.y + a.dt * v.y, z = p.z + a.dt * v.z;
-        const double x0 = x, y0 = y, z0 = z;
-        wrap_into_box(a.box, x, y, z);
+        wrap_with_image(a.box, x, y, z, a.image, idx);
         store_scalar4(a.pos, idx, x, y, z, p.w);
-        if (a.image)
-            {
-            // which way was it wrapped (orthorhombic shortcut is exact; for triclinic
-            // boxes the z shift is read off z, the y shift off y after removing z's tilt)
-            const int iz = (z < z0) - (z > z0);
-            const double y1 = y0 - iz * a.box.Lz * a.box.yz;
-            const int iy = (y < y1) - (y > y1);
-            const double x1 = x0 - iz * a.box.Lz * a.box.xz - iy * a.box.Ly * a.box.xy;
-            const int ix = (x < x1) - (x > x1);
-            a.image[3 * idx + 0] += ix; a.image[3 * idx + 1] += iy; a.image[3 * idx + 2] += iz;
-            }
         }
     }
 

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../../include/azp.h"
@@ -307,6 +308,62 @@ template<class P, bool GPU> void export_bond(py::module_& m, const std::string& 
         .def_property_readonly_static("param_size", [](py::object) { return C::paramSize(); });
     }
 
+// ---- flow fields (src/ConstantFlow.h, src/ParabolicFlow.h; exports src/ConstantFlow.cc, src/ParabolicFlow.cc) ----
+// The host-side field objects; libazp's kernels evaluate the same formulas from azp_flow {kind, p[3]}.
+typedef std::tuple<double, double, double> Vec3;
+
+class ConstantFlow
+    {
+    public:
+    explicit ConstantFlow(const Vec3& velocity) : U(velocity) { }
+    Vec3 operator()(const Vec3& /*r*/) const { return U; }
+    Vec3 getVelocity() const { return U; }
+    void setVelocity(const Vec3& U_) { U = U_; }
+
+    private:
+    Vec3 U;
+    };
+
+class ParabolicFlow
+    {
+    public:
+    ParabolicFlow(double mean_velocity, double separation)
+        {
+        setMeanVelocity(mean_velocity);
+        setSeparation(separation);
+        }
+    Vec3 operator()(const Vec3& r) const
+        {
+        const double yr = (std::get<1>(r) / L);
+        return Vec3(Umax * (1. - yr * yr), 0.0, 0.0);
+        }
+    double getMeanVelocity() const { return Umax / 1.5; }
+    void setMeanVelocity(double U) { Umax = 1.5 * U; }
+    double getSeparation() const { return 2.0 * L; }
+    void setSeparation(double L_) { L = 0.5 * L_; }
+    double getUmax() const { return Umax; }
+    double getL() const { return L; }
+
+    private:
+    double Umax; // 1.5 x mean velocity
+    double L;    // half the separation
+    };
+
+void export_flows(py::module_& m)
+    {
+    py::class_<ConstantFlow>(m, "ConstantFlow")
+        .def(py::init<const Vec3&>(), py::arg("velocity"))
+        .def_property("velocity", &ConstantFlow::getVelocity, &ConstantFlow::setVelocity)
+        .def("__call__", &ConstantFlow::operator(), py::arg("r"));
+    py::class_<ParabolicFlow>(m, "ParabolicFlow")
+        .def(py::init<double, double>(), py::arg("mean_velocity"), py::arg("separation"))
+        .def_property("mean_velocity", &ParabolicFlow::getMeanVelocity, &ParabolicFlow::setMeanVelocity)
+        .def_property("separation", &ParabolicFlow::getSeparation, &ParabolicFlow::setSeparation)
+        .def_property_readonly("Umax", &ParabolicFlow::getUmax)
+        .def_property_readonly("L", &ParabolicFlow::getL)
+        .def("__call__", &ParabolicFlow::operator(), py::arg("r"));
+    }
+
 template<class P, int MODES> void export_pair_both(py::module_& m, const std::string& name)
     {
     export_pair<P, MODES, false>(m, name);
@@ -332,5 +389,7 @@ PYBIND11_MODULE(_azplugins, m)
     // conservative-only PotentialPair<DPDPairEvaluatorGeneralWeight>, CPU class only)
     export_pair<azp_dpd_params, 0x1, false, 1>(m, "PotentialPairConservativeGeneralWeight");
     export_pair_both<azp_dpd_params, 0x1>(m, "PotentialPairDPDThermoGeneralWeight");
+    // flow fields (src/module.cc:128-129)
+    export_flows(m);
     m.attr("azp_version") = azp_version();
     }

@@ -25,7 +25,8 @@ class All:
 
 class Type:
     """``hoomd.filter.Type``: the particles of the named types. ``types`` is one type name or an iterable of type
-    names. Computes accept it; integration methods keep integrating all particles (``All`` only)."""
+    names. Computes and the flow methods (``flow.Langevin``, ``flow.Brownian``) accept it; ``ConstantVolume``
+    integrates all particles (``All`` only)."""
 
     def __init__(self, types):
         if isinstance(types, str):
@@ -67,7 +68,9 @@ class ConstantVolume:
 class Integrator:
     """``hoomd.md.Integrator`` reduced: ``dt``, ``forces``, ``methods``,
     ``integrate_rotational_dof`` (orientations and angular momenta of particles with a
-    non-zero moment of inertia are integrated with the net torque, HOOMD's default False)."""
+    non-zero moment of inertia are integrated with the net torque, HOOMD's default False).
+    ``methods`` holds one ``ConstantVolume``, or one or more ``flow.Langevin`` / ``flow.Brownian`` with
+    pairwise-disjoint filters (an ``All()`` filter stands alone)."""
 
     def __init__(self, dt, forces=None, methods=None, integrate_rotational_dof=False):
         self.dt = float(dt)
@@ -263,11 +266,14 @@ class Simulation:
         self._attach_all()
         integ = self.operations.integrator
         st = self.state
+        flow_methods = self._check_flow_methods(integ)
         if self.domain is not None:
             self._wire_domain()
         self._compute_forces()
         if steps == 0 or not integ.methods:
             return
+        if flow_methods:
+            return self._run_flow(steps, flow_methods)
         if len(integ.methods) != 1 or not isinstance(integ.methods[0], ConstantVolume):
             raise _lib.AzpError("Integrator.methods must hold exactly one ConstantVolume (all particles); got %r" % (integ.methods,))
         import ctypes as C
@@ -342,24 +348,91 @@ class Simulation:
             # (also when a tile plan could not be compiled from the cells because the members of some tile have drifted
             # apart -- a DPD fluid diffuses a cell width in ~200 steps: sorting now costs 0.5 ms, the list-based rebuilds
             # that would follow until the sorter's next period 2.5 ms each; at most once per 20 steps)
-            lists = [f.nlist for f in integ.forces if getattr(f, "nlist", None) is not None]
-            wanted = any(getattr(nl, "_sort_wanted", False) for nl in lists)
-            for tuner in self.operations.tuners:
-                due = tuner.trigger_period > 0 and self.timestep % tuner.trigger_period == 0
-                on_demand = wanted and tuner.trigger_period > 0 and self.timestep - getattr(tuner, "_last_sort_step", -(10 ** 9)) >= 20
-                if (due or on_demand) and st.n_ghost == 0:
-                    tuner.sort(self)
-                    tuner._last_sort_step = self.timestep
-                    for nl in lists:
-                        nl._sort_wanted = False
-                        nl._fused_failures = 0
-                        if getattr(nl, "_fused_auto_off", False):
-                            nl.fused, nl._fused_auto_off = True, False
+            self._run_tuners(integ)
             self._compute_forces()
         point_at_state()
         _lib.check(lib.azp_integrate_nve_step_two(C.byref(a), stream), "azp_integrate_nve_step_two")
         if rot is not None:
             rotational_step(False)
+        for f in deferred:
+            f.defer_flag_check = False
+            f.check_flags(wait=True)
+
+    def _run_tuners(self, integ):
+        st = self.state
+        lists = [f.nlist for f in integ.forces if getattr(f, "nlist", None) is not None]
+        wanted = any(getattr(nl, "_sort_wanted", False) for nl in lists)
+        for tuner in self.operations.tuners:
+            due = tuner.trigger_period > 0 and self.timestep % tuner.trigger_period == 0
+            on_demand = wanted and tuner.trigger_period > 0 and self.timestep - getattr(tuner, "_last_sort_step", -(10 ** 9)) >= 20
+            if (due or on_demand) and st.n_ghost == 0:
+                tuner.sort(self)
+                tuner._last_sort_step = self.timestep
+                for nl in lists:
+                    nl._sort_wanted = False
+                    nl._fused_failures = 0
+                    if getattr(nl, "_fused_auto_off", False):
+                        nl.fused, nl._fused_auto_off = True, False
+
+    def _check_flow_methods(self, integ):
+        """The flow methods of ``integ`` (empty if it has none), after checking that they can run together."""
+        from .flow import _FlowMethod
+
+        flow_methods = [m for m in integ.methods if isinstance(m, _FlowMethod)]
+        if not flow_methods:
+            return flow_methods
+        if len(flow_methods) != len(integ.methods):
+            raise _lib.AzpError("Integrator.methods: flow.Langevin / flow.Brownian cannot be mixed with other methods, got %r"
+                                % (integ.methods,))
+        if integ.integrate_rotational_dof:
+            raise _lib.AzpError("flow.Langevin / flow.Brownian do not integrate rotational degrees of freedom "
+                                "(integrate_rotational_dof=True)")
+        if self.domain is not None:
+            raise _lib.AzpError("flow.Langevin / flow.Brownian do not run decomposed (their accelerations do not migrate)")
+        if any(any(m is o for o in flow_methods[:k]) for k, m in enumerate(flow_methods)):
+            raise _lib.AzpError("Integrator.methods holds the same flow method twice")
+        if len(flow_methods) > 1 and any(isinstance(m.filter, All) for m in flow_methods):
+            raise _lib.AzpError("Integrator.methods: a flow method with filter All() must be the only method")
+        seen = set()
+        for m in flow_methods:
+            if isinstance(m.filter, All):
+                continue
+            m.filter.mask(self.state.types)  # (rejects type names the state does not have)
+            overlap = seen & set(m.filter.types)
+            if overlap:
+                raise _lib.AzpError("Integrator.methods: the filters of the flow methods overlap (types %s)" % sorted(overlap))
+            seen |= set(m.filter.types)
+        return flow_methods
+
+    def _run_flow(self, steps, methods):
+        """``steps`` steps of Langevin / Brownian dynamics (HOOMD IntegratorTwoStep::update): every method's step one
+        at the step's timestep t, the forces at t + 1, every method's step two at t. Inside the run step two of one
+        step and step one of the next are one kernel; the last step two comes after the loop."""
+        import torch
+
+        integ = self.operations.integrator
+        st = self.state
+        self._warn_if_seed_unset()
+        if any(m._uses_accel for m in methods) and (st.accel is None or st.accel.shape[0] != st.n_max):
+            # HOOMD computeAccelerations (prepRun): a = F_net / m on the first run of an integrator that needs it
+            st.accel = torch.zeros((st.n_max, 4), dtype=torch.float64, device=st.device)
+            st.accel[: st.N, :3] = st.net_force[: st.N, :3] / st.vel[: st.N, 3:4]
+        for m in methods:
+            m._prepare(self)
+        stream = _lib.raw_stream(st.device)
+        deferred = [f for f in integ.forces if hasattr(f, "defer_flag_check")]
+        for f in deferred:
+            f.defer_flag_check = True
+        for k in range(steps):
+            for m in methods:
+                # (k > 0: step two of the previous step, at its timestep, fused with this step one)
+                m._step(st, self.timestep, stream, fused=k > 0)
+            st.position_generation += 1
+            self.timestep += 1
+            self._run_tuners(integ)
+            self._compute_forces()
+        for m in methods:
+            m._step_two(st, self.timestep - 1, stream)
         for f in deferred:
             f.defer_flag_check = False
             f.check_flags(wait=True)

@@ -2,7 +2,7 @@
 ``hoomd.update.ParticleSorter``. Reorders the local particles along a Hilbert
 curve through small cells so that any 256 consecutive particles form a compact tile -- the order the
 tile plan (``pair_plan.hpp``) and the neighbor-list build rely on. Tags, images,
-velocities, orientations travel with the particles; bonds are re-indexed.
+velocities, orientations (and Langevin accelerations) travel with the particles; bonds are re-indexed.
 
 Keys and the permutation are computed with torch ops on the device (this runs
 every few hundred steps, not on the per-step path)."""
@@ -57,7 +57,10 @@ class ParticleSorter:
             raise _lib.AzpError("ParticleSorter: decomposed states keep their interior | boundary | ghost order")
         N = st.N
         order = torch.sort(self.keys(st), stable=True).indices
-        for name in ("pos", "vel", "orientation", "tag", "image", "angmom", "inertia"):
+        names = ("pos", "vel", "orientation", "tag", "image", "angmom", "inertia")
+        if getattr(st, "accel", None) is not None:
+            names += ("accel",)  # (a Langevin step one reads the acceleration of the previous step two)
+        for name in names:
             a = getattr(st, name)
             a[:N] = a[:N].index_select(0, order)
         if st.n_bonds:

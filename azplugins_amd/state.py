@@ -8,6 +8,7 @@ objects the reference's force classes are attached to (``hoomd.Snapshot``,
 * ``orientation`` (n_max, 4) float64 quaternion, scalar part first
 * ``tag``   (n_max,) uint32 (stored as int32 bit pattern)
 * ``angmom`` (n_max, 4) float64 angular-momentum quaternion, ``inertia`` (n_max, 3) principal moments
+* ``accel`` (n_max, 4) float64 ax, ay, az, 0: ``None`` until a ``flow.Langevin`` run creates it
 """
 
 import numpy as np
@@ -233,6 +234,9 @@ class State:
         self.inertia = torch.from_numpy(np.ascontiguousarray(p.moment_inertia, dtype=np.float64)).to(self.device)
         self.net_force = torch.zeros((self.N, 4), dtype=f64, device=self.device)
         self.image = torch.zeros((p.N, 3), dtype=torch.int32, device=self.device)
+        # (n_max, 4) accelerations of the flow.Langevin method (HOOMD ParticleData accelerations): created by its first
+        # run as F_net / m, then carried from step two to the next step one
+        self.accel = None
         b = snapshot.bonds
         self.bond_types = list(b.types)
         self.bond_group = np.ascontiguousarray(b.group, dtype=np.uint32).reshape(-1, 2)

@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define AZP_VERSION_MAJOR 0
-#define AZP_VERSION_MINOR 1
+#define AZP_VERSION_MINOR 2
 
 typedef enum azp_status
     {
@@ -585,6 +585,64 @@ typedef struct azp_nve_rot_args
 
 int azp_integrate_nve_rot_step_one(const azp_nve_rot_args* args, void* stream);
 int azp_integrate_nve_rot_step_two(const azp_nve_rot_args* args, void* stream);
+
+/* ---- Langevin and Brownian dynamics in a flow field ----
+ * The integration methods of the reference's flow module (TwoStepLangevinFlow, TwoStepBrownianFlow, with the
+ * ConstantFlow / ParabolicFlow fields), restated for HOOMD-blue v5:
+ *   Langevin (src/TwoStepLangevinFlow.h:100-252)
+ *     step one: x += (v + a dt/2) dt, wrap (image counters updated); v += a dt/2
+ *     step two: R_k = -c + 2 c u01_k with c = sqrt(6 gamma kT / dt) (0 if noiseless);
+ *               a = (F_net + R - gamma (v - u(x))) / m; v += a dt/2; a is stored in d_accel
+ *   Brownian (src/TwoStepBrownianFlow.h:105-180), one call per time step:
+ *     x += (u(x) + (F_net + R) / gamma) dt, wrap; velocities untouched.
+ * gamma = d_gamma[type]. The random numbers come from Philox4x32-10 with key {id << 24 | (t >> 32 & 0xff) << 16 |
+ * seed, t & 0xffffffff} and counter {k, tag, 0, 0} for draw k = 0, 1, 2 (id 202 Langevin, 201 Brownian,
+ * src/RNGIdentifiers.h), u01 = (u64 >> 11) 2^-53 + 2^-54 of u64 = c0 << 32 | c1: the construction the DPD
+ * thermostat uses. t = `timestep` is the time step at the start of the step the half belongs to.
+ * Only rows [0, N) whose type t satisfies t < ntypes and (d_type_mask NULL or d_type_mask[t] != 0) are touched;
+ * the Langevin force enters the acceleration only (never the net force, energies or virials). */
+typedef enum azp_flow_kind
+    {
+    AZP_FLOW_CONSTANT = 0, /* u(r) = (p[0], p[1], p[2]) */
+    AZP_FLOW_PARABOLIC = 1 /* u(r) = (p[0] (1 - (y / p[1])^2), 0, 0): p[0] = Umax = 1.5 U, p[1] = L = separation / 2 */
+    } azp_flow_kind;
+
+typedef struct azp_flow
+    {
+    uint32_t kind; /* azp_flow_kind */
+    uint32_t _pad;
+    double p[3];
+    } azp_flow;
+
+typedef struct azp_flow_method_args
+    {
+    double* d_pos;             /* N x 4 (type in w is preserved) */
+    double* d_vel;             /* N x 4 (vx, vy, vz, mass) */
+    double* d_accel;           /* N x 4 (ax, ay, az, unused); Langevin only, may be NULL for Brownian */
+    const double* d_net_force; /* N x 4 */
+    int32_t* d_image;          /* N x 3 periodic image counters, may be NULL */
+    const uint32_t* d_tag;     /* N */
+    const double* d_gamma;     /* ntypes friction coefficients */
+    const uint8_t* d_type_mask; /* ntypes bytes, may be NULL (every type) */
+    azp_box box;
+    double dt;
+    double kT;                 /* kT at `timestep` */
+    uint64_t timestep;
+    uint32_t seed;             /* low 16 bits used */
+    uint32_t noiseless;
+    uint32_t N;
+    uint32_t ntypes;
+    azp_flow flow;
+    uint32_t block_size;       /* 0: 256 */
+    uint32_t _pad;
+    } azp_flow_method_args;
+
+int azp_integrate_langevin_flow_step_one(const azp_flow_method_args* args, void* stream);
+int azp_integrate_langevin_flow_step_two(const azp_flow_method_args* args, void* stream);
+/* Step two of one time step (at args->timestep) and step one of the next in one kernel, bit-identical to the two
+ * calls (as azp_integrate_nve_step_two_one). */
+int azp_integrate_langevin_flow_step_two_one(const azp_flow_method_args* args, void* stream);
+int azp_integrate_brownian_flow_step(const azp_flow_method_args* args, void* stream);
 
 /* ---- velocity / velocity-field computes ----
  * Replaces the reference's GPU drivers of hoomd.azplugins.compute: the per-particle loop of
