@@ -10,8 +10,8 @@
 // kernels have to find out by themselves whether the plan they compiled still describes the
 // list they are handed. Per call (round 3: nothing on the caller's stream waits for the host):
 //
-//   1. one small kernel on the caller's stream (pair_auto.hip: auto_check_kernel; its last
-//      workgroup folds the partial results) leaves in device memory
+//   1. two small kernels on the caller's stream (pair_auto.hip: auto_check_kernel leaves one
+//      partial result per workgroup, auto_fold_kernel folds them) leave in device memory
 //        * a 64-bit fingerprint of the list -- every n_neigh and head_list word, the cutoff
 //          table, the box and N, plus every list entry for lists of up to 2^22 entries and,
 //          beyond that, two entries of every 8th row, the rows rotating from call to call so
@@ -34,7 +34,9 @@
 // TwoPatchMorse kernels). The cache lock is held from the lookup to the last launch of a call.
 // Callers that know when the list changes (the Python layer, HOOMD's
 // NeighborList::getNumUpdates()) either use the explicit azp_pair_plan_* API or pass
-// azp_pair_args.list_generation (non-zero; compared instead of the fingerprint).
+// azp_pair_args.list_generation. With it non-zero the list words are not fingerprinted (N, the
+// box and the cutoffs still are): the plan is recompiled when the number changes, so the caller
+// must change it on every rewrite of the list, re-sorts of the particles included.
 //
 // Restrictions, stated: the call blocks the host for the duration of the check kernel (it
 // cannot be captured into a HIP graph); all calls that share a list must use one stream. Residual
@@ -48,6 +50,7 @@
 #include <functional>
 
 #include "pair_tiled.hpp"
+#include "xtiled.hpp"
 
 namespace azp
 {
@@ -89,5 +92,42 @@ template<class E> int launch_pair_entry(const azp_pair_args* args, const typenam
         [&](const AutoLaunch& l)
             { return launch_pair_planned<E>(reinterpret_cast<azp_pair_plan*>(const_cast<PairPlan*>(l.plan)), l.args, d_params, stream, l.dyn); },
         [&]() { return launch_pair<E>(args, d_params, stream); });
+    }
+
+// Entry points of the policy potentials (xtiled.hpp: XDPD, XTPM). X::validate returns an azp status (< 0), 1 when there
+// is nothing to do, or 0; X::extra builds the kernels' KExtra from the arguments.
+template<class X, class Args>
+int launch_policy_planned(azp_pair_plan* plan_, const Args* args, const typename X::Params* d_params, void* stream)
+    {
+    if (!plan_)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    const int bad = X::validate(args, d_params);
+    if (bad < 0) return bad;
+    if (bad > 0) return AZP_SUCCESS;
+    const PairPlan& plan = *reinterpret_cast<const PairPlan*>(plan_);
+    if (plan.builds == 0 || plan.N != args->pair.N || plan.nlist_ptr != args->pair.d_nlist || plan.head_ptr != args->pair.d_head_list)
+        return AZP_ERROR_INVALID_ARGUMENT; // a plan compiled from a different list is a caller bug
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!xtiled_usable(plan, args->pair)) // (a plan compiled from the cell list has no HOOMD-format list to fall back to)
+        return plan.from_cells ? AZP_ERROR_INVALID_ARGUMENT : launch_xgeneric<X>(args->pair, X::extra(*args), d_params, s);
+    return launch_xtiled<X>(plan, args->pair, X::extra(*args), d_params, s);
+    }
+
+// the tile-staged kernel from libazp's own plan cache unless the caller asks for the generic kernel
+template<class X, class Args> int launch_policy_entry(const Args* args, const typename X::Params* d_params, void* stream)
+    {
+    const int bad = X::validate(args, d_params);
+    if (bad < 0) return bad;
+    if (bad > 0) return AZP_SUCCESS;
+    const typename X::KExtra x = X::extra(*args);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto generic = [&]() { return launch_xgeneric<X>(args->pair, x, d_params, s); };
+    if (!auto_plan_wanted(args->pair))
+        return generic();
+    return auto_plan_run(
+        args->pair, true, s,
+        [&](const AutoLaunch& l)
+            { return xtiled_usable(*l.plan, *l.args) ? launch_xtiled<X>(*l.plan, *l.args, x, d_params, s, l.dyn) : generic(); },
+        generic);
     }
 } // namespace azp

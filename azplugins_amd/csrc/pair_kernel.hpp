@@ -17,6 +17,8 @@
 //     writes force (fx, fy, fz, e) with two 16-B stores.
 #pragma once
 
+#include <type_traits>
+
 #include "evaluators.hpp"
 #include "pair_kernel_host.hpp"
 
@@ -221,21 +223,14 @@ inline uint32_t choose_tpp(const azp_pair_args& args)
     return tpp;
     }
 
-template<class E, int TPP, bool VIRIAL, bool SINGLE, bool XPLOR>
-int launch_pair_instance2(const azp_pair_args& args, const PairKArgs& k, const typename E::Params* d_params,
-                          uint32_t block_size, hipStream_t stream)
+// Launches kern with lds bytes of dynamic LDS and records the launch shape in last_launch(): more than
+// 160 KiB is refused, more than 64 KiB is opted in to first.
+template<class... KArgs, class... Args>
+int launch_dyn_lds(void (*kern)(KArgs...), uint32_t grid, uint32_t block_size, uint32_t tpp, size_t lds, hipStream_t stream,
+                   const Args&... args)
     {
-    PairKArgs ka = k;
-    const uint32_t groups_per_block = block_size / TPP;
-    uint32_t nblocks = (ka.end - ka.first + groups_per_block - 1) / groups_per_block;
-    nblocks = (nblocks + 7u) & ~7u;
-    ka.nblocks_padded = nblocks;
-    size_t lds = 0;
-    if (!SINGLE)
-        lds = (sizeof(typename E::Coeff) + sizeof(double)) * (size_t)args.ntypes * args.ntypes;
     if (lds > 160 * 1024)
         return AZP_ERROR_TOO_MANY_TYPES;
-    auto kern = pair_forces_kernel<E, TPP, VIRIAL, SINGLE, XPLOR>;
     if (lds > 64 * 1024)
         {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -244,9 +239,45 @@ int launch_pair_instance2(const azp_pair_args& args, const PairKArgs& k, const t
             return (int)e;
         }
     LaunchInfo& li = last_launch();
-    li.block_size = block_size; li.tpp = TPP; li.grid = nblocks; li.lds_bytes = (uint32_t)lds;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(block_size), lds, stream, ka, d_params);
+    li.block_size = block_size; li.tpp = tpp; li.grid = grid; li.lds_bytes = (uint32_t)lds;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block_size), lds, stream, args...);
     return (int)hipGetLastError();
+    }
+
+// f(std::integral_constant<int, TPP>()) for the lanes-per-particle counts of the generic kernels
+template<class F> int dispatch_tpp(uint32_t tpp, F&& f)
+    {
+    switch (tpp)
+        {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    case 16: return f(std::integral_constant<int, 16>());
+    case 32: return f(std::integral_constant<int, 32>());
+    default: return AZP_ERROR_INVALID_ARGUMENT;
+        }
+    }
+
+// grid of a generic launch: block_size / TPP particles per workgroup, padded to a multiple of 8 (xcd_remap)
+inline uint32_t generic_grid(const PairKArgs& k, uint32_t block_size, uint32_t tpp)
+    {
+    const uint32_t groups_per_block = block_size / tpp;
+    const uint32_t nblocks = (k.end - k.first + groups_per_block - 1) / groups_per_block;
+    return (nblocks + 7u) & ~7u;
+    }
+
+template<class E, int TPP, bool VIRIAL, bool SINGLE, bool XPLOR>
+int launch_pair_instance2(const azp_pair_args& args, const PairKArgs& k, const typename E::Params* d_params,
+                          uint32_t block_size, hipStream_t stream)
+    {
+    PairKArgs ka = k;
+    ka.nblocks_padded = generic_grid(k, block_size, TPP);
+    size_t lds = 0;
+    if (!SINGLE)
+        lds = (sizeof(typename E::Coeff) + sizeof(double)) * (size_t)args.ntypes * args.ntypes;
+    return launch_dyn_lds(pair_forces_kernel<E, TPP, VIRIAL, SINGLE, XPLOR>, ka.nblocks_padded, block_size, TPP, lds, stream,
+                          ka, d_params);
     }
 
 template<class E, int TPP, bool VIRIAL, bool SINGLE>
@@ -262,16 +293,8 @@ template<class E, bool VIRIAL, bool SINGLE>
 int launch_pair_tpp(const azp_pair_args& args, const PairKArgs& k, const typename E::Params* d_params, uint32_t tpp,
                     uint32_t block_size, hipStream_t stream)
     {
-    switch (tpp)
-        {
-    case 1: return launch_pair_instance<E, 1, VIRIAL, SINGLE>(args, k, d_params, block_size, stream);
-    case 2: return launch_pair_instance<E, 2, VIRIAL, SINGLE>(args, k, d_params, block_size, stream);
-    case 4: return launch_pair_instance<E, 4, VIRIAL, SINGLE>(args, k, d_params, block_size, stream);
-    case 8: return launch_pair_instance<E, 8, VIRIAL, SINGLE>(args, k, d_params, block_size, stream);
-    case 16: return launch_pair_instance<E, 16, VIRIAL, SINGLE>(args, k, d_params, block_size, stream);
-    case 32: return launch_pair_instance<E, 32, VIRIAL, SINGLE>(args, k, d_params, block_size, stream);
-    default: return AZP_ERROR_INVALID_ARGUMENT;
-        }
+    return dispatch_tpp(tpp, [&](auto t)
+        { return launch_pair_instance<E, decltype(t)::value, VIRIAL, SINGLE>(args, k, d_params, block_size, stream); });
     }
 
 inline int validate_pair_args(const azp_pair_args* args, const void* d_params)

@@ -740,20 +740,7 @@ int launch_tiled_instance2(const PairPlan& plan, const azp_pair_args& args, cons
     size_t lds = (size_t)AZP_TILE_STRIDE(CAP) * 24 + (SINGLE ? 0 : (size_t)CAP * 4 + 8);
     if (!SINGLE)
         lds += (sizeof(typename E::Coeff) + sizeof(double)) * (size_t)args.ntypes * args.ntypes;
-    if (lds > 160 * 1024)
-        return AZP_ERROR_TOO_MANY_TYPES;
-    auto kern = pair_forces_tiled_kernel<E, TPP, CAP, VIRIAL, SINGLE, XPLOR>;
-    if (lds > 64 * 1024)
-        {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return (int)e;
-        }
-    LaunchInfo& li = last_launch();
-    li.block_size = 256; li.tpp = TPP; li.grid = nblocks; li.lds_bytes = (uint32_t)lds;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), lds, stream, k, d_params);
-    return (int)hipGetLastError();
+    return launch_dyn_lds(pair_forces_tiled_kernel<E, TPP, CAP, VIRIAL, SINGLE, XPLOR>, nblocks, 256, TPP, lds, stream, k, d_params);
     }
 
 template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE>

@@ -125,8 +125,11 @@ def _planned_call(entry, a, args_struct, p, plan_info):
 
 
 def gpu_dpd_forces(pos, vel, tag, box, nl, params, r_cut, kT, dt, seed, timestep, ntypes=1, N=None, virial=False,
-                   tpp=0, r_list_max=0.0, planned=False, plan_info=None, displacement_bound=None):
+                   tpp=0, r_list_max=0.0, planned=False, plan_info=None, displacement_bound=None, prange=None):
+    """prange=(first, count): compute rows [first, first + count) only; the other rows stay NaN."""
     a, t = gpu_pair_args(pos, box, nl, ntypes, r_cut, 0.0, "none", virial, N, tpp, 0, r_list_max)
+    if prange is not None:
+        a.range_first, a.range_count = prange
     if displacement_bound is not None:
         a.has_displacement_bound, a.displacement_bound = 1, displacement_bound
     p = _dev(np.atleast_2d(params).astype(np.float64))
@@ -148,10 +151,13 @@ def gpu_dpd_forces(pos, vel, tag, box, nl, params, r_cut, kT, dt, seed, timestep
 
 
 def gpu_aniso_forces(pos, orientation, box, nl, params, r_cut, mode="none", ntypes=1, N=None, virial=False, tpp=0,
-                     r_list_max=0.0, planned=False, plan_info=None, displacement_bound=None):
+                     r_list_max=0.0, planned=False, plan_info=None, displacement_bound=None, prange=None):
+    """prange=(first, count): compute rows [first, first + count) only; the other rows stay NaN."""
     import torch
 
     a, t = gpu_pair_args(pos, box, nl, ntypes, r_cut, 0.0, mode, virial, N, tpp, 0, r_list_max)
+    if prange is not None:
+        a.range_first, a.range_count = prange
     if displacement_bound is not None:
         a.has_displacement_bound, a.displacement_bound = 1, displacement_bound
     p = _dev(np.atleast_2d(params).astype(np.float64))

@@ -203,6 +203,16 @@ def test_hertz_c1_golden(oracle):
     assert nl[0].mean() == pytest.approx(float(gold["mean_neighbors"]))
 
 
+GENERIC_TPP = (1, 2, 4, 8, 16, 32)
+
+
+def _assert_generic_launch(tpp, lds_bytes):
+    from azplugins_amd import _lib
+
+    launch = _lib.last_launch()
+    assert launch["threads_per_particle"] == tpp and launch["lds_bytes"] == lds_bytes, launch
+
+
 def test_dpd_thermostat_parity(oracle):
     """Drag + random + conservative forces with the same Philox stream."""
     cfg = syn.config_dpd(4096)
@@ -224,6 +234,20 @@ def test_dpd_thermostat_parity(oracle):
         assert_close(f_gpu[:, :3], f_ref[:, :3], what="dpd force")
         assert_close(f_gpu[:, 3], f_ref[:, 3], what="dpd energy")
         assert_close(v_gpu, v_ref, what="dpd virial")
+        # every lanes-per-particle count of the generic kernel; coefficients in LDS: 56 B per type pair
+        for tpp in GENERIC_TPP:
+            f_t, v_t = H.gpu_dpd_forces(pos, vel, cfg["tag"], (cfg["L"],), nl_f, params, 1.0, virial=True, tpp=tpp, **kw)
+            _assert_generic_launch(tpp, 0 if T == 1 else 56 * T * T)
+            assert_close(f_t[:, :3], f_ref[:, :3], what="dpd force tpp=%d" % tpp)
+            assert_close(f_t[:, 3], f_ref[:, 3], what="dpd energy tpp=%d" % tpp)
+            assert_close(v_t, v_ref, what="dpd virial tpp=%d" % tpp)
+        first, count = 1000, 1500  # a sub-range launch computes its rows only
+        f_r, v_r = H.gpu_dpd_forces(pos, vel, cfg["tag"], (cfg["L"],), nl_f, params, 1.0, virial=True, prange=(first, count), **kw)
+        r = slice(first, first + count)
+        assert_close(f_r[r, :3], f_ref[r, :3], what="dpd range force")
+        assert_close(f_r[r, 3], f_ref[r, 3], what="dpd range energy")
+        assert_close(v_r[:, r], v_ref[:, r], what="dpd range virial")
+        assert np.isnan(f_r[:first]).all() and np.isnan(f_r[first + count:]).all()
         # pairwise noise is antisymmetric: total momentum is conserved
         assert np.abs(f_gpu[:, :3].sum(axis=0)).max() < 1e-9 * np.abs(f_gpu[:, :3]).max()
         # a different timestep or seed draws different noise
@@ -268,6 +292,26 @@ def test_aniso_parity(oracle):
         assert_close(v_gpu, v_ref, what="aniso virial")
         assert not t_gpu[:, 3].any()
         assert np.abs(f_ref[:, :3]).max() > 1e-3 and np.abs(t_ref[:, :3]).max() > 1e-3
+        # every lanes-per-particle count of the generic kernel; coefficients in LDS: 64 B per type pair
+        for tpp in GENERIC_TPP:
+            f_t, t_t, v_t = H.gpu_aniso_forces(pos, cfg["orientation"], (cfg["L"],), nl_f, params, 1.6, mode, ntypes=T,
+                                               virial=True, tpp=tpp)
+            _assert_generic_launch(tpp, 0 if T == 1 else 64 * T * T)
+            assert_close(f_t[:, :3], f_ref[:, :3], what="aniso force tpp=%d" % tpp)
+            assert_close(f_t[:, 3], f_ref[:, 3], what="aniso energy tpp=%d" % tpp)
+            assert_close(t_t[:, :3], t_ref[:, :3], what="aniso torque tpp=%d" % tpp)
+            assert_close(v_t, v_ref, what="aniso virial tpp=%d" % tpp)
+            assert not t_t[:, 3].any()
+        first, count = 100, 300  # a sub-range launch computes its rows only
+        f_r, t_r, v_r = H.gpu_aniso_forces(pos, cfg["orientation"], (cfg["L"],), nl_f, params, 1.6, mode, ntypes=T,
+                                           virial=True, prange=(first, count))
+        r = slice(first, first + count)
+        assert_close(f_r[r, :3], f_ref[r, :3], what="aniso range force")
+        assert_close(f_r[r, 3], f_ref[r, 3], what="aniso range energy")
+        assert_close(t_r[r, :3], t_ref[r, :3], what="aniso range torque")
+        assert_close(v_r[:, r], v_ref[:, r], what="aniso range virial")
+        assert np.isnan(f_r[:first]).all() and np.isnan(f_r[first + count:]).all()
+        assert np.isnan(t_r[:first]).all() and np.isnan(t_r[first + count:]).all()
 
 
 @pytest.mark.parametrize("name", ["DoubleWell", "Quartic"])
