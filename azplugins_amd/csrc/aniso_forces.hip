@@ -4,7 +4,8 @@
 // the reference at src/AnisoPotentialPairGPUKernel.cu.inc:21-25; per-pair
 // arithmetic restated from src/AnisoPairEvaluatorTwoPatchMorse.h:127-216.
 //
-// The policy XTPM drives both kernels of xtiled.hpp (tile-staged and generic).
+// The policy XTPM drives the tile-staged xtiled_kernel (xtiled.hpp) and the generic
+// pair_forces_kernel (pair_kernel.hpp).
 // The patch director n = rotate(q, x^) of particle i is computed once per
 // particle, that of a neighbor once per tile (tile kernel) or per in-range pair
 // (generic kernel). Outputs: force (fx, fy, fz, e) and torque (tx, ty, tz, 0),
@@ -91,7 +92,7 @@ __device__ __forceinline__ void tpm_pair(const TPMCoeff& c, const double3& n_i, 
     T[2] = dU_dgi * __builtin_fma(ux, n_i.y, -uy * n_i.x);
     }
 
-// TwoPatchMorse for the kernels of xtiled.hpp: the tile kernel computes the patch director n_j = rotate(q_j, x^) of
+// TwoPatchMorse as a policy: the tile kernel computes the patch director n_j = rotate(q_j, x^) of
 // every staged particle ONCE per tile and keeps it in LDS next to its position (the reference rotates per pair,
 // src/AnisoPairEvaluatorTwoPatchMorse.h:145-146); the generic kernel computes it per in-range pair
 struct XTPM
@@ -114,9 +115,9 @@ struct XTPM
         {
         double f[3], t[3], pe;
         };
-    static __device__ __forceinline__ Coeff prepare(const Params& p, double rcutsq, const KExtra&, uint32_t shift_mode)
+    static __device__ __forceinline__ Coeff prepare(const Params* params, const PairKArgs& a, uint32_t t, const KExtra&)
         {
-        return tpm_prepare(p, rcutsq, shift_mode == AZP_SHIFT_SHIFT);
+        return tpm_prepare(params[t], a.rcutsq[t], a.shift_mode == AZP_SHIFT_SHIFT);
         }
     static __device__ __forceinline__ void load_extra(const KExtra& x, uint32_t j, double (&e)[3], uint32_t&)
         {

@@ -4,7 +4,8 @@
 // reference at src/PotentialPairDPDThermoGPUKernel.cu.inc:21-24; per-pair
 // arithmetic restated from src/DPDPairEvaluatorGeneralWeight.h:198-255.
 //
-// The policy XDPD drives both kernels of xtiled.hpp (tile-staged and generic).
+// The policy XDPD drives the tile-staged xtiled_kernel (xtiled.hpp) and the generic
+// pair_forces_kernel (pair_kernel.hpp).
 // Per neighbor: velocity (24 B) and tag (4 B). One Philox4x32-10 block per
 // in-range pair, computed in registers, keyed by (seed, timestep, min tag,
 // max tag) so both owners of a pair draw the same number (cross-rank
@@ -41,9 +42,9 @@ __device__ __forceinline__ double weight_pow(double x, double half_s)
     return pow(x, half_s);
     }
 
-// the DPD thermostat for the kernels of xtiled.hpp: the tile kernel stages positions, velocities and tags of a tile's
-// neighbors once in LDS, the generic kernel loads a neighbor's velocity and tag per in-range pair
-struct XDPD
+// the DPD thermostat as a policy: the tile kernel stages positions, velocities and tags of a tile's neighbors once in
+// LDS, the generic kernel loads a neighbor's velocity and tag per in-range pair
+struct XDPD : ForceEnergy
     {
     typedef azp_dpd_params Params;
     typedef DPDCoeff Coeff;
@@ -63,13 +64,9 @@ struct XDPD
         double3 v;
         uint32_t tag;
         };
-    struct Acc
+    static __device__ __forceinline__ Coeff prepare(const Params* params, const PairKArgs& a, uint32_t t, const KExtra& x)
         {
-        double fx, fy, fz, pe;
-        };
-    static __device__ __forceinline__ Coeff prepare(const Params& p, double rcutsq, const KExtra& x, uint32_t)
-        {
-        return dpd_prepare(p, rcutsq, x.deltaT, x.T);
+        return dpd_prepare(params[t], a.rcutsq[t], x.deltaT, x.T);
         }
     static __device__ __forceinline__ void load_extra(const KExtra& x, uint32_t j, double (&e)[3], uint32_t& tag)
         {
@@ -81,14 +78,6 @@ struct XDPD
         {
         o.v = load_scalar3_of4(x.vel, idx);
         o.tag = x.tag[idx];
-        }
-    static __device__ __forceinline__ void zero(Acc& a) { a.fx = a.fy = a.fz = a.pe = 0.0; }
-    template<int TPP> static __device__ __forceinline__ void reduce(Acc& a)
-        {
-        a.fx = group_sum<TPP>(a.fx);
-        a.fy = group_sum<TPP>(a.fy);
-        a.fz = group_sum<TPP>(a.fz);
-        a.pe = group_sum<TPP>(a.pe);
         }
     static __device__ __forceinline__ bool in_range(const Coeff& c, double rsq) { return rsq < c.rcutsq; }
     template<bool VIRIAL>
@@ -117,10 +106,6 @@ struct XDPD
             v[4] = __builtin_fma(fyy, dz, v[4]);
             v[5] = __builtin_fma(force_divr_cons * dz, dz, v[5]);
             }
-        }
-    static __device__ __forceinline__ void store(const Acc& a, const PairKArgs& p, const KExtra&, uint32_t idx)
-        {
-        store_scalar4(p.force, idx, a.fx, a.fy, a.fz, 0.5 * a.pe);
         }
     static int validate(const azp_dpd_args* args, const azp_dpd_params* d_params)
         {

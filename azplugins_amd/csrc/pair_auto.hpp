@@ -77,57 +77,85 @@ inline bool auto_plan_wanted(const azp_pair_args& a)
     return a.threads_per_particle == 0 && !(a.flags & AZP_PAIR_FLAG_NO_AUTO_PLAN) && auto_plan_enabled();
     }
 
-// Entry point behind azp_pair_forces_<evaluator>.
-template<class E> int launch_pair_entry(const azp_pair_args* args, const typename E::Params* d_params, void* stream)
+// What the entry points need to know of a policy besides its generic kernel. XDPD / XTPM: the arguments wrap an
+// azp_pair_args (args.pair); the tile kernel is xtiled_kernel, which takes plans with one lane per particle.
+template<class X> struct PolicyEntry
     {
-    const int bad = validate_pair_args(args, d_params);
-    if (bad < 0) return bad;
-    if (bad > 0) return AZP_SUCCESS;
-    if (!auto_plan_wanted(*args))
-        return launch_pair<E>(args, d_params, stream);
-    // r_list_max is not part of pair_args_t: when the caller leaves it 0 the kernel decides per
-    // tile from the staged positions whether the staged images are minimum images
-    return auto_plan_run(
-        *args, false, static_cast<hipStream_t>(stream),
-        [&](const AutoLaunch& l)
-            { return launch_pair_planned<E>(reinterpret_cast<azp_pair_plan*>(const_cast<PairPlan*>(l.plan)), l.args, d_params, stream, l.dyn); },
-        [&]() { return launch_pair<E>(args, d_params, stream); });
-    }
+    template<class Args> static const azp_pair_args& pair(const Args& a) { return a.pair; }
+    static constexpr bool kLanesOne = true;
+    static bool usable(const PairPlan& plan, const azp_pair_args& a) { return xtiled_usable(plan, a); }
+    static int tiled(const PairPlan& plan, const azp_pair_args& a, const typename X::KExtra& x, const typename X::Params* d_params, hipStream_t s,
+                     const TileDyn* dyn)
+        {
+        return launch_xtiled<X>(plan, a, x, d_params, s, dyn);
+        }
+    static int generic(const azp_pair_args& a, const typename X::KExtra& x, const typename X::Params* d_params, hipStream_t s)
+        {
+        return launch_generic<X>(a, x, d_params, s);
+        }
+    };
 
-// Entry points of the policy potentials (xtiled.hpp: XDPD, XTPM). X::validate returns an azp status (< 0), 1 when there
-// is nothing to do, or 0; X::extra builds the kernels' KExtra from the arguments.
+// The isotropic potentials (XIso): azp_pair_args itself; pair_forces_tiled_kernel at the plan's lanes per particle, split
+// launches included (pair_tiled.hpp); the xplor instance of the generic kernel picked per call
+template<class E, bool XPLOR> struct PolicyEntry<XIso<E, XPLOR>>
+    {
+    static const azp_pair_args& pair(const azp_pair_args& a) { return a; }
+    static constexpr bool kLanesOne = false;
+    static bool usable(const PairPlan& plan, const azp_pair_args&) { return plan.valid; }
+    static int tiled(const PairPlan& plan, const azp_pair_args& a, const typename XIso<E, XPLOR>::KExtra&, const typename E::Params* d_params, hipStream_t s,
+                     const TileDyn* dyn)
+        {
+        return launch_tiled_tpp<E>(plan, a, d_params, s, dyn);
+        }
+    static int generic(const azp_pair_args& a, const typename XIso<E, XPLOR>::KExtra&, const typename E::Params* d_params, hipStream_t s)
+        {
+        if (a.shift_mode == AZP_SHIFT_XPLOR)
+            return launch_generic<XIso<E, true>>(a, {}, d_params, s);
+        return launch_generic<XIso<E, false>>(a, {}, d_params, s);
+        }
+    };
+
+// Entry points of the pair potentials: azp_pair_forces_planned_<evaluator>, azp_dpd_forces_planned_general_weight,
+// azp_aniso_forces_planned_two_patch_morse. X::validate returns an azp status (< 0), 1 when there is nothing to do,
+// or 0; X::extra builds the kernels' KExtra from the arguments.
 template<class X, class Args>
 int launch_policy_planned(azp_pair_plan* plan_, const Args* args, const typename X::Params* d_params, void* stream)
     {
+    typedef PolicyEntry<X> P;
     if (!plan_)
         return AZP_ERROR_INVALID_ARGUMENT;
     const int bad = X::validate(args, d_params);
     if (bad < 0) return bad;
     if (bad > 0) return AZP_SUCCESS;
     const PairPlan& plan = *reinterpret_cast<const PairPlan*>(plan_);
-    if (plan.builds == 0 || plan.N != args->pair.N || plan.nlist_ptr != args->pair.d_nlist || plan.head_ptr != args->pair.d_head_list)
+    const azp_pair_args& pa = P::pair(*args);
+    if (plan.builds == 0 || plan.N != pa.N || plan.nlist_ptr != pa.d_nlist || plan.head_ptr != pa.d_head_list)
         return AZP_ERROR_INVALID_ARGUMENT; // a plan compiled from a different list is a caller bug
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!xtiled_usable(plan, args->pair)) // (a plan compiled from the cell list has no HOOMD-format list to fall back to)
-        return plan.from_cells ? AZP_ERROR_INVALID_ARGUMENT : launch_xgeneric<X>(args->pair, X::extra(*args), d_params, s);
-    return launch_xtiled<X>(plan, args->pair, X::extra(*args), d_params, s);
+    if (!P::usable(plan, pa)) // (a plan compiled from the cell list has no HOOMD-format list to fall back to)
+        return plan.from_cells ? AZP_ERROR_INVALID_ARGUMENT : P::generic(pa, X::extra(*args), d_params, s);
+    return P::tiled(plan, pa, X::extra(*args), d_params, s, nullptr);
     }
 
-// the tile-staged kernel from libazp's own plan cache unless the caller asks for the generic kernel
+// ... and azp_pair_forces_<evaluator>, azp_dpd_forces_general_weight, azp_aniso_forces_two_patch_morse: the tile-staged
+// kernel from libazp's own plan cache unless the caller asks for the generic kernel. r_list_max is not part of
+// pair_args_t: when the caller leaves it 0 the tile kernels decide per tile from the staged positions whether the staged
+// images are minimum images.
 template<class X, class Args> int launch_policy_entry(const Args* args, const typename X::Params* d_params, void* stream)
     {
+    typedef PolicyEntry<X> P;
     const int bad = X::validate(args, d_params);
     if (bad < 0) return bad;
     if (bad > 0) return AZP_SUCCESS;
+    const azp_pair_args& pa = P::pair(*args);
     const typename X::KExtra x = X::extra(*args);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto generic = [&]() { return launch_xgeneric<X>(args->pair, x, d_params, s); };
-    if (!auto_plan_wanted(args->pair))
+    auto generic = [&]() { return P::generic(pa, x, d_params, s); };
+    if (!auto_plan_wanted(pa))
         return generic();
     return auto_plan_run(
-        args->pair, true, s,
-        [&](const AutoLaunch& l)
-            { return xtiled_usable(*l.plan, *l.args) ? launch_xtiled<X>(*l.plan, *l.args, x, d_params, s, l.dyn) : generic(); },
+        pa, P::kLanesOne, s,
+        [&](const AutoLaunch& l) { return P::usable(*l.plan, *l.args) ? P::tiled(*l.plan, *l.args, x, d_params, s, l.dyn) : generic(); },
         generic);
     }
 } // namespace azp

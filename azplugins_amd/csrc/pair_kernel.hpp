@@ -1,6 +1,17 @@
-// pair_kernel.hpp -- the neighbor-list pair-force kernel for isotropic
-// evaluators (replaces HOOMD's gpu_compute_pair_forces<E>, requested by the
-// reference at src/PotentialPairGPUKernel.cu.inc:25-28).
+// pair_kernel.hpp -- the generic neighbor-list kernel of every pair potential
+// (replaces HOOMD's gpu_compute_pair_forces<E>, gpu_compute_dpd_forces<E> and
+// gpu_compute_pair_aniso_forces<E>, requested by the reference at
+// src/PotentialPairGPUKernel.cu.inc:25-28, src/PotentialPairDPDThermoGPUKernel.cu.inc:21-24
+// and src/AnisoPotentialPairGPUKernel.cu.inc:21-25). It runs on the HOOMD-format list
+// for explicit threads_per_particle, without an auto plan and for lists that cannot be
+// tiled; the tile-staged kernels are in pair_tiled.hpp and xtiled.hpp.
+//
+// pair_forces_kernel<X, TPP, VIRIAL, SINGLE> knows no potential. A policy class X holds
+// the physics: coefficients (prepare), what a pair reads beyond the neighbor's position
+// (load_extra: kExtra doubles, a tag with kTag) and of the particle itself (load_own), the
+// in-range test, the pair arithmetic, the reduction over lanes and the store. XIso (below)
+// adapts the isotropic evaluators of evaluators.hpp; XDPD (dpd_forces.hip) and XTPM
+// (aniso_forces.hip) also drive xtiled_kernel.
 //
 // Mapping (gfx950, wave64):
 //   * TPP consecutive lanes cooperate on one particle; a wave covers 64/TPP
@@ -9,7 +20,8 @@
 //   * lanes stride the row: lane s handles entries s, s+TPP, ... ; the next
 //     index is prefetched one iteration ahead.
 //   * neighbor positions are gathered as 16-B loads and rely on L1 / the
-//     XCD's L2 (block -> particle range mapping is XCD-aware).
+//     XCD's L2 (block -> particle range mapping is XCD-aware); the payload of
+//     a neighbor is loaded for in-range pairs only.
 //   * per-type-pair coefficients: registers when ntypes == 1, LDS otherwise.
 //   * interior waves (every particle farther than r_list_max from all periodic
 //     faces) skip the minimum-image arithmetic; the choice is wave-uniform.
@@ -55,57 +67,79 @@ prepare_coeff(const PairKArgs& a, const typename E::Params* params, uint32_t tp)
     return E::prepare(params[tp], rcutsq, energy_shift);
     }
 
-template<class E, int TPP, bool VIRIAL, bool SINGLE, bool XPLOR, bool WRAP>
-__device__ __forceinline__ void pair_loop(const PairKArgs& a, const typename E::Coeff* __restrict__ s_coeff,
-                                          const double* __restrict__ s_ronsq, const typename E::Coeff& c0,
-                                          double ronsq0, uint32_t sub, uint32_t n, uint64_t head, double3 pi,
-                                          int typei, double& fx, double& fy, double& fz, double& pe, double (&v)[6])
+inline int validate_pair_args(const azp_pair_args* args, const void* d_params)
     {
-    const uint32_t* __restrict__ row = a.nlist + head;
-    uint32_t k = sub;
-    uint32_t j = (k < n) ? row[k] : 0u;
-    while (k < n)
-        {
-        const uint32_t kn = k + TPP;
-        const uint32_t jn = (kn < n) ? row[kn] : 0u; // prefetch next index
-        double dx, dy, dz;
-        int typej = 0;
-        if (SINGLE)
-            {
-            const double3 pj = load_scalar3_of4(a.pos, j);
-            dx = pi.x - pj.x; dy = pi.y - pj.y; dz = pi.z - pj.z;
-            }
-        else
-            {
-            const double4 pj = load_scalar4(a.pos, j);
-            dx = pi.x - pj.x; dy = pi.y - pj.y; dz = pi.z - pj.z;
-            typej = type_from_w(pj.w);
-            }
-        if (WRAP)
-            min_image(a.box, dx, dy, dz);
-        const double rsq = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
+    if (!args || !d_params) return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->N == 0) return 1; // nothing to do (caller returns success)
+    if (!args->d_force || !args->d_pos || !args->d_n_neigh || !args->d_nlist || !args->d_head_list || !args->d_rcutsq)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->ntypes == 0 || args->shift_mode > AZP_SHIFT_XPLOR) return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->shift_mode == AZP_SHIFT_XPLOR && !args->d_ronsq) return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->compute_virial && (!args->d_virial || args->virial_pitch < args->N)) return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->n_max < args->N) return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->block_size && (args->block_size % 64 || args->block_size > 256)) return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->range_count && (uint64_t)args->range_first + args->range_count > args->N) return AZP_ERROR_INVALID_ARGUMENT;
+    return 0;
+    }
 
+// force (fx, fy, fz) and pair energy summed over a particle's neighbors (XIso, XDPD)
+struct ForceEnergy
+    {
+    struct Acc
+        {
+        double fx, fy, fz, pe;
+        };
+    static __device__ __forceinline__ void zero(Acc& a) { a.fx = a.fy = a.fz = a.pe = 0.0; }
+    template<int TPP> static __device__ __forceinline__ void reduce(Acc& a)
+        {
+        a.fx = group_sum<TPP>(a.fx);
+        a.fy = group_sum<TPP>(a.fy);
+        a.fz = group_sum<TPP>(a.fz);
+        a.pe = group_sum<TPP>(a.pe);
+        }
+    template<class KExtra> static __device__ __forceinline__ void store(const Acc& a, const PairKArgs& p, const KExtra&, uint32_t idx)
+        {
+        store_scalar4(p.force, idx, a.fx, a.fy, a.fz, 0.5 * a.pe);
+        }
+    };
+
+// An isotropic evaluator E (evaluators.hpp) as a policy: no payload, and every listed pair is evaluated -- E::eval is
+// branch-free and gives zero force and energy beyond the cutoff. XPLOR smoothing is a separate instance, chosen per
+// call from shift_mode (pair_auto.hpp).
+template<class E, bool XPLOR = false> struct XIso : ForceEnergy
+    {
+    typedef typename E::Params Params;
+    struct Coeff
+        {
+        typename E::Coeff c;
+        double ronsq; // (xplor only)
+        };
+    struct KExtra {};
+    struct Own {};
+    static constexpr int kExtra = 0;
+    static constexpr bool kTag = false;
+    static __device__ __forceinline__ Coeff prepare(const Params* params, const PairKArgs& a, uint32_t t, const KExtra&)
+        {
+        Coeff c;
+        c.c = prepare_coeff<E>(a, params, t);
+        c.ronsq = XPLOR ? a.ronsq[t] : 0.0;
+        return c;
+        }
+    static __device__ __forceinline__ void load_own(const KExtra&, uint32_t, Own&) {}
+    static __device__ __forceinline__ void load_extra(const KExtra&, uint32_t, const double*, uint32_t&) {}
+    static __device__ __forceinline__ bool in_range(const Coeff&, double) { return true; }
+    template<bool VIRIAL>
+    static __device__ __forceinline__ void pair(const Coeff& c, const KExtra&, const Own&, double dx, double dy, double dz, double rsq,
+                                                const double*, uint32_t, Acc& a, double (&v)[6])
+        {
         double force_divr, pair_eng;
-        bool evaluated;
-        if (SINGLE)
-            {
-            evaluated = E::eval(c0, rsq, force_divr, pair_eng);
-            if (XPLOR && evaluated)
-                apply_xplor(rsq, ronsq0, c0.rcutsq, force_divr, pair_eng);
-            }
-        else
-            {
-            const uint32_t tp = (uint32_t)typei * a.ntypes + (uint32_t)typej;
-            const typename E::Coeff c = s_coeff[tp];
-            evaluated = E::eval(c, rsq, force_divr, pair_eng);
-            if (XPLOR && evaluated)
-                apply_xplor(rsq, s_ronsq[tp], c.rcutsq, force_divr, pair_eng);
-            }
-        // E::eval returns force_divr = pair_eng = 0 when not evaluated
-        fx = __builtin_fma(dx, force_divr, fx);
-        fy = __builtin_fma(dy, force_divr, fy);
-        fz = __builtin_fma(dz, force_divr, fz);
-        pe += pair_eng;
+        const bool evaluated = E::eval(c.c, rsq, force_divr, pair_eng);
+        if (XPLOR && evaluated)
+            apply_xplor(rsq, c.ronsq, c.c.rcutsq, force_divr, pair_eng);
+        a.fx = __builtin_fma(dx, force_divr, a.fx);
+        a.fy = __builtin_fma(dy, force_divr, a.fy);
+        a.fz = __builtin_fma(dz, force_divr, a.fz);
+        a.pe += pair_eng;
         if (VIRIAL)
             {
             const double fxx = force_divr * dx, fyy = force_divr * dy;
@@ -116,41 +150,33 @@ __device__ __forceinline__ void pair_loop(const PairKArgs& a, const typename E::
             v[4] = __builtin_fma(fyy, dz, v[4]);
             v[5] = __builtin_fma(force_divr * dz, dz, v[5]);
             }
-        k = kn;
-        j = jn;
         }
-    }
+    static int validate(const azp_pair_args* args, const Params* d_params) { return validate_pair_args(args, d_params); }
+    static KExtra extra(const azp_pair_args&) { return KExtra(); }
+    };
 
-template<class E, int TPP, bool VIRIAL, bool SINGLE, bool XPLOR>
-__global__ void __launch_bounds__(256) pair_forces_kernel(const PairKArgs a, const typename E::Params* __restrict__ params)
+// TPP lanes per particle, each striding the row (entries sub, sub + TPP, ...) with the next index
+// prefetched; coefficients in registers (one type) or LDS; the minimum image skipped by waves whose
+// particles are all interior
+template<class X, int TPP, bool VIRIAL, bool SINGLE>
+__global__ void __launch_bounds__(256) pair_forces_kernel(const PairKArgs a, const typename X::KExtra x, const typename X::Params* __restrict__ params)
     {
-    typedef typename E::Coeff Coeff;
+    typedef typename X::Coeff Coeff;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     Coeff* s_coeff = reinterpret_cast<Coeff*>(s_raw);
-    double* s_ronsq = reinterpret_cast<double*>(s_raw + sizeof(Coeff) * (SINGLE ? 0 : a.ntypes * a.ntypes));
-
     Coeff c0;
-    double ronsq0 = 0.0;
     if (SINGLE)
-        {
-        c0 = prepare_coeff<E>(a, params, 0);
-        if (XPLOR)
-            ronsq0 = a.ronsq[0];
-        }
+        c0 = X::prepare(params, a, 0, x);
     else
         {
         const uint32_t ntp = a.ntypes * a.ntypes;
         for (uint32_t t = threadIdx.x; t < ntp; t += blockDim.x)
-            {
-            s_coeff[t] = prepare_coeff<E>(a, params, t);
-            s_ronsq[t] = XPLOR ? a.ronsq[t] : 0.0;
-            }
+            s_coeff[t] = X::prepare(params, a, t, x);
         __syncthreads();
         }
 
     const uint32_t block = xcd_remap(blockIdx.x, a.nblocks_padded);
-    const uint32_t groups_per_block = blockDim.x / TPP;
-    const uint32_t idx = a.first + block * groups_per_block + threadIdx.x / TPP;
+    const uint32_t idx = a.first + block * (blockDim.x / TPP) + threadIdx.x / TPP;
     const uint32_t sub = threadIdx.x % TPP;
     const bool active = idx < a.end;
 
@@ -158,6 +184,7 @@ __global__ void __launch_bounds__(256) pair_forces_kernel(const PairKArgs a, con
     uint64_t head = 0;
     double3 pi = make_double3(0.0, 0.0, 0.0);
     int typei = 0;
+    typename X::Own own = {};
     if (active)
         {
         n = a.n_neigh[idx];
@@ -165,41 +192,76 @@ __global__ void __launch_bounds__(256) pair_forces_kernel(const PairKArgs a, con
         const double4 p = load_scalar4(a.pos, idx);
         pi = make_double3(p.x, p.y, p.z);
         typei = type_from_w(p.w);
+        X::load_own(x, idx, own);
         }
-
-    double fx = 0.0, fy = 0.0, fz = 0.0, pe = 0.0;
+    typename X::Acc acc;
+    X::zero(acc);
     double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
-    // wave-uniform choice: can this wave skip the minimum image?
     bool wrap = true;
     if (a.r_list_max > 0.0 && !a.box.triclinic)
         {
         const bool interior = !active || is_interior(a.box, pi.x, pi.y, pi.z, a.r_list_max);
         wrap = !__all(interior);
         }
+    auto walk = [&](auto wrap_tag)
+        {
+        constexpr bool WRAP = decltype(wrap_tag)::value;
+        const uint32_t* __restrict__ row = a.nlist + head;
+        uint32_t k = sub;
+        uint32_t j = (k < n) ? row[k] : 0u;
+        while (k < n)
+            {
+            const uint32_t kn = k + TPP;
+            const uint32_t jn = (kn < n) ? row[kn] : 0u;
+            double dx, dy, dz;
+            int typej = 0;
+            if (SINGLE)
+                {
+                const double3 pj = load_scalar3_of4(a.pos, j); // (one type: w is not read)
+                dx = pi.x - pj.x; dy = pi.y - pj.y; dz = pi.z - pj.z;
+                }
+            else
+                {
+                const double4 pj = load_scalar4(a.pos, j);
+                dx = pi.x - pj.x; dy = pi.y - pj.y; dz = pi.z - pj.z;
+                typej = type_from_w(pj.w);
+                }
+            if (WRAP)
+                min_image(a.box, dx, dy, dz);
+            const double rsq = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
+            const Coeff c = SINGLE ? c0 : s_coeff[(uint32_t)typei * a.ntypes + (uint32_t)typej];
+            if (X::in_range(c, rsq))
+                {
+                double ext[X::kExtra > 0 ? X::kExtra : 1]; // (XIso: none)
+                uint32_t tagj = 0;
+                X::load_extra(x, j, ext, tagj);
+                X::template pair<VIRIAL>(c, x, own, dx, dy, dz, rsq, ext, tagj, acc, v);
+                }
+            k = kn;
+            j = jn;
+            }
+        };
     if (wrap)
-        pair_loop<E, TPP, VIRIAL, SINGLE, XPLOR, true>(a, s_coeff, s_ronsq, c0, ronsq0, sub, n, head, pi, typei, fx, fy, fz, pe, v);
+        walk(std::true_type());
     else
-        pair_loop<E, TPP, VIRIAL, SINGLE, XPLOR, false>(a, s_coeff, s_ronsq, c0, ronsq0, sub, n, head, pi, typei, fx, fy, fz, pe, v);
+        walk(std::false_type());
 
-    fx = group_sum<TPP>(fx);
-    fy = group_sum<TPP>(fy);
-    fz = group_sum<TPP>(fz);
-    pe = group_sum<TPP>(pe);
+    X::template reduce<TPP>(acc);
     if (VIRIAL)
         {
 #pragma unroll
-        for (int c = 0; c < 6; ++c)
-            v[c] = group_sum<TPP>(v[c]);
+        for (int cidx = 0; cidx < 6; ++cidx)
+            v[cidx] = group_sum<TPP>(v[cidx]);
         }
     if (active && sub == 0)
         {
-        store_scalar4(a.force, idx, fx, fy, fz, 0.5 * pe);
+        X::store(acc, a, x, idx);
         if (VIRIAL)
             {
 #pragma unroll
-            for (int c = 0; c < 6; ++c)
-                a.virial[(uint64_t)c * a.virial_pitch + idx] = 0.5 * v[c];
+            for (int cidx = 0; cidx < 6; ++cidx)
+                a.virial[(uint64_t)cidx * a.virial_pitch + idx] = 0.5 * v[cidx];
             }
         }
     }
@@ -267,51 +329,6 @@ inline uint32_t generic_grid(const PairKArgs& k, uint32_t block_size, uint32_t t
     return (nblocks + 7u) & ~7u;
     }
 
-template<class E, int TPP, bool VIRIAL, bool SINGLE, bool XPLOR>
-int launch_pair_instance2(const azp_pair_args& args, const PairKArgs& k, const typename E::Params* d_params,
-                          uint32_t block_size, hipStream_t stream)
-    {
-    PairKArgs ka = k;
-    ka.nblocks_padded = generic_grid(k, block_size, TPP);
-    size_t lds = 0;
-    if (!SINGLE)
-        lds = (sizeof(typename E::Coeff) + sizeof(double)) * (size_t)args.ntypes * args.ntypes;
-    return launch_dyn_lds(pair_forces_kernel<E, TPP, VIRIAL, SINGLE, XPLOR>, ka.nblocks_padded, block_size, TPP, lds, stream,
-                          ka, d_params);
-    }
-
-template<class E, int TPP, bool VIRIAL, bool SINGLE>
-int launch_pair_instance(const azp_pair_args& args, const PairKArgs& k, const typename E::Params* d_params,
-                         uint32_t block_size, hipStream_t stream)
-    {
-    if (args.shift_mode == AZP_SHIFT_XPLOR)
-        return launch_pair_instance2<E, TPP, VIRIAL, SINGLE, true>(args, k, d_params, block_size, stream);
-    return launch_pair_instance2<E, TPP, VIRIAL, SINGLE, false>(args, k, d_params, block_size, stream);
-    }
-
-template<class E, bool VIRIAL, bool SINGLE>
-int launch_pair_tpp(const azp_pair_args& args, const PairKArgs& k, const typename E::Params* d_params, uint32_t tpp,
-                    uint32_t block_size, hipStream_t stream)
-    {
-    return dispatch_tpp(tpp, [&](auto t)
-        { return launch_pair_instance<E, decltype(t)::value, VIRIAL, SINGLE>(args, k, d_params, block_size, stream); });
-    }
-
-inline int validate_pair_args(const azp_pair_args* args, const void* d_params)
-    {
-    if (!args || !d_params) return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->N == 0) return 1; // nothing to do (caller returns success)
-    if (!args->d_force || !args->d_pos || !args->d_n_neigh || !args->d_nlist || !args->d_head_list || !args->d_rcutsq)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->ntypes == 0 || args->shift_mode > AZP_SHIFT_XPLOR) return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->shift_mode == AZP_SHIFT_XPLOR && !args->d_ronsq) return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->compute_virial && (!args->d_virial || args->virial_pitch < args->N)) return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->n_max < args->N) return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->block_size && (args->block_size % 64 || args->block_size > 256)) return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->range_count && (uint64_t)args->range_first + args->range_count > args->N) return AZP_ERROR_INVALID_ARGUMENT;
-    return 0;
-    }
-
 inline PairKArgs make_pair_kargs(const azp_pair_args& args)
     {
     PairKArgs k;
@@ -335,21 +352,31 @@ inline PairKArgs make_pair_kargs(const azp_pair_args& args)
     return k;
     }
 
-template<class E> int launch_pair(const azp_pair_args* args, const typename E::Params* d_params, void* stream)
+template<class X, int TPP, bool VIRIAL, bool SINGLE>
+int launch_generic_instance(const azp_pair_args& args, const typename X::KExtra& x, const typename X::Params* d_params, uint32_t block_size,
+                            hipStream_t stream)
     {
-    const int bad = validate_pair_args(args, d_params);
-    if (bad < 0) return bad;
-    if (bad > 0) return AZP_SUCCESS;
-    const PairKArgs k = make_pair_kargs(*args);
-    const uint32_t tpp = choose_tpp(*args);
-    const uint32_t bs = args->block_size ? args->block_size : 256u;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool single = (args->ntypes == 1);
-    if (args->compute_virial)
-        return single ? launch_pair_tpp<E, true, true>(*args, k, d_params, tpp, bs, s)
-                      : launch_pair_tpp<E, true, false>(*args, k, d_params, tpp, bs, s);
-    return single ? launch_pair_tpp<E, false, true>(*args, k, d_params, tpp, bs, s)
-                  : launch_pair_tpp<E, false, false>(*args, k, d_params, tpp, bs, s);
+    PairKArgs k = make_pair_kargs(args);
+    k.nblocks_padded = generic_grid(k, block_size, TPP);
+    const size_t lds = SINGLE ? 0 : sizeof(typename X::Coeff) * (size_t)args.ntypes * args.ntypes;
+    return launch_dyn_lds(pair_forces_kernel<X, TPP, VIRIAL, SINGLE>, k.nblocks_padded, block_size, TPP, lds, stream, k, x, d_params);
+    }
+
+// the generic kernel (arguments validated by the caller)
+template<class X>
+int launch_generic(const azp_pair_args& args, const typename X::KExtra& x, const typename X::Params* d_params, hipStream_t s)
+    {
+    const uint32_t bs = args.block_size ? args.block_size : 256u;
+    const bool single = (args.ntypes == 1);
+    return dispatch_tpp(choose_tpp(args), [&](auto t)
+        {
+        constexpr int TPP = decltype(t)::value;
+        if (args.compute_virial)
+            return single ? launch_generic_instance<X, TPP, true, true>(args, x, d_params, bs, s)
+                          : launch_generic_instance<X, TPP, true, false>(args, x, d_params, bs, s);
+        return single ? launch_generic_instance<X, TPP, false, true>(args, x, d_params, bs, s)
+                      : launch_generic_instance<X, TPP, false, false>(args, x, d_params, bs, s);
+        });
     }
 
 } // namespace azp

@@ -704,9 +704,11 @@ __global__ void __launch_bounds__(256, E::kTileWaves) pair_forces_tiled_kernel(c
         }
     }
 
-template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR>
-int launch_tiled_instance2(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params,
-                          hipStream_t stream, const TileDyn* dyn, const uint32_t* tile_ids = nullptr, uint32_t n_tile_ids = 0)
+// Arguments of a tile kernel (this one and xtiled.hpp's) for the tiles of tb particles a launch covers: sub-range
+// launches are rounded outwards to whole tiles (a tile computed by two launches of one step gets the later launch's
+// values: stream order); with tile_ids, those n_tile_ids tiles only. No row phases, no global displacement bound.
+inline TiledKArgs make_tiled_kargs(const PairPlan& plan, const azp_pair_args& args, const TileDyn* dyn, uint32_t tb,
+                                   const uint32_t* tile_ids = nullptr, uint32_t n_tile_ids = 0)
     {
     TiledKArgs k = {};
     k.p = make_pair_kargs(args);
@@ -717,30 +719,48 @@ int launch_tiled_instance2(const PairPlan& plan, const azp_pair_args& args, cons
     k.slice_K = plan.d_slice_K;
     k.slice_Kend = plan.d_slice_Kend;
     k.n_shells = plan_shells_for(plan, args);
+    k.bound = -1.0;
+    fill_local_bound(k, plan, args);
+    k.dyn = dyn;
+    k.slice_head = plan.d_slice_head;
+    k.cnl = plan.d_cnl;
+    const uint32_t t0 = k.p.first / tb, t1 = (k.p.end + tb - 1) / tb;
+    k.p.first = t0 * tb;
+    k.p.end = (t1 * tb < args.N) ? t1 * tb : args.N;
+    k.tile_ids = tile_ids;
+    k.n_tile_ids = n_tile_ids;
+    k.p.nblocks_padded = ((tile_ids ? n_tile_ids : t1 - t0) + 7u) & ~7u;
+    return k;
+    }
+
+// LDS variant of a launch: from the tiles of tb particles it covers (all of them unless a range is given)
+inline uint32_t plan_launch_cap(const PairPlan& plan, const azp_pair_args& args, uint32_t tb)
+    {
+    if (args.range_count == 0 || plan.h_tile_nstage.empty())
+        return plan.cap;
+    const uint32_t end = (args.range_first + args.range_count < args.N) ? args.range_first + args.range_count : args.N;
+    const uint32_t t0 = args.range_first / tb, t1 = (end + tb - 1) / tb;
+    uint32_t most = 0;
+    for (uint32_t t = t0; t < t1 && t < plan.n_tiles; ++t)
+        most = plan.h_tile_nstage[t] > most ? plan.h_tile_nstage[t] : most;
+    return plan_cap_for(most);
+    }
+
+template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR>
+int launch_tiled_instance2(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params,
+                          hipStream_t stream, const TileDyn* dyn, const uint32_t* tile_ids = nullptr, uint32_t n_tile_ids = 0)
+    {
+    TiledKArgs k = make_tiled_kargs(plan, args, dyn, plan.tile, tile_ids, n_tile_ids);
     const bool phases = tuning().row_phases != 0; // (azp_tuning_set: A/B measurements)
     k.slice_Kcore = phases ? plan.d_slice_Kphase : nullptr;
     k.slice_Ksure = (phases && plan.d_slice_Kphase) ? plan.d_slice_Kphase + plan.n_slices : nullptr;
     k.bound = (args.has_displacement_bound && args.displacement_bound >= 0.0) ? args.displacement_bound : -1.0;
     k.core_r = plan.core_r;
     k.sure_r = plan.sure_r;
-    fill_local_bound(k, plan, args);
-    k.dyn = dyn;
-    k.slice_head = plan.d_slice_head;
-    k.cnl = plan.d_cnl;
-    // sub-range launches are rounded outwards to whole tiles (a tile computed by
-    // two launches of one step gets the later launch's values: stream order)
-    const uint32_t tb = plan.tile;
-    const uint32_t t0 = k.p.first / tb, t1 = (k.p.end + tb - 1) / tb;
-    k.p.first = t0 * tb;
-    k.p.end = (t1 * tb < args.N) ? t1 * tb : args.N;
-    k.tile_ids = tile_ids;
-    k.n_tile_ids = n_tile_ids;
-    const uint32_t nblocks = ((tile_ids ? n_tile_ids : t1 - t0) + 7u) & ~7u;
-    k.p.nblocks_padded = nblocks;
     size_t lds = (size_t)AZP_TILE_STRIDE(CAP) * 24 + (SINGLE ? 0 : (size_t)CAP * 4 + 8);
     if (!SINGLE)
         lds += (sizeof(typename E::Coeff) + sizeof(double)) * (size_t)args.ntypes * args.ntypes;
-    return launch_dyn_lds(pair_forces_tiled_kernel<E, TPP, CAP, VIRIAL, SINGLE, XPLOR>, nblocks, 256, TPP, lds, stream, k, d_params);
+    return launch_dyn_lds(pair_forces_tiled_kernel<E, TPP, CAP, VIRIAL, SINGLE, XPLOR>, k.p.nblocks_padded, 256, TPP, lds, stream, k, d_params);
     }
 
 template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE>
@@ -788,18 +808,7 @@ inline int plan_split_tiles(const PairPlan& plan, hipStream_t s)
 template<class E, int TPP, bool VIRIAL, bool SINGLE>
 int launch_tiled_cap(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params, hipStream_t s, const TileDyn* dyn)
     {
-    // LDS variant: from the tiles this launch covers (all of them unless a range is given)
-    uint32_t cap = plan.cap;
-    if (args.range_count != 0 && !plan.h_tile_nstage.empty())
-        {
-        const uint32_t tb = plan.tile;
-        const uint32_t end = (args.range_first + args.range_count < args.N) ? args.range_first + args.range_count : args.N;
-        const uint32_t t0 = args.range_first / tb, t1 = (end + tb - 1) / tb;
-        uint32_t most = 0;
-        for (uint32_t t = t0; t < t1 && t < plan.n_tiles; ++t)
-            most = plan.h_tile_nstage[t] > most ? plan.h_tile_nstage[t] : most;
-        cap = plan_cap_for(most);
-        }
+    const uint32_t cap = plan_launch_cap(plan, args, plan.tile);
     if (TPP == 1 && args.range_count == 0 && cap > 1664u && tuning().split_tiles && plan.h_tile_nstage.size() == plan.n_tiles)
         {
         // a liquid: the tiles that fit the 1,664-slot variant (four workgroups per CU) first, then the rest
@@ -828,41 +837,27 @@ int launch_tiled_cap(const PairPlan& plan, const azp_pair_args& args, const type
         }
     }
 
-template<class E, bool VIRIAL, bool SINGLE>
+// the tile kernel at the plan's lanes per particle (a plan valid for these arguments: pair_auto.hpp)
+template<class E>
 int launch_tiled_tpp(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params, hipStream_t s, const TileDyn* dyn)
     {
+    const bool single = (args.ntypes == 1);
+    auto go = [&](auto t)
+        {
+        constexpr int TPP = decltype(t)::value;
+        if (args.compute_virial)
+            return single ? launch_tiled_cap<E, TPP, true, true>(plan, args, d_params, s, dyn)
+                          : launch_tiled_cap<E, TPP, true, false>(plan, args, d_params, s, dyn);
+        return single ? launch_tiled_cap<E, TPP, false, true>(plan, args, d_params, s, dyn)
+                      : launch_tiled_cap<E, TPP, false, false>(plan, args, d_params, s, dyn);
+        };
     switch (plan.tpp)
         {
-    case 1: return launch_tiled_cap<E, 1, VIRIAL, SINGLE>(plan, args, d_params, s, dyn);
-    case 2: return launch_tiled_cap<E, 2, VIRIAL, SINGLE>(plan, args, d_params, s, dyn);
-    case 4: return launch_tiled_cap<E, 4, VIRIAL, SINGLE>(plan, args, d_params, s, dyn);
+    case 1: return go(std::integral_constant<int, 1>());
+    case 2: return go(std::integral_constant<int, 2>());
+    case 4: return go(std::integral_constant<int, 4>());
     default: return AZP_ERROR_INVALID_ARGUMENT;
         }
-    }
-
-// Entry: use the plan when it is valid for these arguments, else the generic kernel.
-template<class E>
-int launch_pair_planned(azp_pair_plan* plan_, const azp_pair_args* args, const typename E::Params* d_params, void* stream,
-                        const TileDyn* dyn = nullptr)
-    {
-    if (!plan_)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    const PairPlan& plan = *reinterpret_cast<const PairPlan*>(plan_);
-    const int bad = validate_pair_args(args, d_params);
-    if (bad < 0) return bad;
-    if (bad > 0) return AZP_SUCCESS;
-    // a plan compiled from a different list is a caller bug, not a fallback case
-    if (plan.builds == 0 || plan.N != args->N || plan.nlist_ptr != args->d_nlist || plan.head_ptr != args->d_head_list)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    if (!plan.valid) // (a plan compiled from the cell list has no HOOMD-format list to fall back to)
-        return plan.from_cells ? AZP_ERROR_INVALID_ARGUMENT : launch_pair<E>(args, d_params, stream);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool single = (args->ntypes == 1);
-    if (args->compute_virial)
-        return single ? launch_tiled_tpp<E, true, true>(plan, *args, d_params, s, dyn)
-                      : launch_tiled_tpp<E, true, false>(plan, *args, d_params, s, dyn);
-    return single ? launch_tiled_tpp<E, false, true>(plan, *args, d_params, s, dyn)
-                  : launch_tiled_tpp<E, false, false>(plan, *args, d_params, s, dyn);
     }
 
 } // namespace azp

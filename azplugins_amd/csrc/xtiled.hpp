@@ -1,14 +1,13 @@
-// xtiled.hpp -- the two kernels of the pair potentials that need more than the separation
-// of a pair: the DPD thermostat (velocities + tags, src/PotentialPairDPDThermoGPUKernel.cu.inc:21-24)
-// and TwoPatchMorse (orientations, force + torque, src/AnisoPotentialPairGPUKernel.cu.inc:21-25).
-// A policy class X (XDPD in dpd_forces.hip, XTPM in aniso_forces.hip) holds a potential's
-// physics: coefficients, the per-neighbor payload, the in-range test, the pair arithmetic,
-// the reduction over lanes and the store. Both kernels call it; neither knows the potential.
+// xtiled.hpp -- the tile-staged kernel of the pair potentials that need more than the
+// separation of a pair: the DPD thermostat (velocities + tags,
+// src/PotentialPairDPDThermoGPUKernel.cu.inc:21-24) and TwoPatchMorse (orientations, force +
+// torque, src/AnisoPotentialPairGPUKernel.cu.inc:21-25). Its policy class X (XDPD in
+// dpd_forces.hip, XTPM in aniso_forces.hip) is the one the generic pair_forces_kernel
+// (pair_kernel.hpp) takes; the kernel knows no potential.
 //
-// xtiled_kernel: the tile-staged kernel. Same plan, same compiled rows as pair_tiled.hpp, one
-// lane per particle (plans with threads_per_particle = 1); per staged particle the LDS
-// additionally holds what the potential reads of a neighbor, loaded (or derived) ONCE per tile
-// instead of once per pair:
+// xtiled_kernel: same plan, same compiled rows as pair_tiled.hpp, one lane per particle
+// (plans with threads_per_particle = 1); per staged particle the LDS additionally holds what
+// the potential reads of a neighbor, loaded (or derived) ONCE per tile instead of once per pair:
 //
 //   DPD       x | y | z | vx | vy | vz | tag           52 B per slot
 //   TwoPatch  x | y | z | nx | ny | nz                 48 B per slot, n = rotate(q_j, x^):
@@ -19,10 +18,6 @@
 // holds an in-range pair in ~35 % (DPD, <n> = 34.5, 12.6 in range) of the lanes, here the
 // first ~2 chunks are in range in every lane and the rest of the row is skipped by a
 // wave-uniform test (or never walked: displacement bound, as in pair_tiled.hpp).
-//
-// xgeneric_kernel: the generic kernel on the HOOMD-format list, for explicit
-// threads_per_particle, no auto plan, and lists that cannot be tiled. The mapping of
-// pair_forces_kernel (pair_kernel.hpp); the payload is loaded per in-range pair.
 #pragma once
 
 #include <type_traits>
@@ -61,12 +56,12 @@ __global__ void __launch_bounds__(256, X::kMinWaves) xtiled_kernel(const TiledKA
 
     Coeff c0;
     if (SINGLE)
-        c0 = to_uniform(X::prepare(params[0], a.p.rcutsq[0], x, a.p.shift_mode));
+        c0 = to_uniform(X::prepare(params, a.p, 0, x));
     else
         {
         const uint32_t ntp = a.p.ntypes * a.p.ntypes;
         for (uint32_t t = tid; t < ntp; t += 256)
-            s_coeff[t] = X::prepare(params[t], a.p.rcutsq[t], x, a.p.shift_mode);
+            s_coeff[t] = X::prepare(params, a.p, t, x);
         }
 
     // ---- stage ----
@@ -268,31 +263,11 @@ template<class X, int CAP, bool VIRIAL, bool SINGLE>
 int launch_xtiled_instance(const PairPlan& plan, const azp_pair_args& args, const typename X::KExtra& x, const typename X::Params* d_params,
                            hipStream_t stream, const TileDyn* dyn)
     {
-    TiledKArgs k = {};
-    k.p = make_pair_kargs(args);
-    k.tile_nstage = plan.d_tile_nstage;
-    k.tile_head = plan.d_tile_head;
-    k.stage_idx = plan.d_stage_idx;
-    k.perm = plan.balanced ? plan.d_perm : nullptr;
-    k.slice_K = plan.d_slice_K;
-    k.slice_Kend = plan.d_slice_Kend;
-    k.n_shells = plan_shells_for(plan, args);
-    k.slice_Kcore = k.slice_Ksure = nullptr; // (row phases: pair_tiled.hpp only)
-    k.bound = -1.0;
-    k.core_r = k.sure_r = 0.f;
-    fill_local_bound(k, plan, args);
-    k.dyn = dyn;
-    k.slice_head = plan.d_slice_head;
-    k.cnl = plan.d_cnl;
-    const uint32_t t0 = k.p.first / 256u, t1 = (k.p.end + 255u) / 256u;
-    k.p.first = t0 * 256u;
-    k.p.end = (t1 * 256u < args.N) ? t1 * 256u : args.N;
-    const uint32_t nblocks = (t1 - t0 + 7u) & ~7u;
-    k.p.nblocks_padded = nblocks;
+    const TiledKArgs k = make_tiled_kargs(plan, args, dyn, 256);
     size_t lds = xtiled_lds_slots<X, SINGLE>(CAP);
     if (!SINGLE)
         lds += sizeof(typename X::Coeff) * (size_t)args.ntypes * args.ntypes;
-    return launch_dyn_lds(xtiled_kernel<X, CAP, VIRIAL, SINGLE>, nblocks, 256, 1, lds, stream, k, x, d_params);
+    return launch_dyn_lds(xtiled_kernel<X, CAP, VIRIAL, SINGLE>, k.p.nblocks_padded, 256, 1, lds, stream, k, x, d_params);
     }
 
 // true when the plan can drive the xtiled kernel for these arguments
@@ -305,16 +280,7 @@ template<class X, bool VIRIAL, bool SINGLE>
 int launch_xtiled_cap(const PairPlan& plan, const azp_pair_args& args, const typename X::KExtra& x, const typename X::Params* d_params, hipStream_t s,
                       const TileDyn* dyn)
     {
-    uint32_t cap = plan.cap;
-    if (args.range_count != 0 && !plan.h_tile_nstage.empty())
-        {
-        const uint32_t end = (args.range_first + args.range_count < args.N) ? args.range_first + args.range_count : args.N;
-        const uint32_t t0 = args.range_first / 256u, t1 = (end + 255u) / 256u;
-        uint32_t most = 0;
-        for (uint32_t t = t0; t < t1 && t < plan.n_tiles; ++t)
-            most = plan.h_tile_nstage[t] > most ? plan.h_tile_nstage[t] : most;
-        cap = plan_cap_for(most);
-        }
+    const uint32_t cap = plan_launch_cap(plan, args, 256);
     switch (cap)
         {
     case 1024: return launch_xtiled_instance<X, 1024, VIRIAL, SINGLE>(plan, args, x, d_params, s, dyn);
@@ -334,135 +300,5 @@ int launch_xtiled(const PairPlan& plan, const azp_pair_args& args, const typenam
     if (args.compute_virial)
         return single ? launch_xtiled_cap<X, true, true>(plan, args, x, d_params, s, dyn) : launch_xtiled_cap<X, true, false>(plan, args, x, d_params, s, dyn);
     return single ? launch_xtiled_cap<X, false, true>(plan, args, x, d_params, s, dyn) : launch_xtiled_cap<X, false, false>(plan, args, x, d_params, s, dyn);
-    }
-// TPP lanes per particle, each striding the row (entries sub, sub + TPP, ...) with the next index
-// prefetched; coefficients in registers (one type) or LDS; the minimum image skipped by waves whose
-// particles are all interior
-template<class X, int TPP, bool VIRIAL, bool SINGLE>
-__global__ void __launch_bounds__(256) xgeneric_kernel(const PairKArgs a, const typename X::KExtra x, const typename X::Params* __restrict__ params)
-    {
-    typedef typename X::Coeff Coeff;
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    Coeff* s_coeff = reinterpret_cast<Coeff*>(s_raw);
-    Coeff c0;
-    if (SINGLE)
-        c0 = X::prepare(params[0], a.rcutsq[0], x, a.shift_mode);
-    else
-        {
-        const uint32_t ntp = a.ntypes * a.ntypes;
-        for (uint32_t t = threadIdx.x; t < ntp; t += blockDim.x)
-            s_coeff[t] = X::prepare(params[t], a.rcutsq[t], x, a.shift_mode);
-        __syncthreads();
-        }
-
-    const uint32_t block = xcd_remap(blockIdx.x, a.nblocks_padded);
-    const uint32_t idx = a.first + block * (blockDim.x / TPP) + threadIdx.x / TPP;
-    const uint32_t sub = threadIdx.x % TPP;
-    const bool active = idx < a.end;
-
-    uint32_t n = 0;
-    uint64_t head = 0;
-    double3 pi = make_double3(0.0, 0.0, 0.0);
-    int typei = 0;
-    typename X::Own own = {};
-    if (active)
-        {
-        n = a.n_neigh[idx];
-        head = a.head_list[idx];
-        const double4 p = load_scalar4(a.pos, idx);
-        pi = make_double3(p.x, p.y, p.z);
-        typei = type_from_w(p.w);
-        X::load_own(x, idx, own);
-        }
-    typename X::Acc acc;
-    X::zero(acc);
-    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-
-    bool wrap = true;
-    if (a.r_list_max > 0.0 && !a.box.triclinic)
-        {
-        const bool interior = !active || is_interior(a.box, pi.x, pi.y, pi.z, a.r_list_max);
-        wrap = !__all(interior);
-        }
-    auto walk = [&](auto wrap_tag)
-        {
-        constexpr bool WRAP = decltype(wrap_tag)::value;
-        const uint32_t* __restrict__ row = a.nlist + head;
-        uint32_t k = sub;
-        uint32_t j = (k < n) ? row[k] : 0u;
-        while (k < n)
-            {
-            const uint32_t kn = k + TPP;
-            const uint32_t jn = (kn < n) ? row[kn] : 0u;
-            const double4 pj = load_scalar4(a.pos, j);
-            double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
-            if (WRAP)
-                min_image(a.box, dx, dy, dz);
-            const double rsq = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-            Coeff c;
-            if (SINGLE)
-                c = c0;
-            else
-                c = s_coeff[(uint32_t)typei * a.ntypes + (uint32_t)type_from_w(pj.w)];
-            if (X::in_range(c, rsq))
-                {
-                double ext[X::kExtra];
-                uint32_t tagj = 0;
-                X::load_extra(x, j, ext, tagj);
-                X::template pair<VIRIAL>(c, x, own, dx, dy, dz, rsq, ext, tagj, acc, v);
-                }
-            k = kn;
-            j = jn;
-            }
-        };
-    if (wrap)
-        walk(std::true_type());
-    else
-        walk(std::false_type());
-
-    X::template reduce<TPP>(acc);
-    if (VIRIAL)
-        {
-#pragma unroll
-        for (int cidx = 0; cidx < 6; ++cidx)
-            v[cidx] = group_sum<TPP>(v[cidx]);
-        }
-    if (active && sub == 0)
-        {
-        X::store(acc, a, x, idx);
-        if (VIRIAL)
-            {
-#pragma unroll
-            for (int cidx = 0; cidx < 6; ++cidx)
-                a.virial[(uint64_t)cidx * a.virial_pitch + idx] = 0.5 * v[cidx];
-            }
-        }
-    }
-
-template<class X, int TPP, bool VIRIAL, bool SINGLE>
-int launch_xgeneric_instance(const azp_pair_args& args, const typename X::KExtra& x, const typename X::Params* d_params, uint32_t block_size,
-                             hipStream_t stream)
-    {
-    PairKArgs k = make_pair_kargs(args);
-    k.nblocks_padded = generic_grid(k, block_size, TPP);
-    const size_t lds = SINGLE ? 0 : sizeof(typename X::Coeff) * (size_t)args.ntypes * args.ntypes;
-    return launch_dyn_lds(xgeneric_kernel<X, TPP, VIRIAL, SINGLE>, k.nblocks_padded, block_size, TPP, lds, stream, k, x, d_params);
-    }
-
-// the generic kernel (arguments validated by the caller)
-template<class X>
-int launch_xgeneric(const azp_pair_args& args, const typename X::KExtra& x, const typename X::Params* d_params, hipStream_t s)
-    {
-    const uint32_t bs = args.block_size ? args.block_size : 256u;
-    const bool single = (args.ntypes == 1);
-    return dispatch_tpp(choose_tpp(args), [&](auto t)
-        {
-        constexpr int TPP = decltype(t)::value;
-        if (args.compute_virial)
-            return single ? launch_xgeneric_instance<X, TPP, true, true>(args, x, d_params, bs, s)
-                          : launch_xgeneric_instance<X, TPP, true, false>(args, x, d_params, bs, s);
-        return single ? launch_xgeneric_instance<X, TPP, false, true>(args, x, d_params, bs, s)
-                      : launch_xgeneric_instance<X, TPP, false, false>(args, x, d_params, bs, s);
-        });
     }
 } // namespace azp

@@ -46,6 +46,8 @@ PAIR_PARAMS = {
     "Colloid": None,  # below
     "DPDConservative": lambda i, j: dict(A=25.0 - 3 * (i + j), gamma=4.5, s=0.5),
 }
+# LDS bytes per type pair of the generic kernel: the evaluator's coefficients and r_on^2
+PAIR_LDS_BYTES = {"PerturbedLennardJones": 104, "Hertz": 40, "ExpandedYukawa": 48, "Colloid": 168, "DPDConservative": 56}
 
 
 def _params_table(oracle, name, T):
@@ -96,6 +98,14 @@ def test_pair_parity(oracle, name, T, mode):
     # without the virial the force/energy must be bit-identical to the virial build
     f2 = H.gpu_pair_forces(name, pos, (L,), nl_full, params, r_cut, r_on, mode, ntypes=T, virial=False)
     assert np.array_equal(f2, f_gpu)
+    if T > 1:
+        # every lanes-per-particle count of the generic kernel; coefficients (and r_on^2) in LDS
+        for tpp in GENERIC_TPP:
+            f_t, v_t = H.gpu_pair_forces(name, pos, (L,), nl_full, params, r_cut, r_on, mode, ntypes=T, virial=True, tpp=tpp)
+            _assert_generic_launch(tpp, PAIR_LDS_BYTES[name] * T * T)
+            assert_close(f_t[:, :3], f_ref[:, :3], what="force tpp=%d" % tpp)
+            assert_close(f_t[:, 3], f_ref[:, 3], what="energy tpp=%d" % tpp)
+            assert_close(v_t, v_ref, what="virial tpp=%d" % tpp)
 
 
 @pytest.mark.parametrize("tpp", [1, 2, 4, 8, 16, 32])
