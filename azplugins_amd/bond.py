@@ -25,7 +25,6 @@ class Bond(Force):
 
     def _mark_dirty(self):
         self._tables = None
-        self._computed_generation = None
 
     def _readback(self, key):
         """After attaching, ``params[...]`` returns what the C++ object holds (HOOMD:
@@ -112,7 +111,6 @@ class Bond(Force):
             self._flag_host.copy_(self._flags, non_blocking=True)
         self._flag_pending = torch.cuda.Event()
         self._flag_pending.record(self._flag_side)
-        self._computed_generation = st.position_generation
         if not self.defer_flag_check:
             self.check_flags(wait=True)
 

@@ -493,28 +493,14 @@ def bench_main(args, rank, world, local_rank):
     # The list is static in this benchmark, so the argument structs of the force launches are built ONCE (what
     # Pair.compute assembles field by field at every call: ~15 us of Python per launch, as much as a rank's kernel
     # takes at 8-way strong scaling) and a step is the bare C-ABI calls.
-    import ctypes as C
-
     lib = azp._lib.lib()
     main_stream = main.cuda_stream
 
     def bare_launch(first, count):
-        if count:
-            pot.compute(0, particle_range=(first, count))  # (plan compiled, buffers sized)
-        else:
-            pot.compute(0)
-        a = pot._pair_args(for_launch=True)
-        a.range_first, a.range_count = int(first), int(count)
-        planned = pot.use_plan and pot._planned_entry is not None
-        if planned:
-            pot._prepare_plan(a, main_stream)
-        cargs = pot._wrap_args(a, 0)
-        params = pot._tables["params"].data_ptr()
-        if planned:
-            fn, handle = getattr(lib, pot._planned_entry), pot._plan.handle
-            return lambda: azp._lib.check(fn(handle, C.byref(cargs), params, main_stream), pot._planned_entry), cargs
-        fn = getattr(lib, pot._entry)
-        return lambda: azp._lib.check(fn(C.byref(cargs), params, main_stream), pot._entry), cargs
+        pot.compute(0, particle_range=(first, count) if count else None)  # (plan compiled, buffers sized)
+        entry, args = pot._prepare_launch(main_stream, 0, (first, count))
+        fn = getattr(lib, entry)
+        return lambda: azp._lib.check(fn(*args), entry), args
 
     if overlap:
         launch_int, keep_a = bare_launch(0, n_int)

@@ -345,4 +345,4 @@ class DeviceDomain:
         if getattr(state, "bond_tags", None) is not None:
             state.relocalize_bonds()  # bond table and exclusions by local index: every index changed
         state.position_generation += 1
-        state.order_generation = getattr(state, "order_generation", 0) + 1  # every index changed: the list must be rebuilt
+        state.order_generation += 1  # every index changed: the list must be rebuilt

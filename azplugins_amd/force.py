@@ -127,7 +127,6 @@ class Force:
         self._virial = None
         self._torque = None
         self.compute_virial = False
-        self._computed_generation = None
 
     @property
     def _attached(self):
@@ -144,7 +143,6 @@ class Force:
         self._torque = torch.zeros((N, 4), dtype=torch.float64, device=dev)
         self._virial = torch.zeros((6, N), dtype=torch.float64, device=dev)
         self._dirty = True
-        self._computed_generation = None
 
     def _require(self):
         if not self._attached:

@@ -14,6 +14,11 @@ import numpy as np
 from . import _lib
 
 
+def _padded_rows(max_row):
+    """Row capacity for rows of up to ``max_row`` entries: ~6 % head room, a multiple of 8 entries (32-B aligned rows)."""
+    return (int(max_row * 1.06) + 4 + 7) // 8 * 8
+
+
 class NeighborList:
     """Base: holds the device arrays in HOOMD's layout."""
 
@@ -30,6 +35,7 @@ class NeighborList:
         self._n_pairs = 0         # listed pairs = sum(n_neigh)
         self._max_neigh = 0
         self._row_capacity = 0    # > 0: rows of fixed capacity (single-pass rebuilds)
+        self._r_cut_max = 0.0
         self.single_pass = True
         # fused = True: when the list has ONE consumer and that consumer runs the tile kernels, no
         # HOOMD-format list is built at all -- the consumer compiles its tile plan straight from
@@ -37,24 +43,57 @@ class NeighborList:
         # in lazily if something asks for them
         self.fused = True
         self._fused_active = False
+        self._fused_counts_ready = False  # fused mode: n_neigh holds the row lengths of the consumer's plan compile
         self._stats_known = True
         self._consumer_version = 0        # bumped when a consumer's r_cut matrix changes
         self._built_consumer_version = None
+        self._order_generation = 0        # State.order_generation the list was built for
         # domain-decomposed runs (azplugins_amd.domain): the rebuild decision is collective
         # (reduce_flag: bool -> bool, an all-reduce over the ranks) and particles migrate /
         # ghosts are re-selected before the list is rebuilt (before_rebuild(state))
         self.reduce_flag = None
         self.before_rebuild = None
+        self._compact = False
+        self._cells = self._keep = self._pos_at_build = self._box_at_build = None  # the bins of the last build
+        self._rl_max = 0.0
+        self._rlistsq_key = self._rlistsq_dev = self._head_key = self._head_fixed = None
+        # the distance check (begin_check): its ring of flag rows, side stream, readback row and events; what it found
+        self._flag = self._side = self._host_row = self._done_events = None
+        self._flag_i = 0
+        self._verdict = None              # (position generation, rebuild?) of the last check
+        self._disp, self._disp_generation = 0.0, None
+        self._disp_arr = self._disp_arr_generation = None
+        # fused mode (compile_plan): learned row capacity, failed compiles in a row, the particle sort it asks for
+        self._plan_row_capacity = self._fused_failures = self._half_failures = 0
+        self._fused_auto_off = self._sort_wanted = False
+        self._member_cells_key, self._member_cells_sorted = None, 0  # largest member-cell count after the last sort
 
     # -- consumers (pair potentials) register their r_cut matrices ---------
-    def _add_consumer(self, force):
+    def add_consumer(self, force):
         if force not in self._consumers:
             self._consumers.append(force)
-            self._consumers_changed()
+            self.consumers_changed()
 
-    def _consumers_changed(self):
+    def consumers_changed(self):
         """A consumer was added or changed its r_cut: the next compute rebuilds the list."""
         self._consumer_version += 1
+
+    def set_buffer(self, buffer):
+        """A new r_buff: rebuild the list, and the consumers' tables that depend on it (the plan's inner-radius hint)."""
+        self.buffer = buffer
+        self.consumers_changed()
+        for f in self._consumers:
+            f._mark_dirty()
+
+    @property
+    def fused_active(self):
+        """This build has no HOOMD-format list of its own: its sole consumer compiles its plan from the cells."""
+        return self._fused_active
+
+    @property
+    def has_hoomd_rows(self):
+        """The HOOMD-format rows (nlist / head_list) of this build exist (fused mode fills them on first use)."""
+        return self._nlist is not None
 
     def _r_cut_matrix(self, ntypes):
         rc = np.zeros((ntypes, ntypes))
@@ -89,7 +128,7 @@ class NeighborList:
         if not self._stats_known and self.n_neigh is not None:
             import torch
 
-            if self._fused_active and not getattr(self, "_fused_counts_ready", False):
+            if self._fused_active and not self._fused_counts_ready:
                 self._materialize()  # nobody has compiled a plan from the cells yet: count the classic way
                 return
 
@@ -127,6 +166,17 @@ class Cell(NeighborList):
     # callers without the framework, tested for equality with the stable sort.
     native_binning = {"0": False, "1": True}.get(os.environ.get("AZP_NATIVE_BINNING", ""), None)  # None: when the cells number more than 2^16 (the framework sort then needs four radix passes)
 
+    @property
+    def sort_wanted(self):
+        """The members of some tile have drifted apart: a particle sort would let the plan come from the cells again."""
+        return self._sort_wanted
+
+    def particles_sorted(self):
+        """A particle sort ran: the request is met, and fused mode gets its chances back."""
+        self._sort_wanted, self._fused_failures = False, 0
+        if self._fused_auto_off:
+            self.fused, self._fused_auto_off = True, False
+
     def compute(self, state, force=False, compact=False):
         """Rebuild only when needed (HOOMD's criterion): never built, forced, or some
         particle moved farther than buffer / 2 since the last build.
@@ -136,16 +186,15 @@ class Cell(NeighborList):
         protocol: fixed-capacity rows, rebuilt when a row overflows);
         ``compact=True`` forces exact rows."""
         self._compact = compact
-        if getattr(state, "order_generation", 0) != getattr(self, "_order_generation", 0):
-            force = True  # the particles were re-indexed (ParticleSorter): every stored index is stale
-        if self._built_consumer_version != self._consumer_version:
-            force = True  # built for another r_cut matrix
+        if state.order_generation != self._order_generation or self._built_consumer_version != self._consumer_version:
+            force = True  # re-indexed particles (ParticleSorter: every stored index is stale) or a changed r_cut matrix
         if not force and self.built:
             if self._built_generation == state.position_generation:
                 return
-            v = getattr(self, "_verdict", None)
-            # (a caller that queued its kernel behind the check -- Pair._compute_speculative -- has the verdict already)
-            moved = v[1] if (v is not None and v[0] == state.position_generation) else self._moved_too_far(state)
+            v = self._verdict
+            # (a caller that queued its kernel behind the check -- Pair._compute_speculative -- has the verdict already;
+            # else HOOMD's distance check: one kernel and a 16-byte readback)
+            moved = v[1] if (v is not None and v[0] == state.position_generation) else self.end_check(self.begin_check(state))
             if self.reduce_flag is not None:
                 moved = bool(self.reduce_flag(moved))
             if not moved:
@@ -156,10 +205,12 @@ class Cell(NeighborList):
         self._build(state)
         self._built_generation = state.position_generation
 
-    def _moved_too_far(self, state):
-        """One kernel + an 16-byte readback (HOOMD's distance check); also records the
-        largest displacement since the build (``displacement_bound``)."""
-        return self.end_check(self.begin_check(state))
+    def allows_speculative_launch(self, state):
+        """A consumer may queue its kernel behind this step's distance check before the verdict is in: the list holds
+        for the current consumers and particle order, a check is due, and no collective decides the rebuild."""
+        return (self.n_neigh is not None and self.reduce_flag is None and self.before_rebuild is None
+                and self._built_consumer_version == self._consumer_version and self._built_generation != state.position_generation
+                and state.order_generation == self._order_generation)
 
     def begin_check(self, state):
         """Queue the distance check on the current stream and its 16-byte readback on a side stream (ordered after
@@ -169,11 +220,12 @@ class Cell(NeighborList):
         import torch
 
         # [flag, max |dx|^2 bits] per check, a ring of 64 rows zeroed once per 64 checks (not a fill kernel per step)
-        if getattr(self, "_flag", None) is None or self._flag.device != state.pos.device:
+        if self._flag is None or self._flag.device != state.pos.device:
             self._flag = torch.zeros((64, 2), dtype=torch.int64, device=state.pos.device)
             self._flag_i = 0
             self._side = torch.cuda.Stream(device=state.pos.device)
             self._host_row = torch.zeros(2, dtype=torch.int64).pin_memory()
+            self._done_events = [torch.cuda.Event() for _ in range(4)]  # (recorded and waited for within one step)
         if self._flag_i == 64:
             self._flag.zero_()
             self._flag_i = 0
@@ -183,16 +235,13 @@ class Cell(NeighborList):
         stream = _lib.raw_stream(state.device)
         # every particle's own displacement next to the maximum: the tile kernels can take the maximum over what a
         # tile stages (azp_pair_args.d_displacement) instead of the global one
-        if getattr(self, "_disp_arr", None) is None or self._disp_arr.shape[0] != state.n_max or self._disp_arr.device != state.pos.device:
+        if self._disp_arr is None or self._disp_arr.shape[0] != state.n_max or self._disp_arr.device != state.pos.device:
             self._disp_arr = torch.zeros(state.n_max, dtype=torch.float32, device=state.pos.device)
         _lib.check(_lib.lib().azp_nlist_displacements(state.n_max, state.pos.data_ptr(), self._pos_at_build.data_ptr(),
                                                       C.byref(box), (0.5 * self.buffer) ** 2, row.data_ptr(),
                                                       row.data_ptr() + 8, self._disp_arr.data_ptr(), stream),
                    "azp_nlist_displacements")
-        ring = self.__dict__.get("_done_events")
-        if ring is None:
-            ring = self._done_events = [torch.cuda.Event() for _ in range(4)]  # (recorded and waited for within one step)
-        done = ring[self._flag_i & 3]
+        done = self._done_events[self._flag_i & 3]
         done.record()
         with torch.cuda.stream(self._side):
             self._side.wait_event(done)
@@ -200,26 +249,29 @@ class Cell(NeighborList):
         return dict(flag_ptr=row.data_ptr(), bits_ptr=row.data_ptr() + 8, generation=state.position_generation, row=row)
 
     def end_check(self, token):
-        """Wait for the check of ``begin_check`` (not for anything queued after it); True: rebuild."""
+        """Wait for the check of ``begin_check`` (not for anything queued after it); True: rebuild. A verdict of no
+        rebuild that no collective has to confirm makes the list current for the checked positions."""
         self._side.synchronize()
         flag, bits = self._host_row.tolist()
+        gen = token["generation"]
         self._disp = float(np.sqrt(np.array([bits], dtype=np.int64).view(np.float64)[0]))
-        self._disp_generation = token["generation"]
-        self._disp_arr_generation = token["generation"]
-        self._verdict = (token["generation"], bool(flag))
+        self._disp_generation = self._disp_arr_generation = gen
+        self._verdict = (gen, bool(flag))
+        if not flag and self.reduce_flag is None:
+            self._built_generation = gen
         return bool(flag)
 
     def displacement_bound(self, state):
         """Largest distance any particle has moved since the list was built, if known
         for the current positions (else None)."""
-        if getattr(self, "_disp_generation", None) == state.position_generation:
+        if self._disp_generation == state.position_generation:
             return self._disp
         return None
 
     def displacements(self, state):
         """Per-particle displacements since the list was built (float32 device tensor of n_max upper
         bounds), if known for the current positions (else None)."""
-        if getattr(self, "_disp_arr_generation", None) == state.position_generation and getattr(self, "_disp_arr", None) is not None:
+        if self._disp_arr_generation == state.position_generation and self._disp_arr is not None:
             return self._disp_arr
         return None
 
@@ -240,7 +292,6 @@ class Cell(NeighborList):
     def _build(self, state):
         import torch
 
-        l = _lib.lib()
         dev = state.device
         ntypes = len(state.types)
         rc = self._r_cut_matrix(ntypes)
@@ -268,7 +319,7 @@ class Cell(NeighborList):
         a.ntypes = ntypes
         # (kept across rebuilds while the cutoffs stand: a host-to-device copy from pageable memory waits for the stream)
         key = (self._consumer_version, self.buffer, str(dev), ntypes)
-        if getattr(self, "_rlistsq_key", None) != key:
+        if self._rlistsq_key != key:
             self._rlistsq_dev = torch.from_numpy(np.ascontiguousarray((rl * rl).reshape(-1))).to(dev)
             self._rlistsq_key = key
         rlistsq = self._rlistsq_dev
@@ -293,13 +344,14 @@ class Cell(NeighborList):
         self._cells = a
         self._keep = (rlistsq, bins, keep)
         self._pos_at_build = state.pos[:n_total].clone()
+        a.d_pos = self._pos_at_build.data_ptr()  # (the bins stand for these positions from here on)
         self._nlist, self._head_list, self._size = None, None, 0
         self._fused_counts_ready = False
         if self._fused_active:
             self._stats_known = False  # row lengths come from the consumer's plan compile
         else:
             self._fill(stream)
-        self._order_generation = getattr(state, "order_generation", 0)
+        self._order_generation = state.order_generation
         self._built_consumer_version = self._consumer_version
         self._disp, self._disp_generation = 0.0, state.position_generation
         self.num_builds += 1
@@ -315,7 +367,7 @@ class Cell(NeighborList):
 
     def _half_cells_wanted(self, box, rl_max, n_total):
         mode = self.half_cells
-        if mode <= 0 or getattr(self, "_half_failures", 0) >= 2:
+        if mode <= 0 or self._half_failures >= 2:
             return False
         L = box.L
         dims = [max(int(np.floor(L[k] / (0.5 * rl_max))), 1) for k in range(3)]
@@ -369,7 +421,7 @@ class Cell(NeighborList):
         _lib.check(l.azp_nlist_cell_bounds(C.byref(a), stream), "azp_nlist_cell_bounds")
         return (cell_of, cell_sorted, order, cell_start)
 
-    def rebin_full(self):
+    def _rebin_full(self):
         """Half-width cells did not work out for this build (a consumer's plan compile refused them, or somebody needs
         the HOOMD-format list): bin the same positions again into cells of the full list radius."""
         import torch
@@ -377,25 +429,65 @@ class Cell(NeighborList):
         a = self._cells
         if a.cell_subdivision != 2:
             return
-        a.d_pos = self._pos_at_build.data_ptr()
         dev = self._pos_at_build.device
         bins = self._bin(a, self._box_at_build, self._rl_max, a.n_total, 1, dev, torch.cuda.current_stream(dev).cuda_stream)
         self._keep = (self._keep[0], bins, self._keep[2])
 
     def _fused_eligible(self):
-        if not self.fused or getattr(self, "_compact", False) or len(self._consumers) != 1:
-            return False
-        c = self._consumers[0]
-        return bool(getattr(c, "use_plan", False) and getattr(c, "_planned_entry", None)
-                    and getattr(c, "threads_per_particle", 0) in (0, 1) and getattr(c, "use_fused_plan", True))
+        return bool(self.fused and not self._compact and len(self._consumers) == 1 and self._consumers[0].takes_plan_from_cells())
+
+    def compile_plan(self, plan, pair_args, stream):
+        """Fused mode: compile the consumer's tile plan (``_lib.PairPlan``, for its azp_pair_args) straight from the
+        bins of this build, with the row capacity the last compile learned (160 at first); returns the plan's info. A
+        plan that is not valid leaves the list out of fused mode, with its HOOMD-format rows."""
+        cap = self._plan_row_capacity or 160
+        for _ in range(4):
+            plan.build_from_cells(self.cells_args(cap), pair_args, stream)
+            info = plan.info()
+            if info["valid"]:
+                if self._cells.cell_subdivision == 2:
+                    self._half_failures = 0
+                break
+            if info["invalid_reason"] == 3:
+                cap = _padded_rows(info["max_row"])  # a row overflowed: longer rows (HOOMD's protocol)
+            elif self._cells.cell_subdivision == 2:
+                # half-width cells refused (a tile's members too spread out, a very dense run of cells): bin the
+                # same positions into cells of the full list radius and compile from those
+                self._half_failures += 1
+                self._rebin_full()
+            else:
+                break
+        if info["valid"]:
+            self._fused_failures = 0
+            # the members of the tiles drift apart between two particle sorts; past 128 cells under one tile the
+            # compile is refused: ask for a sort when that comes near (and the count has grown since the last sort)
+            mc = int(info.get("max_member_cells", 0))
+            if self._member_cells_key != self._order_generation:
+                self._member_cells_key, self._member_cells_sorted = self._order_generation, mc
+            if mc > 108 and mc > 1.15 * self._member_cells_sorted:
+                self._sort_wanted = True
+            self._plan_row_capacity = max(_padded_rows(info["max_row"]), 32)
+            self._fused_counts_ready = True
+            return info
+        # particles not spatially sorted / a tile stages too much: the list-based path. A list whose tiles fail twice
+        # in a row (e.g. the thin boundary shells of a decomposed DPD fluid: 256 particles in more than 128 cells)
+        # stops trying at every rebuild (until a particle sort: particles_sorted)
+        self._fused_failures += 1
+        if self._fused_failures >= 2:
+            self.fused = False
+            self._fused_auto_off = True
+        if info["invalid_reason"] in (4, 5):
+            # the members of some tile have drifted apart (a fast-diffusing fluid between two particle sorts):
+            # ask for a sort now rather than at the sorter's next period
+            self._sort_wanted = True
+        self.leave_fused_mode()
+        return info
 
     def cells_args(self, row_capacity):
         """The binned particles of the last build as azp_nlist_args (fused plan compile). Positions:
         the ones the bins were made from."""
-        a = self._cells
-        a.d_pos = self._pos_at_build.data_ptr()
-        a.row_capacity = int(row_capacity)
-        return a
+        self._cells.row_capacity = int(row_capacity)
+        return self._cells
 
     def leave_fused_mode(self):
         """The consumer could not compile its plan from the cells (unsorted particles, very long
@@ -408,9 +500,7 @@ class Cell(NeighborList):
         if self._nlist is None and self.n_neigh is not None:
             import torch
 
-            self.rebin_full()
-            a = self._cells
-            a.d_pos = self._pos_at_build.data_ptr()
+            self._rebin_full()
             self._fill(torch.cuda.current_stream(self._pos_at_build.device).cuda_stream)
 
     def _fill(self, stream):
@@ -424,8 +514,10 @@ class Cell(NeighborList):
         dev = n_neigh.device
         done = False
         cap = self._row_capacity
-        if self.single_pass and cap > 0 and N and not getattr(self, "_compact", False):
-            head = self._head_cache(N, cap, dev)
+        if self.single_pass and cap > 0 and N and not self._compact:
+            if self._head_key != (N, cap, str(dev)):  # (rows of fixed capacity: the same heads until N or cap change)
+                self._head_key, self._head_fixed = (N, cap, str(dev)), torch.arange(N, dtype=torch.int64, device=dev) * cap
+            head = self._head_fixed
             size = N * cap
             nlist = torch.empty(size, dtype=torch.int32, device=dev)
             flag = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -450,15 +542,5 @@ class Cell(NeighborList):
             _lib.check(l.azp_nlist_fill(C.byref(a), stream), "azp_nlist_fill")
         self._max_neigh, self._n_pairs = int(stats[0]), int(stats[1])
         self._stats_known = True
-        # next build: rows with ~6 % head room, multiple of 8 entries (32-B aligned rows)
-        self._row_capacity = (int(self._max_neigh * 1.06) + 4 + 7) // 8 * 8
+        self._row_capacity = _padded_rows(self._max_neigh)  # (next build)
         self._head_list, self._nlist, self._size = head, nlist, size
-
-    def _head_cache(self, N, cap, dev):
-        import torch
-
-        key = (N, cap, str(dev))
-        if getattr(self, "_head_key", None) != key:
-            self._head_fixed = torch.arange(N, dtype=torch.int64, device=dev) * cap
-            self._head_key = key
-        return self._head_fixed

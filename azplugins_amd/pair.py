@@ -49,14 +49,17 @@ class Pair(Force):
         self.plan_bank_order = None     # None: bank-aware rows only for long-lived lists (below); True / False: always / never
         self.use_fused_plan = True      # sole consumer of its list: compile the plan straight from the binned particles
         self.use_speculative_launch = True  # queue the force kernel behind the list's distance check (_compute_speculative)
+        self._plan = None               # _lib.PairPlan (created by the first compile)
+        self._plan_builds = None        # _plan_key() the plan was compiled for (None: recompile at the next launch)
         self._plan_valid = False
-        self._plan_ids = None
-        self._plan = None
-        self._plan_builds = None
+        self._plan_ids = None           # (list_id, head_id) of a plan compiled from the cells: the plan is its own list
+        self._plan_disp0 = None         # displacement bound of the list's positions when the plan was compiled
+        self._calls_since_plan = None   # force calls the plan on hand has served (None: no plan compiled yet)
+        self._spec_cache = None         # (signature, box struct, pair args) of the last speculative launch
         self._tables = None
         self._cpp = None            # the _azplugins C++ object (created on attach)
         self._cpp_synced = False
-        nlist._add_consumer(self)
+        nlist.add_consumer(self)
 
     # -- mode ----------------------------------------------------------------
     @property
@@ -73,7 +76,6 @@ class Pair(Force):
     def _mark_dirty(self):
         self._tables = None
         self._cpp_synced = False
-        self._computed_generation = None
         # the tile plan orders and classifies rows against the cutoffs / inner radii it was
         # built with: recompile it with the new tables
         self._plan_builds = None
@@ -82,7 +84,7 @@ class Pair(Force):
         """HOOMD rebuilds the neighbor list when a consumer's r_cut matrix changes: the
         list on hand was built for the old r_cut + buffer."""
         self._mark_dirty()
-        self.nlist._consumers_changed()
+        self.nlist.consumers_changed()
 
     # -- raw parameter structs (host side of the C ABI) ------------------------
     def _pack(self, d):
@@ -125,9 +127,6 @@ class Pair(Force):
                 self._cpp.setROn(a, b, self.r_on[(a, b)])
         self._cpp.mode = self._mode
         self._cpp_synced = True
-
-    def _types(self):
-        return self._state.types if self._attached else None
 
     def _r_cut_matrix(self):
         self._require()
@@ -178,11 +177,15 @@ class Pair(Force):
         tile plan lists such pairs first. 0 = no such branch."""
         return 0.0
 
-    def _pair_args(self, for_launch=False):
-        """azp_pair_args for the current state. Outside a launch the HOOMD-format list is always
-        there (a fused list is materialized first): the struct can be handed to any entry point."""
-        st = self._state
-        nl = self.nlist
+    def takes_plan_from_cells(self):
+        """The neighbor list's question at a build, when this potential is its sole consumer: may the list skip its
+        HOOMD-format rows (fused mode)? Yes when the tile plan is compiled straight from the cells."""
+        return bool(self.use_plan and self._planned_entry and self.threads_per_particle in (0, 1) and self.use_fused_plan)
+
+    def _pair_args(self, particle_range=None):
+        """azp_pair_args for the current state and ``particle_range`` (first, count): the list's HOOMD-format rows, or
+        while the list is in fused mode the ids of the plan compiled from its cells (placeholders until that compile)."""
+        st, nl = self._state, self.nlist
         a = _lib.PairArgs()
         a.d_force = self._force.data_ptr()
         a.d_virial = self._virial.data_ptr()
@@ -192,27 +195,15 @@ class Pair(Force):
         a.d_pos = st.pos.data_ptr()
         a.box = st.box.to_c()
         a.d_n_neigh = nl.n_neigh.data_ptr()
-        fused = getattr(nl, "_fused_active", False)
-        if fused and not (for_launch and self.use_plan and self._planned_entry is not None and self.use_fused_plan):
-            nl.leave_fused_mode()  # this launch needs the HOOMD-format list (generic kernel)
-            fused = False
-        if fused:
-            # no HOOMD-format list: the tile plan compiled from the cells is its own list (ids set
-            # by _prepare_plan; placeholders until then)
+        if nl.fused_active:
             ids = self._plan_ids if self._plan_builds == self._plan_key() else None
             a.d_nlist, a.d_head_list = ids if ids else (nl.n_neigh.data_ptr(), nl.n_neigh.data_ptr())
         else:
-            if self._plan_ids is not None:
-                # the plan on hand was compiled from the cells and is its own list: recompile from the u32 list
-                self._plan_ids = None
-                self._plan_builds = None
-            a.d_nlist = nl.nlist.data_ptr()
-            a.d_head_list = nl.head_list.data_ptr()
+            a.d_nlist, a.d_head_list, a.size_nlist = nl.nlist.data_ptr(), nl.head_list.data_ptr(), nl.size
         a.d_rcutsq = self._tables["rcutsq"].data_ptr()
         a.d_ronsq = self._tables["ronsq"].data_ptr()
         if "rinnersq" in self._tables:
             a.d_rinnersq = self._tables["rinnersq"].data_ptr()
-        a.size_nlist = 0 if fused else nl.size
         a.ntypes = len(st.types)
         a.shift_mode = _SHIFT[self._mode]
         a.compute_virial = 1 if self.compute_virial else 0
@@ -223,25 +214,21 @@ class Pair(Force):
         a.r_list_max = nl.r_list_max
         # displacement of any particle since the PLAN was built <= displacement since the list was
         # built (now) + the same quantity at the time the plan was built (0 in the usual flow)
-        bound = nl.displacement_bound(st) if hasattr(nl, "displacement_bound") else None
-        d0 = getattr(self, "_plan_disp0", None)
+        bound = nl.displacement_bound(st)
+        d0 = self._plan_disp0
         if bound is not None and d0 is not None and self.use_displacement_bound:
             a.has_displacement_bound, a.displacement_bound = 1, bound + d0
-            darr = nl.displacements(st) if (self.use_local_displacement and hasattr(nl, "displacements")) else None
+            darr = nl.displacements(st) if self.use_local_displacement else None
             if darr is not None and darr.shape[0] == st.n_max:
-                self._disp_keepalive = darr
                 a.d_displacement, a.displacement_bound_extra = darr.data_ptr(), d0
-        rng = getattr(self, "_range", None)
-        if rng is not None:
-            a.range_first, a.range_count = int(rng[0]), int(rng[1])
+        if particle_range is not None:
+            a.range_first, a.range_count = int(particle_range[0]), int(particle_range[1])
         return a
 
     def compute(self, timestep=None, particle_range=None):
         """Evaluate the forces. ``particle_range=(first, count)`` restricts the
         launch to a sub-range of the local particles (domain-decomposed runs compute
         the interior while the halo exchange is in flight)."""
-        import torch
-
         self._require()
         st = self._state
         if particle_range is None and self._compute_speculative(timestep):
@@ -250,11 +237,8 @@ class Pair(Force):
         self._ensure_buffers()  # after the list: a rebuild of a decomposed run migrates particles
         if self._tables is None:
             self._build_tables()
-        stream = _lib.raw_stream(st.device)
-        self._range = particle_range
-        self._launch(stream, timestep)
-        self._range = None
-        self._computed_generation = st.position_generation
+        entry, args = self._prepare_launch(_lib.raw_stream(st.device), timestep, particle_range)
+        _lib.check(getattr(_lib.lib(), entry)(*args), entry)
 
     def _compute_speculative(self, timestep):
         """The common MD step -- the list was built earlier, the particles have moved, the plan is current: queue the
@@ -265,14 +249,8 @@ class Pair(Force):
         ordinary path has to run (first call, rebuild, no plan, decomposed run)."""
         nl, st = self.nlist, self._state
         if not (self.use_speculative_launch and self.use_plan and self._planned_entry is not None and self.use_displacement_bound
-                and self._plan is not None and self._tables is not None and hasattr(nl, "begin_check")):
-            return False
-        if not (nl.built and nl.reduce_flag is None and nl.before_rebuild is None and self._plan_builds == self._plan_key()
-                and nl._built_consumer_version == nl._consumer_version and nl._built_generation != st.position_generation
-                and getattr(st, "order_generation", 0) == getattr(nl, "_order_generation", 0)
-                and getattr(self, "_plan_disp0", None) is not None and self._force.shape[0] == st.N):
-            return False
-        if not self._plan_valid:
+                and self._plan_valid and self._tables is not None and self._plan_disp0 is not None
+                and self._plan_builds == self._plan_key() and self._force.shape[0] == st.N and nl.allows_speculative_launch(st)):
             return False
         token = nl.begin_check(st)
         # the argument struct of the previous step, while nothing it points to has moved (the host side of a step has to
@@ -280,69 +258,66 @@ class Pair(Force):
         boxc = st.box.to_c()
         sig = (self._plan_builds, self._force.data_ptr(), self._virial.data_ptr(), st.pos.data_ptr(), nl.n_neigh.data_ptr(), id(self._tables),
                self._mode, self.compute_virial, self._plan_disp0, st.N, st.n_max, self.block_size)
-        cache = self.__dict__.get("_spec_cache")
+        cache = self._spec_cache
         if cache is not None and cache[0] == sig and cache[1] is boxc:
             a = cache[2]
         else:
-            a = self._pair_args(for_launch=True)
+            self._list_mode_for_launch(True)
+            a = self._pair_args()
             a.has_displacement_bound, a.displacement_bound, a.d_displacement = 0, 0.0, None
             a.displacement_bound_extra = self._plan_disp0
             self._spec_cache = (sig, boxc, a)
         a.d_stale_flag, a.d_displacement_sq_bits = token["flag_ptr"], token["bits_ptr"]
-        args = self._wrap_args(a, timestep)
-        stream = _lib.raw_stream(st.device)
-        fn = getattr(_lib.lib(), self._planned_entry)
-        _lib.check(fn(self._plan.handle, C.byref(args), self._tables["params"].data_ptr(), stream), self._planned_entry)
-        self._calls_since_plan = getattr(self, "_calls_since_plan", 0) + 1
+        entry, args = self._prepare_launch(_lib.raw_stream(st.device), timestep, a=a)
+        _lib.check(getattr(_lib.lib(), entry)(*args), entry)
         if nl.end_check(token):
             return False  # rebuild: the kernel left without writing; the ordinary path takes over (it has the verdict)
-        nl._built_generation = st.position_generation
-        self._computed_generation = st.position_generation
         return True
 
-    def _prepare_plan(self, a, stream):
-        """Compile the tile plan when the neighbor list was rebuilt since the last compile and
-        fill in the displacement fields of ``a`` for this launch."""
+    def _prepare_launch(self, stream, timestep, particle_range=None, a=None):
+        """The launch for the current state: the libazp entry point and its arguments -- the tile plan's handle for the
+        planned entry points, this potential's argument struct, the parameter table, ``stream``. Without ``a`` the pair
+        args are filled for ``particle_range`` and the plan step runs; ``a``: pair args for the plan on hand, which the
+        caller has found current (the speculative path)."""
+        planned = self.use_plan and self._planned_entry is not None
+        if a is None:
+            self._list_mode_for_launch(planned)
+            a = self._pair_args(particle_range)
+            if planned:
+                self._plan_step(a, stream)
+        args, params = C.byref(self._wrap_args(a, timestep)), self._tables["params"].data_ptr()
+        if not planned:
+            return self._entry, (args, params, stream)
+        self._calls_since_plan += 1
+        return self._planned_entry, (self._plan.handle, args, params, stream)
+
+    def _list_mode_for_launch(self, planned):
+        """Before a launch's pair args: a launch that does not take its plan from the cells needs the HOOMD-format list,
+        and a plan that was compiled from the cells (its own list) is recompiled once the list has left fused mode."""
+        nl = self.nlist
+        if nl.fused_active and not (planned and self.use_fused_plan):
+            nl.leave_fused_mode()
+        if self._plan_ids is not None and not nl.fused_active:
+            self._plan_ids = self._plan_builds = None
+
+    def _plan_step(self, a, stream):
+        """Compile the tile plan when the neighbor list was rebuilt since the last compile -- from the list's cells in
+        fused mode, else (or when that compile fails) from its HOOMD-format rows -- and fill in the list ids and the
+        displacement fields of ``a`` for this launch."""
+        key = self._plan_key()
+        if self._plan_builds == key:
+            return
         if self._plan is None:
             self._plan = _lib.PairPlan()
-        key = self._plan_key()
         nl = self.nlist
-        if self._plan_builds != key and getattr(nl, "_fused_active", False):
+        first, count = a.range_first, a.range_count
+        a.range_first = a.range_count = 0  # (a plan covers all local particles)
+        if nl.fused_active:
             # the plan straight from the binned particles: no u32 list, no hash set, one kernel
-            first, count = a.range_first, a.range_count
-            a.range_first = a.range_count = 0
-            cap = getattr(nl, "_plan_row_capacity", 0) or 160
-            info = None
             self._plan.set_balance(self._plan_balance)
-            for _ in range(4):
-                self._plan.build_from_cells(nl.cells_args(cap), a, stream)
-                info = self._plan.info()
-                if info["valid"]:
-                    if nl._cells.cell_subdivision == 2:
-                        nl._half_failures = 0
-                    break
-                if info["invalid_reason"] == 3:
-                    cap = (int(info["max_row"] * 1.06) + 4 + 7) // 8 * 8  # a row overflowed: longer rows (HOOMD's protocol)
-                elif nl._cells.cell_subdivision == 2:
-                    # half-width cells refused (a tile's members too spread out, a very dense run of cells): bin the
-                    # same positions into cells of the full list radius and compile from those
-                    nl._half_failures = getattr(nl, "_half_failures", 0) + 1
-                    nl.rebin_full()
-                else:
-                    break
-            a.range_first, a.range_count = first, count
+            info = nl.compile_plan(self._plan, a, stream)
             self._plan_valid = bool(info["valid"])
             if info["valid"]:
-                nl._fused_failures = 0
-                # the members of the tiles drift apart between two particle sorts; past 128 cells under one tile the
-                # compile is refused: ask for a sort when that comes near (and the count has grown since the last sort)
-                mc = int(info.get("max_member_cells", 0))
-                if getattr(nl, "_member_cells_key", None) != getattr(self._state, "order_generation", 0):
-                    nl._member_cells_key, nl._member_cells_sorted = getattr(self._state, "order_generation", 0), mc
-                if mc > 108 and mc > 1.15 * nl._member_cells_sorted:
-                    nl._sort_wanted = True
-                nl._plan_row_capacity = max((int(info["max_row"] * 1.06) + 4 + 7) // 8 * 8, 32)
-                nl._fused_counts_ready = True
                 self._plan_ids = (info["list_id"], info["head_id"])
                 a.d_nlist, a.d_head_list = self._plan_ids
                 self._plan_builds = key
@@ -354,39 +329,21 @@ class Pair(Force):
                 a.has_displacement_bound, a.displacement_bound = (1, b) if known else (0, 0.0)
                 a.displacement_bound_extra = 0.0
             else:
-                # particles not spatially sorted / a tile stages too much: the list-based path. A list
-                # whose tiles fail twice in a row (e.g. the thin boundary shells of a decomposed DPD
-                # fluid: 256 particles in more than 128 cells) stops trying at every rebuild
-                nl._fused_failures = getattr(nl, "_fused_failures", 0) + 1
-                if nl._fused_failures >= 2:
-                    nl.fused = False
-                    nl._fused_auto_off = True   # (a particle sort switches it back on: Simulation.run)
-                if info["invalid_reason"] in (4, 5):
-                    # the members of some tile have drifted apart (a fast-diffusing fluid between two particle sorts):
-                    # ask for a sort now rather than at the sorter's next period
-                    nl._sort_wanted = True
-                nl.leave_fused_mode()
-                a.d_nlist = nl.nlist.data_ptr()
-                a.d_head_list = nl.head_list.data_ptr()
-                a.size_nlist = nl.size
+                a.d_nlist, a.d_head_list, a.size_nlist = nl.nlist.data_ptr(), nl.head_list.data_ptr(), nl.size
         if self._plan_builds != key:
-            # recompile the plan only when the neighbor list was rebuilt
-            first, count = a.range_first, a.range_count
-            a.range_first = a.range_count = 0
             # bank-aware rows pay off only for lists that live long (include/azp.h): keep them
             # for the first build and whenever the previous list served >= 50 force calls
-            calls = getattr(self, "_calls_since_plan", None)
+            calls = self._calls_since_plan
             self._plan.set_bank_order((calls is None or calls >= 50) if self.plan_bank_order is None else self.plan_bank_order)
             self._calls_since_plan = 0
             self._plan.build(a, stream)
-            a.range_first, a.range_count = first, count
             self._plan_valid = bool(self._plan.info()["valid"])
             self._plan_builds = key
-            self._plan_disp0 = self.nlist.displacement_bound(self._state)
+            self._plan_disp0 = nl.displacement_bound(self._state)
             # this launch sees exactly the positions the plan was built from
             a.has_displacement_bound, a.displacement_bound = (1 if self.use_displacement_bound else 0), 0.0
             a.d_displacement = None  # (those refer to the positions the LIST was built from)
-        self._calls_since_plan = getattr(self, "_calls_since_plan", 0) + 1
+        a.range_first, a.range_count = first, count
 
     def _plan_key(self):
         return (id(self.nlist), self.nlist.num_builds, self.threads_per_particle)
@@ -395,27 +352,9 @@ class Pair(Force):
         """The argument struct of this potential's entry points around the common pair args."""
         return a
 
-    def _launch(self, stream, timestep):
-        a = self._pair_args(for_launch=True)
-        planned = self.use_plan and self._planned_entry is not None
-        if planned:
-            self._prepare_plan(a, stream)
-        args = self._wrap_args(a, timestep)
-        params = self._tables["params"].data_ptr()
-        if planned:
-            fn = getattr(_lib.lib(), self._planned_entry)
-            _lib.check(fn(self._plan.handle, C.byref(args), params, stream), self._planned_entry)
-            return
-        fn = getattr(_lib.lib(), self._entry)
-        _lib.check(fn(C.byref(args), params, stream), self._entry)
-
     @property
     def plan_info(self):
         return self._plan.info() if self._plan is not None else None
-
-
-def _d(x):
-    return C.c_double(x)
 
 
 class Colloid(Pair):

@@ -5,6 +5,7 @@ state, ``run(0)`` to evaluate them, and a velocity-Verlet NVE step
 validated as in src/pytest/test_pair_dpd.py.
 """
 
+import ctypes as C
 import warnings
 
 import numpy as np
@@ -252,8 +253,6 @@ class Simulation:
         for f in forces:
             f.compute(self.timestep)
         # one pass over the forces' arrays (azp_sum_forces) instead of a zero + one read-modify-write per force
-        import ctypes as C
-
         for k0 in range(0, len(forces), 7):
             grp = forces[k0:k0 + 7]
             ptrs = ([st.net_force.data_ptr()] if k0 else []) + [f.force_tensor.data_ptr() for f in grp]
@@ -261,8 +260,6 @@ class Simulation:
             _lib.check(_lib.lib().azp_sum_forces(st.N, len(ptrs), arr, st.net_force.data_ptr(), _lib.raw_stream(st.device)), "azp_sum_forces")
 
     def run(self, steps):
-        import torch
-
         self._attach_all()
         integ = self.operations.integrator
         st = self.state
@@ -276,8 +273,6 @@ class Simulation:
             return self._run_flow(steps, flow_methods)
         if len(integ.methods) != 1 or not isinstance(integ.methods[0], ConstantVolume):
             raise _lib.AzpError("Integrator.methods must hold exactly one ConstantVolume (all particles); got %r" % (integ.methods,))
-        import ctypes as C
-
         a = _lib.NVEArgs()
         a.box = st.box.to_c()
         a.dt = integ.dt
@@ -359,20 +354,17 @@ class Simulation:
             f.check_flags(wait=True)
 
     def _run_tuners(self, integ):
-        st = self.state
         lists = [f.nlist for f in integ.forces if getattr(f, "nlist", None) is not None]
-        wanted = any(getattr(nl, "_sort_wanted", False) for nl in lists)
+        wanted = any(nl.sort_wanted for nl in lists)
         for tuner in self.operations.tuners:
             due = tuner.trigger_period > 0 and self.timestep % tuner.trigger_period == 0
-            on_demand = wanted and tuner.trigger_period > 0 and self.timestep - getattr(tuner, "_last_sort_step", -(10 ** 9)) >= 20
-            if (due or on_demand) and st.n_ghost == 0:
+            on_demand = (wanted and tuner.trigger_period > 0
+                         and (tuner.last_sort_step is None or self.timestep - tuner.last_sort_step >= 20))
+            if (due or on_demand) and self.state.n_ghost == 0:
                 tuner.sort(self)
-                tuner._last_sort_step = self.timestep
+                tuner.last_sort_step = self.timestep
                 for nl in lists:
-                    nl._sort_wanted = False
-                    nl._fused_failures = 0
-                    if getattr(nl, "_fused_auto_off", False):
-                        nl.fused, nl._fused_auto_off = True, False
+                    nl.particles_sorted()
 
     def _check_flow_methods(self, integ):
         """The flow methods of ``integ`` (empty if it has none), after checking that they can run together."""

@@ -23,6 +23,8 @@ class ParticleSorter:
         self.block = int(block)
         self.particles_per_block = int(particles_per_block)
         self.num_sorts = 0
+        self.host_seconds = 0.0         # launch-side time of the sorts
+        self.last_sort_step = None      # timestep of the last sort a Simulation ran (on-demand sorts: >= 20 steps apart)
 
     def keys(self, state):
         """int32 sort key per local particle: (block index, position inside the block), one
@@ -58,7 +60,7 @@ class ParticleSorter:
         N = st.N
         order = torch.sort(self.keys(st), stable=True).indices
         names = ("pos", "vel", "orientation", "tag", "image", "angmom", "inertia")
-        if getattr(st, "accel", None) is not None:
+        if st.accel is not None:
             names += ("accel",)  # (a Langevin step one reads the acceleration of the previous step two)
         for name in names:
             a = getattr(st, name)
@@ -70,7 +72,7 @@ class ParticleSorter:
             st.set_bond_group_device(inv[st.bond_group_device()])
             st._bond_table = None
         st.position_generation += 1
-        st.order_generation = getattr(st, "order_generation", 0) + 1
+        st.order_generation += 1
         self.num_sorts += 1
-        self.host_seconds = getattr(self, "host_seconds", 0.0) + time.perf_counter() - t0  # launch-side time only
+        self.host_seconds += time.perf_counter() - t0
         return order

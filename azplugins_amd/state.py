@@ -247,6 +247,7 @@ class State:
         self.bond_tags = None
         self.bond_tags_typeid = None
         self.position_generation = 0  # bumped whenever positions change
+        self.order_generation = 0     # bumped whenever the particles are re-indexed (sort, migration)
 
     @property
     def n_max(self):

@@ -27,14 +27,8 @@ class NeighborListBuffer:
 
         nl = self.nlist
         self.results = {}
-        def set_buffer(b):
-            nl.buffer = b
-            nl._consumers_changed()     # the list on hand was built for another r_cut + buffer: rebuild
-            for f in nl._consumers:     # (tables that depend on the buffer: the tile plan's inner-radius hint)
-                f._mark_dirty()
-
         for b in self.candidates:
-            set_buffer(b)
+            nl.set_buffer(b)
             sim.run(self.steps)         # untimed: first rebuilds at this width, plan capacities learned
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -42,7 +36,7 @@ class NeighborListBuffer:
             torch.cuda.synchronize()
             self.results[b] = self.steps / (time.perf_counter() - t0)
         self.best = max(self.results, key=self.results.get)
-        set_buffer(self.best)
+        nl.set_buffer(self.best)
         return self.best
 
 

@@ -318,7 +318,7 @@ def test_fused_plan_limits_fall_back(oracle):
         sim.operations.integrator = azp.Integrator(dt=0.001, forces=[pot])
         sim.operations.tuners.clear()   # no particle sorter: the memory order stays random
         sim.run(0)
-        assert not nl._fused_active and nl._nlist is not None
+        assert not nl.fused_active and nl.has_hoomd_rows
         onl = oracle.build_nlist(syn.pos4(x), box, r_cut + r_buff)
         f_ref = oracle.pair_forces(PLJ, syn.pos4(x), box, onl, params, r_cut, nthreads=8)
         assert_close(np.c_[pot.forces, pot.energies], f_ref)
@@ -346,9 +346,9 @@ def test_unsorted_tiles_ask_for_a_particle_sort(oracle):
     sorter = azp.ParticleSorter(trigger_period=100000)
     sim.operations.tuners.append(sorter)
     sim.run(0)
-    assert not nl._fused_active and nl._sort_wanted and sorter.num_sorts == 0
+    assert not nl.fused_active and nl.sort_wanted and sorter.num_sorts == 0
     sim.run(3)
-    assert sorter.num_sorts == 1 and nl.fused and nl._fused_active and not nl._sort_wanted
+    assert sorter.num_sorts == 1 and nl.fused and nl.fused_active and not nl.sort_wanted
     assert pot.plan_info["valid"] == 1 and pot.plan_info["from_cells"] == 1
     x = syn.pos4(sim.state.pos[:, :3].cpu().numpy())
     box = oracle.make_box(L)
@@ -378,7 +378,7 @@ def test_fused_plan_through_the_api(oracle):
     sim.operations.integrator = azp.Integrator(dt=0.005, forces=[pot], methods=[azp.ConstantVolume()])
     sim.run(0)
     sim.thermalize_particle_momenta(1.0, seed=3)
-    assert nl._fused_active and nl._nlist is None
+    assert nl.fused_active and not nl.has_hoomd_rows
     assert pot.plan_info["valid"] == 1 and pot.plan_info["from_cells"] == 1
     builds = nl.num_builds
     checked = 0
@@ -392,7 +392,7 @@ def test_fused_plan_through_the_api(oracle):
             assert_close(np.c_[pot.forces, pot.energies], f_ref)
             checked += 1
     assert nl.num_builds >= 3 and checked >= 5
-    assert nl._nlist is None                      # 30 steps, several rebuilds, no u32 list
+    assert not nl.has_hoomd_rows                  # 30 steps, several rebuilds, no u32 list
     assert pot.plan_info["from_cells"] == 1
     # mode change in the middle of a list's life: the plan is recompiled from the bins of the build
     pot.mode = "none"
@@ -402,10 +402,10 @@ def test_fused_plan_through_the_api(oracle):
     assert_close(np.c_[pot.forces, pot.energies], oracle.pair_forces(PLJ, pos, box, onl, params, 3.0, nthreads=8))
     # statistics and arrays on demand
     n_pairs = nl.n_pairs
-    assert nl._nlist is None and n_pairs > 0
+    assert not nl.has_hoomd_rows and n_pairs > 0
     listed = int(nl.n_neigh.sum().item())
     head, rows = nl.head_list, nl.nlist           # materializes the HOOMD-format list for this build
-    assert nl._nlist is not None and rows.numel() >= nl.n_pairs
+    assert nl.has_hoomd_rows and rows.numel() >= nl.n_pairs
     assert 0 <= listed - nl.n_pairs <= 1e-3 * listed
     f_tile = pot.force_tensor.clone()
     pot.use_plan = False                          # generic kernel on the u32 list
@@ -435,7 +435,7 @@ def test_two_consumers_share_a_real_list(oracle):
     hz.params[("A", "A")] = dict(epsilon=3.0)
     sim.operations.integrator = azp.Integrator(dt=0.001, forces=[plj, hz])
     sim.run(0)
-    assert not nl._fused_active and nl._nlist is not None
+    assert not nl.fused_active and nl.has_hoomd_rows
     assert plj.plan_info["from_cells"] == 0 and hz.plan_info["from_cells"] == 0
     onl = oracle.build_nlist(pos, box, 2.8)
     f1 = oracle.pair_forces(PLJ, pos, box, onl, oracle.pack_pair_params(PLJ, PAIR_PARAMS[PLJ](0, 0)), 2.5, 0.0, "shift")

@@ -74,7 +74,7 @@ st.pos.copy_(snaps[0])
 st.position_generation += 1
 nl.compute(st, force=True)
 if args.bank >= 0:
-    pot._calls_since_plan = 1000 if args.bank else 0
+    pot.plan_bank_order = bool(args.bank)
 pot.compute(0)
 b1 = nl.num_builds
 rows = []

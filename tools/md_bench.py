@@ -97,7 +97,7 @@ for _ in range(100):
 ev1.record()
 torch.cuda.synchronize()
 if args.sort_period:
-    print("particle sorts: %d (%.1f ms of host time)" % (sim.operations.tuners[0].num_sorts, 1e3 * getattr(sim.operations.tuners[0], "host_seconds", 0.0)))
+    print("particle sorts: %d (%.1f ms of host time)" % (sim.operations.tuners[0].num_sorts, 1e3 * sim.operations.tuners[0].host_seconds))
 print("force kernel on the final state: %.4f ms/launch; mean neighbors %.1f; plan %s" % (
     ev0.elapsed_time(ev1) / 100, nl.n_pairs / N, {k: pot.plan_info[k] for k in ("valid", "lds_slots", "max_stage")} if pot.use_plan else None))
 if pot.use_plan and pot._plan is not None:

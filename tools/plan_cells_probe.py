@@ -38,10 +38,10 @@ if args.melt:
     sim.run(args.melt)
     azp.ParticleSorter().sort(sim)
 sim.run(0)
-nl._build(sim.state)         # bins only (fused mode fills no list)
+nl.compute(sim.state, force=True)   # bins only (fused mode fills no list)
 if stop:
     os.environ["AZP_PLAN_CELLS_STOP"] = str(stop)
-a = pot._pair_args(for_launch=True)   # (keeps the list fused: no HOOMD-format rows, the bins stay as they are)
+a = pot._pair_args()   # (the list stays fused: no HOOMD-format rows, the bins stay as they are)
 stream = torch.cuda.current_stream().cuda_stream
 plan = azp._lib.PairPlan()
 cells = nl.cells_args(160)
