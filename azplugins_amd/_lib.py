@@ -166,6 +166,7 @@ class AutoPlanStats(C.Structure):
 
 
 PAIR_FLAG_NO_AUTO_PLAN = 1
+ERROR_TOO_MANY_TYPES = -2
 
 
 class HaloField(C.Structure):

@@ -263,7 +263,13 @@ bool auto_plan_enabled()
     return on;
     }
 
-#define AZP_AUTO_TRY(expr)                                   \
+void auto_plan_count_generic_fallback()
+    {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    ++g_stats.generic_fallbacks;
+    }
+
+#define AZP_AUTO_TRY(expr)                                \
     do                                                       \
         {                                                    \
         hipError_t e_ = (expr);                              \
@@ -406,6 +412,7 @@ int auto_plan_run(const azp_pair_args& args, bool lanes_one, hipStream_t stream,
         AZP_AUTO_TRY(hipEventRecord(e->checked, stream));
         AZP_AUTO_TRY(hipStreamWaitEvent(e->side, e->checked, 0));
         AZP_AUTO_TRY(hipMemcpyAsync(e->h_state, e->d_state, AUTO_STATE_HOST_BYTES, hipMemcpyDeviceToHost, e->side));
+        int tiled = AZP_ERROR_INVALID_ARGUMENT; // (no plan: nothing launched)
         if (e->plan.valid)
             {
             azp_pair_args a = args;
@@ -415,17 +422,19 @@ int auto_plan_run(const azp_pair_args& args, bool lanes_one, hipStream_t stream,
             a.d_stale_flag = nullptr;   // (those belong to callers that run their own distance check)
             a.d_displacement_sq_bits = nullptr;
             const AutoLaunch l = {&e->plan, &a, &e->d_state->dyn};
-            const int status = launch_tiled(l);
-            if (status != AZP_SUCCESS)
-                return status;
+            tiled = launch_tiled(l);
             }
+        // (waited for on every path, errors included: the next call reuses h_state)
         AZP_AUTO_TRY(hipStreamSynchronize(e->side));
+        if (e->plan.valid && tiled != AZP_SUCCESS && tiled != AZP_ERROR_TOO_MANY_TYPES)
+            return tiled;
         stale = e->h_state->dyn.stale != 0;
         if (!stale)
             {
             ++g_stats.reuses;
-            if (e->plan.valid)
+            if (tiled == AZP_SUCCESS)
                 return AZP_SUCCESS; // the speculative launch was the launch
+            // no plan, or the tile instance cannot hold the per-type-pair table beside its staged slots
             ++g_stats.generic_fallbacks;
             return launch_generic();
             }
@@ -446,7 +455,11 @@ int auto_plan_run(const azp_pair_args& args, bool lanes_one, hipStream_t stream,
     a.d_stale_flag = nullptr;
     a.d_displacement_sq_bits = nullptr;
     const AutoLaunch l = {&e->plan, &a, nullptr};
-    return launch_tiled(l);
+    const int tiled = launch_tiled(l);
+    if (tiled != AZP_ERROR_TOO_MANY_TYPES)
+        return tiled;
+    ++g_stats.generic_fallbacks; // (the generic kernel's table is smaller: it may still fit)
+    return launch_generic();
     }
 
 } // namespace azp

@@ -70,6 +70,7 @@ typedef std::function<int(const AutoLaunch&)> AutoLauncher;
 int auto_plan_run(const azp_pair_args& args, bool lanes_one, hipStream_t stream, const AutoLauncher& launch_tiled,
                   const std::function<int()>& launch_generic);
 bool auto_plan_enabled();
+void auto_plan_count_generic_fallback(); // azp_auto_plan_stats.generic_fallbacks of a planned entry
 
 inline bool auto_plan_wanted(const azp_pair_args& a)
     {
@@ -134,7 +135,13 @@ int launch_policy_planned(azp_pair_plan* plan_, const Args* args, const typename
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!P::usable(plan, pa)) // (a plan compiled from the cell list has no HOOMD-format list to fall back to)
         return plan.from_cells ? AZP_ERROR_INVALID_ARGUMENT : P::generic(pa, X::extra(*args), d_params, s);
-    return P::tiled(plan, pa, X::extra(*args), d_params, s, nullptr);
+    const int rc = P::tiled(plan, pa, X::extra(*args), d_params, s, nullptr);
+    // the tile instance cannot hold the per-type-pair table beside its staged slots: the generic kernel's table is
+    // smaller (a plan from the cells has no list for it: the caller compiles one from the list)
+    if (rc != AZP_ERROR_TOO_MANY_TYPES || plan.from_cells)
+        return rc;
+    auto_plan_count_generic_fallback();
+    return P::generic(pa, X::extra(*args), d_params, s);
     }
 
 // ... and azp_pair_forces_<evaluator>, azp_dpd_forces_general_weight, azp_aniso_forces_two_patch_morse: the tile-staged

@@ -56,6 +56,7 @@ class Pair(Force):
         self._plan_disp0 = None         # displacement bound of the list's positions when the plan was compiled
         self._calls_since_plan = None   # force calls the plan on hand has served (None: no plan compiled yet)
         self._spec_cache = None         # (signature, box struct, pair args) of the last speculative launch
+        self._fused_refused_types = None  # type count whose table the tile kernel could not hold (no fused plan)
         self._tables = None
         self._cpp = None            # the _azplugins C++ object (created on attach)
         self._cpp_synced = False
@@ -180,7 +181,10 @@ class Pair(Force):
     def takes_plan_from_cells(self):
         """The neighbor list's question at a build, when this potential is its sole consumer: may the list skip its
         HOOMD-format rows (fused mode)? Yes when the tile plan is compiled straight from the cells."""
-        return bool(self.use_plan and self._planned_entry and self.threads_per_particle in (0, 1) and self.use_fused_plan)
+        st = self._state
+        refused = st is not None and self._fused_refused_types == len(st.types)  # (the types' table did not fit)
+        return bool(self.use_plan and self._planned_entry and self.threads_per_particle in (0, 1) and self.use_fused_plan
+                    and not refused)
 
     def _pair_args(self, particle_range=None):
         """azp_pair_args for the current state and ``particle_range`` (first, count): the list's HOOMD-format rows, or
@@ -238,7 +242,16 @@ class Pair(Force):
         if self._tables is None:
             self._build_tables()
         entry, args = self._prepare_launch(_lib.raw_stream(st.device), timestep, particle_range)
-        _lib.check(getattr(_lib.lib(), entry)(*args), entry)
+        rc = getattr(_lib.lib(), entry)(*args)
+        if rc == _lib.ERROR_TOO_MANY_TYPES and self._plan_ids is not None:
+            # the tile kernel cannot hold the per-type-pair table beside its staged slots, and a plan compiled from the
+            # cells has no list for the generic kernel: cannot run fused. The list leaves fused mode as after a failed
+            # compile; the planned entry runs the generic kernel on the plan compiled from the list.
+            self._fused_refused_types = len(st.types)
+            self.nlist.leave_fused_mode()
+            entry, args = self._prepare_launch(_lib.raw_stream(st.device), timestep, particle_range)
+            rc = getattr(_lib.lib(), entry)(*args)
+        _lib.check(rc, entry)
 
     def _compute_speculative(self, timestep):
         """The common MD step -- the list was built earlier, the particles have moved, the plan is current: queue the

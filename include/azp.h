@@ -55,7 +55,9 @@ typedef enum azp_status
     {
     AZP_SUCCESS = 0,
     AZP_ERROR_INVALID_ARGUMENT = -1,
-    AZP_ERROR_TOO_MANY_TYPES = -2, /* per-type-pair table does not fit in LDS */
+    AZP_ERROR_TOO_MANY_TYPES = -2, /* per-type-pair table does not fit in LDS; a pair call returns it only when the
+                                      generic kernel's table does not fit either (a tile kernel that cannot hold the
+                                      table beside its staged slots hands the call to the generic kernel) */
     AZP_ERROR_NO_DEVICE = -3,
     AZP_ERROR_TOO_MANY_BINS = -4   /* velocity field: more than 2^31 - 1 bins */
     } azp_status;
