@@ -1,17 +1,18 @@
 """azplugins_amd -- MI355X-native force-compute hot path of azplugins.
 
-``pair`` / ``bond`` / ``external`` / ``compute`` / ``flow`` mirror ``hoomd.azplugins.pair`` /
-``.bond`` / ``.external`` / ``.compute`` / ``.flow`` (class names, parameters, modes). The compute path is libazp.so (hand-written
+``pair`` / ``bond`` / ``external`` / ``compute`` / ``flow`` / ``update`` / ``evaporate`` / ``variant`` mirror ``hoomd.azplugins.pair`` /
+``.bond`` / ``.external`` / ``.compute`` / ``.flow`` / ``.update`` / ``.evaporate`` / ``.variant`` (class names, parameters, modes). The compute path is libazp.so (hand-written
 HIP for gfx950, C ABI in ``include/azp.h``); there is no CPU fallback.
 """
 
-from . import _lib, bond, compute, external, flow, nlist, pair, sorter, synthetic, tune
+from . import _lib, bond, compute, evaporate, external, flow, nlist, pair, sorter, synthetic, tune, update, variant
 from ._lib import AzpError
-from .simulation import All, ConstantVolume, Integrator, Simulation, Type
+from .simulation import All, ConstantVolume, Integrator, Periodic, Simulation, Type
 from .sorter import ParticleSorter
 from .state import (Box, Snapshot, State, bonded_two_particle_snapshot, lattice_snapshot, two_particle_snapshot)
 
 __version__ = "0.1.0"
 
-__all__ = ["All", "AzpError", "Box", "ParticleSorter", "ConstantVolume", "Integrator", "Simulation", "Snapshot", "State", "Type", "bond", "compute", "external", "flow", "nlist",
-           "pair", "synthetic", "tune", "two_particle_snapshot", "bonded_two_particle_snapshot", "lattice_snapshot"]
+__all__ = ["All", "AzpError", "Box", "ParticleSorter", "ConstantVolume", "Integrator", "Periodic", "Simulation", "Snapshot", "State", "Type", "bond", "compute",
+           "evaporate", "external", "flow", "nlist", "pair", "synthetic", "tune", "update", "variant", "two_particle_snapshot", "bonded_two_particle_snapshot",
+           "lattice_snapshot"]

@@ -258,6 +258,42 @@ class FlowMethodArgs(C.Structure):
     ]
 
 
+class TypeUpdateArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("N", C.c_uint32),
+        ("inside_type", C.c_uint32),
+        ("outside_type", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("z_lo", C.c_double),
+        ("z_hi", C.c_double),
+    ]
+
+
+EVAPORATE_NO_LIMIT = 0xFFFFFFFF
+
+
+class EvaporateArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("N", C.c_uint32),
+        ("solvent_type", C.c_uint32),
+        ("evaporated_type", C.c_uint32),
+        ("Nmax", C.c_uint32),
+        ("z_lo", C.c_double),
+        ("z_hi", C.c_double),
+        ("timestep", C.c_uint64),
+        ("seed", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+        ("d_counts", C.c_void_p),
+        ("d_keys_out", C.c_void_p),
+        ("d_n_keys_out", C.c_void_p),
+    ]
+
+
 # every symbol include/azp.h declares: name -> (restype, argtypes)
 _D = C.c_double
 _PD = C.POINTER(C.c_double)
@@ -327,6 +363,11 @@ SYMBOLS = {
     "azp_integrate_langevin_flow_step_two": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
     "azp_integrate_langevin_flow_step_two_one": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
     "azp_integrate_brownian_flow_step": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
+    "azp_type_update_region": (C.c_int, [C.POINTER(TypeUpdateArgs), _VP]),
+    "azp_evaporate_scratch_size": (C.c_uint64, [C.c_uint32]),
+    "azp_evaporate": (C.c_int, [C.POINTER(EvaporateArgs), _VP]),
+    "azp_evaporate_local_keys": (C.c_int, [C.POINTER(EvaporateArgs), _VP]),
+    "azp_evaporate_apply_below": (C.c_int, [C.POINTER(EvaporateArgs), C.c_uint64, _VP]),
     "azp_velocity_field_scratch_size": (C.c_int, [C.POINTER(VelocityFieldArgs), C.POINTER(C.c_uint64)]),
     "azp_velocity_field_sums": (C.c_int, [C.POINTER(VelocityFieldArgs), _VP]),
     "azp_velocity_field_normalize": (C.c_int, [_VP, C.c_uint64, _VP, _VP]),

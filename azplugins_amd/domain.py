@@ -146,6 +146,21 @@ class DeviceDomain:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return bool(t.item())
 
+    def all_gather_rows(self, row):
+        """Every rank's ``row`` (a 1-D tensor of the same length and dtype on every rank) as a (world, len) tensor
+        on ``row``'s device (the evaporator's keys and counts)."""
+        import torch
+        import torch.distributed as dist
+
+        if self.world == 1 or not dist.is_initialized():
+            return row.reshape(1, -1).clone()
+        staged = row.is_cuda and dist.get_backend(self.group) == "gloo"  # (gloo has no device collectives)
+        send = row.cpu() if staged else row
+        parts = [torch.empty_like(send) for _ in range(self.world)]
+        dist.all_gather(parts, send.contiguous(), group=self.group)
+        out = torch.stack(parts)
+        return out.to(row.device) if staged else out
+
     def _a2a_rows(self, send, send_splits, recv_splits, out=None):
         import torch
         import torch.distributed as dist

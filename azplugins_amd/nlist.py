@@ -48,6 +48,7 @@ class NeighborList:
         self._consumer_version = 0        # bumped when a consumer's r_cut matrix changes
         self._built_consumer_version = None
         self._order_generation = 0        # State.order_generation the list was built for
+        self._type_generation = 0         # State.type_generation the list was built for
         # domain-decomposed runs (azplugins_amd.domain): the rebuild decision is collective
         # (reduce_flag: bool -> bool, an all-reduce over the ranks) and particles migrate /
         # ghosts are re-selected before the list is rebuilt (before_rebuild(state))
@@ -186,6 +187,13 @@ class Cell(NeighborList):
         protocol: fixed-capacity rows, rebuilt when a row overflows);
         ``compact=True`` forces exact rows."""
         self._compact = compact
+        if state.type_generation != self._type_generation:
+            # an updater rewrote types in pos.w: the per-type-pair cutoffs the rows were cut with, and the row classes
+            # of a tile plan, no longer hold. A decomposed run re-selects its ghosts first, as for any rebuild (every
+            # rank runs its updaters at the same steps, so the collective is entered by all)
+            if not force and self.built and self.before_rebuild is not None:
+                self.before_rebuild(state)
+            force = True
         if state.order_generation != self._order_generation or self._built_consumer_version != self._consumer_version:
             force = True  # re-indexed particles (ParticleSorter: every stored index is stale) or a changed r_cut matrix
         if not force and self.built:
@@ -210,7 +218,7 @@ class Cell(NeighborList):
         for the current consumers and particle order, a check is due, and no collective decides the rebuild."""
         return (self.n_neigh is not None and self.reduce_flag is None and self.before_rebuild is None
                 and self._built_consumer_version == self._consumer_version and self._built_generation != state.position_generation
-                and state.order_generation == self._order_generation)
+                and state.order_generation == self._order_generation and state.type_generation == self._type_generation)
 
     def begin_check(self, state):
         """Queue the distance check on the current stream and its 16-byte readback on a side stream (ordered after
@@ -352,6 +360,7 @@ class Cell(NeighborList):
         else:
             self._fill(stream)
         self._order_generation = state.order_generation
+        self._type_generation = state.type_generation
         self._built_consumer_version = self._consumer_version
         self._disp, self._disp_generation = 0.0, state.position_generation
         self.num_builds += 1

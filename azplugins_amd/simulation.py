@@ -53,6 +53,29 @@ class Type:
         return "Type(%r)" % (list(self.types),)
 
 
+class Periodic:
+    """``hoomd.trigger.Periodic``: fires at the timesteps t with ``(t - phase) % period == 0``."""
+
+    def __init__(self, period, phase=0):
+        if isinstance(period, bool) or int(period) != period or int(period) < 1:
+            raise _lib.AzpError("Periodic: period must be a positive integer, got %r" % (period,))
+        if isinstance(phase, bool) or int(phase) != phase:
+            raise _lib.AzpError("Periodic: phase must be an integer, got %r" % (phase,))
+        self.period, self.phase = int(period), int(phase)
+
+    def __call__(self, timestep):
+        return (int(timestep) - self.phase) % self.period == 0
+
+    def __eq__(self, other):
+        return isinstance(other, Periodic) and (other.period, other.phase) == (self.period, self.phase)
+
+    def __hash__(self):
+        return hash(("Periodic", self.period, self.phase))
+
+    def __repr__(self):
+        return "Periodic(period=%d, phase=%d)" % (self.period, self.phase)
+
+
 class ConstantVolume:
     """NVE integration method (velocity Verlet) on all particles
     (``hoomd.md.methods.ConstantVolume(filter=hoomd.filter.All())`` without a
@@ -127,6 +150,9 @@ class _Operations:
     def __init__(self, sim=None):
         self.integrator = None
         self.computes = _Computes(sim)
+        # HOOMD's sim.operations.updaters: run ahead of the integrator's step at the timesteps their trigger fires
+        # (azplugins_amd.update.TypeUpdater, azplugins_amd.evaporate.ParticleEvaporator)
+        self.updaters = []
         # HOOMD puts a ParticleSorter into sim.operations.tuners by default; so does this
         # (remove it from the list, or set trigger_period = 0, to keep the initial order)
         from .sorter import ParticleSorter
@@ -134,11 +160,26 @@ class _Operations:
         self.tuners = [ParticleSorter(trigger_period=200)]
 
     def add(self, op):
-        """Add a compute (``hoomd.Operations.add``); it is attached while the simulation has a state."""
+        """Add an updater or a compute (``hoomd.Operations.add``); a compute is attached while the simulation has a
+        state."""
+        from .update import _Updater
+
+        if isinstance(op, _Updater):
+            if not any(u is op for u in self.updaters):
+                self.updaters.append(op)
+            return
         self.computes.append(op)
 
     def remove(self, op):
-        """Remove a compute; reading its results raises ``compute.DataAccessError`` afterwards."""
+        """Remove an updater or a compute; reading a removed compute's results raises ``compute.DataAccessError``."""
+        from .update import _Updater
+
+        if isinstance(op, _Updater):
+            for i, u in enumerate(self.updaters):
+                if u is op:
+                    del self.updaters[i]
+                    return
+            raise ValueError("%r is not in sim.operations.updaters" % (op,))
         self.computes.remove(op)
 
 
@@ -323,7 +364,9 @@ class Simulation:
         for k in range(steps):
             # velocity Verlet (libazp kernels): v += a dt/2, x += v dt, wrap | forces | v += a dt/2. Inside a run
             # nothing reads the velocities between step two of one step and step one of the next: they are one
-            # kernel (same arithmetic, one pass over the arrays); the last step two comes after the loop
+            # kernel (same arithmetic, one pass over the arrays); the last step two comes after the loop. An updater
+            # changes types alone, which these kernels do not read: they stay fused
+            self._run_updaters()
             point_at_state()
             if k == 0:
                 _lib.check(lib.azp_integrate_nve_step_one(C.byref(a), stream), "azp_integrate_nve_step_one")
@@ -352,6 +395,20 @@ class Simulation:
         for f in deferred:
             f.defer_flag_check = False
             f.check_flags(wait=True)
+
+    def _updaters_due(self):
+        return [u for u in self.operations.updaters if u.trigger(self.timestep)]
+
+    def _run_updaters(self, due=None):
+        """The updaters whose trigger fires at this timestep (HOOMD runs its updaters ahead of the integrator's
+        step). They change particle types: every neighbor list and tile plan is rebuilt before the next force
+        evaluation (the reference: notifyParticleSort(), src/TypeUpdater.cc:86-87) -- whether or not a type really
+        changed, so that nothing is read back from the device."""
+        due = self._updaters_due() if due is None else due
+        for u in due:
+            u._update(self, self.timestep)
+        if due:
+            self.state.type_generation += 1
 
     def _run_tuners(self, integ):
         lists = [f.nlist for f in integ.forces if getattr(f, "nlist", None) is not None]
@@ -416,9 +473,18 @@ class Simulation:
         for f in deferred:
             f.defer_flag_check = True
         for k in range(steps):
+            # a method filtered by type reads the types when its kernel runs: where an updater is due, step two of the
+            # previous step runs on its own ahead of the updater, as in HOOMD (the fused kernel is bit-identical to
+            # the two halves)
+            due = self._updaters_due()
+            if due:
+                if k > 0:
+                    for m in methods:
+                        m._step_two(st, self.timestep - 1, stream)
+                self._run_updaters(due)
             for m in methods:
                 # (k > 0: step two of the previous step, at its timestep, fused with this step one)
-                m._step(st, self.timestep, stream, fused=k > 0)
+                m._step(st, self.timestep, stream, fused=k > 0 and not due)
             st.position_generation += 1
             self.timestep += 1
             self._run_tuners(integ)

@@ -248,6 +248,7 @@ class State:
         self.bond_tags_typeid = None
         self.position_generation = 0  # bumped whenever positions change
         self.order_generation = 0     # bumped whenever the particles are re-indexed (sort, migration)
+        self.type_generation = 0      # bumped whenever an updater may have changed the types in pos.w
 
     @property
     def n_max(self):

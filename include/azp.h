@@ -646,6 +646,76 @@ int azp_integrate_langevin_flow_step_two(const azp_flow_method_args* args, void*
 int azp_integrate_langevin_flow_step_two_one(const azp_flow_method_args* args, void* stream);
 int azp_integrate_brownian_flow_step(const azp_flow_method_args* args, void* stream);
 
+/* ---- type updates: region type updater and particle evaporator ----
+ * The reference's evaporation tools (HOOMD-2-era sources that its CMake no longer builds), restated. Both calls are
+ * asynchronous on `stream`, touch rows [0, N) only (ghost rows follow their owner at the next exchange) and write
+ * nothing but the type word (low 32 bits) of pos.w: x, y, z keep their bits. A particle ON a face of the slab is
+ * inside: inside = !(z > z_hi || z < z_lo).
+ *
+ * azp_type_update_region (src/TypeUpdater.cc:93-127): every row whose type is inside_type or outside_type gets
+ * inside_type if it is inside the slab, else outside_type; rows of other types are untouched. */
+typedef struct azp_type_update_args
+    {
+    double* d_pos;          /* N x 4 */
+    uint32_t N;
+    uint32_t inside_type;
+    uint32_t outside_type;
+    uint32_t block_size;    /* 0: 256 */
+    double z_lo, z_hi;
+    } azp_type_update_args;
+
+int azp_type_update_region(const azp_type_update_args* args, void* stream);
+
+/* azp_evaporate (src/ParticleEvaporator.cc:100-260), one call, no host round trip inside it:
+ *   candidates: rows of solvent_type inside the slab (:176-203), M of them;
+ *   key of a candidate: u64 = c0 << 32 | tag, c0 the first output word of Philox4x32-10 with counter {0, tag, 0, 0}
+ *     and key {203 << 24 | (timestep >> 32 & 0xff) << 16 | seed & 0xffff, timestep & 0xffffffff}: draw 0 of the flow
+ *     methods' stream layout with the reference's evaporator id (src/RNGIdentifiers.h). Tags are unique, so are keys;
+ *   selection: the min(Nmax, M) candidates with the smallest keys (M < Nmax: all of them, :110-116;
+ *     Nmax = 0xffffffff: no limit);
+ *   apply: the picked rows get evaporated_type.
+ * d_counts (optional): two uint32, M and the number picked.
+ *
+ * DEPARTURE FROM THE REFERENCE. The reference gathers the candidates' indices in rank order and shuffles them on the
+ * host with HOOMD's RandomGenerator / UniformIntDistribution (:229-259). HOOMD's source is not available to this
+ * project, so that stream could not be reproduced in any case; and a pick by index changes with the particle sorter
+ * and with the number of ranks. The smallest of independent per-tag keys keeps what matters -- every subset of
+ * min(Nmax, M) candidates is equally likely, every rank reaches the same result -- and is invariant under
+ * re-indexing and under decomposition.
+ *
+ * Decomposed runs do the same work in two phases: azp_evaporate_local_keys writes this rank's min(Nmax, M) smallest
+ * keys in ascending order to d_keys_out (room for min(Nmax, N) keys) and their number to d_n_keys_out (and M, 0 to
+ * d_counts); the ranks gather them and take the Nmax-th smallest as the threshold; azp_evaporate_apply_below flips
+ * every local candidate whose key is <= threshold_key (d_counts: local candidates, local rows flipped).
+ * azp_evaporate is these two with the threshold taken on the device.
+ *
+ * azp_evaporate (with a limit) and azp_evaporate_local_keys need d_scratch of azp_evaporate_scratch_size(N) bytes;
+ * the order of the candidate buffer may differ from call to call, the picked set does not. The selection is an
+ * exact most-significant-digit radix select (8-bit digits, integer histograms); no floating-point atomics. */
+typedef struct azp_evaporate_args
+    {
+    double* d_pos;           /* N x 4 */
+    const uint32_t* d_tag;   /* N */
+    uint32_t N;
+    uint32_t solvent_type;
+    uint32_t evaporated_type;
+    uint32_t Nmax;           /* 0xffffffff: no limit */
+    double z_lo, z_hi;
+    uint64_t timestep;
+    uint32_t seed;           /* low 16 bits used */
+    uint32_t block_size;     /* 0: 256 (the passes over the particles; the selection runs 256 wide) */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    uint32_t* d_counts;      /* 2 x uint32, may be NULL */
+    uint64_t* d_keys_out;    /* azp_evaporate_local_keys only */
+    uint32_t* d_n_keys_out;  /* azp_evaporate_local_keys only */
+    } azp_evaporate_args;
+
+uint64_t azp_evaporate_scratch_size(uint32_t N);
+int azp_evaporate(const azp_evaporate_args* args, void* stream);
+int azp_evaporate_local_keys(const azp_evaporate_args* args, void* stream);
+int azp_evaporate_apply_below(const azp_evaporate_args* args, uint64_t threshold_key, void* stream);
+
 /* ---- velocity / velocity-field computes ----
  * Replaces the reference's GPU drivers of hoomd.azplugins.compute: the per-particle loop of
  * src/VelocityFieldComputeGPU.cuh:35-71 (CartesianVelocityFieldCompute, CylindricalVelocityFieldCompute) and
