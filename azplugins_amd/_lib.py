@@ -226,6 +226,30 @@ class VelocityFieldArgs(C.Structure):
     ]
 
 
+THERMO_NSUMS = 20
+THERMO_MAX_FORCES = 8
+
+
+class ThermoArgs(C.Structure):
+    _fields_ = [
+        ("d_vel", C.c_void_p),
+        ("d_pos", C.c_void_p),
+        ("d_type_mask", C.c_void_p),
+        ("d_force", C.c_void_p * THERMO_MAX_FORCES),
+        ("d_virial", C.c_void_p * THERMO_MAX_FORCES),
+        ("d_orientation", C.c_void_p),
+        ("d_angmom", C.c_void_p),
+        ("d_inertia", C.c_void_p),
+        ("d_out", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("n_forces", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 FLOW_CONSTANT = 0
 FLOW_PARABOLIC = 1
 
@@ -371,6 +395,8 @@ SYMBOLS = {
     "azp_velocity_field_scratch_size": (C.c_int, [C.POINTER(VelocityFieldArgs), C.POINTER(C.c_uint64)]),
     "azp_velocity_field_sums": (C.c_int, [C.POINTER(VelocityFieldArgs), _VP]),
     "azp_velocity_field_normalize": (C.c_int, [_VP, C.c_uint64, _VP, _VP]),
+    "azp_thermo_scratch_size": (C.c_int, [C.POINTER(ThermoArgs), C.POINTER(C.c_uint64)]),
+    "azp_thermo_sums": (C.c_int, [C.POINTER(ThermoArgs), _VP]),
     "azp_version": (C.c_int, []),
     "azp_status_string": (C.c_char_p, [C.c_int]),
     "azp_last_launch": (None, [C.POINTER(C.c_uint32)] * 4),

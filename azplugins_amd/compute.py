@@ -6,6 +6,11 @@ kernels (``csrc/velocity_field.hip``).
 attached while it is in ``sim.operations.computes`` of a simulation that has a state; its result is computed when
 the property is read, on the current state. On a decomposed run (``sim.domain`` set) every rank sums its own rows,
 the sums are added over the domain's process group and every rank gets the same result.
+
+``ThermodynamicQuantities`` (``hoomd.md.compute.ThermodynamicQuantities``) is temperature, pressure and the energies
+of a group from one deterministic pass over the particles (``csrc/thermo.hip``); ``ThermodynamicRecorder`` appends the
+sums of that pass to a device table at the timesteps its trigger fires inside ``Simulation.run``, without a host
+synchronisation.
 """
 
 import ctypes as C
@@ -14,7 +19,7 @@ import itertools
 import numpy as np
 
 from . import _lib
-from .simulation import All, Type
+from .simulation import All, ConstantVolume, Periodic, Type
 
 
 class DataAccessError(_lib.AzpError):
@@ -261,5 +266,247 @@ class CylindricalVelocityFieldCompute(VelocityFieldCompute):
     _coordinates = _lib.COORDINATES_CYLINDRICAL
 
 
-__all__ = ["CartesianVelocityFieldCompute", "CylindricalVelocityFieldCompute", "DataAccessError", "VelocityCompute",
-           "VelocityFieldCompute"]
+# ---------------------------------------------------------------------------
+# thermodynamic quantities
+# ---------------------------------------------------------------------------
+THERMO_PROPERTIES = ("num_particles", "volume", "translational_degrees_of_freedom", "rotational_degrees_of_freedom",
+                     "degrees_of_freedom", "translational_kinetic_energy", "rotational_kinetic_energy", "kinetic_energy",
+                     "potential_energy", "kinetic_temperature", "pressure_tensor", "pressure", "linear_momentum")
+
+
+def thermo_quantities(sums, n_global, volume, conserves_momentum, rotational):
+    """The quantities of ``THERMO_PROPERTIES`` from one row of sums (the 20 slots of ``azp_thermo_sums``, added over the
+    ranks of a decomposed run). ``n_global``: particles of the whole system; ``volume``: box volume;
+    ``conserves_momentum``: the integration method conserves the linear momentum (``ConstantVolume``), which removes
+    the group's share 3 N_g / N_global of the three center-of-mass degrees of freedom; ``rotational``: the integrator
+    integrates the rotational degrees of freedom. Plain Python floats in a fixed order: the properties and the
+    recorder's table go through here and agree bit for bit."""
+    s = [float(x) for x in sums]
+    n_g = s[0]
+    tdof = 3.0 * n_g
+    if conserves_momentum and n_global > 0:
+        tdof -= 3.0 * n_g / float(n_global)
+    rdof = s[18] if rotational else 0.0
+    dof = tdof + rdof
+    ke_t = 0.5 * (s[4] + s[7] + s[9])
+    ke_r = s[17]
+    ke = ke_t + (ke_r if rotational else 0.0)
+    p = tuple((s[4 + c] + s[10 + c]) / volume for c in range(6))
+    return dict(num_particles=int(n_g), volume=volume, translational_degrees_of_freedom=tdof,
+                rotational_degrees_of_freedom=rdof, degrees_of_freedom=dof, translational_kinetic_energy=ke_t,
+                rotational_kinetic_energy=ke_r, kinetic_energy=ke, potential_energy=s[16],
+                kinetic_temperature=2.0 * ke / dof if dof > 0.0 else 0.0, pressure_tensor=p,
+                pressure=(p[0] + p[3] + p[5]) / 3.0, linear_momentum=(s[1], s[2], s[3]))
+
+
+def _integrator_flags(integ):
+    """(conserves_momentum, rotational) of ``thermo_quantities`` for an integrator: ``ConstantVolume`` conserves the
+    linear momentum, ``flow.Langevin`` / ``flow.Brownian`` and an integrator without a method do not."""
+    if integ is None:
+        return False, False
+    return any(isinstance(m, ConstantVolume) for m in integ.methods), bool(integ.integrate_rotational_dof)
+
+
+class ThermodynamicQuantities(_Compute):
+    """Thermodynamic properties of a group (``hoomd.md.compute.ThermodynamicQuantities``; D = 3). ``filter``:
+    ``All()`` or ``Type(...)``. With K_ab = sum m v_a v_b, W_ab the sum of the per-particle virials and U the sum of
+    the per-particle energies of every force of the integrator, over the group's particles, and V the box volume:
+
+    - ``translational_kinetic_energy`` = (K_xx + K_yy + K_zz) / 2, ``rotational_kinetic_energy`` = sum_k s_k^2 / (2 I_k)
+      over the axes with I_k != 0 (s = conj(q) p / 2), ``kinetic_energy`` their sum (the rotational part counts only if
+      ``integrator.integrate_rotational_dof``), ``potential_energy`` = U;
+    - ``translational_degrees_of_freedom`` = 3 N_g - 3 N_g / N_global under ``ConstantVolume`` (it conserves the
+      momentum), 3 N_g under ``flow.Langevin`` / ``flow.Brownian`` or without a method;
+      ``rotational_degrees_of_freedom`` = the number of non-zero inertia components if
+      ``integrator.integrate_rotational_dof``, else 0;
+    - ``kinetic_temperature`` = 2 ``kinetic_energy`` / ``degrees_of_freedom`` (0 without degrees of freedom);
+    - ``pressure_tensor`` = (K_ab + W_ab) / V in the order xx, xy, xz, yy, yz, zz, ``pressure`` a third of its trace;
+    - ``linear_momentum`` = sum m v.
+
+    While a ``ThermodynamicQuantities`` is in ``sim.operations.computes``, ``Simulation.run`` turns ``compute_virial``
+    on for every force of the integrator: THE VIRIAL PASS OF THE FORCE KERNELS THEN RUNS EVERY STEP. The pressure is
+    available once the forces have been evaluated that way (``sim.run(0)``). At most 8 forces. Every property is
+    computed when it is read, from the current state; two reads of the same state agree bit for bit."""
+
+    def __init__(self, filter):
+        if not isinstance(filter, (All, Type)):
+            raise _lib.AzpError("ThermodynamicQuantities: filter must be All() or Type(...), got %r" % (filter,))
+        super().__init__(filter, False)
+        self._scratch = None
+        self._row = None
+        self._rotation = None  # (state, any particle has a non-zero moment of inertia)
+
+    # -- one launch ----------------------------------------------------------
+    def _forces_evaluated(self):
+        """(energies known, virials known) for the forces of the integrator on the current state."""
+        sim = self._sim
+        integ = sim.operations.integrator
+        forces = integ.forces if integ is not None else []
+        st = sim.state
+        ok = all(f._state is st and f._force is not None and f._force.shape[0] == st.N for f in forces)
+        return ok, ok and all(getattr(f, "_virial_evaluated", False) for f in forces)
+
+    def _launch(self, d_out):
+        """Queue ``azp_thermo_sums`` for the simulation's current state with the 20 doubles going to ``d_out``."""
+        import torch
+
+        sim = self._sim
+        st = sim.state
+        integ = sim.operations.integrator
+        forces = list(integ.forces) if integ is not None else []
+        if len(forces) > _lib.THERMO_MAX_FORCES:
+            raise _lib.AzpError("ThermodynamicQuantities sums at most %d forces, the integrator has %d"
+                                % (_lib.THERMO_MAX_FORCES, len(forces)))
+        a = _lib.ThermoArgs()
+        a.d_vel = st.vel.data_ptr()
+        a.N = st.N
+        mask = self._type_mask(st)
+        if mask is not None:
+            a.d_pos = st.pos.data_ptr()
+            a.d_type_mask = mask.data_ptr()
+            a.ntypes = len(st.types)
+        if self._forces_evaluated()[0]:
+            a.n_forces = len(forces)
+            for k, f in enumerate(forces):
+                a.d_force[k] = f._force.data_ptr()
+                a.d_virial[k] = f._virial.data_ptr() if getattr(f, "_virial_evaluated", False) else None
+        if st.N and self._reads_rotation():
+            # (a rank without particles has nothing to point at; the kernel zeroes the row)
+            a.d_orientation, a.d_angmom, a.d_inertia = st.orientation.data_ptr(), st.angmom.data_ptr(), st.inertia.data_ptr()
+        lib = _lib.lib()
+        need = C.c_uint64(0)
+        _lib.check(lib.azp_thermo_scratch_size(C.byref(a), C.byref(need)), "azp_thermo_scratch_size")
+        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
+            self._scratch = torch.empty(int(need.value), dtype=torch.uint8, device=st.device)
+        a.d_scratch = self._scratch.data_ptr()
+        a.scratch_bytes = self._scratch.numel()
+        a.d_out = d_out
+        _lib.check(lib.azp_thermo_sums(C.byref(a), _lib.raw_stream(st.device)), "azp_thermo_sums")
+
+    def _prepare(self):
+        """Called by ``Simulation.run`` ahead of the first step: does any particle have a moment of inertia? Without
+        one the three rotational arrays (88 of the pass's bytes per particle) are not read and slots 17 and 18 are the
+        zeros they would sum to. One small readback per ``run``, none inside it; a decomposed run always reads them
+        (particles migrate between the ranks)."""
+        sim = self._sim
+        st = sim.state
+        self._rotation = (st, bool(sim.domain is not None or st.N == 0 or (st.inertia[: st.N] != 0.0).any().item()))
+
+    def _reads_rotation(self):
+        if self._rotation is None or self._rotation[0] is not self._sim.state:
+            self._prepare()
+        integ = self._sim.operations.integrator
+        return self._rotation[1] or bool(integ is not None and integ.integrate_rotational_dof)
+
+    def _context(self, rows):
+        """What ``thermo_quantities`` needs beside the rows (a (k, 20) device tensor of per-rank sums): the rows added
+        over the ranks, as numpy, and (n_global, volume, conserves_momentum, rotational)."""
+        import torch
+
+        sim = self._sim
+        st = sim.state
+        dom = sim.domain
+        if dom is not None:
+            rows = _all_reduce_sum(dom, rows.clone())
+        host = rows.cpu().numpy()
+        if dom is None:
+            n_global = st.N
+        elif isinstance(self._filter, All):
+            n_global = int(host[0, 0]) if host.shape[0] else 0  # (no particle is created or destroyed during a run)
+        else:
+            n = _all_reduce_sum(dom, torch.tensor([float(st.N)], dtype=torch.float64, device=st.device))
+            n_global = int(n.item())
+        box = st.box
+        return host, (n_global, box.Lx * box.Ly * box.Lz) + _integrator_flags(sim.operations.integrator)
+
+    def _sums(self):
+        """The row of sums of the current state, per rank, as a (1, 20) device tensor."""
+        import torch
+
+        st = self._sim.state
+        if self._row is None or self._row.device != st.device:
+            self._row = torch.empty((1, _lib.THERMO_NSUMS), dtype=torch.float64, device=st.device)
+        self._launch(self._row.data_ptr())
+        return self._row
+
+    def _get(self, name):
+        if not self._attached:
+            raise DataAccessError(name)
+        energies, virials = self._forces_evaluated()
+        if name == "potential_energy" and not energies:
+            raise _lib.AzpError("potential_energy: the forces have not been evaluated on this state; call sim.run(0)")
+        if name in ("pressure", "pressure_tensor") and not virials:
+            raise _lib.AzpError("%s: the last force evaluation ran without virials; call sim.run(0) with this compute in "
+                                "sim.operations.computes" % name)
+        host, ctx = self._context(self._sums())
+        return thermo_quantities(host[0], *ctx)[name]
+
+
+def _thermo_property(name):
+    return property(lambda self: self._get(name), doc="``%s`` of the group at the current state." % name)
+
+
+for _name in THERMO_PROPERTIES:
+    setattr(ThermodynamicQuantities, _name, _thermo_property(_name))
+
+
+class ThermodynamicRecorder:
+    """Writer (``sim.operations.writers``) that appends the sums behind ``thermo`` (a ``ThermodynamicQuantities`` in
+    ``computes`` of the same simulation) to a device table at the timesteps ``trigger`` (an ``int`` period or a
+    ``Periodic``) fires -- the kernel writes straight into row k of the table, nothing is read back and the host never
+    waits. In ``run(n)`` starting at timestep t0 the trigger is evaluated at t0 + 1 ... t0 + n; the row of timestep t
+    is the state after t complete steps (after step two, with the forces of that configuration). ``Simulation.run``
+    runs step two of that step on its own there instead of fused with the next step one: the trajectory is the same
+    bit for bit with and without a recorder. ``timesteps`` and ``table`` are read after the run."""
+
+    def __init__(self, thermo, trigger):
+        if not isinstance(thermo, ThermodynamicQuantities):
+            raise _lib.AzpError("ThermodynamicRecorder: thermo must be a ThermodynamicQuantities, got %r" % (thermo,))
+        self.thermo = thermo
+        self.trigger = trigger if isinstance(trigger, Periodic) else Periodic(trigger)
+        self._rows = None  # (capacity, 20) device tensor
+        self._steps = []
+
+    def timesteps_in_run(self, t0, n):
+        """The timesteps at which ``run(n)`` starting at timestep ``t0`` records: those of t0 + 1 ... t0 + n at which the
+        trigger fires."""
+        return [t for t in range(int(t0) + 1, int(t0) + int(n) + 1) if self.trigger(t)]
+
+    def _record(self, sim, timestep):
+        import torch
+
+        st = sim.state
+        k = len(self._steps)
+        rows = self._rows
+        if rows is None or rows.device != st.device or k >= rows.shape[0]:
+            # (grown by doubling; the copy is queued on the stream like everything else)
+            grown = torch.empty((max(64, 2 * k), _lib.THERMO_NSUMS), dtype=torch.float64, device=st.device)
+            if k:
+                grown[:k].copy_(rows[:k])
+            self._rows = rows = grown
+        self.thermo._launch(rows.data_ptr() + k * _lib.THERMO_NSUMS * 8)
+        self._steps.append(int(timestep))
+
+    @property
+    def timesteps(self):
+        """numpy int64: the timesteps recorded so far."""
+        return np.array(self._steps, dtype=np.int64)
+
+    @property
+    def table(self):
+        """dict of numpy arrays keyed by the property names of ``ThermodynamicQuantities``, one entry per recorded
+        timestep (``pressure_tensor``: (rows, 6), ``linear_momentum``: (rows, 3)). On a decomposed run the rows of all
+        ranks are added here, in one reduction."""
+        k = len(self._steps)
+        if k == 0:
+            return {name: np.zeros((0,) + ((6,) if name == "pressure_tensor" else (3,) if name == "linear_momentum" else ()),
+                                   dtype=np.int64 if name == "num_particles" else np.float64) for name in THERMO_PROPERTIES}
+        if not self.thermo._attached:
+            raise DataAccessError("table")
+        host, ctx = self.thermo._context(self._rows[:k])
+        rows = [thermo_quantities(host[i], *ctx) for i in range(k)]
+        return {name: np.array([r[name] for r in rows]) for name in THERMO_PROPERTIES}
+
+
+__all__ = ["CartesianVelocityFieldCompute", "CylindricalVelocityFieldCompute", "DataAccessError", "ThermodynamicQuantities",
+           "ThermodynamicRecorder", "VelocityCompute", "VelocityFieldCompute", "thermo_quantities"]

@@ -153,6 +153,9 @@ class _Operations:
         # HOOMD's sim.operations.updaters: run ahead of the integrator's step at the timesteps their trigger fires
         # (azplugins_amd.update.TypeUpdater, azplugins_amd.evaporate.ParticleEvaporator)
         self.updaters = []
+        # HOOMD's sim.operations.writers: run after the integrator's step at the timesteps their trigger fires
+        # (azplugins_amd.compute.ThermodynamicRecorder)
+        self.writers = []
         # HOOMD puts a ParticleSorter into sim.operations.tuners by default; so does this
         # (remove it from the list, or set trigger_period = 0, to keep the initial order)
         from .sorter import ParticleSorter
@@ -160,26 +163,31 @@ class _Operations:
         self.tuners = [ParticleSorter(trigger_period=200)]
 
     def add(self, op):
-        """Add an updater or a compute (``hoomd.Operations.add``); a compute is attached while the simulation has a
-        state."""
+        """Add an updater, a writer or a compute (``hoomd.Operations.add``); a compute is attached while the simulation
+        has a state."""
+        from .compute import ThermodynamicRecorder
         from .update import _Updater
 
-        if isinstance(op, _Updater):
-            if not any(u is op for u in self.updaters):
-                self.updaters.append(op)
-            return
+        for cls, ops in ((_Updater, self.updaters), (ThermodynamicRecorder, self.writers)):
+            if isinstance(op, cls):
+                if not any(u is op for u in ops):
+                    ops.append(op)
+                return
         self.computes.append(op)
 
     def remove(self, op):
-        """Remove an updater or a compute; reading a removed compute's results raises ``compute.DataAccessError``."""
+        """Remove an updater, a writer or a compute; reading a removed compute's results raises
+        ``compute.DataAccessError``."""
+        from .compute import ThermodynamicRecorder
         from .update import _Updater
 
-        if isinstance(op, _Updater):
-            for i, u in enumerate(self.updaters):
-                if u is op:
-                    del self.updaters[i]
-                    return
-            raise ValueError("%r is not in sim.operations.updaters" % (op,))
+        for cls, ops, name in ((_Updater, self.updaters, "updaters"), (ThermodynamicRecorder, self.writers, "writers")):
+            if isinstance(op, cls):
+                for i, u in enumerate(ops):
+                    if u is op:
+                        del ops[i]
+                        return
+                raise ValueError("%r is not in sim.operations.%s" % (op, name))
         self.computes.remove(op)
 
 
@@ -266,6 +274,38 @@ class Simulation:
                 f._attach(self)
                 if f not in self._attached:
                     self._attached.append(f)
+        if self._has_thermo():
+            # (a ThermodynamicQuantities reads the per-particle virials: the virial pass of every force runs every step)
+            for f in integ.forces:
+                f.compute_virial = True
+            for c in self._thermo_computes():
+                c._prepare()
+
+    def _thermo_computes(self):
+        from .compute import ThermodynamicQuantities
+
+        return [c for c in self.operations.computes if isinstance(c, ThermodynamicQuantities)]
+
+    def _has_thermo(self):
+        return bool(self.operations.computes) and bool(self._thermo_computes())
+
+    def _check_writers(self):
+        """A recorder reads its compute through this simulation's state: the compute has to be in ``computes``."""
+        for w in self.operations.writers:
+            if not any(c is w.thermo for c in self.operations.computes):
+                raise _lib.AzpError("%s: its ThermodynamicQuantities is not in sim.operations.computes of this simulation"
+                                    % type(w).__name__)
+        integ = self.operations.integrator
+        if integ is not None and len(integ.forces) > _lib.THERMO_MAX_FORCES and self._has_thermo():
+            raise _lib.AzpError("ThermodynamicQuantities sums at most %d forces, the integrator has %d"
+                                % (_lib.THERMO_MAX_FORCES, len(integ.forces)))
+
+    def _writers_due(self):
+        return [w for w in self.operations.writers if w.trigger(self.timestep)]
+
+    def _run_writers(self, due):
+        for w in due:
+            w._record(self, self.timestep)
 
     def _compute_forces(self):
         import torch
@@ -287,12 +327,14 @@ class Simulation:
         if len(forces) == 1:
             # a single force: its own array is the net force (no 32 MB zero + add per step)
             forces[0].compute(self.timestep)
+            forces[0]._virial_evaluated = bool(forces[0].compute_virial)
             st.net_force = forces[0].force_tensor
             return
         if st.net_force.shape[0] != st.N or any(st.net_force is f.force_tensor for f in forces):
             st.net_force = torch.zeros((st.N, 4), dtype=torch.float64, device=st.device)
         for f in forces:
             f.compute(self.timestep)
+            f._virial_evaluated = bool(f.compute_virial)
         # one pass over the forces' arrays (azp_sum_forces) instead of a zero + one read-modify-write per force
         for k0 in range(0, len(forces), 7):
             grp = forces[k0:k0 + 7]
@@ -301,6 +343,7 @@ class Simulation:
             _lib.check(_lib.lib().azp_sum_forces(st.N, len(ptrs), arr, st.net_force.data_ptr(), _lib.raw_stream(st.device)), "azp_sum_forces")
 
     def run(self, steps):
+        self._check_writers()
         self._attach_all()
         integ = self.operations.integrator
         st = self.state
@@ -365,15 +408,24 @@ class Simulation:
             # velocity Verlet (libazp kernels): v += a dt/2, x += v dt, wrap | forces | v += a dt/2. Inside a run
             # nothing reads the velocities between step two of one step and step one of the next: they are one
             # kernel (same arithmetic, one pass over the arrays); the last step two comes after the loop. An updater
-            # changes types alone, which these kernels do not read: they stay fused
+            # changes types alone, which these kernels do not read: they stay fused. Where a writer is due, the
+            # full-step velocities of the previous step have to exist: its step two runs on its own (the same arithmetic,
+            # bit for bit), the writer records, and this step starts with a plain step one
+            writers = self._writers_due() if k else []
+            if writers:
+                point_at_state()
+                _lib.check(lib.azp_integrate_nve_step_two(C.byref(a), stream), "azp_integrate_nve_step_two")
+                if rot is not None:
+                    rotational_step(False)
+                self._run_writers(writers)
             self._run_updaters()
             point_at_state()
-            if k == 0:
+            if k == 0 or writers:
                 _lib.check(lib.azp_integrate_nve_step_one(C.byref(a), stream), "azp_integrate_nve_step_one")
             else:
                 _lib.check(lib.azp_integrate_nve_step_two_one(C.byref(a), stream), "azp_integrate_nve_step_two_one")
             if rot is not None:
-                if k:
+                if k and not writers:
                     rotational_step(False)  # (step two of the previous step: the torques are still its own)
                 rotational_step(True)
             if self.domain is not None:
@@ -392,6 +444,7 @@ class Simulation:
         _lib.check(lib.azp_integrate_nve_step_two(C.byref(a), stream), "azp_integrate_nve_step_two")
         if rot is not None:
             rotational_step(False)
+        self._run_writers(self._writers_due())
         for f in deferred:
             f.defer_flag_check = False
             f.check_flags(wait=True)
@@ -477,20 +530,23 @@ class Simulation:
             # previous step runs on its own ahead of the updater, as in HOOMD (the fused kernel is bit-identical to
             # the two halves)
             due = self._updaters_due()
-            if due:
+            writers = self._writers_due() if k else []
+            if due or writers:
                 if k > 0:
                     for m in methods:
                         m._step_two(st, self.timestep - 1, stream)
+                self._run_writers(writers)  # (the state after self.timestep complete steps)
                 self._run_updaters(due)
             for m in methods:
                 # (k > 0: step two of the previous step, at its timestep, fused with this step one)
-                m._step(st, self.timestep, stream, fused=k > 0 and not due)
+                m._step(st, self.timestep, stream, fused=k > 0 and not due and not writers)
             st.position_generation += 1
             self.timestep += 1
             self._run_tuners(integ)
             self._compute_forces()
         for m in methods:
             m._step_two(st, self.timestep - 1, stream)
+        self._run_writers(self._writers_due())
         for f in deferred:
             f.defer_flag_check = False
             f.check_flags(wait=True)

@@ -761,6 +761,48 @@ int azp_velocity_field_scratch_size(const azp_velocity_field_args* args, uint64_
 int azp_velocity_field_sums(const azp_velocity_field_args* args, void* stream);
 int azp_velocity_field_normalize(const double* d_sums, uint64_t n_bins, double* d_velocity, void* stream);
 
+/* ---- thermodynamic sums (compute.ThermodynamicQuantities) ----
+ * One deterministic pass over rows [0, N) of a group (d_type_mask[type] != 0 with the type from d_pos[i].w;
+ * d_type_mask NULL: every particle, d_pos is then not read) that OVERWRITES the AZP_THERMO_NSUMS doubles at d_out:
+ *   0      particle count
+ *   1-3    sum m v
+ *   4-9    sum m v_a v_b, order xx, xy, xz, yy, yz, zz
+ *   10-15  sum of the per-particle virials of every force array with a non-NULL d_virial entry, same order
+ *   16     sum of the .w (energy) of every force array
+ *   17     sum_k s_k^2 / (2 I_k) over the axes with I_k != 0, s = 1/2 conj(q) p (rotational kinetic energy)
+ *   18     number of non-zero inertia components
+ *   19     0
+ * Slots 17 and 18 are 0 unless d_orientation, d_angmom and d_inertia are given (all three or none). d_out is any
+ * device address (8-byte aligned), e.g. a row of a larger table. No floating-point atomics: two calls on the same
+ * input give bit-identical rows, and no term passes through more than 200 additions for N <= 2^24
+ * (csrc/thermo.hip). Asynchronous on `stream`; needs a device scratch buffer of azp_thermo_scratch_size bytes
+ * (depends on N only). AZP_ERROR_INVALID_ARGUMENT: more than AZP_THERMO_MAX_FORCES forces, a NULL d_vel, d_out or
+ * listed force array, only some of the three rotational arrays, a mask without d_pos, too small a scratch. */
+#define AZP_THERMO_NSUMS 20
+#define AZP_THERMO_MAX_FORCES 8
+
+typedef struct azp_thermo_args
+    {
+    const double* d_vel;         /* N x 4 (vx, vy, vz, mass) */
+    const double* d_pos;         /* N x 4, read for the type only; may be NULL without a mask */
+    const uint8_t* d_type_mask;  /* ntypes bytes, may be NULL */
+    const double* d_force[AZP_THERMO_MAX_FORCES];  /* n_forces arrays, N x 4 */
+    const double* d_virial[AZP_THERMO_MAX_FORCES]; /* per force: 6 rows of pitch N, or NULL (no virial) */
+    const double* d_orientation; /* N x 4, may be NULL */
+    const double* d_angmom;      /* N x 4, may be NULL */
+    const double* d_inertia;     /* N x 3, may be NULL */
+    double* d_out;               /* AZP_THERMO_NSUMS doubles, overwritten */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    uint32_t N;
+    uint32_t ntypes;             /* entries of d_type_mask */
+    uint32_t n_forces;
+    uint32_t _pad;
+    } azp_thermo_args;
+
+int azp_thermo_scratch_size(const azp_thermo_args* args, uint64_t* bytes);
+int azp_thermo_sums(const azp_thermo_args* args, void* stream);
+
 /* ---- misc ---- */
 int azp_version(void);                    /* major * 1000 + minor       */
 const char* azp_status_string(int status);
