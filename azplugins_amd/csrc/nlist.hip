@@ -322,8 +322,9 @@ struct NlistKArgs
 // accepted ones, and the row is written as contiguous runs -- the list is
 // streamed out once instead of with scattered 4-byte stores.
 // FILL = false: count; FILL = true: write rows at head_list[i].
-// MI = true: per-pair minimum image (boxes with < 4 cells along a periodic axis,
-// triclinic boxes); MI = false: images resolved once per staged candidate.
+// MI = true: per-pair minimum image (boxes with < 4 cells along a periodic axis);
+// MI = false: images resolved once per staged candidate. Orthorhombic boxes only
+// (nlist_scan refuses tilted ones).
 // Dense cells are handled in batches of NL_CAP candidates x NL_HOME home particles.
 // ---------------------------------------------------------------------------
 constexpr uint32_t NL_CAP = 1280;
@@ -678,14 +679,18 @@ static int nlist_scan(const azp_nlist_args* args, void* stream, bool fill)
         return AZP_ERROR_INVALID_ARGUMENT; // the 27-cell search needs cells as wide as the list radius
     if (fill && args->row_capacity && (!args->d_n_neigh || !args->d_max_neigh))
         return AZP_ERROR_INVALID_ARGUMENT;
+    // The cells are Cartesian and the search reaches +-1 cell: across a periodic y or z face of a tilted box the image of
+    // a neighbor is shifted by xy Ly (xz Lz, yz Lz), not a whole number of cells, and pairs would be dropped silently
+    if (args->box.tilt[0] != 0.0 || args->box.tilt[1] != 0.0 || args->box.tilt[2] != 0.0)
+        return AZP_ERROR_INVALID_ARGUMENT;
     if (args->N == 0)
         return AZP_SUCCESS;
     const NlistKArgs k = make_nlist_kargs(*args);
     const uint32_t ncell = args->grid.dim[0] * args->grid.dim[1] * args->grid.dim[2];
     const uint32_t grid = (ncell + 7u) & ~7u;
     // images can be resolved once per staged candidate when every periodic axis
-    // has >= 4 cells (cell width + r_list <= L/2 with margin) and the box is orthorhombic
-    bool mi = k.box.triclinic;
+    // has >= 4 cells (cell width + r_list <= L/2 with margin)
+    bool mi = false;
     for (int d = 0; d < 3; ++d)
         if (args->grid.periodic[d] && args->grid.dim[d] < 4)
             mi = true;

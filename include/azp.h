@@ -441,6 +441,11 @@ int azp_nlist_cell_bounds(const azp_nlist_args* args, void* stream);
  * grid has more than 32,768 cells). Grids of many small cells (cell_subdivision = 2) get a multi-workgroup scan
  * and a thread-per-cell sort. */
 int azp_nlist_bin(const azp_nlist_args* args, uint32_t* d_cursor, uint32_t* d_order_tmp, void* stream);
+/* Orthorhombic boxes only: the cells are Cartesian and the search reaches +-1 cell, while across a periodic y or z
+ * face of a tilted box the image of a neighbor is shifted by xy Ly (xz Lz, yz Lz), which is no whole number of
+ * cells. A box with a non-zero tilt is refused with AZP_ERROR_INVALID_ARGUMENT before anything is launched or
+ * written (as azp_pair_plan_build_from_cells refuses it with invalid_reason 6): build the u32 list for such a box
+ * elsewhere (HOOMD's own list, as the adapter does) and hand it to the force kernels / azp_pair_plan_build. */
 int azp_nlist_count(const azp_nlist_args* args, void* stream);
 int azp_nlist_fill(const azp_nlist_args* args, void* stream);
 

@@ -198,13 +198,23 @@ def bond_table(N, bonds, bond_type):
     return table, bpos, nb
 
 
-def gpu_bond_forces(name, pos, box, bonds, bond_type, params, N=None, virial=False):
+def gpu_bond_forces(name, pos, box, bonds, bond_type, params, N=None, virial=False, pitch=None):
+    """pitch (>= N; default N): column pitch of the bond table; the columns past N hold entries that point at real
+    particles with a valid bond type, so that a kernel reading them computes wrong forces rather than faulting."""
     import torch
 
     pos = np.ascontiguousarray(pos, dtype=np.float64)
     n_total = pos.shape[0]
     N = n_total if N is None else N
     table, bpos, nb = bond_table(N, bonds, bond_type)
+    pitch = N if pitch is None else int(pitch)
+    if pitch != N:
+        assert pitch > N
+        pad = pitch - N
+        tpad = np.zeros((table.shape[0], pad, 2), dtype=np.uint32)
+        tpad[:, :, 0] = (np.arange(pad)[None, :] * 7 + np.arange(table.shape[0])[:, None] * 3 + 1) % max(N, 1)
+        table = np.concatenate([table, tpad], axis=1)
+        bpos = np.concatenate([bpos, np.ones((bpos.shape[0], pad), dtype=np.uint32)], axis=1)
     t = dict(pos=_dev(pos), table=_dev(table), bpos=_dev(bpos), nb=_dev(nb),
              force=torch.full((N, 4), float("nan"), dtype=torch.float64, device="cuda:0"),
              virial=torch.full((6, N), float("nan"), dtype=torch.float64, device="cuda:0"),
@@ -221,7 +231,7 @@ def gpu_bond_forces(name, pos, box, bonds, bond_type, params, N=None, virial=Fal
     a.d_gpu_bondlist = t["table"].data_ptr()
     a.d_gpu_bond_pos = t["bpos"].data_ptr()
     a.d_gpu_n_bonds = t["nb"].data_ptr()
-    a.pitch = N
+    a.pitch = pitch
     a.n_bond_types = np.atleast_2d(params).shape[0]
     a.compute_virial = int(bool(virial))
     entry = {"DoubleWell": "azp_bond_forces_double_well", "Quartic": "azp_bond_forces_quartic"}[name]
@@ -263,12 +273,14 @@ def rel_err(a, b):
 # ---------------------------------------------------------------------------
 # binned particles (azp_nlist_args) for the plan-from-cells compiler
 # ---------------------------------------------------------------------------
-def gpu_cells(pos, box, r_list, ntypes=1, N=None, exclusions=None, row_capacity=0, sub=1):
+def gpu_cells(pos, box, r_list, ntypes=1, N=None, exclusions=None, row_capacity=0, sub=1, dims=None, excl_pitch=None):
     """Bin ``pos`` (n_total x 4, ghosts after the N locals) into cells of width >= max r_list / sub with
     libazp's own kernels (azp_nlist_cell_assign / _cell_bounds) and return (azp_nlist_args, keepalive).
     ``box``: (L, tilt, periodic) as for gpu_pair_args; ``exclusions``: (n_excl, excl[N, max]). ``sub`` = 2: cells of
     half the list radius (azp_nlist_args.cell_subdivision) where the plan compiler can take them (>= 5 cells along
-    every periodic axis), else cells of the full radius as the product does."""
+    every periodic axis), else cells of the full radius as the product does. ``dims``: cells per axis instead of
+    the product's floor(L / r_list) (fewer, wider cells only). ``excl_pitch`` (>= N; default N): column pitch of
+    the exclusion table, the columns past N filled with arbitrary particle indices (a builder that read them would drop pairs)."""
     import torch
 
     pos = np.ascontiguousarray(pos, dtype=np.float64)
@@ -288,6 +300,9 @@ def gpu_cells(pos, box, r_list, ntypes=1, N=None, exclusions=None, row_capacity=
     a.cell_subdivision = sub
     for k in range(3):
         dim = max(int(np.floor(L[k] / (rl.max() / sub))), 1)
+        if dims is not None:
+            assert 1 <= dims[k] <= dim
+            dim = int(dims[k])
         a.grid.dim[k] = dim
         a.grid.width[k] = L[k] / dim
         a.grid.lo[k] = -0.5 * L[k]
@@ -308,11 +323,77 @@ def gpu_cells(pos, box, r_list, ntypes=1, N=None, exclusions=None, row_capacity=
     if exclusions is not None:
         n_excl, excl = exclusions
         t["n_excl"] = _dev(n_excl, np.uint32)
-        t["excl"] = _dev(np.ascontiguousarray(np.asarray(excl, dtype=np.uint32).T))  # [max][N]
+        excl_t = np.ascontiguousarray(np.asarray(excl, dtype=np.uint32).T)  # [max][N]
+        pitch = N if excl_pitch is None else int(excl_pitch)
+        if pitch != N:
+            assert pitch > N
+            pad = (np.arange(pitch - N)[None, :] * 5 + np.arange(excl_t.shape[0])[:, None]) % max(n_total, 1)
+            excl_t = np.ascontiguousarray(np.concatenate([excl_t, pad.astype(np.uint32)], axis=1))
+        t["excl"] = _dev(excl_t)
         a.d_n_excl = t["n_excl"].data_ptr()
         a.d_excl = t["excl"].data_ptr()
-        a.excl_pitch = N
+        a.excl_pitch = pitch
     t["n_neigh"] = torch.zeros(max(N, 1), dtype=torch.int32, device="cuda:0")
     a.d_n_neigh = t["n_neigh"].data_ptr()
     a.row_capacity = row_capacity
     return a, t
+
+
+NLIST_SENTINEL = 0x5A5A5A5A  # no particle index (systems here are far smaller), not the builder's own pad index either
+
+
+def gpu_nlist_rows(a, t, row_capacity=0, guard=64):
+    """HOOMD-format rows from the binned particles of ``gpu_cells`` through the C ABI.
+
+    row_capacity = 0: azp_nlist_count, an exclusive scan on the host, azp_nlist_fill into exact rows.
+    row_capacity > 0: the single-pass fill alone, rows at i * row_capacity, *d_max_neigh zeroed beforehand.
+    Every output buffer is pre-filled with NLIST_SENTINEL and carries ``guard`` extra words.
+    Returns a dict: rc_count / rc_fill (status codes; a refused call leaves the later steps out), n_count (d_n_neigh
+    after the count pass), n_neigh (d_n_neigh at the end), head, nlist (whole buffer, guard words included), size
+    (words that belong to rows), max_neigh (*d_max_neigh at the end), n_guard (d_n_neigh's guard words)."""
+    import torch
+
+    l = _lib.lib()
+    N = int(a.N)
+    sent = NLIST_SENTINEL
+
+    def words(n):
+        return torch.full((n + guard,), sent, dtype=torch.int32, device="cuda:0")
+
+    def host(x):
+        return x.cpu().numpy().view(np.uint32).astype(np.int64)
+
+    t["n_neigh"] = words(N)
+    a.d_n_neigh = t["n_neigh"].data_ptr()
+    t["max_neigh"] = torch.zeros(1 + guard, dtype=torch.int32, device="cuda:0")
+    out = dict(rc_count=None, rc_fill=None, n_count=None, max_neigh=None)
+    if row_capacity:
+        head = np.arange(N, dtype=np.uint64) * np.uint64(row_capacity)
+        size = N * int(row_capacity)
+    else:
+        a.row_capacity = 0
+        a.d_max_neigh = None
+        a.d_head_list = None
+        a.d_nlist = None
+        out["rc_count"] = l.azp_nlist_count(C.byref(a), _stream())
+        torch.cuda.synchronize()
+        n_all = host(t["n_neigh"])
+        out["n_count"], out["n_guard"] = n_all[:N], n_all[N:]
+        if out["rc_count"] != 0:
+            out["n_neigh"] = out["n_count"]
+            return out
+        counted = np.where(out["n_count"] == sent, 0, out["n_count"])  # (rows nobody counted hold no words)
+        head = (np.cumsum(counted) - counted).astype(np.uint64)
+        size = int(counted.sum())
+    t["head"] = _dev(head, np.uint64)
+    t["nlist"] = words(size)
+    a.d_head_list = t["head"].data_ptr()
+    a.d_nlist = t["nlist"].data_ptr()
+    a.row_capacity = int(row_capacity)
+    a.d_max_neigh = t["max_neigh"].data_ptr() if row_capacity else None
+    out["rc_fill"] = l.azp_nlist_fill(C.byref(a), _stream())
+    torch.cuda.synchronize()
+    n_all = host(t["n_neigh"])
+    out.update(n_neigh=n_all[:N], n_guard=n_all[N:], head=head.astype(np.int64), nlist=host(t["nlist"]), size=size,
+               max_neigh=host(t["max_neigh"]))
+    return out

@@ -357,6 +357,66 @@ def test_bond_parity(oracle, name):
     assert_close(f_bad, f_ref_bad)
 
 
+@pytest.mark.parametrize("name", ["DoubleWell", "Quartic"])
+def test_bond_parity_branched_topology(oracle, name):
+    """Stars with 0, 1, 4, 5 and 9 bonds per particle: the kernel's loop past its first BATCH = 4 table columns,
+    lanes without bonds, a table pitch wider than N, N no multiple of the block (363 = 256 + 107), bonds across the
+    periodic faces. And State.bond_table() for the same snapshot against the table restated in numpy."""
+    import azplugins_amd as azp
+    import nlist_ref as R
+
+    n_stars, n_free = 20, 23
+    n = n_stars * R.STAR_SIZE + n_free
+    L = np.array([7.0, 8.0, 9.0])
+    bonds = R.star_bonds(n_stars)
+    tag = np.arange(n, dtype=np.uint64)
+    xyz = np.stack([(syn.u01(61, tag, c) - 0.5) * L[c] for c in range(3)], axis=1)
+    btag = np.arange(bonds.shape[0], dtype=np.uint64)
+    u = np.stack([syn.normal(62, btag, c) for c in range(3)], axis=1)
+    u *= ((0.8 + 0.7 * syn.u01(63, btag, 0)) / np.linalg.norm(u, axis=1))[:, None]  # bond lengths 0.8 .. 1.5
+    parent, child = bonds.min(axis=1), bonds.max(axis=1)
+    xyz[np.arange(n_stars) * R.STAR_SIZE, 0] = 0.5 * L[0] - 0.4 * (np.arange(n_stars) % 3)  # hubs near the +x face
+    for b in np.argsort(child, kind="stable"):
+        xyz[child[b]] = xyz[parent[b]] + u[b]
+    xyz = syn.wrap(xyz, L)
+    across = np.abs(xyz[bonds[:, 0]] - xyz[bonds[:, 1]]) > 0.5 * L
+    assert across[:, 0].sum() > 20 and across.any(axis=0).all()  # bonds through the faces of every axis
+    counts = np.bincount(bonds.ravel(), minlength=n)
+    assert sorted(set(counts.tolist())) == [0, 1, 4, 5, 9] and n % 256 and n > 256
+    btype = (np.arange(bonds.shape[0]) % 2).astype(np.uint32)
+    if name == "DoubleWell":
+        ps = [dict(r_0=1.0, r_1=1.5, U_1=1.0, U_tilt=0.5), dict(r_0=0.9, r_1=1.3, U_1=2.0, U_tilt=0.0)]
+    else:
+        ps = [dict(k=1434.3, r_0=1.5, b_1=-0.7589, b_2=0.0, U_0=67.2234, sigma=1.0, epsilon=1.0, delta=0.0),
+              dict(k=1000.0, r_0=1.6, b_1=-0.5, b_2=0.1, U_0=50.0, sigma=0.9, epsilon=1.2, delta=0.15)]
+    params = np.array([oracle.pack_bond_params(name, p) for p in ps])
+    pos = syn.pos4(xyz)
+    f_ref, bad, v_ref = oracle.bond_forces(name, pos, oracle.make_box(L), bonds, btype, params, virial=True)
+    assert bad == 0
+    for pitch in (None, n + 29):
+        f_gpu, flag, v_gpu = H.gpu_bond_forces(name, pos, (L,), bonds, btype, params, virial=True, pitch=pitch)
+        assert flag == 0
+        assert_close(f_gpu[:, :3], f_ref[:, :3], what="bond force")
+        assert_close(f_gpu[:, 3], f_ref[:, 3], what="bond energy")
+        assert_close(v_gpu, v_ref, what="bond virial")
+    assert not f_gpu[counts == 0].any() and not v_gpu[:, counts == 0].any()
+    # State.bond_table(): per particle the (partner, bond type, own position in the bond) of each of its bonds
+    snap = azp.Snapshot.from_arrays(xyz, L, bonds=bonds, bond_typeid=btype, bond_types=("A-A", "B-B"))
+    sim = azp.Simulation(device="cuda:0", seed=1)
+    sim.create_state_from_snapshot(snap)
+    tb = sim.state.bond_table()
+    table, bpos, nb = tb["table"].cpu().numpy(), tb["bond_pos"].cpu().numpy(), tb["n_bonds"].cpu().numpy()
+    assert tb["width"] == 9 and table.shape == (9, n, 2) and bpos.shape == (9, n) and tb["pitch"] == n
+    assert np.array_equal(nb, counts)
+    want = [[] for _ in range(n)]
+    for (a_, b_), t_ in zip(bonds.tolist(), btype.tolist()):
+        want[a_].append((b_, t_, 0))
+        want[b_].append((a_, t_, 1))
+    for i in range(n):
+        got = sorted((int(table[s, i, 0]), int(table[s, i, 1]), int(bpos[s, i])) for s in range(nb[i]))
+        assert got == sorted(want[i]), i
+
+
 def test_plj_c2_full_size(oracle):
     """BASELINE.json configs[1] at full size: PerturbedLJ, N=262,144, rho*=0.8,
     r_cut=3.0 vs the oracle (OpenMP full-list loop, same arithmetic per pair)
@@ -648,7 +708,7 @@ def test_product_nlist_matches_oracle(oracle):
     pos = syn.pos4(cfg["xyz"], typeid)
     o_n, o_head, o_list = oracle.build_nlist(pos, oracle.make_box(cfg["L"]), rl, ntypes=2, exclusions=(n_excl, excl))
     assert np.array_equal(n_neigh, o_n)
-    for i in range(0, n, 37):
+    for i in range(n):
         mine = np.sort(nlist[head[i]: head[i] + n_neigh[i]])
         assert np.array_equal(mine, o_list[o_head[i]: o_head[i] + o_n[i]])
     # and the forces through the API (multi-type tables, plan or fallback) match the oracle
