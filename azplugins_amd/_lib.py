@@ -348,7 +348,6 @@ SYMBOLS = {
     "azp_pair_plan_tile_stage": (C.c_int, [_VP, C.POINTER(C.c_uint32), C.c_uint32]),
     "azp_pair_plan_query": (C.c_int, [_VP, C.POINTER(PlanInfo)]),
     "azp_pair_plan_phase_chunks": (C.c_int, [_VP, C.POINTER(C.c_float)]),
-    "azp_tuning_set": (C.c_int, [C.c_int, C.c_int]),
     "azp_sum_forces": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), _VP, _VP]),
     "azp_pair_auto_plan_get_stats": (None, [C.POINTER(AutoPlanStats)]),
     "azp_pair_auto_plan_clear": (None, []),

@@ -1,5 +1,6 @@
 // pair_auto.hip -- plan cache + change detector behind the HOOMD-signature entry points
 // (see pair_auto.hpp for the protocol).
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -16,7 +17,7 @@ namespace
 constexpr uint64_t AUTO_FULL_HASH_ENTRIES = 1ull << 22; // lists up to this size are fingerprinted entry by entry
 constexpr size_t AUTO_MAX_PLANS = 8;                    // cache capacity (least recently used plan is evicted)
 
-struct AutoState // device words of one cached plan (pinned host mirror: the first 48 bytes)
+struct AutoState // device words of one cached plan (pinned host mirror: the words before "device only")
     {
     TileDyn dyn;                        // what the speculatively launched tile kernel reads
     unsigned long long fingerprint;     // of this call
@@ -26,7 +27,7 @@ struct AutoState // device words of one cached plan (pinned host mirror: the fir
     // device only
     unsigned long long expected[8];     // fingerprint learned at the compile, per sample phase
     };
-constexpr size_t AUTO_STATE_HOST_BYTES = 48;
+constexpr size_t AUTO_STATE_HOST_BYTES = offsetof(AutoState, expected);
 
 struct CheckKArgs
     {
@@ -204,7 +205,6 @@ __global__ void __launch_bounds__(256) auto_fold_kernel(const CheckKArgs a, cons
         st.fingerprint = fp;
         st.d2_bits = (unsigned long long)__double_as_longlong(dd);
         st.types_changed = tc;
-        st.dyn.bound = (bound < 1.0e100) ? bound : -1.0;
         st.dyn.n_shells = tile_shells_for(bound, a.shell_winv);
         st.dyn.stale = stale ? 1u : 0u;
         }

@@ -31,7 +31,8 @@ struct PlanKArgs
     const double* rcutsq;
     const double* rinnersq; // optional (may be null): "core" class radius^2 per type pair
     uint32_t* slice_Kend;   // PLAN_SHELLS + 1 per slice, zeroed before the build kernel
-    uint32_t* slice_Kphase; // [2][n_slices]: core chunks (zeroed before the build kernel), sure chunks (set to ~0 before it)
+    uint32_t* slice_Kphase; // [2][n_slices]: core chunks (zeroed before the build kernel), sure chunks (set to ~0 before it);
+                            // diagnostic, no kernel consumes the phase counts
     uint32_t n_slices;
     double r_list_max;      // caller's hint (r_cut_max + 2 r_buff), 0 = unknown
     double r_list_estimate; // used when r_list_max is unknown: an estimate of r_cut_max + r_buff (0: one shell holds
@@ -424,7 +425,8 @@ __global__ void __launch_bounds__(PLAN_BUILD_THREADS) plan_build_kernel(const Pl
 #pragma unroll
             for (uint32_t sh = 0; sh <= PLAN_SHELLS; ++sh)
                 atomicMax(&a.slice_Kend[(PLAN_SHELLS + 1) * slice + sh], (seg[PLAN_CLS_SHELL0 + sh] + 8u * TPP - 1u) / (8u * TPP));
-            // row phases of the force kernel: chunks that cover the core entries, chunks made of core / sure entries alone
+            // ordering class and diagnostic (no kernel consumes the phase counts): chunks that cover the core entries,
+            // chunks made of core / sure entries alone
             atomicMax(&a.slice_Kphase[slice], (seg[PLAN_CLS_SURE] + 8u * TPP - 1u) / (8u * TPP));
             atomicMin(&a.slice_Kphase[a.n_slices + slice], seg[PLAN_CLS_NEAR] / (8u * TPP));
             }
@@ -579,7 +581,6 @@ void plan_free(PairPlan& p)
     if (p.d_slice_K) (void)hipFree(p.d_slice_K);
     if (p.d_slice_Kend) (void)hipFree(p.d_slice_Kend);
     if (p.d_slice_Kphase) (void)hipFree(p.d_slice_Kphase);
-    if (p.d_tile_ids) (void)hipFree(p.d_tile_ids);
     if (p.d_slice_head) (void)hipFree(p.d_slice_head);
     if (p.d_cnl) (void)hipFree(p.d_cnl);
     if (p.d_flags) (void)hipFree(p.d_flags);

@@ -41,6 +41,7 @@ constexpr double PLAN_FAR = 1.0e30;          // coordinate of the dummy slot
 constexpr uint32_t PLAN_SHELLS = 8;          // the Verlet-buffer entries of every row are ordered into this many shells
                                               // of equal width by their separation when the plan is built
 constexpr uint32_t PLAN_CLASSES = PLAN_SHELLS + 3; // row order: core | sure | near | shell 0 | ... | shell PLAN_SHELLS - 1
+                                                   // (the order fixes the summation order, hence the bits of every force)
 constexpr uint32_t PLAN_CLS_CORE = 0;  // closer than the evaluator's inner radius hint (azp_pair_args.d_rinnersq) at build time
 constexpr uint32_t PLAN_CLS_SURE = 1;  // certainly closer than r_cut - r_buff at build time (one particle type only): such a pair
                                        // stays inside the cutoff while no particle has moved farther than r_buff / 2
@@ -72,7 +73,9 @@ struct PairPlan
     uint32_t* d_slice_Kend = nullptr;      // (PLAN_SHELLS + 1) x n_slices: chunks up to the end of the in-range entries [0] /
                                            // of buffer shell s [1 + s]
     uint32_t* d_slice_Kphase = nullptr;    // [2][n_slices]: chunks covering every entry of class core [0][slice]; chunks up to which
-                                           // every row of the slice holds only entries of the classes core and sure [1][slice]
+                                           // every row of the slice holds only entries of the classes core and sure [1][slice].
+                                           // Ordering class and diagnostic (azp_pair_plan_phase_chunks); no kernel consumes the
+                                           // phase counts or the two radii below
     size_t cap_kphase = 0;
     float core_r = 0.f;                    // entries outside class core were at least this far apart at build time (the inner
                                            // radius hint minus a margin for the single-precision test); 0: no core class
@@ -106,15 +109,6 @@ struct PairPlan
     // host copy of d_tile_nstage: a launch over a sub-range of tiles (domain-decomposed
     // runs: interior | boundary) picks the LDS variant from the tiles it covers
     std::vector<uint32_t> h_tile_nstage;
-    // Two launches by staged-set size (pair_tiled.hpp: launch_tiled_cap). In a liquid the staged sets spread (1,400 ..
-    // 1,850 at the north star's density): the largest one used to pick the LDS variant of the WHOLE launch (2,048 slots,
-    // three workgroups per CU) although four tiles in five fit the 1,664-slot variant (four per CU). Tile numbers of the
-    // two groups, small first; made on the first launch after a build from h_tile_nstage.
-    mutable std::vector<uint32_t> h_tile_ids;
-    mutable uint32_t* d_tile_ids = nullptr;
-    mutable size_t cap_tile_ids = 0;
-    mutable uint64_t tile_ids_build = 0;
-    mutable uint32_t n_small_tiles = 0;
     };
 
 // Buffer shells a launch has to walk, from the caller's displacement bound: an entry of

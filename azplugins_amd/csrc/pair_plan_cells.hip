@@ -99,6 +99,7 @@ struct PlanCellsKArgs
     uint32_t* slice_K;
     uint32_t* slice_Kend;
     uint32_t* slice_Kphase; // [2][n_slices]: chunks covering class core; chunks holding only core / sure entries in every row
+                            // (diagnostic, no kernel consumes the phase counts)
     uint64_t* slice_head;
     uint4* cnl;
     uint32_t* flags;        // [0] sure radius, [1] invalid, [2] max staged set, [3] shell width, [4] most member cells of a tile, [5] longest row, [6] reason, [7] core radius
@@ -1328,7 +1329,7 @@ int plan_build_from_cells(PairPlan& p, const azp_nlist_args& c, const azp_pair_a
         __builtin_memcpy(&p.sure_r, &h_flags[0], sizeof(float));
         __builtin_memcpy(&p.core_r, &h_flags[7], sizeof(float));
         if (c.ntypes != 1)
-            p.sure_r = p.core_r = 0.f; // (the phases serve the one-type split form of an evaluator only)
+            p.sure_r = p.core_r = 0.f; // (ordering classes of the one-type split form of an evaluator only)
         }
     p.cap = plan_cap_for(p.max_stage);
     // identity of "the list" for the planned entry points: the plan's own raw rows and slice heads

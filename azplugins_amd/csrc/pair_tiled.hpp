@@ -8,19 +8,21 @@
 //   2. loop: each lane reads one 16-byte chunk = 8 u16 byte offsets per
 //      iteration (a wave reads 1 KiB contiguous), then for each of the 8
 //      neighbors three LDS gathers and the evaluator, software-pipelined in
-//      batches of 4 pairs. No global gathers, no minimum image, no row-length
-//      test (rows are padded with the dummy). Rows are ordered core | near |
-//      buffer shell A | B (pair_plan.hip): a batch with no pair in range is
-//      skipped after the separations, a batch with no pair in the evaluator's
-//      core uses the cheaper tail form (PerturbedLJ), and the row ends before
-//      the buffer entries when the caller bounds the displacement since the
-//      plan was built (skip_level).
+//      batches of 4 pairs. No global gathers, no minimum image (unless the tile
+//      is wide compared with the box), no row-length test (rows are padded with
+//      the dummy). Rows are ordered core | sure | near | buffer shell 0 .. 7
+//      (pair_plan.hpp): a batch with no pair in range is skipped after the
+//      separations, and a batch with no pair in the evaluator's core uses the
+//      cheaper tail form (PerturbedLJ); both are tested on the actual
+//      separations. The row ends after the buffer shells that the displacement
+//      since the plan was built can have brought into range (n_shells): from
+//      the caller's bound, from the words of the list's distance check, or per
+//      tile from per-particle displacements.
 //   3. DPP butterfly over the TPP lanes, lane 0 stores force (and virial).
 // Same evaluators, same outputs as pair_kernel.hpp; results agree with it to
 // rounding (the periodic shift is applied to r_j instead of to r_i - r_j).
 #pragma once
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "pair_kernel.hpp"
@@ -44,7 +46,6 @@ struct TileDyn
     {
     uint32_t n_shells;   // buffer shells to walk for the displacement measured by the check
     uint32_t stale;      // != 0: the plan does not describe the list any more -- leave at once (the call is repeated)
-    double bound;        // that displacement (< 0: unknown)
     };
 
 struct TiledKArgs
@@ -61,28 +62,17 @@ struct TiledKArgs
     const uint64_t* slice_head;
     const uint4* cnl;
     const uint8_t* perm;         // balanced plans (one lane per particle): lane -> member of the tile; NULL = identity
-    // Row phases (evaluators with a split form, one type pair): per slice the chunk count that covers every
-    // entry of class "core" [0] and the chunk count up to which every lane holds only entries of the classes
-    // core / sure [1] (pair_plan.hpp). With a displacement bound from the caller the chunks beyond [0] cannot
-    // hold a pair inside the evaluator's core, and the chunks [0] .. [1] hold only pairs that are certainly
-    // inside the cutoff: their tests are dropped (decided per wave from the bound and the radii below; exact).
-    const uint32_t* slice_Kcore;  // per slice; NULL: no phases
-    const uint32_t* slice_Ksure;
-    double bound;                 // the caller's displacement bound, < 0: unknown
-    float core_r, sure_r;         // class radii at build time, margins included; 0: class not built
+    const TileDyn* dyn;           // NULL: n_shells above is final
+    // the same idea with the raw words of the neighbor list's distance check (azp_pair_args.d_stale_flag,
+    // d_displacement_sq_bits): leave when *dflag != 0, displacement = sqrt(double(*dbits)) + bound_extra
+    const uint32_t* dflag;
+    const unsigned long long* dbits;
     // Local displacement bound (azp_pair_args.d_displacement): per-particle upper bounds on the distance moved since the
     // plan was built. A tile then walks the shells ITS members and staged neighbors can have crossed -- an entry of shell s
     // was at least r_cut + s w away, and the two particles of a pair have closed in by at most the sum of their own
     // displacements <= 2 x the largest one in the tile -- instead of the shells the fastest particle of the whole system
     // dictates. bound_extra is added to every entry (a plan compiled later than the positions the displacements refer to).
-    const uint32_t* tile_ids;     // NULL: workgroup b computes tile first / TB + b; else tile_ids[b], b < n_tile_ids
-    uint32_t n_tile_ids;
-    const TileDyn* dyn;           // NULL: n_shells / bound above are final
-    // the same idea with the raw words of the neighbor list's distance check (azp_pair_args.d_stale_flag,
-    // d_displacement_sq_bits): leave when *dflag != 0, bound = sqrt(double(*dbits)) + bound_extra
-    const uint32_t* dflag;
-    const unsigned long long* dbits;
-    const float* disp;            // n_max entries; NULL: the global bound above
+    const float* disp;            // n_max entries; NULL: n_shells above
     double shell_w;               // shell width of the plan
     double shell_winv;            // 1 / shell_w (0: no shells)
     double bound_extra;
@@ -115,20 +105,15 @@ __device__ __forceinline__ uint32_t tile_shells_for(double b, double shell_winv)
 // rate of ds_read_b64 (MI355X_MICROARCH.md, LDS table); an odd stride (CAP + 1) keeps them two
 // ds_read_b64: whole rows 0.143 -> 0.135 ms, MD cycle mean 0.127 -> 0.124 ms (the kernel is
 // as much LDS- as VALU-bound).
-#ifndef AZP_TILE_SOA_PAD
-#define AZP_TILE_SOA_PAD 1
-#endif
-#define AZP_TILE_STRIDE(CAP) ((CAP) + AZP_TILE_SOA_PAD)
+#define AZP_TILE_STRIDE(CAP) ((CAP) + 1)
 
-#ifndef AZP_TILE_BATCH
-#define AZP_TILE_BATCH 4 // pairs per register batch: 4 = half a chunk, 8 = a whole chunk
-#endif
+constexpr int TILE_BATCH = 4; // pairs per register batch: half a chunk (a whole chunk spills: 1,099 VGPRs)
 
-// A batch of gathered neighbor data (NB = 4: half a chunk, NB = 8: a whole chunk).
+// A batch of gathered neighbor data (half a chunk).
 struct TileBatch
     {
-    double x[AZP_TILE_BATCH], y[AZP_TILE_BATCH], z[AZP_TILE_BATCH];
-    uint32_t off[AZP_TILE_BATCH];
+    double x[TILE_BATCH], y[TILE_BATCH], z[TILE_BATCH];
+    uint32_t off[TILE_BATCH];
     };
 
 // the local-displacement fields of the kernel arguments (pair_tiled.hpp and xtiled.hpp launchers)
@@ -138,7 +123,7 @@ inline void fill_local_bound(TiledKArgs& k, const PairPlan& plan, const azp_pair
     // tracks displacements since the plan build at all; displacement_bound_extra covers a plan built later than the
     // reference positions of d_displacement
     const bool local = args.d_displacement && args.has_displacement_bound && args.displacement_bound >= 0.0;
-    k.disp = (local && tuning().local_bound != 0) ? args.d_displacement : nullptr;
+    k.disp = local ? args.d_displacement : nullptr;
     k.dflag = (args.d_stale_flag && args.d_displacement_sq_bits) ? args.d_stale_flag : nullptr;
     k.dbits = k.dflag ? args.d_displacement_sq_bits : nullptr;
     if (k.dflag)
@@ -148,35 +133,21 @@ inline void fill_local_bound(TiledKArgs& k, const PairPlan& plan, const azp_pair
     k.bound_extra = args.displacement_bound_extra > 0.0 ? args.displacement_bound_extra : 0.0;
     }
 
-// phase 1: issue the LDS gathers of a batch (half H of the chunk when NB = 4)
+// phase 1: issue the LDS gathers of a batch (half H of the chunk)
 template<int CAP, int H> __device__ __forceinline__ void tile_gather(TileBatch& b, const uint4& u, const char* bx)
     {
-    constexpr int NB = AZP_TILE_BATCH;
-    if (NB == 4)
-        {
-        const uint32_t w0 = H ? u.z : u.x, w1 = H ? u.w : u.y;
-        b.off[0] = w0 & 0xffffu;
-        b.off[1] = w0 >> 16;
-        b.off[2] = w1 & 0xffffu;
-        b.off[3] = w1 >> 16;
-        }
-    else
-        {
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int e = 0; e < NB; ++e)
-            b.off[e] = (e & 1) ? (w[(e >> 1) & 3] >> 16) : (w[(e >> 1) & 3] & 0xffffu);
-        }
+    constexpr int NB = TILE_BATCH;
+    const uint32_t w0 = H ? u.z : u.x, w1 = H ? u.w : u.y;
+    b.off[0] = w0 & 0xffffu;
+    b.off[1] = w0 >> 16;
+    b.off[2] = w1 & 0xffffu;
+    b.off[3] = w1 >> 16;
 #pragma unroll
     for (int e = 0; e < NB; ++e)
         {
-#if defined(AZP_ABLATE) && (AZP_ABLATE == 2)
-        b.x[e] = (double)b.off[e]; b.y[e] = 1.0; b.z[e] = 2.0; // ablation 2: no LDS gathers
-#else
         b.x[e] = *reinterpret_cast<const double*>(bx + b.off[e]);
         b.y[e] = *reinterpret_cast<const double*>(bx + b.off[e] + AZP_TILE_STRIDE(CAP) * 8);
         b.z[e] = *reinterpret_cast<const double*>(bx + b.off[e] + AZP_TILE_STRIDE(CAP) * 16);
-#endif
         }
     }
 
@@ -184,11 +155,7 @@ template<int CAP, int H> __device__ __forceinline__ void tile_gather(TileBatch& 
 // are formed first; if no lane of the wave has any of them inside the (largest)
 // cutoff, the evaluator work is skipped -- exact, and the common case at the far
 // end of the near-first ordered rows.
-// MODE (split evaluators only; everything else runs MODE 0): 0 = every test (pairs may be in the evaluator's
-// core, in its tail, or out of range), 1 = "sure": every pair of the batch is inside the cutoff and outside the
-// core -- no test at all, 2 = "tail": no pair is inside the core; cutoff test and the skip of batches without a
-// pair in range as in mode 0.
-template<class E, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR, bool WRAP, int MODE = 0>
+template<class E, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR, bool WRAP>
 __device__ __forceinline__ void tile_compute(const TileBatch& b, const TiledKArgs& a, const char* bt,
                                              const typename E::Coeff* __restrict__ s_coeff,
                                              const double* __restrict__ s_ronsq, const typename E::Coeff& c0, double ronsq0,
@@ -196,7 +163,7 @@ __device__ __forceinline__ void tile_compute(const TileBatch& b, const TiledKArg
                                              double& fz, double& pe, double (&v)[6], uint32_t& n_core, uint32_t& n_in, double (&es)[2])
     {
     typedef typename E::Coeff Coeff;
-    constexpr int NB = AZP_TILE_BATCH;
+    constexpr int NB = TILE_BATCH;
     constexpr bool SPLIT = SINGLE && !XPLOR && E::kSplitEnergy; // energy offsets counted, see EvalPLJ::eval_split
     double dx[NB], dy[NB], dz[NB], rsq[NB];
     bool any_in = false;
@@ -210,57 +177,30 @@ __device__ __forceinline__ void tile_compute(const TileBatch& b, const TiledKArg
         if (WRAP)
             rsq[e] = (b.off[e] == 0) ? 1.0e60 : rsq[e]; // the minimum image would fold the padding slot back into the box
                                                         // (1e60: out of range, and a product of four stays finite for rcp4)
-        if (MODE != 1)
-            any_in = any_in || (rsq[e] < rcutsq_max);
+        any_in = any_in || (rsq[e] < rcutsq_max);
         }
-#if defined(AZP_ABLATE) && (AZP_ABLATE == 3)
-    fx += rsq[0] + rsq[1] + rsq[2] + rsq[3]; // ablation 3: gathers + separations only
-    return;
-#endif
-    if (MODE != 1 && !__any(any_in))
+    // (SPLIT: the hint lays the code out for the walked part of a row, where some lane nearly always has a pair in range --
+    // rows end at the shell the displacement bound allows. Without it the register allocator parks the core path's energy
+    // accumulator in scratch inside the hot loop: +2 % on the north star, profiles/tile_kernel_options_removed.md)
+    const bool none_in = !__any(any_in);
+    if (SPLIT ? __builtin_expect(none_in, 0) : none_in)
         return;
-#ifdef AZP_TILE_LANE_MASK
-    // experiment: lanes without a pair in range in this batch sit the evaluator out (EXEC
-    // mask): the same issue cycles, fewer active FP64 lanes (the kernel runs into the power
-    // limit)
-    if (!any_in)
-        return;
-#endif
     double fd[NB]; // force / r of the batch (SPLIT: filled by one of two forms of the evaluator)
     if constexpr (SPLIT)
         {
         // one v_rcp_f64 for the four pairs of the batch (EvalPLJ::rcp4)
         double x[NB];
-#ifndef AZP_NO_RCP4
-        if constexpr (NB == 4)
-            E::rcp4(rsq, x);
-        else
-#endif
-            {
-#pragma unroll
-            for (int e = 0; e < NB; ++e)
-                x[e] = fast_rcp1(rsq[e]);
-            }
+        E::rcp4(rsq, x);
         // rows list the pairs inside the evaluator's core first (plan hint), so beyond
         // the first chunks no lane of the wave has one and the cheaper tail-only form
         // applies to the whole batch (exact: tested on the actual separations). Both
         // branches only produce fd[]; the accumulation below is shared, so the force
         // accumulators are not live-out of either branch (no register copies at the join).
         bool any_core = false;
-        if (MODE == 0)
-            {
 #pragma unroll
-            for (int e = 0; e < NB; ++e)
-                any_core = any_core || E::in_core(c0, rsq[e]);
-            }
-        if (MODE == 1)
-            {
-#pragma unroll
-            for (int e = 0; e < NB; ++e)
-                E::eval_split_sure(c0, x[e], fd[e], es[0], es[1]);
-            n_in += NB; // every pair of the batch is in range (finish_split ignores the count when the shift is zero)
-            }
-        else if (MODE == 2 || !__any(any_core))
+        for (int e = 0; e < NB; ++e)
+            any_core = any_core || E::in_core(c0, rsq[e]);
+        if (!__any(any_core))
             {
             const bool count_in = c0.tail_add != 0.0;
 #pragma unroll
@@ -324,82 +264,37 @@ __device__ __forceinline__ void tiled_loop(const TiledKArgs& a, const char* bx, 
                                            const typename E::Coeff* __restrict__ s_coeff,
                                            const double* __restrict__ s_ronsq, const typename E::Coeff& c0, double ronsq0,
                                            double rcutsq_max, const char* __restrict__ slice_base, uint32_t lane_off, uint32_t K,
-                                           uint32_t K1, uint32_t K2, double3 pi,
-                                           int typei, double& fx, double& fy, double& fz, double& pe, double (&v)[6], uint32_t& n_core,
+                                           double3 pi, int typei, double& fx, double& fy, double& fz, double& pe, double (&v)[6], uint32_t& n_core,
                                            uint32_t& n_in, double (&es)[2])
     {
     const uint4 zero4 = make_uint4(0, 0, 0, 0);
     // chunk kk of this lane: uniform base + kk KiB (scalar) + 16 lane (one VGPR)
-#if defined(AZP_ABLATE) && (AZP_ABLATE == 4)
-    // ablation 4: HALF the index stream (8 bytes per lane and chunk, used twice): same LDS gathers, same arithmetic
-    auto chunk_at = [&](uint32_t kk) -> uint4
-        {
-        const uint2 h = *reinterpret_cast<const uint2*>(slice_base + (uint64_t)kk * 512u + (lane_off >> 1));
-        return make_uint4(h.x, h.y, h.x, h.y);
-        };
-#else
     auto chunk_at = [&](uint32_t kk) -> uint4
         { return *reinterpret_cast<const uint4*>(slice_base + (uint64_t)kk * 1024u + lane_off); };
-#endif
-#if AZP_TILE_BATCH == 4
     // (prefetching the chunk indices two iterations ahead instead of one costs 9 more
     // spilled registers and measures 3 % slower)
     uint4 u = (K > 0) ? chunk_at(0) : zero4;
     uint4 un = (K > 1) ? chunk_at(1) : u;
     TileBatch A, B;
     tile_gather<CAP, 0>(A, u, bx);
-    uint32_t kk = 0;
-    // the three phases of a row (K1 = K2 = K: one phase, every test) share the pipeline state
-    auto run = [&](auto mode, const uint32_t kend)
+    for (uint32_t kk = 0; kk < K; ++kk)
         {
-        constexpr int MODE = decltype(mode)::value;
-        for (; kk < kend; ++kk)
-            {
-            // indices two chunks ahead (consumed 1.5 iterations from now: one iteration
-            // does not always cover an HBM round trip); past the end the last chunk is
-            // reloaded (an unconditional 16-byte load: a predicated one is split into
-            // four 4-byte loads)
-            const uint4 un2 = chunk_at((kk + 2 < K) ? kk + 2 : K - 1);
-            tile_gather<CAP, 1>(B, u, bx);
-            __builtin_amdgcn_sched_barrier(0);
-            tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP, MODE>(A, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
-            __builtin_amdgcn_sched_barrier(0);
-            tile_gather<CAP, 0>(A, un, bx); // when kk + 1 == K: gathered, never used
-            __builtin_amdgcn_sched_barrier(0);
-            tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP, MODE>(B, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
-            __builtin_amdgcn_sched_barrier(0);
-            u = un;
-            un = un2;
-            }
-        };
-    run(std::integral_constant<int, 0>(), K1);
-    if constexpr (SINGLE && !XPLOR && E::kSplitEnergy)
-        {
-        run(std::integral_constant<int, 1>(), K2);
-        run(std::integral_constant<int, 2>(), K);
-        }
-#else
-    // whole-chunk batches: chunk k+1's 24 gathers fly while chunk k is evaluated
-    uint4 u0 = (K > 0) ? chunk_at(0) : zero4;
-    uint4 u1 = (K > 1) ? chunk_at(1) : zero4;
-    TileBatch A, B;
-    tile_gather<CAP, 0>(A, u0, bx);
-    for (uint32_t kk = 0; kk < K; kk += 2)
-        {
-        const uint4 u2 = (kk + 2 < K) ? chunk_at(kk + 2) : zero4;
-        const uint4 u3 = (kk + 3 < K) ? chunk_at(kk + 3) : zero4;
-        tile_gather<CAP, 0>(B, u1, bx);
+        // indices two chunks ahead (consumed 1.5 iterations from now: one iteration
+        // does not always cover an HBM round trip); past the end the last chunk is
+        // reloaded (an unconditional 16-byte load: a predicated one is split into
+        // four 4-byte loads)
+        const uint4 un2 = chunk_at((kk + 2 < K) ? kk + 2 : K - 1);
+        tile_gather<CAP, 1>(B, u, bx);
         __builtin_amdgcn_sched_barrier(0);
         tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP>(A, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
         __builtin_amdgcn_sched_barrier(0);
-        tile_gather<CAP, 0>(A, u2, bx);
+        tile_gather<CAP, 0>(A, un, bx); // when kk + 1 == K: gathered, never used
         __builtin_amdgcn_sched_barrier(0);
-        if (kk + 1 < K)
-            tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP>(B, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
+        tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP>(B, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
         __builtin_amdgcn_sched_barrier(0);
-        u1 = u3;
+        u = un;
+        un = un2;
         }
-#endif
     }
 
 template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR>
@@ -417,26 +312,17 @@ __global__ void __launch_bounds__(256, E::kTileWaves) pair_forces_tiled_kernel(c
     double* s_ronsq = reinterpret_cast<double*>(s_coeff + (SINGLE ? 0 : a.p.ntypes * a.p.ntypes));
 
     const uint32_t tid = threadIdx.x;
-#ifndef AZP_NO_STAGE_PRIO
     // A new tile's waves share their SIMDs with three older waves that are deep in
     // the pair loop; raise the priority while staging so the short prologue is not
     // starved (tools/timeline.py: the staging took 17 of a tile's 41 us).
     __builtin_amdgcn_s_setprio(3);
-#endif
 #ifdef AZP_TIMELINE
     const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();
     const unsigned long long tl_c0 = __builtin_amdgcn_s_memtime(); // shader clock
     unsigned long long tl_tb = 0, tl_tc = 0, tl_td = 0, tl_ta = 0;
 #endif
     // a.p.first / a.p.end are tile-aligned outwards by the launcher
-    uint32_t tile = a.p.first / TB + xcd_remap(blockIdx.x, a.p.nblocks_padded);
-    if (a.tile_ids)
-        {
-        const uint32_t b = xcd_remap(blockIdx.x, a.p.nblocks_padded);
-        if (b >= a.n_tile_ids)
-            return;
-        tile = a.tile_ids[b];
-        }
+    const uint32_t tile = a.p.first / TB + xcd_remap(blockIdx.x, a.p.nblocks_padded);
     const uint32_t first = tile * TB;
     if (first >= a.p.end)
         return;
@@ -600,29 +486,18 @@ __global__ void __launch_bounds__(256, E::kTileWaves) pair_forces_tiled_kernel(c
             s_dmax[wave] = dmax;
         }
     const bool wide = __syncthreads_or(lane_wide); // also publishes the staged tile
-#ifndef AZP_NO_STAGE_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
 #ifdef AZP_TIMELINE
     const unsigned long long tl_t1 = __builtin_amdgcn_s_memrealtime();
 #endif
-    // the displacement bound of this tile and the shells it has to walk
-    double bound = a.dyn ? a.dyn->bound : a.bound;
+    // the shells this tile has to walk
     uint32_t n_shells = a.dyn ? min(a.dyn->n_shells, PLAN_SHELLS) : a.n_shells;
     if (a.dbits)
-        {
-        bound = to_uniform(sqrt(__longlong_as_double((long long)*a.dbits)) + a.bound_extra);
-        n_shells = tile_shells_for(bound, a.shell_winv);
-        if (!(bound >= 0.0) || !(bound < 1.0e300))
-            bound = -1.0;
-        }
+        n_shells = tile_shells_for(to_uniform(sqrt(__longlong_as_double((long long)*a.dbits)) + a.bound_extra), a.shell_winv);
     if (a.disp)
         {
         const float d4 = fmaxf(fmaxf(s_dmax[0], s_dmax[1]), fmaxf(s_dmax[2], s_dmax[3]));
-        bound = to_uniform((double)d4 + a.bound_extra); // NaN / inf displacements: whole rows, every test
-        n_shells = tile_shells_for(bound, a.shell_winv);
-        if (!(bound >= 0.0) || !(bound < 1.0e300))
-            bound = -1.0;
+        n_shells = tile_shells_for(to_uniform((double)d4 + a.bound_extra), a.shell_winv); // NaN / inf displacements: whole rows
         }
 
     const uint32_t slice = tile * 4 + wave;
@@ -641,31 +516,11 @@ __global__ void __launch_bounds__(256, E::kTileWaves) pair_forces_tiled_kernel(c
     double es[2] = {0.0, 0.0}; // tail-path energy sums (EvalPLJ::eval_split_tail)
     const char* bx = reinterpret_cast<const char*>(s_x);
     const char* bt = reinterpret_cast<const char*>(s_t);
-    // row phases: [0, K1) every test, [K1, K2) no test, [K2, K) no core test (see TiledKArgs)
-    uint32_t K1 = K, K2 = K;
-    if constexpr (SINGLE && !XPLOR && E::kSplitEnergy)
-        {
-        if (a.slice_Kcore && bound >= 0.0 && a.core_r > 0.f)
-            {
-            const double reach = 2.0 * bound;
-            const bool core_ok = E::core_radius(c0) + reach <= (double)a.core_r; // false for NaN (no interaction: c0.rcutsq < 0)
-            const bool sure_ok = core_ok && a.sure_r > 0.f && (double)a.sure_r + reach <= sqrt(c0.rcutsq);
-            if (core_ok)
-                {
-                K1 = to_uniform(min(a.slice_Kcore[slice], K));
-                K2 = sure_ok ? to_uniform(min(max(a.slice_Ksure[slice], K1), K)) : K1;
-                }
-            }
-        }
-#ifdef AZP_DEBUG_PHASES
-    if (tile == 7 && lane == 0)
-        printf("tile %u wave %u: K1 %u K2 %u K %u bound %g (global %g) core_r %g sure_r %g n_shells %u (global %u) wide %d\n", tile, wave, K1, K2, K, bound, a.bound, (double)a.core_r, (double)a.sure_r, n_shells, a.n_shells, (int)wide);
-#endif
     if (wide)
-        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, true>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, K, K1, K2, pi,
+        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, true>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, K, pi,
                                                             typei, fx, fy, fz, pe, v, n_core, n_in, es);
     else
-        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, false>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, K, K1, K2, pi,
+        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, false>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, K, pi,
                                                              typei, fx, fy, fz, pe, v, n_core, n_in, es);
     if constexpr (SINGLE && !XPLOR && E::kSplitEnergy)
         pe = E::finish_split(c0, pe, es[0], es[1], n_core, n_in);
@@ -706,9 +561,8 @@ __global__ void __launch_bounds__(256, E::kTileWaves) pair_forces_tiled_kernel(c
 
 // Arguments of a tile kernel (this one and xtiled.hpp's) for the tiles of tb particles a launch covers: sub-range
 // launches are rounded outwards to whole tiles (a tile computed by two launches of one step gets the later launch's
-// values: stream order); with tile_ids, those n_tile_ids tiles only. No row phases, no global displacement bound.
-inline TiledKArgs make_tiled_kargs(const PairPlan& plan, const azp_pair_args& args, const TileDyn* dyn, uint32_t tb,
-                                   const uint32_t* tile_ids = nullptr, uint32_t n_tile_ids = 0)
+// values: stream order).
+inline TiledKArgs make_tiled_kargs(const PairPlan& plan, const azp_pair_args& args, const TileDyn* dyn, uint32_t tb)
     {
     TiledKArgs k = {};
     k.p = make_pair_kargs(args);
@@ -719,7 +573,6 @@ inline TiledKArgs make_tiled_kargs(const PairPlan& plan, const azp_pair_args& ar
     k.slice_K = plan.d_slice_K;
     k.slice_Kend = plan.d_slice_Kend;
     k.n_shells = plan_shells_for(plan, args);
-    k.bound = -1.0;
     fill_local_bound(k, plan, args);
     k.dyn = dyn;
     k.slice_head = plan.d_slice_head;
@@ -727,9 +580,7 @@ inline TiledKArgs make_tiled_kargs(const PairPlan& plan, const azp_pair_args& ar
     const uint32_t t0 = k.p.first / tb, t1 = (k.p.end + tb - 1) / tb;
     k.p.first = t0 * tb;
     k.p.end = (t1 * tb < args.N) ? t1 * tb : args.N;
-    k.tile_ids = tile_ids;
-    k.n_tile_ids = n_tile_ids;
-    k.p.nblocks_padded = ((tile_ids ? n_tile_ids : t1 - t0) + 7u) & ~7u;
+    k.p.nblocks_padded = (t1 - t0 + 7u) & ~7u;
     return k;
     }
 
@@ -746,86 +597,23 @@ inline uint32_t plan_launch_cap(const PairPlan& plan, const azp_pair_args& args,
     return plan_cap_for(most);
     }
 
-template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR>
-int launch_tiled_instance2(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params,
-                          hipStream_t stream, const TileDyn* dyn, const uint32_t* tile_ids = nullptr, uint32_t n_tile_ids = 0)
+template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE>
+int launch_tiled_instance(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params,
+                          hipStream_t stream, const TileDyn* dyn)
     {
-    TiledKArgs k = make_tiled_kargs(plan, args, dyn, plan.tile, tile_ids, n_tile_ids);
-    const bool phases = tuning().row_phases != 0; // (azp_tuning_set: A/B measurements)
-    k.slice_Kcore = phases ? plan.d_slice_Kphase : nullptr;
-    k.slice_Ksure = (phases && plan.d_slice_Kphase) ? plan.d_slice_Kphase + plan.n_slices : nullptr;
-    k.bound = (args.has_displacement_bound && args.displacement_bound >= 0.0) ? args.displacement_bound : -1.0;
-    k.core_r = plan.core_r;
-    k.sure_r = plan.sure_r;
+    const TiledKArgs k = make_tiled_kargs(plan, args, dyn, plan.tile);
     size_t lds = (size_t)AZP_TILE_STRIDE(CAP) * 24 + (SINGLE ? 0 : (size_t)CAP * 4 + 8);
     if (!SINGLE)
         lds += (sizeof(typename E::Coeff) + sizeof(double)) * (size_t)args.ntypes * args.ntypes;
-    return launch_dyn_lds(pair_forces_tiled_kernel<E, TPP, CAP, VIRIAL, SINGLE, XPLOR>, k.p.nblocks_padded, 256, TPP, lds, stream, k, d_params);
-    }
-
-template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE>
-int launch_tiled_instance(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params,
-                          hipStream_t stream, const TileDyn* dyn, const uint32_t* tile_ids = nullptr, uint32_t n_tile_ids = 0)
-    {
     if (args.shift_mode == AZP_SHIFT_XPLOR)
-        return launch_tiled_instance2<E, TPP, CAP, VIRIAL, SINGLE, true>(plan, args, d_params, stream, dyn, tile_ids, n_tile_ids);
-    return launch_tiled_instance2<E, TPP, CAP, VIRIAL, SINGLE, false>(plan, args, d_params, stream, dyn, tile_ids, n_tile_ids);
-    }
-
-// tile numbers of the two groups of a split launch (see PairPlan::h_tile_ids), uploaded once per build
-inline int plan_split_tiles(const PairPlan& plan, hipStream_t s)
-    {
-    if (plan.tile_ids_build == plan.builds && plan.d_tile_ids)
-        return AZP_SUCCESS;
-    const uint32_t n = plan.n_tiles;
-    plan.h_tile_ids.resize(n);
-    uint32_t small = 0;
-    for (uint32_t t = 0; t < n; ++t)
-        if (plan.h_tile_nstage[t] + 1u <= 1664u)
-            plan.h_tile_ids[small++] = t;
-    uint32_t large = small;
-    for (uint32_t t = 0; t < n; ++t)
-        if (plan.h_tile_nstage[t] + 1u > 1664u)
-            plan.h_tile_ids[large++] = t;
-    if (plan.cap_tile_ids < n)
-        {
-        if (plan.d_tile_ids) (void)hipFree(plan.d_tile_ids);
-        plan.d_tile_ids = nullptr;
-        plan.cap_tile_ids = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&plan.d_tile_ids), sizeof(uint32_t) * (size_t)(n + 64));
-        if (e != hipSuccess)
-            return (int)e;
-        plan.cap_tile_ids = n + 64;
-        }
-    hipError_t e = hipMemcpyAsync(plan.d_tile_ids, plan.h_tile_ids.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess)
-        return (int)e;
-    plan.n_small_tiles = small;
-    plan.tile_ids_build = plan.builds;
-    return AZP_SUCCESS;
+        return launch_dyn_lds(pair_forces_tiled_kernel<E, TPP, CAP, VIRIAL, SINGLE, true>, k.p.nblocks_padded, 256, TPP, lds, stream, k, d_params);
+    return launch_dyn_lds(pair_forces_tiled_kernel<E, TPP, CAP, VIRIAL, SINGLE, false>, k.p.nblocks_padded, 256, TPP, lds, stream, k, d_params);
     }
 
 template<class E, int TPP, bool VIRIAL, bool SINGLE>
 int launch_tiled_cap(const PairPlan& plan, const azp_pair_args& args, const typename E::Params* d_params, hipStream_t s, const TileDyn* dyn)
     {
     const uint32_t cap = plan_launch_cap(plan, args, plan.tile);
-    if (TPP == 1 && args.range_count == 0 && cap > 1664u && tuning().split_tiles && plan.h_tile_nstage.size() == plan.n_tiles)
-        {
-        // a liquid: the tiles that fit the 1,664-slot variant (four workgroups per CU) first, then the rest
-        const int rc = plan_split_tiles(plan, s);
-        if (rc != AZP_SUCCESS)
-            return rc;
-        const uint32_t n_small = plan.n_small_tiles, n_large = plan.n_tiles - n_small;
-        if (n_small * 2u >= plan.n_tiles && n_large > 0)
-            {
-            const int r1 = launch_tiled_instance<E, TPP, 1664, VIRIAL, SINGLE>(plan, args, d_params, s, dyn, plan.d_tile_ids, n_small);
-            if (r1 != AZP_SUCCESS)
-                return r1;
-            if (cap == 2048u)
-                return launch_tiled_instance<E, TPP, 2048, VIRIAL, SINGLE>(plan, args, d_params, s, dyn, plan.d_tile_ids + n_small, n_large);
-            return launch_tiled_instance<E, TPP, 2560, VIRIAL, SINGLE>(plan, args, d_params, s, dyn, plan.d_tile_ids + n_small, n_large);
-            }
-        }
     switch (cap)
         {
     case 1024: return launch_tiled_instance<E, TPP, 1024, VIRIAL, SINGLE>(plan, args, d_params, s, dyn);

@@ -189,18 +189,13 @@ __global__ void __launch_bounds__(256, X::kMinWaves) xtiled_kernel(const TiledKA
         for (uint32_t t = 0; t < a.p.ntypes * a.p.ntypes; ++t)
             rcutsq_max = fmax(rcutsq_max, a.p.rcutsq[t]);
 
-#if defined(AZP_XTILED_ABLATE) && AZP_XTILED_ABLATE == 1
-    const uint32_t Kloop = 0; // ablation: staging only
-#else
-    const uint32_t Kloop = K;
-#endif
     auto walk = [&](auto wide_tag)
         {
         constexpr bool WIDE = decltype(wide_tag)::value;
-        uint4 u = (Kloop > 0) ? rows[0] : make_uint4(0, 0, 0, 0);
-        for (uint32_t kk = 0; kk < Kloop; ++kk)
+        uint4 u = (K > 0) ? rows[0] : make_uint4(0, 0, 0, 0);
+        for (uint32_t kk = 0; kk < K; ++kk)
             {
-            const uint4 un = rows[(uint64_t)((kk + 1 < Kloop) ? kk + 1 : kk) * 64u]; // next chunk in flight
+            const uint4 un = rows[(uint64_t)((kk + 1 < K) ? kk + 1 : kk) * 64u]; // next chunk in flight
             const uint32_t w[4] = {u.x, u.y, u.z, u.w};
             uint32_t slot[8];
             double dx[8], dy[8], dz[8], rsq[8];

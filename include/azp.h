@@ -252,8 +252,8 @@ typedef struct azp_pair_plan_info
                                     entry points (the plan is its own list; there is no u32 list) */
     int32_t balanced;            /* 1: rows handed to the lanes in the order of their in-range lengths
                                     (azp_pair_plan_set_balance) */
-    float core_radius;           /* row phases (one particle type): entries outside row class "core" were at least this
-                                    far apart when the plan was built; 0: no such class */
+    float core_radius;           /* ordering class and diagnostic (one particle type; no kernel consumes it): entries outside
+                                    row class "core" were at least this far apart when the plan was built; 0: no such class */
     float sure_radius;           /* ... entries of row class "sure" at most this far apart; 0: no such class */
     uint32_t max_member_cells;   /* azp_pair_plan_build_from_cells, cells of the full list radius: the largest number of
                                     distinct cells the members of one tile sit in (beyond 128 the plan is refused with
@@ -281,9 +281,9 @@ int azp_pair_plan_tile_stage(const azp_pair_plan* plan, uint32_t* out, uint32_t 
  * live for more than ~50 force calls; callers that rebuild more often turn it off. */
 int azp_pair_plan_set_bank_order(azp_pair_plan* plan, int enabled);
 int azp_pair_plan_query(const azp_pair_plan* plan, azp_pair_plan_info* info);
-/* Diagnostics (copies from the device, synchronises): the row phases of the last build as means over the slices --
- * out[0] chunks that cover the core entries, out[1] chunks up to the end of the all-sure part of the rows, out[2]
- * chunks of the whole rows. */
+/* Diagnostics (copies from the device, synchronises; no kernel consumes the phase counts): the row classes of the
+ * last build as means over the slices -- out[0] chunks that cover the core entries, out[1] chunks up to the end of
+ * the all-sure part of the rows, out[2] chunks of the whole rows. */
 int azp_pair_plan_phase_chunks(const azp_pair_plan* plan, float out[3]);
 
 /* The plan cache behind azp_pair_forces_* (diagnostics and tests). */
@@ -814,16 +814,10 @@ const char* azp_status_string(int status);
 /* Resolved launch configuration of the last pair-force call on this thread
  * (for benchmarks / profiling reports). */
 void azp_last_launch(uint32_t* block_size, uint32_t* threads_per_particle, uint32_t* grid, uint32_t* lds_bytes);
-/* Process-wide switches of the tile kernels, for A/B measurements (results are identical either way):
- * AZP_TUNE_ROW_PHASES (default 0: it measures 1.5 % slower on the north star although it issues fewer
- * instructions): the test-free / core-test-free parts of a row (csrc/pair_tiled.hpp);
- * AZP_TUNE_LOCAL_BOUND (default 1): azp_pair_args.d_displacement is used when given;
- * AZP_TUNE_SPLIT_TILES (default 0: measured 5 % slower; AZP_SPLIT_TILES=1): plans whose largest staged set needs more than
- * 1,664 LDS slots are launched in two parts, the tiles that fit the 1,664-slot variant (four workgroups per CU) and the rest.
- * Returns the previous value, or -1 for an unknown key. The environment variables AZP_ROW_PHASES=1 /
- * AZP_LOCAL_BOUND=0 set the initial values. */
-enum { AZP_TUNE_ROW_PHASES = 1, AZP_TUNE_LOCAL_BOUND = 2, AZP_TUNE_SPLIT_TILES = 3 };
-int azp_tuning_set(int key, int value);
+/* The library has no process-wide switches. Two exact options of the tile kernel were measured and removed (last
+ * present in 26438a0): test-free / core-test-free row phases (1.5 % slower on the north star although
+ * they issue fewer instructions) and two launches by staged-set size (5 % slower). azp_pair_args.d_displacement is used
+ * whenever it is given together with a valid displacement bound. */
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,6 @@ MODE = dict({n: "shift" for n in ISO}, dpd="none", tpm="shift")
 CAPS = [1024, 1536, 1664, 2048, 2560]
 R_BUFF = 0.3
 LDS_LIMIT = 160 * 1024
-SPLIT_TILES = 3  # AZP_TUNE_SPLIT_TILES
 DPD_KW = dict(kT=1.0, dt=0.01, seed=7, timestep=4242)
 _PACK = {"dpd": "DPDGeneralWeight", "tpm": "TwoPatchMorse"}
 _ENTRY = dict(H.ENTRY, dpd="azp_dpd_forces_general_weight", tpm="azp_aniso_forces_two_patch_morse")
@@ -282,26 +281,16 @@ def test_staged_set_over_budget():
 @pytest.mark.parametrize("big", [2048, 2560])
 @pytest.mark.parametrize("T", [1, 3])
 @pytest.mark.parametrize("name", ISO)
-def test_split_launch(name, T, big):
-    """AZP_TUNE_SPLIT_TILES: the tiles that fit 1,664 slots, then the rest at `big` slots; bit-identical to one launch."""
+def test_largest_lds_variants(name, T, big):
+    """A plan in which most tiles would fit 1,664 slots and a few need `big`: one launch of the `big`-slot instance."""
     key = (big - 1, 256, S.LIQUID)  # as many isolated particles as liquid ones: half the tiles stage nothing
     stage = _stages(key, 256)
     large = int((stage + 1 > 1664).sum())
     assert 2 * (stage.size - large) >= stage.size and large > 0
-    lib = _lib.lib()
-    old = lib.azp_tuning_set(SPLIT_TILES, 0)
-    try:
-        out = _run(name, T, "shift", True, 1, key, "planned")
-        assert out["launch"]["lds_bytes"] == _tile_lds(big, T, name)
-        assert out["launch"]["grid"] == (stage.size + 7) & ~7
-        lib.azp_tuning_set(SPLIT_TILES, 1)
-        split = out["again"]()
-    finally:
-        lib.azp_tuning_set(SPLIT_TILES, old)
-    # the second part of the split launch: the large tiles alone, at `big` slots
-    assert split["launch"]["lds_bytes"] == _tile_lds(big, T, name) and split["launch"]["grid"] == (large + 7) & ~7
-    assert np.array_equal(split["f"], out["f"]) and np.array_equal(split["v"], out["v"])
-    _check(split, _ref(name, T, "shift", key), True, "split")
+    out = _run(name, T, "shift", True, 1, key, "planned")
+    assert out["launch"]["lds_bytes"] == _tile_lds(big, T, name)
+    assert out["launch"]["grid"] == (stage.size + 7) & ~7
+    _check(out, _ref(name, T, "shift", key), True, "largest LDS variants")
 
 
 def test_sub_range_launch_takes_the_smaller_instance():

@@ -7,7 +7,6 @@ clock and thermal drift hit both alike.
     variants: comma-separated key=value settings of the potential / environment-free knobs:
       local=0|1   per-particle displacements passed or not
       bound=0|1   displacement bound passed or not (whole rows)
-      phases=0|1  row phases of the tile kernel (azp_tuning_set)
 """
 import argparse
 import os
@@ -66,8 +65,6 @@ def main():
                 pot.use_local_displacement = bool(int(val))
             elif k == "bound":
                 pot.use_displacement_bound = bool(int(val))
-            elif k == "phases":
-                azp._lib.lib().azp_tuning_set(1, int(val))
             else:
                 raise SystemExit("unknown knob %r" % k)
 

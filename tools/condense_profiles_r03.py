@@ -140,8 +140,8 @@ open(os.path.join(P, "r03_md_bench.log"), "w").write("\n".join(logs) + "\n")
 ab = ["# A/B of the two tile-kernel options of round 3 (tools/ab_cycle.py: one process, variants alternate pass by pass, a pass = 8 cycle states x 100 launches)", "", "```"]
 if os.path.exists(os.path.join(O, "ab_cycle.log")):
     ab += [l.rstrip() for l in open(os.path.join(O, "ab_cycle.log"))]
-ab += ["```", "", "phases = the test-free / core-test-free row phases (azp_tuning_set AZP_TUNE_ROW_PHASES), local = per-particle displacement bounds "
-       "(azp_pair_args.d_displacement). Both are exact; both issue fewer LDS gathers or VALU instructions and both run SLOWER: off by default."]
+ab += ["```", "", "phases = the test-free / core-test-free row phases (removed; last present in 26438a0), local = per-particle displacement bounds "
+       "(azp_pair_args.d_displacement). Both are exact; both issue fewer LDS gathers or VALU instructions and both run SLOWER: the phases are gone, the local bounds are opt-in."]
 if os.path.exists(os.path.join(O, "entry.log")):
     ab += ["", "# The HOOMD-signature entry (tests/test_gpu_auto_plan.py::test_hoomd_signature_entry_runs_at_plan_speed, N = 2^20)", "", "```", open(os.path.join(O, "entry.log")).read().strip(), "```"]
 for f in ("c4_noprof.log", "c5_noprof.log"):
