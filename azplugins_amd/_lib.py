@@ -318,6 +318,34 @@ class EvaporateArgs(C.Structure):
     ]
 
 
+WALL_MAX = 16
+WALL_PARAM_DOUBLES = 8
+WALL_PLANE = 0
+WALL_SPHERE = 1
+WALL_CYLINDER = 2
+
+
+class Wall(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("inside", C.c_uint32), ("origin", C.c_double * 3), ("axis", C.c_double * 3),
+                ("radius", C.c_double)]
+
+
+class WallArgs(C.Structure):
+    _fields_ = [
+        ("d_force", C.c_void_p),
+        ("d_virial", C.c_void_p),
+        ("virial_pitch", C.c_uint64),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("d_pos", C.c_void_p),
+        ("box", Box),
+        ("d_params", C.c_void_p),
+        ("n_walls", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("walls", Wall * WALL_MAX),
+    ]
+
+
 # every symbol include/azp.h declares: name -> (restype, argtypes)
 _D = C.c_double
 _PD = C.POINTER(C.c_double)
@@ -396,6 +424,13 @@ SYMBOLS = {
     "azp_velocity_field_normalize": (C.c_int, [_VP, C.c_uint64, _VP, _VP]),
     "azp_thermo_scratch_size": (C.c_int, [C.POINTER(ThermoArgs), C.POINTER(C.c_uint64)]),
     "azp_thermo_sums": (C.c_int, [C.POINTER(ThermoArgs), _VP]),
+    "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
+    "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
+    "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),
+    "azp_wall_forces_colloid": (C.c_int, [C.POINTER(WallArgs), _VP]),
+    "azp_wall_net_forces_scratch_size": (C.c_int, [C.POINTER(WallArgs), C.POINTER(C.c_uint64)]),
+    "azp_wall_net_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP, _VP, C.c_uint64, _VP]),
+    "azp_wall_net_forces_colloid": (C.c_int, [C.POINTER(WallArgs), _VP, _VP, C.c_uint64, _VP]),
     "azp_version": (C.c_int, []),
     "azp_status_string": (C.c_char_p, [C.c_int]),
     "azp_last_launch": (None, [C.POINTER(C.c_uint32)] * 4),

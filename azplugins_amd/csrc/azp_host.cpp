@@ -106,6 +106,93 @@ void azp_quartic_params_unpack(const azp_quartic_params* p, double* k, double* r
     *delta = p->delta;
     }
 
+// ---- wall potentials: one type's dict folded into its parameter row (include/azp.h, "wall potentials") ----
+// V and F = -dV/dr in plain IEEE double, in the order written: tests/wall_ref.py restates the two folds and agrees
+// to a few ulp. src/WallEvaluatorLJ93.h:34-48 gives V and F / r for LJ93, src/WallEvaluatorColloid.h:36-41 for the
+// colloid; F of the colloid is our own derivative of V:
+//   d/dz (7a - z) / (z - a)^7 = 6 (z - 8a) / (z - a)^8,   d/dz (7a + z) / (z + a)^7 = -6 (z + 8a) / (z + a)^8,
+//   d/dz [2az / (z^2 - a^2) + ln((z - a) / (z + a))] = -4 a^3 / (z^2 - a^2)^2.
+static void wall_lj93_at(double epsilon, double sigma, double r, double* V, double* F)
+    {
+    const double s = sigma / r;
+    const double s3 = s * s * s;
+    const double s9 = s3 * s3 * s3;
+    *V = epsilon * ((2.0 / 15.0) * s9 - s3);
+    *F = epsilon * (1.2 * s9 - 3.0 * s3) / r;
+    }
+
+static void wall_colloid_at(double C1, double C2, double a, double z, double* V, double* F)
+    {
+    const double m = z - a, p = z + a;
+    const double m2 = m * m, p2 = p * p;
+    const double m4 = m2 * m2, p4 = p2 * p2;
+    const double m7 = m4 * m2 * m, p7 = p4 * p2 * p;
+    const double q = z * z - a * a;
+    *V = C1 * ((7.0 * a - z) / m7 + (7.0 * a + z) / p7) - C2 * (2.0 * a * z / q + std::log(m / p));
+    *F = 6.0 * C1 * ((8.0 * a - z) / (m7 * m) + (8.0 * a + z) / (p7 * p)) - 4.0 * C2 * (a * a * a) / (q * q);
+    }
+
+static int wall_row_check(double r_cut, double r_extrap, int shift_mode, double* row)
+    {
+    if (!row)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    for (int k = 0; k < AZP_WALL_PARAM_DOUBLES; ++k)
+        row[k] = 0.0;
+    if (!(r_cut >= 0.0) || !(r_extrap >= 0.0) || (r_cut > 0.0 && r_extrap >= r_cut)
+        || (shift_mode != AZP_SHIFT_NONE && shift_mode != AZP_SHIFT_SHIFT))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    return AZP_SUCCESS;
+    }
+
+int azp_wall_lj93_params_make(double epsilon, double sigma, double r_cut, double r_extrap, int shift_mode, double* row)
+    {
+    const int rc = wall_row_check(r_cut, r_extrap, shift_mode, row);
+    if (rc != AZP_SUCCESS)
+        return rc;
+    if (epsilon == 0.0 || r_cut == 0.0)
+        return AZP_SUCCESS; // feels nothing: a row of zeros
+    row[0] = epsilon; // (not folded into epsilon sigma^9, epsilon sigma^3: see EvalWallLJ93 in wall_forces.hip)
+    row[1] = sigma;
+    row[2] = r_cut;
+    row[3] = r_extrap;
+    double V, F;
+    if (shift_mode == AZP_SHIFT_SHIFT)
+        {
+        wall_lj93_at(epsilon, sigma, r_cut, &V, &F);
+        row[4] = V; // the reference evaluates it per particle ("could be cached once per type", WallEvaluatorLJ93.h:126)
+        }
+    if (r_extrap > 0.0)
+        wall_lj93_at(epsilon, sigma, r_extrap, &row[5], &row[6]);
+    return AZP_SUCCESS;
+    }
+
+int azp_wall_colloid_params_make(double A, double sigma, double a, double r_cut, double r_extrap, int shift_mode, double* row)
+    {
+    const int rc = wall_row_check(r_cut, r_extrap, shift_mode, row);
+    if (rc != AZP_SUCCESS)
+        return rc;
+    if (A == 0.0 || !(a > 0.0) || r_cut == 0.0)
+        return AZP_SUCCESS;
+    if (r_cut <= a || (r_extrap > 0.0 && r_extrap <= a))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    const double s2 = sigma * sigma;
+    const double C1 = A * (s2 * s2 * s2) / 7560.0, C2 = A / 6.0;
+    row[0] = C1;
+    row[1] = C2;
+    row[2] = r_cut;
+    row[3] = r_extrap;
+    row[7] = a;
+    double V, F;
+    if (shift_mode == AZP_SHIFT_SHIFT)
+        {
+        wall_colloid_at(C1, C2, a, r_cut, &V, &F);
+        row[4] = V;
+        }
+    if (r_extrap > 0.0)
+        wall_colloid_at(C1, C2, a, r_extrap, &row[5], &row[6]);
+    return AZP_SUCCESS;
+    }
+
 int azp_version(void)
     {
     return AZP_VERSION_MAJOR * 1000 + AZP_VERSION_MINOR;

@@ -65,7 +65,8 @@ class ConstantFlow(FlowField):
 
 class ParabolicFlow(FlowField):
     """Parabolic flow between parallel plates at y = +-separation/2: u_x(y) = 3/2 U (1 - (y / H)^2), H =
-    separation / 2, along x with the gradient in y. The walls are the user's business (e.g. harmonic barriers)."""
+    separation / 2, along x with the gradient in y. The walls are the user's business (e.g. a
+    two-plane ``wall.LJ93`` slit, or harmonic barriers)."""
 
     def __init__(self, mean_velocity, separation):
         self.mean_velocity = mean_velocity
