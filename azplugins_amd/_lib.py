@@ -250,6 +250,30 @@ class ThermoArgs(C.Structure):
     ]
 
 
+RDF_MAX_BINS = 8192
+RDF_PATH_AUTO, RDF_PATH_ALL_PAIRS, RDF_PATH_CELLS = 0, 1, 2
+
+
+class RdfArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("N", C.c_uint32),
+        ("n_total", C.c_uint32),
+        ("box", Box),
+        ("ntypes", C.c_uint32),
+        ("num_bins", C.c_uint32),
+        ("d_type_mask_a", C.c_void_p),
+        ("d_type_mask_b", C.c_void_p),
+        ("r_max", C.c_double),
+        ("scale", C.c_double),
+        ("path", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("d_out", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 FLOW_CONSTANT = 0
 FLOW_PARABOLIC = 1
 
@@ -424,6 +448,8 @@ SYMBOLS = {
     "azp_velocity_field_normalize": (C.c_int, [_VP, C.c_uint64, _VP, _VP]),
     "azp_thermo_scratch_size": (C.c_int, [C.POINTER(ThermoArgs), C.POINTER(C.c_uint64)]),
     "azp_thermo_sums": (C.c_int, [C.POINTER(ThermoArgs), _VP]),
+    "azp_rdf_scratch_size": (C.c_int, [C.POINTER(RdfArgs), C.POINTER(C.c_uint64)]),
+    "azp_rdf_counts": (C.c_int, [C.POINTER(RdfArgs), _VP]),
     "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
     "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
     "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),

@@ -11,6 +11,10 @@ the sums are added over the domain's process group and every rank gets the same 
 of a group from one deterministic pass over the particles (``csrc/thermo.hip``); ``ThermodynamicRecorder`` appends the
 sums of that pass to a device table at the timesteps its trigger fires inside ``Simulation.run``, without a host
 synchronisation.
+
+``RadialDistributionFunction`` is g(r) between two groups from exact integer pair counts (``csrc/rdf.hip``; not part of
+the reference: azplugins had ``analyze.rdf`` in its HOOMD-2 line, the semantics are this project's, DESIGN 4.14);
+``RDFRecorder`` appends the counts to a device table inside ``Simulation.run`` in the same way.
 """
 
 import ctypes as C
@@ -450,21 +454,16 @@ for _name in THERMO_PROPERTIES:
     setattr(ThermodynamicQuantities, _name, _thermo_property(_name))
 
 
-class ThermodynamicRecorder:
-    """Writer (``sim.operations.writers``) that appends the sums behind ``thermo`` (a ``ThermodynamicQuantities`` in
-    ``computes`` of the same simulation) to a device table at the timesteps ``trigger`` (an ``int`` period or a
-    ``Periodic``) fires -- the kernel writes straight into row k of the table, nothing is read back and the host never
-    waits. In ``run(n)`` starting at timestep t0 the trigger is evaluated at t0 + 1 ... t0 + n; the row of timestep t
-    is the state after t complete steps (after step two, with the forces of that configuration). ``Simulation.run``
-    runs step two of that step on its own there instead of fused with the next step one: the trajectory is the same
-    bit for bit with and without a recorder. ``timesteps`` and ``table`` are read after the run."""
+class _Recorder:
+    """What the recorders share: a compute of the same simulation (``_compute``), a trigger, and a device table of one
+    row per recorded timestep that the compute's kernel writes straight into -- nothing is read back and the host
+    never waits. The table grows by doubling; the copy is queued on the stream like everything else."""
 
-    def __init__(self, thermo, trigger):
-        if not isinstance(thermo, ThermodynamicQuantities):
-            raise _lib.AzpError("ThermodynamicRecorder: thermo must be a ThermodynamicQuantities, got %r" % (thermo,))
-        self.thermo = thermo
+    _dtype = "float64"
+
+    def __init__(self, trigger):
         self.trigger = trigger if isinstance(trigger, Periodic) else Periodic(trigger)
-        self._rows = None  # (capacity, 20) device tensor
+        self._rows = None  # (capacity, row width) device tensor
         self._steps = []
 
     def timesteps_in_run(self, t0, n):
@@ -477,20 +476,47 @@ class ThermodynamicRecorder:
 
         st = sim.state
         k = len(self._steps)
+        width = self._row_width()
         rows = self._rows
-        if rows is None or rows.device != st.device or k >= rows.shape[0]:
+        if rows is not None and k and rows.shape[1] != width:
+            raise _lib.AzpError("%s: the row width changed from %d to %d with rows recorded; call reset() first"
+                                % (type(self).__name__, rows.shape[1], width))
+        if rows is None or rows.device != st.device or k >= rows.shape[0] or rows.shape[1] != width:
             # (grown by doubling; the copy is queued on the stream like everything else)
-            grown = torch.empty((max(64, 2 * k), _lib.THERMO_NSUMS), dtype=torch.float64, device=st.device)
+            grown = torch.empty((max(64, 2 * k), width), dtype=getattr(torch, self._dtype), device=st.device)
             if k:
                 grown[:k].copy_(rows[:k])
             self._rows = rows = grown
-        self.thermo._launch(rows.data_ptr() + k * _lib.THERMO_NSUMS * 8)
+        self._compute._launch(rows.data_ptr() + k * width * 8)
         self._steps.append(int(timestep))
 
     @property
     def timesteps(self):
         """numpy int64: the timesteps recorded so far."""
         return np.array(self._steps, dtype=np.int64)
+
+
+class ThermodynamicRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) that appends the sums behind ``thermo`` (a ``ThermodynamicQuantities`` in
+    ``computes`` of the same simulation) to a device table at the timesteps ``trigger`` (an ``int`` period or a
+    ``Periodic``) fires -- the kernel writes straight into row k of the table, nothing is read back and the host never
+    waits. In ``run(n)`` starting at timestep t0 the trigger is evaluated at t0 + 1 ... t0 + n; the row of timestep t
+    is the state after t complete steps (after step two, with the forces of that configuration). ``Simulation.run``
+    runs step two of that step on its own there instead of fused with the next step one: the trajectory is the same
+    bit for bit with and without a recorder. ``timesteps`` and ``table`` are read after the run."""
+
+    def __init__(self, thermo, trigger):
+        if not isinstance(thermo, ThermodynamicQuantities):
+            raise _lib.AzpError("ThermodynamicRecorder: thermo must be a ThermodynamicQuantities, got %r" % (thermo,))
+        self.thermo = thermo
+        super().__init__(trigger)
+
+    @property
+    def _compute(self):
+        return self.thermo
+
+    def _row_width(self):
+        return _lib.THERMO_NSUMS
 
     @property
     def table(self):
@@ -508,5 +534,304 @@ class ThermodynamicRecorder:
         return {name: np.array([r[name] for r in rows]) for name in THERMO_PROPERTIES}
 
 
-__all__ = ["CartesianVelocityFieldCompute", "CylindricalVelocityFieldCompute", "DataAccessError", "ThermodynamicQuantities",
-           "ThermodynamicRecorder", "VelocityCompute", "VelocityFieldCompute", "thermo_quantities"]
+# ---------------------------------------------------------------------------
+# radial distribution function
+# ---------------------------------------------------------------------------
+def _shell_volumes(num_bins, r_max):
+    edges = np.linspace(0.0, float(r_max), int(num_bins) + 1)
+    return (4.0 * np.pi / 3.0) * (edges[1:] ** 3 - edges[:-1] ** 3)
+
+
+def _rdf_normalize(counts, n_pairs, volume, r_max):
+    counts = np.asarray(counts)
+    if n_pairs == 0:
+        return np.zeros(counts.shape, dtype=np.float64)
+    return counts.astype(np.float64) * (float(volume) / (float(n_pairs) * _shell_volumes(counts.shape[-1], r_max)))
+
+
+def rdf_from_counts(counts, n_a, n_b, n_ab, volume, r_max):
+    """g(r) from ordered pair counts: ``counts[k]`` pairs (i in A, j in B, i != j) in bin k of ``len(counts)`` equal
+    bins on [0, r_max), ``n_a`` / ``n_b`` / ``n_ab`` the sizes of A, B and of their intersection, ``volume`` the box
+    volume: g[k] = counts[k] V / (n_pairs (4 pi / 3)(r_(k+1)^3 - r_k^3)), n_pairs = n_a n_b - n_ab; zero when n_pairs is
+    0. An ideal gas gives 1. The compute, the recorder and the tests all go through here."""
+    return _rdf_normalize(counts, int(n_a) * int(n_b) - int(n_ab), volume, r_max)
+
+
+def perpendicular_widths(box):
+    """Distances between opposite faces of ``box`` (a ``state.Box``; HOOMD ``BoxDim.getNearestPlaneDistance``)."""
+    t = box.xy * box.yz - box.xz
+    return (box.Lx / np.sqrt(1.0 + box.xy * box.xy + t * t), box.Ly / np.sqrt(1.0 + box.yz * box.yz), box.Lz)
+
+
+def _check_rdf_filter(name, f):
+    if not isinstance(f, (All, Type)):
+        raise _lib.AzpError("RadialDistributionFunction: %s must be All() or Type(...), got %r" % (name, f))
+    return f
+
+
+class RadialDistributionFunction(_Compute):
+    """Radial distribution function g(r) between the groups ``filter_a`` and ``filter_b`` (``All()`` or ``Type(...)``;
+    they may overlap) of a 3-D system, on ``num_bins`` equal bins of [0, ``r_max``).
+
+    ``counts[k]`` is the number of ORDERED pairs (i in A, j in B, i != j) whose minimum-image distance r lies in bin k: a
+    pair counts iff r^2 < r_max^2 (lower bin edges inclusive, r == r_max excluded), r is the correctly rounded square
+    root and k = min(int(r * (num_bins / r_max)), num_bins - 1). The counts are exact integers and two reads of one
+    state agree bit for bit. ``rdf`` = ``rdf_from_counts(counts, N_A, N_B, N_AB, V, r_max)``, i.e.
+    counts[k] V / (num_pairs (4 pi / 3)(r_(k+1)^3 - r_k^3)) with ``num_pairs`` = N_A N_B - N_AB.
+
+    Refused with ``AzpError``: ``r_max <= 0``, ``num_bins`` outside [1, 8192], a filter that is not ``All()`` or
+    ``Type(...)`` (at construction or assignment); ``r_max`` larger than half the smallest perpendicular width of a
+    periodic axis of the box (when a property is read: the minimum image would not be unique). ``path``: 0 (default)
+    takes the cell-list kernel wherever the box allows it (orthorhombic, at least three cells of width ``r_max`` on
+    every periodic axis) and the all-pairs kernel elsewhere, 1 / 2 force one of them; a forced path the box does not
+    allow is refused. On a decomposed run each rank counts its own particles against its own particles and ghosts and
+    the counts are added over the ranks (every rank gets the same result); ghosts are complete out to the
+    decomposition's ``r_ghost`` minus the neighbor-list buffer, a larger ``r_max`` is refused.
+
+    Every property is computed when it is read, from the current state."""
+
+    def __init__(self, filter_a, filter_b, r_max, num_bins):
+        super().__init__(_check_rdf_filter("filter_a", filter_a), False)
+        self._filter_b = _check_rdf_filter("filter_b", filter_b)
+        self.r_max = r_max
+        self.num_bins = num_bins
+        self.path = _lib.RDF_PATH_AUTO
+        self._masks = None    # (types, mask a, mask b)
+        self._row = None
+        self._scratch = None
+
+    filter_a = _Compute.filter
+
+    @property
+    def filter_b(self):
+        return self._filter_b
+
+    @property
+    def r_max(self):
+        return self._r_max
+
+    @r_max.setter
+    def r_max(self, value):
+        value = float(value)
+        if not (value > 0.0 and np.isfinite(value)):
+            raise _lib.AzpError("RadialDistributionFunction: r_max must be positive, got %r" % (value,))
+        self._r_max = value
+
+    @property
+    def num_bins(self):
+        return self._num_bins
+
+    @num_bins.setter
+    def num_bins(self, value):
+        if isinstance(value, bool) or int(value) != value or int(value) < 1:
+            raise _lib.AzpError("RadialDistributionFunction: num_bins must be a positive integer, got %r" % (value,))
+        if int(value) > _lib.RDF_MAX_BINS:
+            raise _lib.AzpError("RadialDistributionFunction: num_bins = %d is more than the %d bins of AZP_RDF_MAX_BINS"
+                                % (value, _lib.RDF_MAX_BINS))
+        self._num_bins = int(value)
+
+    @property
+    def path(self):
+        return self._path
+
+    @path.setter
+    def path(self, value):
+        if value not in (_lib.RDF_PATH_AUTO, _lib.RDF_PATH_ALL_PAIRS, _lib.RDF_PATH_CELLS):
+            raise _lib.AzpError("RadialDistributionFunction: path must be 0 (auto), 1 (all-pairs) or 2 (cells), got %r" % (value,))
+        self._path = int(value)
+
+    @property
+    def bin_edges(self):
+        """numpy.ndarray: the ``num_bins + 1`` edges of the bins."""
+        return np.linspace(0.0, self._r_max, self._num_bins + 1)
+
+    @property
+    def bin_centers(self):
+        e = self.bin_edges
+        return 0.5 * (e[1:] + e[:-1])
+
+    # -- one launch ----------------------------------------------------------
+    def _check_box(self, sim):
+        box = sim.state.box
+        widths = perpendicular_widths(box)
+        for d in range(3):
+            if not widths[d] > 0.0:
+                raise _lib.AzpError("RadialDistributionFunction: a 3-D box is needed (2-D systems are not supported), got %r" % (box,))
+            if box.periodic[d] and self._r_max > 0.5 * widths[d]:
+                raise _lib.AzpError("RadialDistributionFunction: r_max = %r is larger than half the perpendicular width %r of "
+                                    "periodic axis %d: the minimum image would not be unique" % (self._r_max, widths[d], d))
+        dom = sim.domain
+        if dom is not None:
+            integ = sim.operations.integrator
+            lists = [f.nlist for f in (integ.forces if integ is not None else []) if getattr(f, "nlist", None) is not None]
+            buffer = max([float(nl.buffer) for nl in lists], default=0.0)
+            if self._r_max > dom.decomp.r_ghost - buffer:
+                raise _lib.AzpError("RadialDistributionFunction: r_max = %r is beyond the ghost coverage %r of this decomposed run "
+                                    "(r_ghost = %r minus the neighbor-list buffer %r)"
+                                    % (self._r_max, dom.decomp.r_ghost - buffer, dom.decomp.r_ghost, buffer))
+
+    def _type_masks(self, st):
+        import torch
+
+        if self._masks is None or self._masks[0] != st.types or self._masks[3] != st.device:
+            m = [None if isinstance(f, All) else torch.from_numpy(f.mask(st.types)).to(st.device) for f in (self._filter, self._filter_b)]
+            self._masks = (list(st.types), m[0], m[1], st.device)
+        return self._masks[1], self._masks[2]
+
+    def _launch(self, d_out):
+        """Queue ``azp_rdf_counts`` for the simulation's current state with the ``num_bins + 4`` words going to ``d_out``."""
+        import torch
+
+        sim = self._sim
+        st = sim.state
+        self._check_box(sim)
+        a = _lib.RdfArgs()
+        a.d_pos = st.pos.data_ptr()
+        a.N = st.N
+        a.n_total = st.n_max
+        a.box = st.box.to_c()
+        a.ntypes = len(st.types)
+        mask_a, mask_b = self._type_masks(st)
+        a.d_type_mask_a = mask_a.data_ptr() if mask_a is not None else None
+        a.d_type_mask_b = mask_b.data_ptr() if mask_b is not None else None
+        a.num_bins = self._num_bins
+        a.r_max = self._r_max
+        a.scale = self._num_bins / self._r_max
+        a.path = self._path
+        lib = _lib.lib()
+        need = C.c_uint64(0)
+        _lib.check(lib.azp_rdf_scratch_size(C.byref(a), C.byref(need)), "azp_rdf_scratch_size")
+        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
+            # (sized for this N, box, r_max and path: grown when any of them asks for more)
+            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
+        a.d_scratch = self._scratch.data_ptr()
+        a.scratch_bytes = self._scratch.numel()
+        a.d_out = d_out
+        _lib.check(lib.azp_rdf_counts(C.byref(a), _lib.raw_stream(st.device)), "azp_rdf_counts")
+
+    def _reduce(self, rows):
+        """Rows of per-rank words (a (k, num_bins + 4) int64 device tensor: the uint64 words of the kernel, all below
+        2^63) added over the ranks of a decomposed run, as numpy int64."""
+        dom = self._sim.domain
+        if dom is not None:
+            rows = _all_reduce_sum(dom, rows.clone())
+        return rows.cpu().numpy()
+
+    def _read(self, name):
+        import torch
+
+        if not self._attached:
+            raise DataAccessError(name)
+        st = self._sim.state
+        width = self._num_bins + 4
+        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
+            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
+        self._launch(self._row.data_ptr())
+        return self._reduce(self._row)[0]
+
+    def _volume(self):
+        box = self._sim.state.box
+        return box.Lx * box.Ly * box.Lz
+
+    @property
+    def counts(self):
+        """numpy int64 (num_bins,): ordered pair counts per bin."""
+        return self._read("counts")[: self._num_bins].copy()
+
+    @property
+    def group_sizes(self):
+        """tuple[int]: (N_A, N_B, N_AB), the sizes of the two groups and of their intersection."""
+        return tuple(int(x) for x in self._read("group_sizes")[self._num_bins:self._num_bins + 3])
+
+    @property
+    def num_pairs(self):
+        """int: N_A N_B - N_AB over the owned particles of the whole system."""
+        n_a, n_b, n_ab = (int(x) for x in self._read("num_pairs")[self._num_bins:self._num_bins + 3])
+        return n_a * n_b - n_ab
+
+    @property
+    def rdf(self):
+        """numpy float64 (num_bins,): g(r) on ``bin_centers``."""
+        row = self._read("rdf")
+        nb = self._num_bins
+        return rdf_from_counts(row[:nb], row[nb], row[nb + 1], row[nb + 2], self._volume(), self._r_max)
+
+
+class RDFRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) that appends the pair counts of ``rdf`` (a ``RadialDistributionFunction`` in
+    ``computes`` of the same simulation) to a device table of ``num_bins + 4`` words per row at the timesteps ``trigger``
+    (an ``int`` period or a ``Periodic``) fires, as ``ThermodynamicRecorder`` does with its sums: the kernel writes row k
+    itself, nothing is read back and the host does not wait; the trajectory is the same bit for bit with and without
+    the recorder. Read after the run: ``timesteps``, ``counts`` and ``rdf`` (frames, num_bins) -- each frame normalised
+    with its own N_A, N_B and N_AB, which keeps it right while an evaporator changes types -- and ``mean_rdf``, the sum of
+    the counts over the sum of the pair numbers. On a decomposed run the whole table is reduced once, when it is read.
+    ``reset()`` forgets the recorded frames (needed before ``rdf.num_bins`` changes)."""
+
+    _dtype = "int64"
+
+    def __init__(self, rdf, trigger):
+        if not isinstance(rdf, RadialDistributionFunction):
+            raise _lib.AzpError("RDFRecorder: rdf must be a RadialDistributionFunction, got %r" % (rdf,))
+        self.rdf_compute = rdf
+        super().__init__(trigger)
+
+    @property
+    def _compute(self):
+        return self.rdf_compute
+
+    def _row_width(self):
+        return self.rdf_compute.num_bins + 4
+
+    def reset(self):
+        self._rows = None
+        self._steps = []
+
+    def _table(self, name):
+        k = len(self._steps)
+        if k == 0:
+            return np.zeros((0, self.rdf_compute.num_bins + 4), dtype=np.int64)
+        if not self.rdf_compute._attached:
+            raise DataAccessError(name)
+        return self.rdf_compute._reduce(self._rows[:k])
+
+    @property
+    def counts(self):
+        """numpy int64 (frames, num_bins)."""
+        t = self._table("counts")
+        return t[:, : t.shape[1] - 4].copy()
+
+    @staticmethod
+    def _pairs(t):
+        nb = t.shape[1] - 4
+        return [int(r[nb]) * int(r[nb + 1]) - int(r[nb + 2]) for r in t]
+
+    @property
+    def num_pairs(self):
+        """list of int: N_A N_B - N_AB of each frame."""
+        return self._pairs(self._table("num_pairs"))
+
+    @property
+    def rdf(self):
+        """numpy float64 (frames, num_bins): each frame with its own normalisation."""
+        t = self._table("rdf")
+        nb = t.shape[1] - 4
+        c = self.rdf_compute
+        if t.shape[0] == 0:
+            return np.zeros((0, nb))
+        vol = c._volume()
+        return np.stack([rdf_from_counts(r[:nb], r[nb], r[nb + 1], r[nb + 2], vol, c.r_max) for r in t])
+
+    @property
+    def mean_rdf(self):
+        """numpy float64 (num_bins,): sum of the counts of all frames over the sum of their pair numbers."""
+        t = self._table("mean_rdf")
+        nb = t.shape[1] - 4
+        if t.shape[0] == 0:
+            return np.zeros(nb)
+        c = self.rdf_compute
+        return _rdf_normalize(t[:, :nb].sum(axis=0), sum(self._pairs(t)), c._volume(), c.r_max)
+
+
+__all__ = ["CartesianVelocityFieldCompute", "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder",
+           "RadialDistributionFunction", "ThermodynamicQuantities", "ThermodynamicRecorder", "VelocityCompute",
+           "VelocityFieldCompute", "perpendicular_widths", "rdf_from_counts", "thermo_quantities"]

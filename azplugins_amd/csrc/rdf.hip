@@ -1,0 +1,575 @@
+// rdf.hip -- the pair counts behind compute.RadialDistributionFunction: for two groups A and B (per-type byte masks,
+// NULL = every particle) counts[k] = number of ORDERED pairs (i in A, j in B, i != j), i over rows [0, N), j over rows
+// [0, n_total), whose minimum-image distance r (min_image of azp_device.hpp) lies in bin k of num_bins equal bins on
+// [0, r_max): counted iff rsq < r_max^2, r = sqrt(rsq) correctly rounded, k = min((uint32_t)(r * scale), num_bins - 1)
+// with scale = num_bins / r_max from the host. The output row is num_bins + 4 uint64: the counts, then N_A, N_B and
+// N_(A and B) over rows [0, N), then one zero. The call zeroes the row itself (hipMemsetAsync on the stream).
+//
+// Two paths, the same integers wherever both are valid:
+//   all-pairs  (any box, any N) grid (ceil(N / 256), segments of B). Thread t of a workgroup holds row
+//              i = 256 blockIdx.x + t in registers; the workgroup streams its segment of rows [0, n_total) through LDS
+//              in chunks of 256 (x, y, z as three double arrays; a candidate outside B is staged as NaN, which fails
+//              rsq < r_max^2), every lane tests every staged candidate (one LDS address per wave: a broadcast read).
+//   cells      (orthorhombic box, >= 3 cells of width >= r_max on every periodic axis; a non-periodic axis has
+//              clamped cells, as azp_cell_grid.periodic = 0). All n_total particles are binned by a counting sort that
+//              lives in this file's scratch: histogram of the cells (integer atomics), one-workgroup exclusive scan,
+//              scatter of (x, y, z, flags) rows into cell order. No order is imposed inside a cell: pair counts do not
+//              depend on it. rdf_cells then gives every workgroup a contiguous range of cells (xcd_remap: one eighth of
+//              the cells per XCD); per cell, its rows are taken 256 at a time, a tile of T rows is served by
+//              256 / pow2ceil(T) lanes per row, and the members of the 27 stencil cells are staged through LDS in
+//              chunks of 256 as above (never read straight from global memory by the pair loop).
+//
+// Accumulation is integer throughout and on chip first: one uint32 histogram of num_bins words per workgroup in LDS,
+// incremented with LDS integer atomics (ds_add_u32 without return). Overflow bound: between two flushes a bin
+// receives at most one increment per (row, staged candidate) test; each staged chunk adds at most 256 x 256 = 2^16
+// tests, the workgroup counts them in `pending` (the same value in every thread) and flushes before pending can pass
+// 2^32 - 1. A flush adds the non-zero bins to the output row with 64-bit integer atomicAdd and clears them; the row is
+// uint64, 2^64 > (2^32)^2 >= N n_total. Integer sums do not depend on the order of the adds: two calls on the same
+// state give the same bits. No floating-point atomics.
+//
+// LDS: 3 x 256 doubles of staging (6 KB) + 4 num_bins bytes of histogram (32 KB at AZP_RDF_MAX_BINS = 8192) + the
+// stencil table of the cells path (224 B).
+// Bytes: all-pairs reads 32 B per (row tile, candidate): 32 n_total ceil(N / 256) in all. Cells: binning reads pos
+// twice (64 B per particle) and writes 36 B per particle; the pair kernel reads 32 B per staged candidate, i.e.
+// 32 x 27 x ceil(rows of the cell / 256) per particle, plus 32 B per row.
+#include <algorithm>
+#include <cmath>
+
+#include "azp_device.hpp"
+
+namespace azp
+{
+constexpr uint32_t RDF_BLOCK = 256;
+constexpr uint32_t RDF_CHUNK = 256;
+constexpr uint32_t RDF_CHUNK_TESTS = RDF_BLOCK * RDF_CHUNK;       // most increments a bin gets from one staged chunk
+constexpr uint32_t RDF_FLUSH_AT = 0xFFFFFFFFu - RDF_CHUNK_TESTS;  // flush once `pending` has passed this
+constexpr uint32_t RDF_TARGET_BLOCKS = 2048;                      // 256 CUs x 8
+constexpr uint32_t RDF_SCAN_BLOCK = 1024;
+constexpr uint32_t RDF_MAX_CELLS = 1u << 21;
+constexpr uint32_t RDF_AUTO_CELLS_MIN_N = 0;  // path 0 takes the cells wherever they are valid
+
+struct RdfGrid
+    {
+    double lo[3];
+    double inv_w[3];
+    uint32_t dim[3];
+    int periodic[3];
+    uint32_t ncell;
+    };
+
+struct RdfKArgs
+    {
+    const double* pos;
+    const uint8_t* mask_a;
+    const uint8_t* mask_b;
+    unsigned long long* out;
+    BoxDev box;
+    double rmaxsq;
+    double scale;
+    uint32_t N;
+    uint32_t n_total;
+    uint32_t ntypes;
+    uint32_t num_bins;
+    // cells path
+    RdfGrid grid;
+    double* sorted;        // n_total x 4: x, y, z, flags (1: row of A below N, 2: member of B)
+    uint32_t* cell_id;     // n_total
+    uint32_t* count;       // ncell: histogram, then the scatter's cursors
+    uint32_t* start;       // ncell + 1
+    uint32_t cells_per_block;
+    uint32_t seg_len;      // all-pairs: candidates per segment of B (a multiple of RDF_CHUNK)
+    };
+
+__device__ __forceinline__ bool rdf_in_mask(const uint8_t* mask, uint32_t ntypes, double w)
+    {
+    if (!mask)
+        return true;
+    const uint32_t t = (uint32_t)type_from_w(w);
+    return t < ntypes && mask[t] != 0;
+    }
+
+// one (row, candidate) test: d = r_i - r_j before the minimum image
+__device__ __forceinline__ void rdf_test(const BoxDev& b, double dx, double dy, double dz, double rmaxsq, double scale,
+                                         uint32_t last_bin, uint32_t* hist)
+    {
+    min_image(b, dx, dy, dz);
+    const double rsq = dx * dx + dy * dy + dz * dz;
+    if (rsq < rmaxsq)
+        {
+        const double r = sqrt(rsq);  // (IEEE, correctly rounded: the bin of a pair is a property of its rsq alone)
+        const uint32_t k = min((uint32_t)(r * scale), last_bin);
+        atomicAdd(&hist[k], 1u);
+        }
+    }
+
+// add the non-zero bins of the workgroup's histogram to the output row and clear them
+__device__ __forceinline__ void rdf_flush(uint32_t* hist, uint32_t num_bins, unsigned long long* out)
+    {
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < num_bins; k += RDF_BLOCK)
+        {
+        const uint32_t v = hist[k];
+        if (v)
+            {
+            atomicAdd(&out[k], (unsigned long long)v);
+            hist[k] = 0;
+            }
+        }
+    __syncthreads();
+    }
+
+__global__ void __launch_bounds__(RDF_BLOCK) rdf_all_pairs(const RdfKArgs a)
+    {
+    extern __shared__ uint32_t s_hist[];
+    __shared__ double s_x[RDF_CHUNK], s_y[RDF_CHUNK], s_z[RDF_CHUNK];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < a.num_bins; k += RDF_BLOCK)
+        s_hist[k] = 0;
+    const uint64_t i = (uint64_t)blockIdx.x * RDF_BLOCK + tid;
+    bool row = false;
+    double xi = 0.0, yi = 0.0, zi = 0.0;
+    if (i < a.N)
+        {
+        const double4 p = load_scalar4(a.pos, (uint32_t)i);
+        xi = p.x; yi = p.y; zi = p.z;
+        row = rdf_in_mask(a.mask_a, a.ntypes, p.w);
+        }
+    const uint64_t j0 = (uint64_t)blockIdx.y * a.seg_len;
+    const uint64_t j1 = std::min<uint64_t>(j0 + a.seg_len, a.n_total);
+    const uint32_t last_bin = a.num_bins - 1;
+    const double nan = __builtin_nan("");
+    uint32_t pending = 0;
+    __syncthreads();
+    for (uint64_t jb = j0; jb < j1; jb += RDF_CHUNK)
+        {
+        const uint64_t j = jb + tid;
+        double x = nan, y = nan, z = nan;
+        if (j < j1)
+            {
+            const double4 p = load_scalar4(a.pos, (uint32_t)j);
+            if (rdf_in_mask(a.mask_b, a.ntypes, p.w))
+                {
+                x = p.x; y = p.y; z = p.z;
+                }
+            }
+        s_x[tid] = x; s_y[tid] = y; s_z[tid] = z;
+        __syncthreads();
+        const uint32_t n = (uint32_t)std::min<uint64_t>(RDF_CHUNK, j1 - jb);
+        if (row)
+            {
+            for (uint32_t c = 0; c < n; ++c)
+                if (jb + c != i)
+                    rdf_test(a.box, xi - s_x[c], yi - s_y[c], zi - s_z[c], a.rmaxsq, a.scale, last_bin, s_hist);
+            }
+        __syncthreads();
+        pending += RDF_CHUNK_TESTS;
+        if (pending > RDF_FLUSH_AT)
+            {
+            rdf_flush(s_hist, a.num_bins, a.out);
+            pending = 0;
+            }
+        }
+    rdf_flush(s_hist, a.num_bins, a.out);
+    }
+
+// ---------------------------------------------------------------------------------------------------------------
+// binning: histogram, scan, scatter
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rdf_cell_axis(const RdfGrid& g, int d, double x)
+    {
+    // (fmin / fmax drop a NaN: such a particle lands in cell 0 of the axis and pairs with nothing)
+    const double f = fmin(fmax((x - g.lo[d]) * g.inv_w[d], -1.0e9), 1.0e9);
+    int c = (int)floor(f);
+    const int dim = (int)g.dim[d];
+    if (g.periodic[d])
+        {
+        c %= dim;
+        if (c < 0)
+            c += dim;
+        }
+    else
+        c = min(max(c, 0), dim - 1);
+    return (uint32_t)c;
+    }
+
+__global__ void __launch_bounds__(RDF_BLOCK) rdf_bin_count(const RdfKArgs a)
+    {
+    const uint64_t p = (uint64_t)blockIdx.x * RDF_BLOCK + threadIdx.x;
+    if (p >= a.n_total)
+        return;
+    const double3 r = load_scalar3_of4(a.pos, (uint32_t)p);
+    const uint32_t c = (rdf_cell_axis(a.grid, 2, r.z) * a.grid.dim[1] + rdf_cell_axis(a.grid, 1, r.y)) * a.grid.dim[0]
+                       + rdf_cell_axis(a.grid, 0, r.x);
+    a.cell_id[p] = c;
+    atomicAdd(&a.count[c], 1u);
+    }
+
+// exclusive scan of count[0, ncell) into start[0, ncell], one workgroup; count is cleared (the scatter's cursors).
+// Tiles of 1024 cells, lane t on cell base + t (coalesced: a lane-contiguous span per thread costs one cache line per
+// lane and load, 97 us for 46,656 cells at the rate of one CU's address unit); a shuffle scan inside each wave, the 16
+// wave totals through LDS, the running total carried from tile to tile.
+__global__ void __launch_bounds__(RDF_SCAN_BLOCK) rdf_bin_scan(uint32_t* count, uint32_t* start, uint32_t ncell)
+    {
+    constexpr uint32_t NW = RDF_SCAN_BLOCK / WAVE;
+    __shared__ uint32_t s_wave[NW];
+    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < ncell; base += RDF_SCAN_BLOCK)
+        {
+        const uint32_t k = base + tid;  // (ncell <= RDF_MAX_CELLS: no overflow)
+        const uint32_t c = k < ncell ? count[k] : 0u;
+        uint32_t v = c;
+#pragma unroll
+        for (uint32_t d = 1; d < WAVE; d <<= 1)
+            {
+            const uint32_t up = __shfl_up(v, d, WAVE);
+            if (lane >= d)
+                v += up;
+            }
+        if (lane == WAVE - 1)
+            s_wave[wave] = v;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < NW; ++w)
+            {
+            const uint32_t t = s_wave[w];
+            before += w < wave ? t : 0u;
+            total += t;
+            }
+        if (k < ncell)
+            {
+            start[k] = carry + before + (v - c);
+            count[k] = 0;
+            }
+        carry += total;
+        __syncthreads();
+        }
+    if (tid == 0)
+        start[ncell] = carry;
+    }
+
+__global__ void __launch_bounds__(RDF_BLOCK) rdf_bin_scatter(const RdfKArgs a)
+    {
+    const uint64_t p = (uint64_t)blockIdx.x * RDF_BLOCK + threadIdx.x;
+    if (p >= a.n_total)
+        return;
+    const double4 r = load_scalar4(a.pos, (uint32_t)p);
+    const uint32_t c = a.cell_id[p];
+    const uint32_t slot = a.start[c] + atomicAdd(&a.count[c], 1u);
+    const uint32_t flags = ((p < a.N && rdf_in_mask(a.mask_a, a.ntypes, r.w)) ? 1u : 0u)
+                           | (rdf_in_mask(a.mask_b, a.ntypes, r.w) ? 2u : 0u);
+    store_scalar4(a.sorted, slot, r.x, r.y, r.z, (double)flags);
+    }
+
+// ---------------------------------------------------------------------------------------------------------------
+// pair counts from the binned particles
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(RDF_BLOCK) rdf_cells(const RdfKArgs a)
+    {
+    extern __shared__ uint32_t s_hist[];
+    __shared__ double s_x[RDF_CHUNK], s_y[RDF_CHUNK], s_z[RDF_CHUNK];
+    __shared__ uint32_t s_seg_start[27], s_seg_end[28];  // s_seg_end[s + 1]: candidates in segments 0 .. s
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < a.num_bins; k += RDF_BLOCK)
+        s_hist[k] = 0;
+    const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+    const uint64_t c0 = (uint64_t)b * a.cells_per_block;
+    const uint32_t c1 = (uint32_t)std::min<uint64_t>(c0 + a.cells_per_block, a.grid.ncell);
+    const uint32_t last_bin = a.num_bins - 1;
+    const double nan = __builtin_nan("");
+    const uint32_t dx = a.grid.dim[0], dy = a.grid.dim[1], dz = a.grid.dim[2];
+    uint32_t pending = 0;
+    __syncthreads();
+    for (uint32_t c = (uint32_t)c0; c < c1; ++c)
+        {
+        const uint32_t rs = a.start[c], rn = a.start[c + 1] - rs;
+        if (rn == 0)
+            continue;
+        if (tid < 27)
+            {
+            const int cell[3] = {(int)(c % dx), (int)((c / dx) % dy), (int)(c / (dx * dy))};
+            const int off[3] = {(int)(tid % 3) - 1, (int)((tid / 3) % 3) - 1, (int)(tid / 9) - 1};
+            const int dim[3] = {(int)dx, (int)dy, (int)dz};
+            int nb[3];
+            bool ok = true;
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+                {
+                int v = cell[d] + off[d];
+                if (a.grid.periodic[d])
+                    v = v < 0 ? v + dim[d] : (v >= dim[d] ? v - dim[d] : v);
+                else if (v < 0 || v >= dim[d])
+                    ok = false;
+                nb[d] = v;
+                }
+            uint32_t s0 = 0, cnt = 0;
+            if (ok)
+                {
+                const uint32_t nc = ((uint32_t)nb[2] * dy + (uint32_t)nb[1]) * dx + (uint32_t)nb[0];
+                s0 = a.start[nc];
+                cnt = a.start[nc + 1] - s0;
+                }
+            s_seg_start[tid] = s0;
+            s_seg_end[tid + 1] = cnt;
+            }
+        __syncthreads();
+        if (tid == 0)
+            {
+            uint32_t run = 0;
+            s_seg_end[0] = 0;
+            for (uint32_t s = 1; s <= 27; ++s)
+                {
+                run += s_seg_end[s];
+                s_seg_end[s] = run;
+                }
+            }
+        __syncthreads();
+        const uint32_t M = s_seg_end[27];
+        const uint32_t own0 = s_seg_end[13];  // the cell's own members start here in the flat candidate list
+        for (uint32_t rt = 0; rt < rn; rt += RDF_BLOCK)
+            {
+            const uint32_t T = min(RDF_BLOCK, rn - rt);
+            // T rows, Tp = pow2ceil(T) row slots, G = 256 / Tp lanes per row
+            const uint32_t lg = T > 1 ? 32u - (uint32_t)__builtin_clz(T - 1) : 0u;
+            const uint32_t G = RDF_BLOCK >> lg;
+            const uint32_t r = tid & ((1u << lg) - 1u), sub = tid >> lg;
+            bool row = false;
+            double xi = 0.0, yi = 0.0, zi = 0.0;
+            if (r < T)
+                {
+                const double4 p = load_scalar4(a.sorted, rs + rt + r);
+                xi = p.x; yi = p.y; zi = p.z;
+                row = ((uint32_t)p.w & 1u) != 0;
+                }
+            const uint32_t self = own0 + rt + r;
+            if (!__syncthreads_or(row))
+                continue;
+            for (uint32_t cb = 0; cb < M; cb += RDF_CHUNK)
+                {
+                const uint32_t q = cb + tid;
+                double x = nan, y = nan, z = nan;
+                if (q < M)
+                    {
+                    uint32_t s = 0;
+                    while (q >= s_seg_end[s + 1])
+                        ++s;
+                    const double4 p = load_scalar4(a.sorted, s_seg_start[s] + (q - s_seg_end[s]));
+                    if ((uint32_t)p.w & 2u)
+                        {
+                        x = p.x; y = p.y; z = p.z;
+                        }
+                    }
+                s_x[tid] = x; s_y[tid] = y; s_z[tid] = z;
+                __syncthreads();
+                const uint32_t n = min(RDF_CHUNK, M - cb);
+                if (row)
+                    {
+                    for (uint32_t cc = sub; cc < n; cc += G)
+                        if (cb + cc != self)
+                            rdf_test(a.box, xi - s_x[cc], yi - s_y[cc], zi - s_z[cc], a.rmaxsq, a.scale, last_bin, s_hist);
+                    }
+                __syncthreads();
+                pending += RDF_CHUNK_TESTS;
+                if (pending > RDF_FLUSH_AT)
+                    {
+                    rdf_flush(s_hist, a.num_bins, a.out);
+                    pending = 0;
+                    }
+                }
+            }
+        }
+    rdf_flush(s_hist, a.num_bins, a.out);
+    }
+
+// N_A, N_B, N_(A and B) over rows [0, N) into out[num_bins .. num_bins + 2]
+__global__ void __launch_bounds__(RDF_BLOCK) rdf_group_counts(const RdfKArgs a)
+    {
+    __shared__ uint32_t s_n[3];
+    const uint32_t tid = threadIdx.x;
+    if (tid < 3)
+        s_n[tid] = 0;
+    __syncthreads();
+    uint32_t n[3] = {0, 0, 0};
+    for (uint64_t i = (uint64_t)blockIdx.x * RDF_BLOCK + tid; i < a.N; i += (uint64_t)gridDim.x * RDF_BLOCK)
+        {
+        const double w = a.pos[4ull * i + 3];
+        const bool in_a = rdf_in_mask(a.mask_a, a.ntypes, w), in_b = rdf_in_mask(a.mask_b, a.ntypes, w);
+        n[0] += in_a; n[1] += in_b; n[2] += in_a && in_b;
+        }
+#pragma unroll
+    for (uint32_t k = 0; k < 3; ++k)
+        if (n[k])
+            atomicAdd(&s_n[k], n[k]);
+    __syncthreads();
+    if (tid < 3 && s_n[tid])
+        atomicAdd(&a.out[a.num_bins + tid], (unsigned long long)s_n[tid]);
+    }
+
+// ---------------------------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------------------------
+// perpendicular widths of the box (HOOMD BoxDim::getNearestPlaneDistance)
+static void rdf_widths(const azp_box& b, double w[3])
+    {
+    const double xy = b.tilt[0], xz = b.tilt[1], yz = b.tilt[2];
+    const double t = xy * yz - xz;
+    w[0] = b.L[0] / std::sqrt(1.0 + xy * xy + t * t);
+    w[1] = b.L[1] / std::sqrt(1.0 + yz * yz);
+    w[2] = b.L[2];
+    }
+
+// the cell grid of the cells path; false if the box does not allow it
+static bool rdf_make_grid(const azp_box& b, double r_max, uint32_t n_total, RdfGrid& g)
+    {
+    if (b.tilt[0] != 0.0 || b.tilt[1] != 0.0 || b.tilt[2] != 0.0)
+        return false;
+    double dim[3];
+    for (int d = 0; d < 3; ++d)
+        {
+        dim[d] = std::floor(b.L[d] / r_max);
+        if (b.periodic[d] && dim[d] < 3.0)
+            return false;
+        dim[d] = std::min(std::max(dim[d], 1.0), 1024.0);
+        }
+    // (a sparse system: no more cells than a few per particle, at most RDF_MAX_CELLS; wider cells stay valid)
+    const double cap = std::min<double>(RDF_MAX_CELLS, std::max<double>(64.0, 2.0 * n_total));
+    for (int pass = 0; pass < 64 && dim[0] * dim[1] * dim[2] > cap; ++pass)
+        {
+        const double f = std::cbrt(cap / (dim[0] * dim[1] * dim[2]));
+        for (int d = 0; d < 3; ++d)
+            dim[d] = std::max(b.periodic[d] ? 3.0 : 1.0, std::floor(dim[d] * std::min(f, 0.95)));
+        }
+    if (dim[0] * dim[1] * dim[2] > (double)RDF_MAX_CELLS)
+        return false;
+    for (int d = 0; d < 3; ++d)
+        {
+        g.dim[d] = (uint32_t)dim[d];
+        g.lo[d] = -0.5 * b.L[d];
+        g.inv_w[d] = dim[d] / b.L[d];
+        g.periodic[d] = b.periodic[d] != 0;
+        }
+    g.ncell = g.dim[0] * g.dim[1] * g.dim[2];
+    return true;
+    }
+
+struct RdfPlan
+    {
+    int path;  // 1 all-pairs, 2 cells
+    RdfGrid grid;
+    uint64_t off_cell_id, off_count, off_start, bytes;
+    };
+
+static uint64_t rdf_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+
+static int rdf_plan(const azp_rdf_args* a, RdfPlan& p)
+    {
+    if (!a || !(a->r_max > 0.0) || !std::isfinite(a->r_max) || a->num_bins < 1 || a->num_bins > AZP_RDF_MAX_BINS
+        || !(a->scale > 0.0) || a->path > 2 || a->N > a->n_total)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    if ((a->d_type_mask_a || a->d_type_mask_b) && a->ntypes == 0)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    for (int d = 0; d < 3; ++d)
+        if (!(a->box.L[d] > 0.0))
+            return AZP_ERROR_INVALID_ARGUMENT;
+    double w[3];
+    rdf_widths(a->box, w);
+    for (int d = 0; d < 3; ++d)
+        if (a->box.periodic[d] && a->r_max > 0.5 * w[d])
+            return AZP_ERROR_INVALID_ARGUMENT;  // the minimum image would not be unique
+    const bool cells = rdf_make_grid(a->box, a->r_max, a->n_total, p.grid);
+    if (a->path == 2 && !cells)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    p.path = (a->path == 1 || !cells || (a->path == 0 && a->n_total < RDF_AUTO_CELLS_MIN_N)) ? 1 : 2;
+    p.bytes = 0;
+    if (p.path == 2)
+        {
+        p.off_cell_id = rdf_align((uint64_t)a->n_total * 32);
+        p.off_count = p.off_cell_id + rdf_align((uint64_t)a->n_total * 4);
+        p.off_start = p.off_count + rdf_align((uint64_t)p.grid.ncell * 4);
+        p.bytes = p.off_start + rdf_align(((uint64_t)p.grid.ncell + 1) * 4);
+        }
+    return AZP_SUCCESS;
+    }
+
+} // namespace azp
+
+extern "C" int azp_rdf_scratch_size(const azp_rdf_args* args, uint64_t* bytes)
+    {
+    using namespace azp;
+    if (!bytes)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    RdfPlan p;
+    const int rc = rdf_plan(args, p);
+    if (rc != AZP_SUCCESS)
+        return rc;
+    *bytes = p.bytes;
+    return AZP_SUCCESS;
+    }
+
+extern "C" int azp_rdf_counts(const azp_rdf_args* args, void* stream)
+    {
+    using namespace azp;
+    RdfPlan p;
+    const int rc = rdf_plan(args, p);
+    if (rc != AZP_SUCCESS)
+        return rc;
+    if (!args->d_out || (args->n_total && !args->d_pos))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    if (p.bytes && (!args->d_scratch || args->scratch_bytes < p.bytes))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(args->d_out, 0, ((uint64_t)args->num_bins + 4) * sizeof(uint64_t), st);
+    if (e != hipSuccess || args->N == 0)
+        return (int)e;
+    RdfKArgs k = {};
+    k.pos = args->d_pos;
+    k.mask_a = args->d_type_mask_a;
+    k.mask_b = args->d_type_mask_b;
+    k.out = reinterpret_cast<unsigned long long*>(args->d_out);
+    k.box = make_box_dev(args->box);
+    k.rmaxsq = args->r_max * args->r_max;
+    k.scale = args->scale;
+    k.N = args->N;
+    k.n_total = args->n_total;
+    k.ntypes = args->ntypes;
+    k.num_bins = args->num_bins;
+    const uint32_t n_tiles = (args->N + RDF_BLOCK - 1) / RDF_BLOCK;
+    hipLaunchKernelGGL(rdf_group_counts, dim3(std::min(n_tiles, 1024u)), dim3(RDF_BLOCK), 0, st, k);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return (int)e;
+    const uint32_t lds = args->num_bins * sizeof(uint32_t);
+    if (p.path == 1)
+        {
+        const uint32_t n_chunks = (uint32_t)(((uint64_t)args->n_total + RDF_CHUNK - 1) / RDF_CHUNK);
+        uint32_t n_seg = std::min(n_chunks, std::max(1u, RDF_TARGET_BLOCKS / n_tiles));
+        const uint32_t chunks_per_seg = (n_chunks + n_seg - 1) / n_seg;
+        n_seg = (n_chunks + chunks_per_seg - 1) / chunks_per_seg;
+        k.seg_len = chunks_per_seg * RDF_CHUNK;
+        hipLaunchKernelGGL(rdf_all_pairs, dim3(n_tiles, n_seg), dim3(RDF_BLOCK), lds, st, k);
+        return (int)hipGetLastError();
+        }
+    char* base = static_cast<char*>(args->d_scratch);
+    k.grid = p.grid;
+    k.sorted = reinterpret_cast<double*>(base);
+    k.cell_id = reinterpret_cast<uint32_t*>(base + p.off_cell_id);
+    k.count = reinterpret_cast<uint32_t*>(base + p.off_count);
+    k.start = reinterpret_cast<uint32_t*>(base + p.off_start);
+    if ((e = hipMemsetAsync(k.count, 0, (uint64_t)p.grid.ncell * 4, st)) != hipSuccess)
+        return (int)e;
+    const uint32_t n_blocks = (uint32_t)(((uint64_t)args->n_total + RDF_BLOCK - 1) / RDF_BLOCK);
+    hipLaunchKernelGGL(rdf_bin_count, dim3(n_blocks), dim3(RDF_BLOCK), 0, st, k);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return (int)e;
+    hipLaunchKernelGGL(rdf_bin_scan, dim3(1), dim3(RDF_SCAN_BLOCK), 0, st, k.count, k.start, p.grid.ncell);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return (int)e;
+    hipLaunchKernelGGL(rdf_bin_scatter, dim3(n_blocks), dim3(RDF_BLOCK), 0, st, k);
+    if ((e = hipGetLastError()) != hipSuccess)
+        return (int)e;
+    // (a multiple of 8 workgroups, each a contiguous range of cells: xcd_remap gives every XCD one eighth of the grid)
+    const uint32_t grid = (std::min(p.grid.ncell, RDF_TARGET_BLOCKS) + 7u) & ~7u;
+    k.cells_per_block = (p.grid.ncell + grid - 1) / grid;
+    hipLaunchKernelGGL(rdf_cells, dim3(grid), dim3(RDF_BLOCK), lds, st, k);
+    return (int)hipGetLastError();
+    }

@@ -154,7 +154,7 @@ class _Operations:
         # (azplugins_amd.update.TypeUpdater, azplugins_amd.evaporate.ParticleEvaporator)
         self.updaters = []
         # HOOMD's sim.operations.writers: run after the integrator's step at the timesteps their trigger fires
-        # (azplugins_amd.compute.ThermodynamicRecorder)
+        # (azplugins_amd.compute.ThermodynamicRecorder, azplugins_amd.compute.RDFRecorder)
         self.writers = []
         # HOOMD puts a ParticleSorter into sim.operations.tuners by default; so does this
         # (remove it from the list, or set trigger_period = 0, to keep the initial order)
@@ -165,10 +165,10 @@ class _Operations:
     def add(self, op):
         """Add an updater, a writer or a compute (``hoomd.Operations.add``); a compute is attached while the simulation
         has a state."""
-        from .compute import ThermodynamicRecorder
+        from .compute import _Recorder
         from .update import _Updater
 
-        for cls, ops in ((_Updater, self.updaters), (ThermodynamicRecorder, self.writers)):
+        for cls, ops in ((_Updater, self.updaters), (_Recorder, self.writers)):
             if isinstance(op, cls):
                 if not any(u is op for u in ops):
                     ops.append(op)
@@ -178,10 +178,10 @@ class _Operations:
     def remove(self, op):
         """Remove an updater, a writer or a compute; reading a removed compute's results raises
         ``compute.DataAccessError``."""
-        from .compute import ThermodynamicRecorder
+        from .compute import _Recorder
         from .update import _Updater
 
-        for cls, ops, name in ((_Updater, self.updaters, "updaters"), (ThermodynamicRecorder, self.writers, "writers")):
+        for cls, ops, name in ((_Updater, self.updaters, "updaters"), (_Recorder, self.writers, "writers")):
             if isinstance(op, cls):
                 for i, u in enumerate(ops):
                     if u is op:
@@ -292,9 +292,9 @@ class Simulation:
     def _check_writers(self):
         """A recorder reads its compute through this simulation's state: the compute has to be in ``computes``."""
         for w in self.operations.writers:
-            if not any(c is w.thermo for c in self.operations.computes):
-                raise _lib.AzpError("%s: its ThermodynamicQuantities is not in sim.operations.computes of this simulation"
-                                    % type(w).__name__)
+            if not any(c is w._compute for c in self.operations.computes):
+                raise _lib.AzpError("%s: its %s is not in sim.operations.computes of this simulation"
+                                    % (type(w).__name__, type(w._compute).__name__))
         integ = self.operations.integrator
         if integ is not None and len(integ.forces) > _lib.THERMO_MAX_FORCES and self._has_thermo():
             raise _lib.AzpError("ThermodynamicQuantities sums at most %d forces, the integrator has %d"

@@ -808,6 +808,53 @@ typedef struct azp_thermo_args
 int azp_thermo_scratch_size(const azp_thermo_args* args, uint64_t* bytes);
 int azp_thermo_sums(const azp_thermo_args* args, void* stream);
 
+/* ---- radial distribution function (compute.RadialDistributionFunction) ----
+ * Not part of the reference (azplugins had analyze.rdf in its HOOMD-2 line): the semantics are DEFINED HERE
+ * (DESIGN 4.14). For two groups A and B (d_type_mask_a / d_type_mask_b: one byte per type, NULL = every particle; the
+ * groups may overlap) in a 3-D box, counts[k] is the number of ORDERED pairs (i in A, j in B, i != j), i over rows
+ * [0, N), j over rows [0, n_total) (ghost rows count as partners, never as i), whose minimum-image distance r lies in
+ * bin k of num_bins equal bins on [0, r_max):
+ *   the pair counts iff rsq < r_max * r_max (the lower edge of a bin is inclusive, r == r_max is excluded);
+ *   r = sqrt(rsq), the correctly rounded FP64 square root; k = min((uint32_t)(r * scale), num_bins - 1);
+ *   scale = num_bins / r_max is computed once by the caller in double and passed in;
+ *   the minimum image is the one the force kernels use (triclinic boxes included).
+ * azp_rdf_counts OVERWRITES the num_bins + 4 uint64 at d_out (uninitialised memory is fine, the call zeroes the row
+ * on the stream): the counts, then N_A, N_B and N_(A and B) over rows [0, N), then one reserved zero. From these,
+ * g[k] = counts[k] V / (n_pairs (4 pi / 3)(r_(k+1)^3 - r_k^3)) with n_pairs = N_A N_B - N_(A and B)
+ * (compute.rdf_from_counts). Integer accumulation only (LDS integer atomics, then 64-bit integer atomic adds): two
+ * calls on the same state give the same bits. Asynchronous on `stream`, no host synchronisation, no readback.
+ * path: 0 = automatic (the cells wherever they are valid), 1 = all-pairs (any box, O(N_A n_total)), 2 = cells
+ * (orthorhombic box with at least three cells of width >= r_max on every periodic axis; a non-periodic axis has
+ * clamped cells as azp_cell_grid.periodic = 0); both give the same integers. d_scratch: azp_rdf_scratch_size bytes
+ * (depends on n_total, box, r_max and path; 0 for all-pairs, then d_scratch may be NULL).
+ * AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written: r_max <= 0, num_bins < 1 or > AZP_RDF_MAX_BINS,
+ * scale <= 0, r_max larger than half the smallest perpendicular width of a periodic axis (the minimum image would not
+ * be unique), path = 2 where the cells are not valid (never silently replaced), N > n_total, a NULL d_out, too small a
+ * scratch. */
+#define AZP_RDF_MAX_BINS 8192
+
+typedef struct azp_rdf_args
+    {
+    const double* d_pos;          /* n_total x 4 (x, y, z, type bits) */
+    uint32_t N;                   /* rows that count as i */
+    uint32_t n_total;             /* rows that count as j (N + ghosts) */
+    azp_box box;                  /* global box */
+    uint32_t ntypes;              /* entries of the masks */
+    uint32_t num_bins;
+    const uint8_t* d_type_mask_a; /* ntypes bytes, may be NULL */
+    const uint8_t* d_type_mask_b; /* ntypes bytes, may be NULL */
+    double r_max;
+    double scale;                 /* num_bins / r_max */
+    uint32_t path;                /* 0 auto, 1 all-pairs, 2 cells */
+    uint32_t _pad;
+    uint64_t* d_out;              /* num_bins + 4, overwritten */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_rdf_args;
+
+int azp_rdf_scratch_size(const azp_rdf_args* args, uint64_t* bytes);
+int azp_rdf_counts(const azp_rdf_args* args, void* stream);
+
 /* ---- wall potentials (azplugins_amd.wall) ----
  * Replace the reference's legacy wall evaluators src/WallEvaluatorLJ93.h:50-150 and
  * src/WallEvaluatorColloid.h:52-195 with their instantiation src/WallPotentials.h / src/WallPotentials.cu. The two
