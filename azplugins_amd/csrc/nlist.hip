@@ -201,6 +201,44 @@ __global__ void __launch_bounds__(1024) bin_scan_local_kernel(uint32_t ncell, co
         block_total[blockIdx.x] = total;
     }
 
+// The scan of the block totals, in place: x[0 .. n) become their exclusive prefix sums and x[n] the grand total. ONE
+// pointer (bin_scan_kernel's two are __restrict__ and may not name the same array); one value per thread and trip,
+// a trip's reads all precede its writes (the barriers), the carry in a register.
+__global__ void __launch_bounds__(1024) bin_scan_totals_kernel(uint32_t n, uint32_t* x)
+    {
+    __shared__ uint32_t s_wave[16];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    uint32_t carry = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += 1024u)
+        {
+        const uint32_t c = c0 + t;
+        const uint32_t mine = (c < n) ? x[c] : 0u;
+        uint32_t incl = mine;
+        for (int off = 1; off < 64; off <<= 1)
+            {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
+            if ((int)lane >= off)
+                incl += up;
+            }
+        if (lane == 63u)
+            s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < 16u; ++w)
+            {
+            const uint32_t v = s_wave[w];
+            before += (w < wave) ? v : 0u;
+            total += v;
+            }
+        __syncthreads();
+        if (c < n)
+            x[c] = carry + before + incl - mine;
+        carry += total;
+        }
+    if (t == 0)
+        x[n] = carry;
+    }
+
 __global__ void __launch_bounds__(256) bin_scan_add_kernel(uint32_t ncell, const uint32_t* __restrict__ block_start, uint32_t* __restrict__ count,
                                                            uint32_t* __restrict__ cell_start)
     {
@@ -635,10 +673,10 @@ extern "C" int azp_nlist_bin(const azp_nlist_args* args, uint32_t* d_cursor, uin
     const uint32_t nblk = (ncell + 4095u) / 4096u;
     if (nblk > 8u && nblk + 1u <= n)
         {
-        // (the totals live in d_order_tmp, which the scatter fills only afterwards; bin_scan_kernel turns n totals into
-        // their n starts + the grand total at [n])
+        // (the totals live in d_order_tmp, which the scatter fills only afterwards; bin_scan_totals_kernel turns nblk
+        // totals into their nblk starts + the grand total at [nblk]: nblk + 1 <= n words)
         hipLaunchKernelGGL(bin_scan_local_kernel, dim3(nblk), dim3(1024), 0, s, ncell, d_cursor, args->d_cell_start, d_order_tmp);
-        hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, s, nblk, d_order_tmp, d_order_tmp);
+        hipLaunchKernelGGL(bin_scan_totals_kernel, dim3(1), dim3(1024), 0, s, nblk, d_order_tmp);
         hipLaunchKernelGGL(bin_scan_add_kernel, dim3((ncell + 1u + 255u) / 256u), dim3(256), 0, s, ncell, d_order_tmp, d_cursor, args->d_cell_start);
         }
     else

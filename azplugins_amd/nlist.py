@@ -168,6 +168,12 @@ class Cell(NeighborList):
     native_binning = {"0": False, "1": True}.get(os.environ.get("AZP_NATIVE_BINNING", ""), None)  # None: when the cells number more than 2^16 (the framework sort then needs four radix passes)
 
     @property
+    def binning_path(self):
+        """Which branch of ``_bin`` the last build took: "native" (azp_nlist_bin), "sort16" (framework sort on 16-bit
+        keys) or "sort32" (framework sort on the 32-bit cell ids); None before the first build."""
+        return getattr(self, "_binning_path", None)
+
+    @property
     def sort_wanted(self):
         """The members of some tile have drifted apart: a particle sort would let the plan come from the cells again."""
         return self._sort_wanted
@@ -414,8 +420,10 @@ class Cell(NeighborList):
             a.d_order = order.data_ptr()
             a.d_cell_start = cell_start.data_ptr()
             _lib.check(l.azp_nlist_bin(C.byref(a), cursor.data_ptr(), order_tmp.data_ptr(), stream), "azp_nlist_bin")
+            self._binning_path = "native"
             return (cell_of, order, cell_start, cursor, order_tmp)
         _lib.check(l.azp_nlist_cell_assign(C.byref(a), stream), "azp_nlist_cell_assign")
+        self._binning_path = "sort16" if ncell <= 65536 else "sort32"
         if ncell <= 65536:
             # 16-bit keys: two radix passes instead of four (0.06 instead of 0.16 ms at N = 2^20); same permutation
             k16, order = torch.sort((cell_of - 32768).to(torch.int16), stable=True)

@@ -273,14 +273,17 @@ def rel_err(a, b):
 # ---------------------------------------------------------------------------
 # binned particles (azp_nlist_args) for the plan-from-cells compiler
 # ---------------------------------------------------------------------------
-def gpu_cells(pos, box, r_list, ntypes=1, N=None, exclusions=None, row_capacity=0, sub=1, dims=None, excl_pitch=None):
+def gpu_cells(pos, box, r_list, ntypes=1, N=None, exclusions=None, row_capacity=0, sub=1, dims=None, excl_pitch=None,
+              binning="sort"):
     """Bin ``pos`` (n_total x 4, ghosts after the N locals) into cells of width >= max r_list / sub with
     libazp's own kernels (azp_nlist_cell_assign / _cell_bounds) and return (azp_nlist_args, keepalive).
     ``box``: (L, tilt, periodic) as for gpu_pair_args; ``exclusions``: (n_excl, excl[N, max]). ``sub`` = 2: cells of
     half the list radius (azp_nlist_args.cell_subdivision) where the plan compiler can take them (>= 5 cells along
     every periodic axis), else cells of the full radius as the product does. ``dims``: cells per axis instead of
     the product's floor(L / r_list) (fewer, wider cells only). ``excl_pitch`` (>= N; default N): column pitch of
-    the exclusion table, the columns past N filled with arbitrary particle indices (a builder that read them would drop pairs)."""
+    the exclusion table, the columns past N filled with arbitrary particle indices (a builder that read them would drop pairs).
+    ``binning``: "sort" (azp_nlist_cell_assign, the framework's stable sort, azp_nlist_cell_bounds) or "native"
+    (azp_nlist_bin, the library's own counting sort)."""
     import torch
 
     pos = np.ascontiguousarray(pos, dtype=np.float64)
@@ -312,14 +315,24 @@ def gpu_cells(pos, box, r_list, ntypes=1, N=None, exclusions=None, row_capacity=
     t["cell_of"] = torch.empty(n_total, dtype=torch.int32, device="cuda:0")
     a.d_cell_of = t["cell_of"].data_ptr()
     l = _lib.lib()
-    _lib.check(l.azp_nlist_cell_assign(C.byref(a), _stream()), "azp_nlist_cell_assign")
-    t["cell_sorted"], order = torch.sort(t["cell_of"], stable=True)
-    t["order"] = order.to(torch.int32)
-    t["cell_start"] = torch.empty(ncell + 1, dtype=torch.int32, device="cuda:0")
-    a.d_cell_sorted = t["cell_sorted"].data_ptr()
-    a.d_order = t["order"].data_ptr()
-    a.d_cell_start = t["cell_start"].data_ptr()
-    _lib.check(l.azp_nlist_cell_bounds(C.byref(a), _stream()), "azp_nlist_cell_bounds")
+    assert binning in ("sort", "native")
+    if binning == "native":
+        t["order"] = torch.empty(max(n_total, 1), dtype=torch.int32, device="cuda:0")
+        t["cell_start"] = torch.empty(ncell + 1, dtype=torch.int32, device="cuda:0")
+        t["cursor"] = torch.empty(ncell, dtype=torch.int32, device="cuda:0")
+        t["order_tmp"] = torch.empty(max(n_total, 1), dtype=torch.int32, device="cuda:0")
+        a.d_order = t["order"].data_ptr()
+        a.d_cell_start = t["cell_start"].data_ptr()
+        _lib.check(l.azp_nlist_bin(C.byref(a), t["cursor"].data_ptr(), t["order_tmp"].data_ptr(), _stream()), "azp_nlist_bin")
+    else:
+        _lib.check(l.azp_nlist_cell_assign(C.byref(a), _stream()), "azp_nlist_cell_assign")
+        t["cell_sorted"], order = torch.sort(t["cell_of"], stable=True)
+        t["order"] = order.to(torch.int32)
+        t["cell_start"] = torch.empty(ncell + 1, dtype=torch.int32, device="cuda:0")
+        a.d_cell_sorted = t["cell_sorted"].data_ptr()
+        a.d_order = t["order"].data_ptr()
+        a.d_cell_start = t["cell_start"].data_ptr()
+        _lib.check(l.azp_nlist_cell_bounds(C.byref(a), _stream()), "azp_nlist_cell_bounds")
     if exclusions is not None:
         n_excl, excl = exclusions
         t["n_excl"] = _dev(n_excl, np.uint32)
