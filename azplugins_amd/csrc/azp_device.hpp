@@ -172,6 +172,47 @@ template<int TPP> __device__ __forceinline__ double group_sum(double v)
     }
 
 // ---------------------------------------------------------------------------
+// Prefix sums of uint32 counters (every counting sort and compaction here). The reproducible sums of doubles are in
+// azp_reduce.hpp.
+// ---------------------------------------------------------------------------
+// Inclusive prefix sum over the 64 lanes of the calling wave (all 64 call it): lane l gets v_0 + ... + v_l.
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v)
+    {
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+#pragma unroll
+    for (uint32_t d = 1; d < WAVE; d <<= 1)
+        {
+        const uint32_t up = (uint32_t)__shfl_up((int)v, d, WAVE);
+        if (lane >= d)
+            v += up;
+        }
+    return v;
+    }
+
+// Exclusive prefix sum of `mine` over a workgroup of NW full waves, in thread order; `total` gets the workgroup's sum.
+// s_wave: NW words of LDS that the caller owns (the wave totals take one hop through it). ONE barrier, between
+// writing and reading s_wave: a caller that calls again with the same s_wave (a kernel that scans in trips) places a
+// barrier of its own before the next call, or a fast wave overwrites a total that a slow one has yet to read.
+template<uint32_t NW> __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t mine, uint32_t* s_wave, uint32_t& total)
+    {
+    const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const uint32_t incl = wave_inclusive_scan(mine);
+    if (lane == WAVE - 1)
+        s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < NW; ++w)
+        {
+        const uint32_t x = s_wave[w];
+        before += (w < wave) ? x : 0u;
+        total += x;
+        }
+    return before + (incl - mine);
+    }
+
+// ---------------------------------------------------------------------------
 // FP64 reciprocal: v_rcp_f64 seed (measured on gfx950: relative error 2^-24.4,
 // ~14 issue cycles) + one third-order correction x (1 + e + e^2), e = 1 - a x:
 // error e^3 ~ 2^-73, i.e. correct to rounding (<= 1 ulp), in 3 FMAs instead of

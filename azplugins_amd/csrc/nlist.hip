@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(256) bin_assign_count_kernel(uint32_t n_total,
 __global__ void __launch_bounds__(1024) bin_scan_kernel(uint32_t ncell, uint32_t* __restrict__ count, uint32_t* __restrict__ cell_start)
     {
     __shared__ uint32_t s_wave[16];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint32_t carry = 0;
     for (uint32_t c0 = 0; c0 < ncell; c0 += 4096u)
         {
@@ -122,26 +122,9 @@ __global__ void __launch_bounds__(1024) bin_scan_kernel(uint32_t ncell, uint32_t
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k)
             v[k] = (c + k < ncell) ? count[c + k] : 0u;
-        const uint32_t mine = v[0] + v[1] + v[2] + v[3];
-        uint32_t incl = mine;
-        for (int off = 1; off < 64; off <<= 1)
-            {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-            if ((int)lane >= off)
-                incl += up;
-            }
-        if (lane == 63u)
-            s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < 16u; ++w)
-            {
-            const uint32_t x = s_wave[w];
-            before += (w < wave) ? x : 0u;
-            total += x;
-            }
-        __syncthreads();
-        uint32_t acc = carry + before + incl - mine;
+        uint32_t total;
+        uint32_t acc = carry + block_exclusive_scan<16>(v[0] + v[1] + v[2] + v[3], s_wave, total);
+        __syncthreads(); // (the next trip writes s_wave again)
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k)
             {
@@ -165,31 +148,14 @@ __global__ void __launch_bounds__(1024) bin_scan_local_kernel(uint32_t ncell, co
                                                               uint32_t* __restrict__ block_total)
     {
     __shared__ uint32_t s_wave[16];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t t = threadIdx.x;
     const uint32_t c = blockIdx.x * 4096u + 4u * t;
     uint32_t v[4];
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k)
         v[k] = (c + k < ncell) ? count[c + k] : 0u;
-    const uint32_t mine = v[0] + v[1] + v[2] + v[3];
-    uint32_t incl = mine;
-    for (int off = 1; off < 64; off <<= 1)
-        {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-        if ((int)lane >= off)
-            incl += up;
-        }
-    if (lane == 63u)
-        s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (uint32_t w = 0; w < 16u; ++w)
-        {
-        const uint32_t x = s_wave[w];
-        before += (w < wave) ? x : 0u;
-        total += x;
-        }
-    uint32_t acc = before + incl - mine;
+    uint32_t total;
+    uint32_t acc = block_exclusive_scan<16>(v[0] + v[1] + v[2] + v[3], s_wave, total);
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k)
         {
@@ -207,32 +173,17 @@ __global__ void __launch_bounds__(1024) bin_scan_local_kernel(uint32_t ncell, co
 __global__ void __launch_bounds__(1024) bin_scan_totals_kernel(uint32_t n, uint32_t* x)
     {
     __shared__ uint32_t s_wave[16];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint32_t carry = 0;
     for (uint32_t c0 = 0; c0 < n; c0 += 1024u)
         {
         const uint32_t c = c0 + t;
         const uint32_t mine = (c < n) ? x[c] : 0u;
-        uint32_t incl = mine;
-        for (int off = 1; off < 64; off <<= 1)
-            {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-            if ((int)lane >= off)
-                incl += up;
-            }
-        if (lane == 63u)
-            s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < 16u; ++w)
-            {
-            const uint32_t v = s_wave[w];
-            before += (w < wave) ? v : 0u;
-            total += v;
-            }
-        __syncthreads();
+        uint32_t total;
+        const uint32_t before = block_exclusive_scan<16>(mine, s_wave, total);
+        __syncthreads(); // (every read of x[] and s_wave of this trip is done)
         if (c < n)
-            x[c] = carry + before + incl - mine;
+            x[c] = carry + before;
         carry += total;
         }
     if (t == 0)

@@ -516,19 +516,8 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
                 v[q] = (t < G) ? s_cnt[t] : 0u;
                 sum += v[q];
                 }
-            uint32_t incl = sum;
-            for (int off = 1; off < 64; off <<= 1)
-                {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-                if ((int)lane >= off)
-                    incl += up;
-                }
-            if (lane == 63)
-                s_wtot[wave] = incl;
-            __syncthreads();
-            uint32_t acc = incl - sum;
-            for (uint32_t w = 0; w < wave; ++w)
-                acc += s_wtot[w];
+            uint32_t total;
+            uint32_t acc = block_exclusive_scan<PC_THREADS / 64>(sum, s_wtot, total);
 #pragma unroll
             for (uint32_t q = 0; q < PER; ++q)
                 {
@@ -589,14 +578,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
                 v[q] = (t < ncell_blk) ? s_coff[t + 1] : 0u;
                 sum += v[q];
                 }
-            uint32_t incl = sum;
-            for (int off = 1; off < 64; off <<= 1)
-                {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-                if ((int)lane >= off)
-                    incl += up;
-                }
-            uint32_t acc = incl - sum;
+            uint32_t acc = wave_inclusive_scan(sum) - sum;
     #pragma unroll
             for (uint32_t q = 0; q < PER; ++q)
                 {
@@ -1060,13 +1042,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
             w[q] = (uint32_t)__popc(s_used[PER * tid + q]);
             sum += w[q];
             }
-        uint32_t incl = sum;
-        for (int off = 1; off < 64; off <<= 1)
-            {
-            const uint32_t v = (uint32_t)__shfl_up((int)incl, off, 64);
-            if ((int)lane >= off)
-                incl += v;
-            }
+        const uint32_t incl = wave_inclusive_scan(sum);
         uint32_t acc = incl - sum;
 #pragma unroll
         for (uint32_t q = 0; q < PER; ++q)

@@ -212,38 +212,21 @@ __global__ void __launch_bounds__(RDF_SCAN_BLOCK) rdf_bin_scan(uint32_t* count, 
     {
     constexpr uint32_t NW = RDF_SCAN_BLOCK / WAVE;
     __shared__ uint32_t s_wave[NW];
-    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const uint32_t tid = threadIdx.x;
     uint32_t carry = 0;
     for (uint32_t base = 0; base < ncell; base += RDF_SCAN_BLOCK)
         {
         const uint32_t k = base + tid;  // (ncell <= RDF_MAX_CELLS: no overflow)
         const uint32_t c = k < ncell ? count[k] : 0u;
-        uint32_t v = c;
-#pragma unroll
-        for (uint32_t d = 1; d < WAVE; d <<= 1)
-            {
-            const uint32_t up = __shfl_up(v, d, WAVE);
-            if (lane >= d)
-                v += up;
-            }
-        if (lane == WAVE - 1)
-            s_wave[wave] = v;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < NW; ++w)
-            {
-            const uint32_t t = s_wave[w];
-            before += w < wave ? t : 0u;
-            total += t;
-            }
+        uint32_t total;
+        const uint32_t before = block_exclusive_scan<NW>(c, s_wave, total);
         if (k < ncell)
             {
-            start[k] = carry + before + (v - c);
+            start[k] = carry + before;
             count[k] = 0;
             }
         carry += total;
-        __syncthreads();
+        __syncthreads(); // (the next tile writes s_wave again)
         }
     if (tid == 0)
         start[ncell] = carry;

@@ -12,19 +12,10 @@
 // available here, the definitions are those of compute.py). Rows [0, N) only: ghost rows are never counted. An
 // optional per-type byte mask selects the group (the type is read from pos.w, as velocity_field.hip does).
 //
-// Nothing is atomic and every order is fixed by N alone, so two calls on the same state give bit-identical rows:
-//   thermo_partial  lane t of workgroup b takes the particles b * 256 * per_lane + j * 256 + t, j < per_lane, in
-//                   turn (coalesced across the lanes); the 64 lanes of a wave are added with the DPP butterfly
-//                   (group_sum<64>); the four waves meet in LDS and are added in wave order; one partial row per
-//                   workgroup goes to the scratch buffer, slot-major (scratch[slot * n_blocks + b]).
-//   thermo_fold     one wave per slot: lane l adds the partial rows l, l + 64, ... in turn, then the butterfly; lane
-//                   0 writes d_out[slot]. d_out is any device address (a row of a recorder's table).
-//
-// Addition depth (the longest chain of additions a term passes through). per_lane = ceil(N / (2048 * 256)) clamped
-// to [1, 128], n_blocks = ceil(N / (256 * per_lane)). Up to N = 2^24: per_lane <= 32 and n_blocks <= 2048, so a term
-// passes at most 7 adds across the force arrays of its particle, 32 in its lane, 6 in the wave, 3 across the waves,
-// 32 in the fold's lane and 6 in its butterfly: 86 <= 200. (Up to N = 2^26 the lane takes up to 128: 182. Beyond,
-// n_blocks exceeds 2048 and the fold's serial part grows with N / 2^26.)
+// The sums are the reproducible two-stage sum of azp_reduce.hpp (thermo_partial: this file's particle loop, then
+// reduce_block_store; reduce_fold): its header states the order of the additions and their depth. A term here passes
+// at most A = 7 additions before it reaches its lane's accumulator (across the AZP_THERMO_MAX_FORCES force arrays of
+// its particle), so the depth is 86 up to N = 2^24 and 182 up to N = 2^26.
 //
 // The terms themselves are plain IEEE operations in the order written (no contraction), so a host restatement
 // reproduces every term bit for bit: m v_a v_b = (m v_a) v_b; s_x = 0.5 ((q_s p_x - p_s q_x) - (q_y p_z - q_z p_y)) and
@@ -33,34 +24,13 @@
 // Bytes per particle: 32 (vel) + per force 32 (the force row: 8 are used, the row's sectors are fetched) + per
 // virial 48 (six coalesced streams) + 88 with the rotational arrays (orientation 32, angmom 32, inertia 24) + 32
 // (pos) when a mask is given. The north-star liquid (one pair force with virial): 112 B, 117 MB at N = 2^20.
-#include <algorithm>
-
-#include "azp_device.hpp"
+#include "azp_reduce.hpp"
 
 namespace azp
 {
-constexpr uint32_t TH_BLOCK = 256;
-constexpr uint32_t TH_WAVES = TH_BLOCK / WAVE;
-constexpr uint32_t TH_TARGET_BLOCKS = 2048;  // partial rows to aim for (256 CUs x 8)
-constexpr uint32_t TH_MAX_PER_LANE = 128;
+constexpr uint32_t TH_BLOCK = REDUCE_BLOCK;
 constexpr uint32_t TH_NS = AZP_THERMO_NSUMS;
 constexpr uint32_t TH_LIVE = 19;             // slots that are summed (19 is the pad)
-
-struct THShape
-    {
-    uint32_t per_lane;
-    uint32_t n_blocks;
-    };
-
-static THShape th_shape(uint32_t N)
-    {
-    THShape s;
-    const uint64_t per = ((uint64_t)N + (uint64_t)TH_TARGET_BLOCKS * TH_BLOCK - 1) / ((uint64_t)TH_TARGET_BLOCKS * TH_BLOCK);
-    s.per_lane = (uint32_t)std::min<uint64_t>(TH_MAX_PER_LANE, std::max<uint64_t>(1, per));
-    const uint64_t span = (uint64_t)TH_BLOCK * s.per_lane;
-    s.n_blocks = (uint32_t)std::max<uint64_t>(1, ((uint64_t)N + span - 1) / span);
-    return s;
-    }
 
 struct THKArgs
     {
@@ -82,8 +52,8 @@ struct THKArgs
 #pragma clang fp contract(off)
 __global__ void __launch_bounds__(TH_BLOCK) thermo_partial(const THKArgs a)
     {
-    __shared__ double s_wave[TH_WAVES][TH_NS];
-    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    __shared__ double s_wave[REDUCE_WAVES * TH_NS];
+    const uint32_t tid = threadIdx.x;
     double acc[TH_LIVE];
 #pragma unroll
     for (uint32_t k = 0; k < TH_LIVE; ++k)
@@ -150,40 +120,9 @@ __global__ void __launch_bounds__(TH_BLOCK) thermo_partial(const THKArgs a)
             acc[18] += ndof;
             }
         }
-#pragma unroll
-    for (uint32_t k = 0; k < TH_LIVE; ++k)
-        {
-        const double s = group_sum<WAVE>(acc[k]);
-        if (lane == 0)
-            s_wave[wave][k] = s;
-        }
-    __syncthreads();
-    if (tid < TH_NS)
-        {
-        double s = 0.0;
-        if (tid < TH_LIVE)
-            {
-            s = s_wave[0][tid];
-            for (uint32_t w = 1; w < TH_WAVES; ++w)
-                s += s_wave[w][tid];
-            }
-        a.scratch[(uint64_t)tid * gridDim.x + blockIdx.x] = s;
-        }
-    }
-
-// one wave per slot (grid = 20 workgroups of one wave)
-__global__ void __launch_bounds__(WAVE) thermo_fold(const double* scratch, uint32_t n_blocks, double* out)
-    {
-    const uint32_t slot = blockIdx.x, lane = threadIdx.x;
-    const double* row = scratch + (uint64_t)slot * n_blocks;
-    double s = 0.0;
-    // (unrolled: eight independent loads in flight per lane; the adds keep their order)
-#pragma unroll 8
-    for (uint32_t b = lane; b < n_blocks; b += WAVE)
-        s += row[b];
-    s = group_sum<WAVE>(s);
-    if (lane == 0)
-        out[slot] = s;
+    reduce_block_store<TH_LIVE>(acc, s_wave, a.scratch, 0, gridDim.x, blockIdx.x);
+    if (tid == TH_LIVE)
+        a.scratch[(uint64_t)TH_LIVE * gridDim.x + blockIdx.x] = 0.0;
     }
 #pragma clang fp contract(on)
 
@@ -212,7 +151,7 @@ extern "C" int azp_thermo_scratch_size(const azp_thermo_args* args, uint64_t* by
     const int rc = th_check(args);
     if (rc != AZP_SUCCESS)
         return rc;
-    *bytes = (uint64_t)th_shape(args->N).n_blocks * TH_NS * sizeof(double);
+    *bytes = (uint64_t)reduce_shape(args->N).n_blocks * TH_NS * sizeof(double);
     return AZP_SUCCESS;
     }
 
@@ -227,7 +166,7 @@ extern "C" int azp_thermo_sums(const azp_thermo_args* args, void* stream)
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (args->N == 0)
         return (int)hipMemsetAsync(args->d_out, 0, TH_NS * sizeof(double), st);
-    const THShape s = th_shape(args->N);
+    const ReduceShape s = reduce_shape(args->N);
     if (!args->d_scratch || args->scratch_bytes < (uint64_t)s.n_blocks * TH_NS * sizeof(double))
         return AZP_ERROR_INVALID_ARGUMENT;
     THKArgs k;
@@ -251,6 +190,7 @@ extern "C" int azp_thermo_sums(const azp_thermo_args* args, void* stream)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return (int)e;
-    hipLaunchKernelGGL(thermo_fold, dim3(TH_NS), dim3(WAVE), 0, st, k.scratch, s.n_blocks, args->d_out);
+    // one wave per slot, the pad included
+    hipLaunchKernelGGL(reduce_fold<false>, dim3(TH_NS), dim3(WAVE), 0, st, k.scratch, s.n_blocks, args->d_out);
     return (int)hipGetLastError();
     }

@@ -139,22 +139,10 @@ __device__ SelState advance(const EvapHeader* h, int p, uint32_t* s_wave, SelSta
     const SelState prev = h->state[p - 1];
     if (prev.mode != MODE_SELECT) // (uniform over the workgroup)
         return prev;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t c = h->hist[p - 1][tid];
-    uint32_t incl = c;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1)
-        {
-        const uint32_t up = __shfl_up(incl, d, WAVE);
-        if ((int)lane >= d)
-            incl += up;
-        }
-    if (lane == 63)
-        s_wave[wave] = incl;
-    __syncthreads();
-    for (uint32_t w = 0; w < wave; ++w)
-        incl += s_wave[w];
-    const uint32_t excl = incl - c;
+    uint32_t total;
+    const uint32_t excl = block_exclusive_scan<4>(c, s_wave, total), incl = excl + c;
     // the digit whose bucket holds the k-th key: excl < k <= incl (exactly one digit: the counts sum to >= k)
     if (excl < prev.k && prev.k <= incl)
         {

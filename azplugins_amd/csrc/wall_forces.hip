@@ -8,27 +8,23 @@
 //                       over them is wave-uniform and each wall's data arrives by scalar loads. A particle is
 //                       rejected on its distance d before any evaluator arithmetic (most particles of a real system
 //                       are out of range of every wall).
-//   wall_net_partial    the force on each wall, -sum_i F_i^(w), and its energy: blockIdx.y is the wall, the particles
-//   wall_net_fold       are walked as thermo.hip walks them (lane t of workgroup b takes b * 256 * per_lane + j * 256
-//                       + t in turn, DPP butterfly over the wave, the four waves added in wave order, one partial per
-//                       workgroup in the scratch, one wave per output slot folds them). Nothing is atomic and every
-//                       order is fixed by N: two calls on the same state give the same bits.
+//   wall_net_partial    the force on each wall, -sum_i F_i^(w), and its energy: blockIdx.y is the wall; the reproducible
+//                       two-stage sum of azp_reduce.hpp (its header states the order and the depth), four slots per
+//                       wall, finished by reduce_fold<true>, which changes the sign of the three force slots. One
+//                       term per particle and slot goes straight to the lane's accumulator (A = 0 in the header's
+//                       depth). Two calls on the same state give the same bits.
 //
 // The signed distance is computed without contraction, sums left to right, with the correctly rounded square root, so
 // a host restatement has the same d to the bit (the force varies as d^-10 near a wall: an ulp of rho is 1e-13 of the
 // force at d = 0.01). The evaluators are free to contract and use the refined reciprocal.
-#include <algorithm>
-
-#include "azp_device.hpp"
+#include "azp_reduce.hpp"
 #include "pair_kernel_host.hpp"
 
 namespace azp
 {
 constexpr uint32_t WALL_ROW = AZP_WALL_PARAM_DOUBLES;
-constexpr uint32_t WALL_NET_BLOCK = 256;
-constexpr uint32_t WALL_NET_WAVES = WALL_NET_BLOCK / WAVE;
-constexpr uint32_t WALL_NET_TARGET_BLOCKS = 2048; // partials per slot to aim for (256 CUs x 8)
-constexpr uint32_t WALL_NET_MAX_PER_LANE = 128;
+constexpr uint32_t WALL_NET_BLOCK = REDUCE_BLOCK;
+constexpr uint32_t WALL_NET_WAVES = REDUCE_WAVES;
 
 struct WallRow
     {
@@ -193,7 +189,7 @@ template<class Eval> __global__ void __launch_bounds__(WALL_NET_BLOCK) wall_net_
     double* s_rows = reinterpret_cast<double*>(s_raw);
     double* s_wave = s_rows + (size_t)a.ntypes * WALL_ROW;
     wall_stage_rows(a, s_rows);
-    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const uint32_t tid = threadIdx.x;
     const azp_wall& wall = a.walls[blockIdx.y];
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     const uint64_t base = (uint64_t)blockIdx.x * WALL_NET_BLOCK * a.per_lane;
@@ -211,51 +207,7 @@ template<class Eval> __global__ void __launch_bounds__(WALL_NET_BLOCK) wall_net_
         for (uint32_t k = 0; k < 4; ++k)
             acc[k] += f[k];
         }
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k)
-        {
-        const double s = group_sum<WAVE>(acc[k]);
-        if (lane == 0)
-            s_wave[wave * 4 + k] = s;
-        }
-    __syncthreads();
-    if (tid < 4)
-        {
-        double s = s_wave[tid];
-        for (uint32_t w = 1; w < WALL_NET_WAVES; ++w)
-            s += s_wave[w * 4 + tid];
-        a.scratch[((uint64_t)blockIdx.y * 4 + tid) * gridDim.x + blockIdx.x] = s;
-        }
-    }
-
-// one wave per output slot (grid = 4 n_walls workgroups of one wave); the force components change sign: the force ON the wall
-__global__ void __launch_bounds__(WAVE) wall_net_fold(const double* scratch, uint32_t n_blocks, double* out)
-    {
-    const uint32_t slot = blockIdx.x, lane = threadIdx.x;
-    const double* row = scratch + (uint64_t)slot * n_blocks;
-    double s = 0.0;
-#pragma unroll 8
-    for (uint32_t b = lane; b < n_blocks; b += WAVE)
-        s += row[b];
-    s = group_sum<WAVE>(s);
-    if (lane == 0)
-        out[slot] = ((slot & 3u) == 3u) ? s : -s;
-    }
-
-struct WallNetShape
-    {
-    uint32_t per_lane;
-    uint32_t n_blocks;
-    };
-
-static WallNetShape wall_net_shape(uint32_t N)
-    {
-    WallNetShape s;
-    const uint64_t chunk = (uint64_t)WALL_NET_TARGET_BLOCKS * WALL_NET_BLOCK;
-    s.per_lane = (uint32_t)std::min<uint64_t>(WALL_NET_MAX_PER_LANE, std::max<uint64_t>(1, ((uint64_t)N + chunk - 1) / chunk));
-    const uint64_t span = (uint64_t)WALL_NET_BLOCK * s.per_lane;
-    s.n_blocks = (uint32_t)std::max<uint64_t>(1, ((uint64_t)N + span - 1) / span);
-    return s;
+    reduce_block_store<4>(acc, s_wave, a.scratch, blockIdx.y * 4, gridDim.x, blockIdx.x);
     }
 
 // what does not depend on the arrays: walls, block size, table size
@@ -322,7 +274,7 @@ template<class Eval> static int launch_wall_forces(const azp_wall_args* args, vo
 
 static uint64_t wall_net_scratch_bytes(const azp_wall_args* a)
     {
-    return (uint64_t)wall_net_shape(a->N).n_blocks * 4 * a->n_walls * sizeof(double);
+    return (uint64_t)reduce_shape(a->N).n_blocks * 4 * a->n_walls * sizeof(double);
     }
 
 template<class Eval>
@@ -338,7 +290,7 @@ static int launch_wall_net(const azp_wall_args* args, double* d_out, void* d_scr
         return (int)hipMemsetAsync(d_out, 0, sizeof(double) * 4 * args->n_walls, s);
     if (!args->d_pos || !args->d_params || args->ntypes == 0 || !d_scratch || scratch_bytes < wall_net_scratch_bytes(args))
         return AZP_ERROR_INVALID_ARGUMENT;
-    const WallNetShape shape = wall_net_shape(args->N);
+    const ReduceShape shape = reduce_shape(args->N);
     WallKArgs k;
     wall_fill(k, args);
     k.force = nullptr;
@@ -349,7 +301,7 @@ static int launch_wall_net(const azp_wall_args* args, double* d_out, void* d_scr
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return (int)e;
-    hipLaunchKernelGGL(wall_net_fold, dim3(4 * args->n_walls), dim3(WAVE), 0, s, k.scratch, shape.n_blocks, d_out);
+    hipLaunchKernelGGL(reduce_fold<true>, dim3(4 * args->n_walls), dim3(WAVE), 0, s, k.scratch, shape.n_blocks, d_out);
     return (int)hipGetLastError();
     }
 } // namespace azp

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import reduction_ref as red
 import thermo_ref as ref
 from azplugins_amd import synthetic as syn
 
@@ -119,6 +120,37 @@ def test_reduction_against_exact_sums(N, n_forces):
         _check_row(got, _host_terms(sim, select[key]), "N=%d forces=%d filter=%s" % (N, n_forces, key))
         assert thermo.num_particles == int(select[key].sum())
         assert thermo.linear_momentum == (got[1], got[2], got[3])
+
+
+@pytest.mark.parametrize("n_forces", [1, 3])
+@pytest.mark.parametrize("N", [1, 64, 65, 257, 10007, 524289])
+def test_reduction_order_bit_for_bit(N, n_forces):
+    """The row is the documented tree (csrc/azp_reduce.hpp, restated in tests/reduction_ref.py) over the per-particle
+    terms, in every bit. 65 and 257 put the tail in a second wave and a second workgroup; 524,289 is the smallest N with
+    two particles per lane: 1,025 partials, 17 trips of the fold's lanes."""
+    import azplugins_amd as azp
+    from azplugins_amd import compute
+
+    sim = _gas(N, seed=300 + N % 89 + n_forces, n_forces=n_forces)
+    thermos = {"All": compute.ThermodynamicQuantities(azp.All()), "A": compute.ThermodynamicQuantities(azp.Type(["A"]))}
+    for t in thermos.values():
+        sim.operations.add(t)
+    sim.run(0)
+    st = sim.state
+    forces = sim.operations.integrator.forces
+    select = {"All": np.ones(N, bool), "A": st.typeid_host == 0}
+    for key, thermo in thermos.items():
+        got = thermo._sums().cpu().numpy()[0]
+        terms = ref.particle_terms(st.vel[:N].cpu().numpy(), select[key], [f._force.cpu().numpy() for f in forces],
+                                   [f._virial.cpu().numpy() for f in forces], st.orientation[:N].cpu().numpy(),
+                                   st.angmom[:N].cpu().numpy(), st.inertia[:N].cpu().numpy())
+        want = red.tree_sum(terms)
+        differ = np.flatnonzero(got.view(np.int64) != want.view(np.int64))
+        print("N=%d forces=%d filter=%s: slots that differ in bits: %s" % (N, n_forces, key, differ.tolist()))
+        for k in differ:
+            print("  %2d %r %r" % (k, got[k], want[k]))
+        assert differ.size == 0, (key, differ.tolist())
+        assert got[0] == select[key].sum() and (N < 64 or got[16] != 0.0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import azplugins_amd as azp
+import reduction_ref as red
 import wall_ref as ref
 from azplugins_amd import _lib
 from azplugins_amd import synthetic as syn
@@ -398,3 +399,32 @@ def test_wall_forces(kind, extrap):
     assert np.array_equal(rows[:, :3], got)
     for k, (want_e, total_e) in enumerate(energies):  # the fourth column: the energy of each wall
         assert abs(rows[k, 3] - want_e) <= BOUND[kind] * total_e
+
+
+def _bits(x):
+    return np.asarray(x, dtype=np.float64).view(np.int64)
+
+
+@pytest.mark.parametrize("kind,extrap,n,geometries", [("lj93", False, 1000, "all"), ("colloid", True, 1000, "all"),
+                                                      ("lj93", False, 20000, "all"), ("colloid", True, 20000, "all"),
+                                                      ("lj93", False, 524289, "plane_z")])
+def test_wall_forces_order_bit_for_bit(kind, extrap, n, geometries):
+    """One wall at a time: its net force and energy are the documented tree (csrc/azp_reduce.hpp, restated in
+    tests/reduction_ref.py) over the per-particle forces and energies of that wall, in every bit -- wall_term gives the
+    same bits in both kernels, as the single-wall assertion of test_wall_forces already assumes. 1,000 particles: 4
+    partials; 20,000: 79, a second trip of the fold's lanes; 524,289: two particles per lane in the wall's own loop."""
+    params = type_params(kind, extrap)
+    pos, tid = positions(kind, "", [], n, extrap, seed=11)
+    for g in (list(SINGLE) if geometries == "all" else [geometries]):
+        one = make_wall(kind, [SINGLE[g]], params, "shift")
+        sim = make_sim(pos, tid, [one])
+        sim.run(0)
+        f, e = one.forces, one.energies
+        got_f = one.wall_forces[0]
+        got_e = one._net[0][0, 3].item()  # the row the call left behind: force on the wall, then its energy
+        want_f = -red.tree_sum(f.T)
+        want_e = red.tree_sum(e)
+        print("%s %s N=%d: %r %r | tree %r %r" % (kind, g, n, got_f.tolist(), got_e, want_f.tolist(), float(want_e)))
+        assert np.count_nonzero(e) >= n // 100
+        assert np.array_equal(_bits(got_f), _bits(want_f)), g
+        assert _bits(got_e) == _bits(want_e), g

@@ -14,7 +14,8 @@ NSUMS = 20
 ORDER = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))  # xx, xy, xz, yy, yz, zz
 
 # the error bound of a slot relative to the sum of the magnitudes of its terms: no term passes through more than 200
-# additions (each at most 2^-53 relative to the partial sum, which the sum of the magnitudes bounds), a few roundings
+# additions (the depth is derived in csrc/azp_reduce.hpp: 86 up to N = 2^24, 182 up to 2^26 for thermo.hip's terms;
+# each addition at most 2^-53 relative to the partial sum, which the sum of the magnitudes bounds), a few roundings
 # inside each term, and slack
 REL_BOUND = 256.0 * 2.0 ** -53
 
@@ -55,6 +56,44 @@ def terms(vel, select, forces=(), virials=(), orientation=None, angmom=None, ine
         nz = I != 0.0
         out[17] = 0.5 * (s[nz] * s[nz] / I[nz])
         out[18] = np.ones(int(nz.sum()))
+    return out
+
+
+def particle_terms(vel, select, forces=(), virials=(), orientation=None, angmom=None, inertia=None):
+    """The arguments of ``terms``; returns the ``(20, N)`` array of what each particle adds to each slot in
+    ``thermo_partial``, bit for bit: the virial and energy terms are added over the forces serially from ``0.0``, the
+    rotational term over the axes serially, unselected rows are ``+0.0``. ``reduction_ref.tree_sum`` of it is the
+    kernel's row."""
+    vel = np.asarray(vel, dtype=np.float64)
+    sel = np.asarray(select, dtype=bool)
+    N = vel.shape[0]
+    out = np.zeros((NSUMS, N))
+    v, m = vel[:, :3], vel[:, 3]
+    out[0] = 1.0
+    p = m[:, None] * v
+    for a in range(3):
+        out[1 + a] = p[:, a]
+    for c, (a, b) in enumerate(ORDER):
+        out[4 + c] = p[:, a] * v[:, b]
+    for k, f in enumerate(forces):
+        out[16] = out[16] + np.asarray(f, dtype=np.float64)[:, 3]
+        w = virials[k] if k < len(virials) else None
+        if w is not None:
+            for c in range(6):
+                out[10 + c] = out[10 + c] + np.asarray(w, dtype=np.float64)[c]
+    if orientation is not None:
+        q = np.asarray(orientation, dtype=np.float64)
+        l = np.asarray(angmom, dtype=np.float64)
+        I = np.asarray(inertia, dtype=np.float64)
+        s = np.stack([0.5 * ((q[:, 0] * l[:, 1] - l[:, 0] * q[:, 1]) - (q[:, 2] * l[:, 3] - q[:, 3] * l[:, 2])),
+                      0.5 * ((q[:, 0] * l[:, 2] - l[:, 0] * q[:, 2]) - (q[:, 3] * l[:, 1] - q[:, 1] * l[:, 3])),
+                      0.5 * ((q[:, 0] * l[:, 3] - l[:, 0] * q[:, 3]) - (q[:, 1] * l[:, 2] - q[:, 2] * l[:, 1]))], axis=1)
+        for k in range(3):
+            nz = I[:, k] != 0.0
+            ke = 0.5 * (s[:, k] * s[:, k] / np.where(nz, I[:, k], 1.0))
+            out[17] = out[17] + np.where(nz, ke, 0.0)
+            out[18] = out[18] + np.where(nz, 1.0, 0.0)
+    out[:, ~sel] = 0.0
     return out
 
 
