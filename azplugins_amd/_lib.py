@@ -96,6 +96,29 @@ class BondArgs(C.Structure):
     ]
 
 
+class AngleEntry(C.Structure):
+    _fields_ = [("idx", C.c_uint32 * 2), ("type", C.c_uint32), ("pos", C.c_uint32)]
+
+
+class AngleArgs(C.Structure):
+    _fields_ = [
+        ("d_force", C.c_void_p),
+        ("d_virial", C.c_void_p),
+        ("virial_pitch", C.c_uint64),
+        ("N", C.c_uint32),
+        ("n_max", C.c_uint32),
+        ("d_pos", C.c_void_p),
+        ("box", Box),
+        ("d_gpu_anglelist", C.c_void_p),
+        ("d_gpu_n_angles", C.c_void_p),
+        ("pitch", C.c_uint64),
+        ("n_angle_types", C.c_uint32),
+        ("compute_virial", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 class BarrierArgs(C.Structure):
     _fields_ = [
         ("d_force", C.c_void_p),
@@ -414,6 +437,12 @@ SYMBOLS = {
     "azp_aniso_forces_planned_two_patch_morse": (C.c_int, [_VP, C.POINTER(AnisoArgs), _VP, _VP]),
     "azp_bond_forces_double_well": (C.c_int, [C.POINTER(BondArgs), _VP, _VP, _VP]),
     "azp_bond_forces_quartic": (C.c_int, [C.POINTER(BondArgs), _VP, _VP, _VP]),
+    "azp_angle_harmonic_params_make": (None, [_D] * 2 + [_VP]),
+    "azp_angle_harmonic_params_unpack": (None, [_VP] + [_PD] * 2),
+    "azp_angle_cossq_params_make": (None, [_D] * 2 + [_VP]),
+    "azp_angle_cossq_params_unpack": (None, [_VP] + [_PD] * 2),
+    "azp_angle_forces_harmonic": (C.c_int, [C.POINTER(AngleArgs), _VP, _VP]),
+    "azp_angle_forces_cosine_squared": (C.c_int, [C.POINTER(AngleArgs), _VP, _VP]),
     "azp_nlist_cell_assign": (C.c_int, [C.POINTER(NlistArgs), _VP]),
     "azp_nlist_cell_bounds": (C.c_int, [C.POINTER(NlistArgs), _VP]),
     "azp_nlist_bin": (C.c_int, [C.POINTER(NlistArgs), _VP, _VP, _VP]),

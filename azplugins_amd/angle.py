@@ -1,0 +1,130 @@
+"""Angle potentials: harmonic and cosine-squared bending on libazp's gfx950 angle kernel (``csrc/angle_forces.hip``).
+
+The reference holds no angle code (with HOOMD-blue, bending stiffness comes from ``hoomd.md.angle`` next to the
+plugin), so the semantics are DEFINED HERE and in ``include/azp.h``: HOOMD's documented
+``md.angle.Harmonic`` and ``md.angle.CosineSquared`` conventions.
+
+An angle has members ``a, b, c`` with ``b`` the vertex (``Snapshot.angles.group``). With ``dab = r_a - r_b`` and
+``dcb = r_c - r_b`` (minimum image), ``c = dab.dcb / (|dab||dcb|)`` clamped to [-1, 1] and
+``s = max(sqrt(1 - c^2), 1e-3)`` (HOOMD's floor):
+
+* ``Harmonic``: ``U = 1/2 k (theta - t0)^2`` with ``theta = acos(c)``, ``dU/dc = -k (theta - t0) / s``;
+* ``CosineSquared``: ``U = 1/2 k (c - cos t0)^2``, ``dU/dc = k (c - cos t0)``.
+
+``F_a = -dU/dc (dcb / (|dab||dcb|) - c dab / |dab|^2)``, ``F_c`` likewise with a and c exchanged, ``F_b = -F_a - F_c``.
+Every member gets a third of ``U`` and, with ``compute_virial``, a third of ``dab (x) F_a + dcb (x) F_c``. Coincident
+members (``|dab|`` or ``|dcb|`` equal to 0) are undefined. Angles add no neighbor-list exclusions.
+
+Out of scope: dihedrals and impropers, tabulated angles, 1-3 exclusions, an ``_azplugins`` class."""
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from .force import Force, TypeParameter
+
+
+class _AngleParameter(TypeParameter):
+    """``TypeParameter`` whose values are also range-checked when they are set."""
+
+    def _validate(self, value):
+        out = super()._validate(value)
+        if not math.isfinite(out["k"]):
+            raise ValueError("%s: k must be finite, got %r" % (self.name, out["k"]))
+        if not 0.0 <= out["t0"] <= math.pi:  # (false for a NaN too)
+            raise ValueError("%s: t0 must lie in [0, pi], got %r" % (self.name, out["t0"]))
+        return out
+
+
+class Angle(Force):
+    """Reduced ``hoomd.md.angle.Angle``: per-angle-type ``params``. ``block_size``: 0 (256) or 64, 128, 256."""
+
+    _entry = None
+    _make = None
+    _unpack_entry = None
+    _schema = dict(k=float, t0=float)
+    _cpp_class_name = None  # the reference's module.cc registers no angle class
+
+    def __init__(self):
+        super().__init__()
+        self.params = _AngleParameter("params", self._schema, 1, self._mark_dirty)
+        self._tables = None
+        self.block_size = 0
+
+    def _mark_dirty(self):
+        self._tables = None
+
+    def _attach(self, sim):
+        super()._attach(sim)
+        self._tables = None
+
+    def _pack(self, d):
+        """One type's dict folded into its two doubles by libazp."""
+        out = np.zeros(2)
+        getattr(_lib.lib(), self._make)(d["k"], d["t0"], out.ctypes.data)
+        return out
+
+    def _unpack(self, raw):
+        raw = np.ascontiguousarray(raw, dtype=np.float64)
+        k, t0 = C.c_double(), C.c_double()
+        getattr(_lib.lib(), self._unpack_entry)(raw.ctypes.data, C.byref(k), C.byref(t0))
+        return dict(k=k.value, t0=t0.value)
+
+    def _build_tables(self):
+        import torch
+
+        types = self._state.angle_types
+        raw = np.zeros((max(len(types), 1), 2))
+        for i, t in enumerate(types):
+            d = self.params.get_raw(t)
+            if d is None:
+                raise _lib.AzpError("%s.params[%r] is not set" % (type(self).__name__, t))
+            raw[i] = self._pack(d)
+        self._tables = torch.from_numpy(raw).to(self._state.device)
+
+    def compute(self, timestep=None):
+        self._require()
+        st = self._state
+        self._ensure_buffers()
+        if self._tables is None or self._tables.shape[0] != max(len(st.angle_types), 1):
+            self._build_tables()
+        tab = st.angle_table()
+        a = _lib.AngleArgs()
+        a.d_force = self._force.data_ptr()
+        a.d_virial = self._virial.data_ptr()
+        a.virial_pitch = st.N
+        a.N = st.N
+        a.n_max = st.n_max
+        a.d_pos = st.pos.data_ptr()
+        a.box = st.box.to_c()
+        a.d_gpu_anglelist = tab["table"].data_ptr()
+        a.d_gpu_n_angles = tab["n_angles"].data_ptr()
+        a.pitch = tab["pitch"]
+        a.n_angle_types = max(len(st.angle_types), 1)
+        a.compute_virial = 1 if self.compute_virial else 0
+        a.block_size = self.block_size
+        _lib.check(getattr(_lib.lib(), self._entry)(C.byref(a), self._tables.data_ptr(), _lib.raw_stream(st.device)),
+                   self._entry)
+
+
+class Harmonic(Angle):
+    """Harmonic angle potential ``U = 1/2 k (theta - t0)^2`` (HOOMD ``md.angle.Harmonic``).
+    ``params[type] = dict(k, t0)``, ``k`` finite, ``0 <= t0 <= pi`` (radians)."""
+
+    _entry = "azp_angle_forces_harmonic"
+    _make = "azp_angle_harmonic_params_make"
+    _unpack_entry = "azp_angle_harmonic_params_unpack"
+
+
+class CosineSquared(Angle):
+    """Cosine-squared angle potential ``U = 1/2 k (cos theta - cos t0)^2`` (HOOMD ``md.angle.CosineSquared``).
+    ``params[type] = dict(k, t0)``, ``k`` finite, ``0 <= t0 <= pi`` (radians); ``cos t0`` is folded on the host."""
+
+    _entry = "azp_angle_forces_cosine_squared"
+    _make = "azp_angle_cossq_params_make"
+    _unpack_entry = "azp_angle_cossq_params_unpack"
+
+
+__all__ = ["Angle", "Harmonic", "CosineSquared"]

@@ -106,6 +106,28 @@ void azp_quartic_params_unpack(const azp_quartic_params* p, double* k, double* r
     *delta = p->delta;
     }
 
+// ---- angle potentials (include/azp.h, "angle forces"): harmonic keeps (k, t0), cosine squared folds cos t0 ----
+void azp_angle_harmonic_params_make(double k, double t0, azp_angle_harmonic_params* out)
+    {
+    out->k = k;
+    out->t0 = t0;
+    }
+void azp_angle_harmonic_params_unpack(const azp_angle_harmonic_params* p, double* k, double* t0)
+    {
+    *k = p->k;
+    *t0 = p->t0;
+    }
+void azp_angle_cossq_params_make(double k, double t0, azp_angle_cossq_params* out)
+    {
+    out->k = k;
+    out->cos_t0 = std::cos(t0);
+    }
+void azp_angle_cossq_params_unpack(const azp_angle_cossq_params* p, double* k, double* t0)
+    {
+    *k = p->k;
+    *t0 = std::acos(p->cos_t0);
+    }
+
 // ---- wall potentials: one type's dict folded into its parameter row (include/azp.h, "wall potentials") ----
 // V and F = -dV/dr in plain IEEE double, in the order written: tests/wall_ref.py restates the two folds and agrees
 // to a few ulp. src/WallEvaluatorLJ93.h:34-48 gives V and F / r for LJ93, src/WallEvaluatorColloid.h:36-41 for the

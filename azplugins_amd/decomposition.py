@@ -258,6 +258,21 @@ class HaloExchange:
         self.transfer(self.pack(*arrays), state=state)
 
 
+def _snapshot_topology(snap):
+    """The bonded topology of a snapshot by particle TAG: ``bond_tags`` / ``bond_typeid`` / ``bond_types`` and, when the
+    snapshot has angles, ``angle_tags`` / ``angle_typeid`` / ``angle_types`` (absent without angles; a snapshot with
+    angles but no bonds carries an empty bond list). None when there are neither bonds nor angles."""
+    if not (snap.bonds.N or snap.angles.N):
+        return None
+    tag = snap.particles.tag.astype(np.int64)
+    topo = dict(bond_tags=tag[snap.bonds.group.astype(np.int64)].reshape(-1, 2), bond_typeid=snap.bonds.typeid.copy(),
+                bond_types=tuple(snap.bonds.types))
+    if snap.angles.N:
+        topo.update(angle_tags=tag[snap.angles.group.astype(np.int64)].reshape(-1, 3), angle_typeid=snap.angles.typeid.copy(),
+                    angle_types=tuple(snap.angles.types))
+    return topo
+
+
 def build_rank_state(cfg, decomp, rank, device):
     """State of one rank (local + ghost particles) from a replicated synthetic
     configuration dict (see synthetic.py)."""
@@ -294,13 +309,21 @@ def rank_simulation(cfg, decomp, rank, device, seed=1):
         b = np.asarray(cfg["bonds"], dtype=np.int64).reshape(-1, 2)
         topology = dict(bond_tags=gtag[b], bond_typeid=cfg.get("bond_typeid", np.zeros(b.shape[0], dtype=np.uint32)),
                         bond_types=cfg.get("bond_types", ("A-A",)))
+    if cfg.get("angles") is not None and len(cfg["angles"]):
+        gtag = np.asarray(cfg["tag"], dtype=np.int64) if "tag" in cfg else np.arange(xyz.shape[0], dtype=np.int64)
+        g = np.asarray(cfg["angles"], dtype=np.int64).reshape(-1, 3)
+        if topology is None:
+            topology = dict(bond_tags=np.zeros((0, 2), dtype=np.int64), bond_typeid=np.zeros(0, dtype=np.uint32), bond_types=())
+        topology.update(angle_tags=gtag[g], angle_typeid=cfg.get("angle_typeid", np.zeros(g.shape[0], dtype=np.uint32)),
+                        angle_types=cfg.get("angle_types", ("A-A-A",)))
     return rank_simulation_from_snapshot(snap, xyz.shape[0], decomp, rank, device, seed=seed, topology=topology)
 
 
 def rank_simulation_from_snapshot(snap, n_global, decomp, rank, device, seed=1, topology=None):
     """Simulation of one rank from the snapshot of ITS particles (``distribute_snapshot`` hands every rank its share of
     a snapshot that only the root holds): DeviceDomain with ghosts selected, State pointed at the domain's arrays,
-    bonds (``topology``: the global bond list by tag, ``distribute_snapshot``'s second result) localized."""
+    bonds and angles (``topology``: the global bond and angle lists by tag, ``distribute_snapshot``'s third result)
+    localized."""
     from .domain import DeviceDomain
     from .simulation import Simulation
 
@@ -309,11 +332,16 @@ def rank_simulation_from_snapshot(snap, n_global, decomp, rank, device, seed=1, 
     arrays = dict(pos=st.pos, vel=st.vel, orientation=st.orientation, tag=st.tag, image=st.image, angmom=st.angmom, inertia=st.inertia)
     dom = DeviceDomain(decomp, rank, arrays, density=n_global / float(np.prod(decomp.L)))
     dom.rebuild()
-    if topology is not None and len(topology["bond_tags"]):
+    has_bonds = topology is not None and len(topology["bond_tags"]) > 0
+    has_angles = topology is not None and len(topology.get("angle_tags", ())) > 0
+    if has_bonds or has_angles:
         st.N, st.n_ghost = dom.N_local, dom.n_ghost
         for n in dom.names:
             setattr(st, n, dom.arrays[n])
+    if has_bonds:
         st.set_global_bonds(np.asarray(topology["bond_tags"], dtype=np.int64), topology["bond_typeid"], topology["bond_types"])
+    if has_angles:
+        st.set_global_angles(np.asarray(topology["angle_tags"], dtype=np.int64), topology["angle_typeid"], topology["angle_types"])
     sim.attach_domain(dom)
     return sim, dom
 
@@ -325,21 +353,18 @@ _WIRE = (("position", 3), ("typeid", 1), ("orientation", 4), ("velocity", 3), ("
 
 def distribute_snapshot(snap, decomp, root=0, device=None, group=None):
     """HOOMD's ``create_state_from_snapshot`` under MPI: only ``root`` holds the snapshot (the others pass ``None``),
-    every rank gets the particles its sub-box owns. Collective: the small things (box, type names, the bond topology by
-    tag, the per-rank counts) are broadcast, the particle rows travel in ONE ``all_to_all_single`` in which only the root
+    every rank gets the particles its sub-box owns. Collective: the small things (box, type names, the bond and angle
+    topology by tag, the per-rank counts) are broadcast, the particle rows travel in ONE ``all_to_all_single`` in which only the root
     sends (RCCL; gloo on CPU tensors in the tests). Returns ``(local_snapshot, n_global, topology)`` for
-    ``rank_simulation_from_snapshot``; ``topology`` is None without bonds."""
+    ``rank_simulation_from_snapshot``; ``topology`` is None without bonds and angles, and holds the ``angle_*`` keys only when there
+    are angles."""
     import torch
     import torch.distributed as dist
 
     from .state import Snapshot
 
     if not dist.is_initialized() or dist.get_world_size(group) == 1:
-        topo = None
-        if snap.bonds.N:
-            topo = dict(bond_tags=snap.particles.tag.astype(np.int64)[snap.bonds.group.astype(np.int64)], bond_typeid=snap.bonds.typeid.copy(),
-                        bond_types=tuple(snap.bonds.types))
-        return snap, snap.particles.N, topo
+        return snap, snap.particles.N, _snapshot_topology(snap)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     width = sum(w for _, w in _WIRE)
     meta = [None]
@@ -356,9 +381,7 @@ def distribute_snapshot(snap, decomp, root=0, device=None, group=None):
         rows = np.ascontiguousarray(rows[order])
         box = snap.configuration.box
         meta = [dict(counts=np.bincount(owner, minlength=world).tolist(), n_global=int(p.N), types=list(p.types), L=list(box.L),
-                     tilt=[box.xy, box.xz, box.yz], periodic=list(box.periodic),
-                     bond_tags=p.tag.astype(np.int64)[snap.bonds.group.astype(np.int64)] if snap.bonds.N else None,
-                     bond_typeid=snap.bonds.typeid.copy() if snap.bonds.N else None, bond_types=tuple(snap.bonds.types))]
+                     tilt=[box.xy, box.xz, box.yz], periodic=list(box.periodic), topology=_snapshot_topology(snap))]
     dist.broadcast_object_list(meta, src=root, group=group)
     m = meta[0]
     dev = "cpu" if dist.get_backend(group) == "gloo" else device
@@ -379,10 +402,7 @@ def distribute_snapshot(snap, decomp, root=0, device=None, group=None):
     from .state import Box
 
     local.configuration.box = Box(m["L"][0], m["L"][1], m["L"][2], *m["tilt"], periodic=tuple(m["periodic"]))
-    topo = None
-    if m["bond_tags"] is not None:
-        topo = dict(bond_tags=m["bond_tags"], bond_typeid=m["bond_typeid"], bond_types=m["bond_types"])
-    return local, m["n_global"], topo
+    return local, m["n_global"], m["topology"]
 
 
 def bench_main(args, rank, world, local_rank):

@@ -359,5 +359,7 @@ class DeviceDomain:
         # an array that does not migrate would keep its old size and order)
         if getattr(state, "bond_tags", None) is not None:
             state.relocalize_bonds()  # bond table and exclusions by local index: every index changed
+        if getattr(state, "angle_tags", None) is not None:
+            state.relocalize_angles()
         state.position_generation += 1
         state.order_generation += 1  # every index changed: the list must be rebuilt

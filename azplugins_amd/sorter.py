@@ -2,7 +2,7 @@
 ``hoomd.update.ParticleSorter``. Reorders the local particles along a Hilbert
 curve through small cells so that any 256 consecutive particles form a compact tile -- the order the
 tile plan (``pair_plan.hpp``) and the neighbor-list build rely on. Tags, images,
-velocities, orientations (and Langevin accelerations) travel with the particles; bonds are re-indexed.
+velocities, orientations (and Langevin accelerations) travel with the particles; bonds and angles are re-indexed.
 
 Keys and the permutation are computed with torch ops on the device (this runs
 every few hundred steps, not on the per-step path)."""
@@ -65,12 +65,16 @@ class ParticleSorter:
         for name in names:
             a = getattr(st, name)
             a[:N] = a[:N].index_select(0, order)
-        if st.n_bonds:
+        if st.n_bonds or st.n_angles:
             inv = torch.empty(N, dtype=torch.int64, device=st.device)
             inv[order] = torch.arange(N, dtype=torch.int64, device=st.device)
+        if st.n_bonds:
             # (the 10^6-entry lookup on the device, and the result stays there: State.bond_group fetches it when asked)
             st.set_bond_group_device(inv[st.bond_group_device()])
             st._bond_table = None
+        if st.n_angles:
+            st.set_angle_group_device(inv[st.angle_group_device()])
+            st._angle_table = None
         st.position_generation += 1
         st.order_generation += 1
         self.num_sorts += 1

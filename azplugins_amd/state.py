@@ -103,6 +103,24 @@ class _Bonds:
         self.typeid = np.zeros(self._N, dtype=np.uint32)
 
 
+class _Angles:
+    def __init__(self):
+        self._N = 0
+        self.types = []
+        self.group = np.zeros((0, 3), dtype=np.uint32)
+        self.typeid = np.zeros(0, dtype=np.uint32)
+
+    @property
+    def N(self):
+        return self._N
+
+    @N.setter
+    def N(self, n):
+        self._N = int(n)
+        self.group = np.zeros((self._N, 3), dtype=np.uint32)
+        self.typeid = np.zeros(self._N, dtype=np.uint32)
+
+
 class _Configuration:
     def __init__(self):
         self.box = Box(1.0)
@@ -112,16 +130,19 @@ class _Configuration:
 class Snapshot:
     """Host-side system description with ``hoomd.Snapshot``'s attribute names
     (``particles.N/position/typeid/types/orientation/velocity/mass``,
-    ``bonds.N/group/typeid/types``, ``configuration.box``)."""
+    ``bonds.N/group/typeid/types``, ``angles.N/group/typeid/types`` with members ``a, b, c`` and ``b`` the vertex,
+    ``configuration.box``)."""
 
     def __init__(self):
         self.particles = _Particles()
         self.bonds = _Bonds()
+        self.angles = _Angles()
         self.configuration = _Configuration()
 
     @classmethod
     def from_arrays(cls, xyz, box, typeid=None, types=("A",), orientation=None, velocity=None, tag=None, bonds=None,
-                    bond_typeid=None, bond_types=("A-A",), moment_inertia=None, angmom=None):
+                    bond_typeid=None, bond_types=("A-A",), moment_inertia=None, angmom=None, angles=None, angle_typeid=None,
+                    angle_types=("A-A-A",)):
         s = cls()
         xyz = np.asarray(xyz, dtype=np.float64)
         s.particles.N = xyz.shape[0]
@@ -147,6 +168,13 @@ class Snapshot:
             s.bonds.types = list(bond_types)
             if bond_typeid is not None:
                 s.bonds.typeid[:] = bond_typeid
+        if angles is not None:
+            angles = np.asarray(angles, dtype=np.uint32).reshape(-1, 3)
+            s.angles.N = angles.shape[0]
+            s.angles.group[:] = angles
+            s.angles.types = list(angle_types)
+            if angle_typeid is not None:
+                s.angles.typeid[:] = angle_typeid
         return s
 
 
@@ -204,6 +232,57 @@ def localize_bonds(tag, n_local, bond_tags, bond_typeid):
     return group, np.asarray(bond_typeid, dtype=np.uint32)[mine]
 
 
+def localize_angles(tag, n_local, angle_tags, angle_typeid):
+    """``localize_bonds`` for angles (triples of particle tags, the vertex in the middle): every angle with at least one
+    LOCAL member, as index triples over this rank's rows. All three members must be on the rank, as locals or ghosts:
+    the far end of an angle is two bonds away from a local end. Returns (angle_group uint32 (n, 3), typeid)."""
+    tag = np.asarray(tag, dtype=np.int64)
+    angle_tags = np.asarray(angle_tags, dtype=np.int64).reshape(-1, 3)
+    n_glob = int(max(angle_tags.max() + 1 if angle_tags.size else 0, tag.max() + 1 if tag.size else 0))
+    rtag = np.full(n_glob + 1, -1, dtype=np.int64)
+    rtag[tag[::-1]] = np.arange(tag.size - 1, -1, -1)  # (the lowest row wins: local before ghost, as for bonds)
+    idx = rtag[angle_tags]
+    mine = np.any((idx >= 0) & (idx < n_local), axis=1)
+    if np.any(mine & np.any(idx < 0, axis=1)):
+        raise _lib.AzpError("a member of an angle with a local particle is neither local nor a ghost on this rank: the "
+                            "ghost shell (r_cut + buffer) is narrower than two bond lengths")
+    return idx[mine].astype(np.uint32).reshape(-1, 3), np.asarray(angle_typeid, dtype=np.uint32)[mine]
+
+
+def build_angle_table(group, typeid, n_local):
+    """The per-particle angle table from the angle members (``group``: integer tensor (n, 3), ``typeid``: integer
+    tensor (n,); any device, CPU included). Particle-major: entry ``s`` of local particle ``i`` is ``table[s, i]`` =
+    (the two other members in angle order, the angle type, ``i``'s position 0 / 1 / 2 in the angle), 16 bytes, for
+    ``s < n_angles[i]``. Only members with index ``< n_local`` get entries; the entries of one particle are ordered by
+    angle index (one stable sort), which fixes the order of the kernel's sums."""
+    import torch
+
+    N = int(n_local)
+    dev = group.device
+    g = group.reshape(-1, 3).to(torch.int64)
+    n = g.shape[0]
+    # one candidate entry per (angle, member), angle-major
+    member = g.reshape(-1)
+    others = torch.stack([g[:, [1, 2]], g[:, [0, 2]], g[:, [0, 1]]], dim=1).reshape(-1, 2)
+    which = torch.arange(3, dtype=torch.int64, device=dev).repeat(n)
+    atype = typeid.to(torch.int64).reshape(-1).repeat_interleave(3)
+    keep = member < N
+    member, others, which, atype = member[keep], others[keep], which[keep], atype[keep]
+    na = torch.bincount(member, minlength=N)[:N] if member.numel() else torch.zeros(N, dtype=torch.int64, device=dev)
+    width = max(int(na.max().item()) if (N and member.numel()) else 0, 1)
+    table = torch.zeros((width, N, 4), dtype=torch.int32, device=dev)
+    if member.numel():
+        order = torch.sort(member, stable=True).indices
+        m = member[order]
+        start = torch.cumsum(na, 0) - na
+        slot = torch.arange(m.numel(), device=dev) - start[m]
+        table[slot, m, 0] = others[order, 0].to(torch.int32)
+        table[slot, m, 1] = others[order, 1].to(torch.int32)
+        table[slot, m, 2] = atype[order].to(torch.int32)
+        table[slot, m, 3] = which[order].to(torch.int32)
+    return dict(table=table, n_angles=na.to(torch.int32), pitch=N, width=width)
+
+
 class State:
     """Device-resident particle data (HOOMD ``ParticleData`` + ``BondData``)."""
 
@@ -246,6 +325,14 @@ class State:
         # index-based table above is rebuilt from it whenever particles migrate (relocalize_bonds)
         self.bond_tags = None
         self.bond_tags_typeid = None
+        # angles: the same arrangement (members a, b, c with b the vertex; set_global_angles / relocalize_angles)
+        ang = snapshot.angles
+        self.angle_types = list(ang.types)
+        self.angle_group = np.ascontiguousarray(ang.group, dtype=np.uint32).reshape(-1, 3)
+        self.angle_typeid = np.ascontiguousarray(ang.typeid, dtype=np.uint32)
+        self._angle_table = None
+        self.angle_tags = None
+        self.angle_tags_typeid = None
         self.position_generation = 0  # bumped whenever positions change
         self.order_generation = 0     # bumped whenever the particles are re-indexed (sort, migration)
         self.type_generation = 0      # bumped whenever an updater may have changed the types in pos.w
@@ -288,6 +375,37 @@ class State:
         self._bond_group_dev = group.reshape(-1, 2)
         self._bond_group_host = None
 
+    # The angle members: a host array (uint32 (n, 3)) and a device tensor (int64 (n, 3)), kept as the bond members are.
+    @property
+    def angle_group(self):
+        if self._angle_group_host is None:
+            import torch
+
+            self._angle_group_host = self._angle_group_dev.to(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 3)
+        return self._angle_group_host
+
+    @angle_group.setter
+    def angle_group(self, group):
+        self._angle_group_host = np.ascontiguousarray(group, dtype=np.uint32).reshape(-1, 3)
+        self._angle_group_dev = None
+
+    @property
+    def n_angles(self):
+        g = self._angle_group_host if self._angle_group_host is not None else self._angle_group_dev
+        return int(g.shape[0])
+
+    def angle_group_device(self):
+        """The angle members as an int64 (n, 3) tensor on the state's device."""
+        if self._angle_group_dev is None:
+            import torch
+
+            self._angle_group_dev = torch.from_numpy(self._angle_group_host.astype(np.int64)).to(self.device).reshape(-1, 3)
+        return self._angle_group_dev
+
+    def set_angle_group_device(self, group):
+        self._angle_group_dev = group.reshape(-1, 3)
+        self._angle_group_host = None
+
     @property
     def typeid_host(self):
         return self.pos[: self.N, 3].cpu().numpy().view(np.int64).astype(np.int64) & 0xFFFFFFFF
@@ -308,6 +426,32 @@ class State:
         tag = self.tag[: self.n_max].cpu().numpy().view(np.uint32).astype(np.int64)
         self.bond_group, self.bond_typeid = localize_bonds(tag, self.N, self.bond_tags, self.bond_tags_typeid)
         self._bond_table = None
+
+    def set_global_angles(self, angle_tags, angle_typeid, angle_types):
+        """Domain-decomposed runs: the angles of the WHOLE system as triples of particle tags, replicated on every rank
+        (as ``set_global_bonds``). ``relocalize_angles`` turns them into this rank's index-based table."""
+        self.angle_tags = np.ascontiguousarray(angle_tags, dtype=np.int64).reshape(-1, 3)
+        self.angle_tags_typeid = np.ascontiguousarray(angle_typeid, dtype=np.uint32)
+        self.angle_types = list(angle_types)
+        self.relocalize_angles()
+
+    def relocalize_angles(self):
+        """(Re)build ``angle_group`` -- index triples over local + ghost rows -- from the tags now on this rank: every
+        angle with at least one LOCAL member, all three members on the rank (the ghost shell is at least two bond
+        lengths wide; ``AzpError`` if a member is missing)."""
+        tag = self.tag[: self.n_max].cpu().numpy().view(np.uint32).astype(np.int64)
+        self.angle_group, self.angle_typeid = localize_angles(tag, self.N, self.angle_tags, self.angle_tags_typeid)
+        self._angle_table = None
+
+    def angle_table(self):
+        """The per-particle angle table the angle kernel walks (``build_angle_table`` on the state's device):
+        ``table`` int32 (width, N, 4), ``n_angles`` int32 (N,), ``pitch`` = N. Rebuilt after a sort or a migration."""
+        import torch
+
+        if self._angle_table is None:
+            at = torch.from_numpy(self.angle_typeid.astype(np.int64)).to(self.device)
+            self._angle_table = build_angle_table(self.angle_group_device(), at, self.N)
+        return self._angle_table
 
     def bond_table(self):
         """HOOMD's per-particle GPU bond table (``BondData::getGPUTable``):
@@ -348,6 +492,7 @@ class State:
 
     def exclusion_table(self):
         """Bonded partners as neighbor-list exclusions (HOOMD's default
-        ``exclusions=('bond',)``): (n_excl int32[N], excl int32[width, N])."""
+        ``exclusions=('bond',)``): (n_excl int32[N], excl int32[width, N]). Bond-only: angles add no exclusions (the
+        1-3 pair of an angle keeps its pair interaction)."""
         t = self.bond_table()
         return t["n_bonds"], t["table"][:, :, 0].contiguous(), t["pitch"]

@@ -15,6 +15,7 @@
  *                                   (src/AnisoPotentialPairGPUKernel.cu.inc:21-25)
  *   azp_bond_forces_*            <- gpu_compute_bond_forces<E, 2>
  *                                   (src/PotentialBondGPUKernel.cu.inc:25-29)
+ *   azp_angle_forces_*           (no counterpart in the reference: HOOMD's md.angle conventions, defined here)
  *
  * Conventions (all restated from HOOMD-blue's ForceCompute data model):
  *   - Scalar = double. Scalar4 arrays are 4 consecutive doubles.
@@ -379,6 +380,65 @@ int azp_bond_forces_double_well(const azp_bond_args* args, const azp_dw_params* 
                                 void* stream);
 int azp_bond_forces_quartic(const azp_bond_args* args, const azp_quartic_params* d_params, unsigned int* d_flags,
                             void* stream);
+
+/* ---- angle forces ----
+ * Three-body bending potentials over a per-particle angle table. The reference holds no angle code; the semantics
+ * are HOOMD's documented md.angle.Harmonic and md.angle.CosineSquared conventions, DEFINED HERE.
+ *
+ * An angle has members a, b, c with b the vertex. With dab = r_a - r_b and dcb = r_c - r_b (both minimum image):
+ *   c = dab.dcb / (|dab| |dcb|), clamped to [-1, 1];   s = max(sqrt(1 - c^2), 1e-3)   (the floor is HOOMD's)
+ * An evaluator yields U and g = dU/d(cos theta):
+ *   harmonic         U = 1/2 k (theta - t0)^2, theta = acos(c);   g = -k (theta - t0) / s
+ *   cosine squared   U = 1/2 k (c - cos t0)^2;                    g = k (c - cos t0)
+ * Forces:  F_a = -g (dcb / (|dab||dcb|) - c dab / |dab|^2),  F_c = -g (dab / (|dab||dcb|) - c dcb / |dcb|^2),
+ *          F_b = -F_a - F_c.
+ * Each member gets U / 3 and, when compute_virial is set, the virial 1/3 (dab (x) F_a + dcb (x) F_c), stored in the
+ * six rows xx, xy, xz, yy, yz, zz with the sign of the bond kernel. Coincident members (|dab| or |dcb| equal to 0)
+ * are undefined. No atomics: one lane per particle sums its entries in table order, so two calls give the same bits.
+ * A particle without angles gets exact zeros. */
+
+/* One entry of the per-particle angle table (16 bytes, read as one load). */
+typedef struct azp_angle_entry
+    {
+    uint32_t idx[2]; /* indices of the two other members, in angle order (a, b, c without this particle) */
+    uint32_t type;   /* angle type                                                                       */
+    uint32_t pos;    /* this particle's position in the angle: 0 = a, 1 = b (vertex), 2 = c              */
+    } azp_angle_entry;
+
+typedef struct azp_angle_harmonic_params { double k, t0; } azp_angle_harmonic_params;
+/* cos t0 is folded on the host */
+typedef struct azp_angle_cossq_params { double k, cos_t0; } azp_angle_cossq_params;
+
+/* Table entry s of particle i is d_gpu_anglelist[s * pitch + i], s < d_gpu_n_angles[i]; only rows [0, N) have
+ * entries, their partners are rows of [0, n_max). */
+typedef struct azp_angle_args
+    {
+    double* d_force;         /* N x 4, overwritten */
+    double* d_virial;        /* 6 x virial_pitch, written when compute_virial is set */
+    uint64_t virial_pitch;
+    uint32_t N;
+    uint32_t n_max;
+    const double* d_pos;     /* n_max x 4 */
+    azp_box box;
+    const azp_angle_entry* d_gpu_anglelist;
+    const uint32_t* d_gpu_n_angles;
+    uint64_t pitch;
+    uint32_t n_angle_types;
+    uint32_t compute_virial;
+    uint32_t block_size;     /* 0: 256; otherwise a multiple of 64, at most 256 */
+    uint32_t _pad;
+    } azp_angle_args;
+
+void azp_angle_harmonic_params_make(double k, double t0, azp_angle_harmonic_params* out);
+void azp_angle_harmonic_params_unpack(const azp_angle_harmonic_params* p, double* k, double* t0);
+void azp_angle_cossq_params_make(double k, double t0, azp_angle_cossq_params* out);
+/* t0 comes back as acos(cos t0): equal to what was given to rounding, not to the bit */
+void azp_angle_cossq_params_unpack(const azp_angle_cossq_params* p, double* k, double* t0);
+/* No flag word: neither evaluator can reject its parameters. NULL args: AZP_ERROR_INVALID_ARGUMENT; N == 0: success,
+ * nothing launched; a missing array, pitch < N, n_angle_types == 0, a block size that is no multiple of 64 or above
+ * 256: AZP_ERROR_INVALID_ARGUMENT; parameters beyond 64 KiB of LDS: AZP_ERROR_TOO_MANY_TYPES. */
+int azp_angle_forces_harmonic(const azp_angle_args* args, const azp_angle_harmonic_params* d_params, void* stream);
+int azp_angle_forces_cosine_squared(const azp_angle_args* args, const azp_angle_cossq_params* d_params, void* stream);
 
 /* ---- neighbor-list build (the step before the path) ----
  * Cell list -> full Verlet list in the layout the force kernels consume.
