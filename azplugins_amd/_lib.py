@@ -119,6 +119,33 @@ class AngleArgs(C.Structure):
     ]
 
 
+class DihedralEntry(C.Structure):
+    _fields_ = [("idx", C.c_uint32 * 3), ("type_pos", C.c_uint32)]
+
+
+class DihedralPeriodicParams(C.Structure):
+    _fields_ = [("k", C.c_double), ("cos_phi0", C.c_double), ("sin_phi0", C.c_double), ("d", C.c_int32), ("n", C.c_uint32)]
+
+
+class DihedralArgs(C.Structure):
+    _fields_ = [
+        ("d_force", C.c_void_p),
+        ("d_virial", C.c_void_p),
+        ("virial_pitch", C.c_uint64),
+        ("N", C.c_uint32),
+        ("n_max", C.c_uint32),
+        ("d_pos", C.c_void_p),
+        ("box", Box),
+        ("d_gpu_dihedrallist", C.c_void_p),
+        ("d_gpu_n_dihedrals", C.c_void_p),
+        ("pitch", C.c_uint64),
+        ("n_dihedral_types", C.c_uint32),
+        ("compute_virial", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 class BarrierArgs(C.Structure):
     _fields_ = [
         ("d_force", C.c_void_p),
@@ -443,6 +470,12 @@ SYMBOLS = {
     "azp_angle_cossq_params_unpack": (None, [_VP] + [_PD] * 2),
     "azp_angle_forces_harmonic": (C.c_int, [C.POINTER(AngleArgs), _VP, _VP]),
     "azp_angle_forces_cosine_squared": (C.c_int, [C.POINTER(AngleArgs), _VP, _VP]),
+    "azp_dihedral_periodic_params_make": (None, [_D, C.c_int, C.c_uint, _D, _VP]),
+    "azp_dihedral_periodic_params_unpack": (None, [_VP, _PD, _PI, C.POINTER(C.c_uint), _PD]),
+    "azp_dihedral_opls_params_make": (None, [_D] * 4 + [_VP]),
+    "azp_dihedral_opls_params_unpack": (None, [_VP] + [_PD] * 4),
+    "azp_dihedral_forces_periodic": (C.c_int, [C.POINTER(DihedralArgs), _VP, _VP]),
+    "azp_dihedral_forces_opls": (C.c_int, [C.POINTER(DihedralArgs), _VP, _VP]),
     "azp_nlist_cell_assign": (C.c_int, [C.POINTER(NlistArgs), _VP]),
     "azp_nlist_cell_bounds": (C.c_int, [C.POINTER(NlistArgs), _VP]),
     "azp_nlist_bin": (C.c_int, [C.POINTER(NlistArgs), _VP, _VP, _VP]),

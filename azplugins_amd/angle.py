@@ -15,7 +15,7 @@ An angle has members ``a, b, c`` with ``b`` the vertex (``Snapshot.angles.group`
 Every member gets a third of ``U`` and, with ``compute_virial``, a third of ``dab (x) F_a + dcb (x) F_c``. Coincident
 members (``|dab|`` or ``|dcb|`` equal to 0) are undefined. Angles add no neighbor-list exclusions.
 
-Out of scope: dihedrals and impropers, tabulated angles, 1-3 exclusions, an ``_azplugins`` class."""
+Out of scope: impropers, tabulated angles, 1-3 exclusions, an ``_azplugins`` class."""
 
 import ctypes as C
 import math

@@ -128,6 +128,37 @@ void azp_angle_cossq_params_unpack(const azp_angle_cossq_params* p, double* k, d
     *t0 = std::acos(p->cos_t0);
     }
 
+// ---- dihedral potentials (include/azp.h, "dihedral forces"): periodic folds cos phi0 and sin phi0, OPLS keeps k1..k4 ----
+void azp_dihedral_periodic_params_make(double k, int d, unsigned int n, double phi0, azp_dihedral_periodic_params* out)
+    {
+    out->k = k;
+    out->cos_phi0 = std::cos(phi0);
+    out->sin_phi0 = std::sin(phi0);
+    out->d = d;
+    out->n = n;
+    }
+void azp_dihedral_periodic_params_unpack(const azp_dihedral_periodic_params* p, double* k, int* d, unsigned int* n, double* phi0)
+    {
+    *k = p->k;
+    *d = p->d;
+    *n = p->n;
+    *phi0 = std::atan2(p->sin_phi0, p->cos_phi0);
+    }
+void azp_dihedral_opls_params_make(double k1, double k2, double k3, double k4, azp_dihedral_opls_params* out)
+    {
+    out->k1 = k1;
+    out->k2 = k2;
+    out->k3 = k3;
+    out->k4 = k4;
+    }
+void azp_dihedral_opls_params_unpack(const azp_dihedral_opls_params* p, double* k1, double* k2, double* k3, double* k4)
+    {
+    *k1 = p->k1;
+    *k2 = p->k2;
+    *k3 = p->k3;
+    *k4 = p->k4;
+    }
+
 // ---- wall potentials: one type's dict folded into its parameter row (include/azp.h, "wall potentials") ----
 // V and F = -dV/dr in plain IEEE double, in the order written: tests/wall_ref.py restates the two folds and agrees
 // to a few ulp. src/WallEvaluatorLJ93.h:34-48 gives V and F / r for LJ93, src/WallEvaluatorColloid.h:36-41 for the

@@ -1,0 +1,240 @@
+// dihedral_forces.hip -- four-body torsion forces over a per-particle dihedral table. The reference holds no dihedral
+// code: the semantics (HOOMD's md.dihedral.Periodic and md.dihedral.OPLS class names and parameter keys, the IUPAC
+// angle) are defined in include/azp.h ("dihedral forces") and DESIGN 4.17.
+//
+// One lane per particle, no atomics: the lane walks its table entries in order and keeps, of each dihedral, the force
+// on its own position, a quarter of the energy and a quarter of the virial. The four lanes of one dihedral evaluate
+// the same expression on the same operands, so two calls give the same bits whatever the block size. Table columns
+// are particle-major (entry s of particle i at s * pitch + i): every table read is one coalesced 16-byte load; the
+// three partner positions are the only gathers. Per-dihedral-type parameters are staged in LDS.
+//
+// cos phi and sin phi come straight from the geometry (no atan2, no sincos): with n1 = b1 x b2, n2 = b2 x b3 and
+// q = 1 / (|n1||n2|), cos phi = (n1 . n2) q and sin phi = |b2| (b1 . n2) q. The multiples of phi follow from the
+// angle-addition recurrence, cos phi0 and sin phi0 are folded on the host.
+#include "azp_device.hpp"
+#include "pair_kernel_host.hpp"
+
+#ifndef AZP_DIHEDRAL_BATCH
+#define AZP_DIHEDRAL_BATCH 3
+#endif
+
+namespace azp
+{
+// U and dU = dU/dphi from c = cos phi and s = sin phi
+struct EvalDihedralPeriodic
+    {
+    typedef azp_dihedral_periodic_params Params;
+    static __device__ __forceinline__ void eval(const Params& p, double c, double s, double& U, double& dU)
+        {
+        // (cos m phi, sin m phi) for m = 1 .. n by angle addition; n is a small per-type integer
+        double cm = c, sm = s;
+        for (uint32_t m = 1; m < p.n; ++m)
+            {
+            const double cn = cm * c - sm * s;
+            sm = sm * c + cm * s;
+            cm = cn;
+            }
+        const double hkd = 0.5 * p.k * (double)p.d;
+        U = hkd * (cm * p.cos_phi0 + sm * p.sin_phi0) + 0.5 * p.k;   // 1/2 k (1 + d cos(n phi - phi0))
+        dU = -hkd * (double)p.n * (sm * p.cos_phi0 - cm * p.sin_phi0); // -1/2 k d n sin(n phi - phi0)
+        }
+    };
+
+struct EvalDihedralOPLS
+    {
+    typedef azp_dihedral_opls_params Params;
+    static __device__ __forceinline__ void eval(const Params& p, double c, double s, double& U, double& dU)
+        {
+        const double c2 = c * c - s * s, s2 = 2.0 * s * c;
+        const double c3 = c2 * c - s2 * s, s3 = s2 * c + c2 * s;
+        const double c4 = c2 * c2 - s2 * s2, s4 = 2.0 * s2 * c2;
+        U = 0.5 * (p.k1 * (1.0 + c) + p.k2 * (1.0 - c2) + p.k3 * (1.0 + c3) + p.k4 * (1.0 - c4));
+        dU = 0.5 * (-p.k1 * s + 2.0 * p.k2 * s2 - 3.0 * p.k3 * s3 + 4.0 * p.k4 * s4);
+        }
+    };
+
+struct DihedralKArgs
+    {
+    double* force;
+    double* virial;
+    uint64_t virial_pitch;
+    const double* pos;
+    const azp_dihedral_entry* dihedrallist;
+    const uint32_t* n_dihedrals;
+    uint64_t pitch;
+    BoxDev box;
+    uint32_t N;
+    uint32_t n_dihedral_types;
+    uint32_t compute_virial;
+    uint32_t _pad;
+    };
+
+__device__ __forceinline__ azp_dihedral_entry load_dihedral_entry(const azp_dihedral_entry* table, uint64_t at)
+    {
+    const uint4 w = reinterpret_cast<const uint4*>(table)[at];
+    azp_dihedral_entry e;
+    e.idx[0] = w.x; e.idx[1] = w.y; e.idx[2] = w.z; e.type_pos = w.w;
+    return e;
+    }
+
+// component-wise select (a ?: on the structs makes the compiler pick between addresses and park the batch in scratch)
+__device__ __forceinline__ double3 dihedral_select3(bool take_first, const double3& x, const double3& y)
+    {
+    return make_double3(take_first ? x.x : y.x, take_first ? x.y : y.y, take_first ? x.z : y.z);
+    }
+
+template<class E>
+__global__ void __launch_bounds__(256) dihedral_forces_kernel(const DihedralKArgs a, const typename E::Params* __restrict__ params)
+    {
+    typedef typename E::Params Params;
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    Params* s_params = reinterpret_cast<Params*>(s_raw);
+    for (uint32_t t = threadIdx.x; t < a.n_dihedral_types; t += blockDim.x)
+        s_params[t] = params[t];
+    __syncthreads();
+
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= a.N)
+        return;
+    const uint32_t nd = a.n_dihedrals[idx];
+    const double3 p = load_scalar3_of4(a.pos, idx);
+    double fx = 0.0, fy = 0.0, fz = 0.0, pe = 0.0;
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    auto one_dihedral = [&](const azp_dihedral_entry& ent, const double3& q0, const double3& q1, const double3& q2)
+        {
+        // members in dihedral order: this lane's own position goes into slot m, the partners fill the rest
+        const uint32_t m = ent.type_pos >> 30;
+        const double3 ra = dihedral_select3(m == 0, p, q0);
+        const double3 rb = dihedral_select3(m == 0, q0, dihedral_select3(m == 1, p, q1));
+        const double3 rc = dihedral_select3(m <= 1, q1, dihedral_select3(m == 2, p, q2));
+        const double3 rd = dihedral_select3(m == 3, p, q2);
+        double b1x = rb.x - ra.x, b1y = rb.y - ra.y, b1z = rb.z - ra.z;
+        double b2x = rc.x - rb.x, b2y = rc.y - rb.y, b2z = rc.z - rb.z;
+        double b3x = rd.x - rc.x, b3y = rd.y - rc.y, b3z = rd.z - rc.z;
+        min_image(a.box, b1x, b1y, b1z);
+        min_image(a.box, b2x, b2y, b2z);
+        min_image(a.box, b3x, b3y, b3z);
+        const double n1x = b1y * b2z - b1z * b2y, n1y = b1z * b2x - b1x * b2z, n1z = b1x * b2y - b1y * b2x;
+        const double n2x = b2y * b3z - b2z * b3y, n2y = b2z * b3x - b2x * b3z, n2z = b2x * b3y - b2y * b3x;
+        const double n1sq = n1x * n1x + n1y * n1y + n1z * n1z;
+        const double n2sq = n2x * n2x + n2y * n2y + n2z * n2z;
+        const double b2sq = b2x * b2x + b2y * b2y + b2z * b2z;
+        const double b2len = fast_sqrt(b2sq);
+        const double q = fast_rsqrt(n1sq * n2sq); // 1 / (|n1| |n2|)
+        const double c = (n1x * n2x + n1y * n2y + n1z * n2z) * q;
+        const double s = b2len * (b1x * n2x + b1y * n2y + b1z * n2z) * q;
+        double U, dU;
+        E::eval(s_params[ent.type_pos & 0x3fffffffu], c, s, U, dU);
+        // F_m = -dU g_m (Blondel-Karplus): g_a = -|b2| / |n1|^2 n1, g_d = |b2| / |n2|^2 n2,
+        // g_b = -(1 + s12) g_a + s32 g_d, g_c = -(1 + s32) g_d + s12 g_a
+        const double wa = dU * b2len * fast_rcp(n1sq);  // F_a = wa n1
+        const double wd = -dU * b2len * fast_rcp(n2sq); // F_d = wd n2
+        const double ib2 = fast_rcp(b2sq);
+        const double s12 = (b1x * b2x + b1y * b2y + b1z * b2z) * ib2;
+        const double s32 = (b3x * b2x + b3y * b2y + b3z * b2z) * ib2;
+        const double fax = wa * n1x, fay = wa * n1y, faz = wa * n1z;
+        const double fdx = wd * n2x, fdy = wd * n2y, fdz = wd * n2z;
+        const double fcx = s12 * fax - (1.0 + s32) * fdx, fcy = s12 * fay - (1.0 + s32) * fdy, fcz = s12 * faz - (1.0 + s32) * fdz;
+        const double fbx = s32 * fdx - (1.0 + s12) * fax, fby = s32 * fdy - (1.0 + s12) * fay, fbz = s32 * fdz - (1.0 + s12) * faz;
+        fx += m == 0 ? fax : (m == 1 ? fbx : (m == 2 ? fcx : fdx));
+        fy += m == 0 ? fay : (m == 1 ? fby : (m == 2 ? fcy : fdy));
+        fz += m == 0 ? faz : (m == 1 ? fbz : (m == 2 ? fcz : fdz));
+        pe += 0.25 * U;
+        if (a.compute_virial)
+            {
+            // separations from b: a at -b1, c at b2, d at b2 + b3 (composed, not re-imaged)
+            const double dx = b2x + b3x, dy = b2y + b3y, dz = b2z + b3z;
+            v[0] += 0.25 * (b2x * fcx + dx * fdx - b1x * fax); v[1] += 0.25 * (b2x * fcy + dx * fdy - b1x * fay);
+            v[2] += 0.25 * (b2x * fcz + dx * fdz - b1x * faz); v[3] += 0.25 * (b2y * fcy + dy * fdy - b1y * fay);
+            v[4] += 0.25 * (b2y * fcz + dy * fdz - b1y * faz); v[5] += 0.25 * (b2z * fcz + dz * fdz - b1z * faz);
+            }
+        };
+    // As the angle and bond kernels: the first BATCH table columns of every lane are loaded together, then their
+    // 3 * BATCH partner positions together -- two dependent round trips for the batch instead of two per dihedral.
+    // BATCH = 3 is the largest that keeps 4 waves per SIMD (124 VGPRs; 143 and 3 waves at 4). An interior bead of a
+    // linear chain has 4 entries and takes one turn of the tail loop; measured on C3, that still beats BATCH = 4 with
+    // its lost wave.
+    constexpr uint32_t BATCH = AZP_DIHEDRAL_BATCH;
+    azp_dihedral_entry ent[BATCH];
+#pragma unroll
+    for (uint32_t b = 0; b < BATCH; ++b)
+        {
+        ent[b].idx[0] = idx; ent[b].idx[1] = idx; ent[b].idx[2] = idx; ent[b].type_pos = 0;
+        if (b < nd)
+            ent[b] = load_dihedral_entry(a.dihedrallist, (uint64_t)b * a.pitch + idx);
+        }
+    double3 q0[BATCH], q1[BATCH], q2[BATCH];
+#pragma unroll
+    for (uint32_t b = 0; b < BATCH; ++b)
+        {
+        q0[b] = load_scalar3_of4(a.pos, ent[b].idx[0]); // unused slots re-read the lane's own (cached) row
+        q1[b] = load_scalar3_of4(a.pos, ent[b].idx[1]);
+        q2[b] = load_scalar3_of4(a.pos, ent[b].idx[2]);
+        }
+#pragma unroll
+    for (uint32_t b = 0; b < BATCH; ++b)
+        if (b < nd)
+            one_dihedral(ent[b], q0[b], q1[b], q2[b]);
+    for (uint32_t b = BATCH; b < nd; ++b)
+        {
+        const azp_dihedral_entry e = load_dihedral_entry(a.dihedrallist, (uint64_t)b * a.pitch + idx);
+        one_dihedral(e, load_scalar3_of4(a.pos, e.idx[0]), load_scalar3_of4(a.pos, e.idx[1]), load_scalar3_of4(a.pos, e.idx[2]));
+        }
+    store_scalar4(a.force, idx, fx, fy, fz, pe);
+    if (a.compute_virial)
+        {
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+            a.virial[(uint64_t)c * a.virial_pitch + idx] = v[c];
+        }
+    }
+
+template<class E>
+static int launch_dihedral(const azp_dihedral_args* args, const typename E::Params* d_params, void* stream)
+    {
+    if (!args)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->N == 0)
+        return AZP_SUCCESS;
+    if (!d_params || !args->d_force || !args->d_pos || !args->d_gpu_dihedrallist || !args->d_gpu_n_dihedrals
+        || args->pitch < args->N || args->n_dihedral_types == 0)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->compute_virial && (!args->d_virial || args->virial_pitch < args->N))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    const uint32_t bs = args->block_size ? args->block_size : 256u;
+    if (bs != 64 && bs != 128 && bs != 256)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    const size_t lds = sizeof(typename E::Params) * (size_t)args->n_dihedral_types;
+    if (lds > 64 * 1024)
+        return AZP_ERROR_TOO_MANY_TYPES;
+    DihedralKArgs k;
+    k.force = args->d_force;
+    k.virial = args->d_virial;
+    k.virial_pitch = args->virial_pitch;
+    k.pos = args->d_pos;
+    k.dihedrallist = args->d_gpu_dihedrallist;
+    k.n_dihedrals = args->d_gpu_n_dihedrals;
+    k.pitch = args->pitch;
+    k.box = make_box_dev(args->box);
+    k.N = args->N;
+    k.n_dihedral_types = args->n_dihedral_types;
+    k.compute_virial = args->compute_virial;
+    k._pad = 0;
+    const uint32_t grid = (args->N + bs - 1) / bs;
+    LaunchInfo& li = last_launch();
+    li.block_size = bs; li.tpp = 1; li.grid = grid; li.lds_bytes = (uint32_t)lds;
+    hipLaunchKernelGGL(dihedral_forces_kernel<E>, dim3(grid), dim3(bs), lds, static_cast<hipStream_t>(stream), k, d_params);
+    return (int)hipGetLastError();
+    }
+} // namespace azp
+
+extern "C" int azp_dihedral_forces_periodic(const azp_dihedral_args* args, const azp_dihedral_periodic_params* d_params,
+                                            void* stream)
+    {
+    return azp::launch_dihedral<azp::EvalDihedralPeriodic>(args, d_params, stream);
+    }
+
+extern "C" int azp_dihedral_forces_opls(const azp_dihedral_args* args, const azp_dihedral_opls_params* d_params, void* stream)
+    {
+    return azp::launch_dihedral<azp::EvalDihedralOPLS>(args, d_params, stream);
+    }

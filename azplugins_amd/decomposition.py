@@ -261,8 +261,9 @@ class HaloExchange:
 def _snapshot_topology(snap):
     """The bonded topology of a snapshot by particle TAG: ``bond_tags`` / ``bond_typeid`` / ``bond_types`` and, when the
     snapshot has angles, ``angle_tags`` / ``angle_typeid`` / ``angle_types`` (absent without angles; a snapshot with
-    angles but no bonds carries an empty bond list). None when there are neither bonds nor angles."""
-    if not (snap.bonds.N or snap.angles.N):
+    angles but no bonds carries an empty bond list), and ``dihedral_tags`` / ``dihedral_typeid`` / ``dihedral_types`` in
+    the same way, only when it has dihedrals. None when there are neither bonds nor angles nor dihedrals."""
+    if not (snap.bonds.N or snap.angles.N or snap.dihedrals.N):
         return None
     tag = snap.particles.tag.astype(np.int64)
     topo = dict(bond_tags=tag[snap.bonds.group.astype(np.int64)].reshape(-1, 2), bond_typeid=snap.bonds.typeid.copy(),
@@ -270,6 +271,9 @@ def _snapshot_topology(snap):
     if snap.angles.N:
         topo.update(angle_tags=tag[snap.angles.group.astype(np.int64)].reshape(-1, 3), angle_typeid=snap.angles.typeid.copy(),
                     angle_types=tuple(snap.angles.types))
+    if snap.dihedrals.N:
+        topo.update(dihedral_tags=tag[snap.dihedrals.group.astype(np.int64)].reshape(-1, 4), dihedral_typeid=snap.dihedrals.typeid.copy(),
+                    dihedral_types=tuple(snap.dihedrals.types))
     return topo
 
 
@@ -316,14 +320,21 @@ def rank_simulation(cfg, decomp, rank, device, seed=1):
             topology = dict(bond_tags=np.zeros((0, 2), dtype=np.int64), bond_typeid=np.zeros(0, dtype=np.uint32), bond_types=())
         topology.update(angle_tags=gtag[g], angle_typeid=cfg.get("angle_typeid", np.zeros(g.shape[0], dtype=np.uint32)),
                         angle_types=cfg.get("angle_types", ("A-A-A",)))
+    if cfg.get("dihedrals") is not None and len(cfg["dihedrals"]):
+        gtag = np.asarray(cfg["tag"], dtype=np.int64) if "tag" in cfg else np.arange(xyz.shape[0], dtype=np.int64)
+        g = np.asarray(cfg["dihedrals"], dtype=np.int64).reshape(-1, 4)
+        if topology is None:
+            topology = dict(bond_tags=np.zeros((0, 2), dtype=np.int64), bond_typeid=np.zeros(0, dtype=np.uint32), bond_types=())
+        topology.update(dihedral_tags=gtag[g], dihedral_typeid=cfg.get("dihedral_typeid", np.zeros(g.shape[0], dtype=np.uint32)),
+                        dihedral_types=cfg.get("dihedral_types", ("A-A-A-A",)))
     return rank_simulation_from_snapshot(snap, xyz.shape[0], decomp, rank, device, seed=seed, topology=topology)
 
 
 def rank_simulation_from_snapshot(snap, n_global, decomp, rank, device, seed=1, topology=None):
     """Simulation of one rank from the snapshot of ITS particles (``distribute_snapshot`` hands every rank its share of
     a snapshot that only the root holds): DeviceDomain with ghosts selected, State pointed at the domain's arrays,
-    bonds and angles (``topology``: the global bond and angle lists by tag, ``distribute_snapshot``'s third result)
-    localized."""
+    bonds, angles and dihedrals (``topology``: the global bond, angle and dihedral lists by tag, ``distribute_snapshot``'s
+    third result) localized."""
     from .domain import DeviceDomain
     from .simulation import Simulation
 
@@ -334,7 +345,8 @@ def rank_simulation_from_snapshot(snap, n_global, decomp, rank, device, seed=1, 
     dom.rebuild()
     has_bonds = topology is not None and len(topology["bond_tags"]) > 0
     has_angles = topology is not None and len(topology.get("angle_tags", ())) > 0
-    if has_bonds or has_angles:
+    has_dihedrals = topology is not None and len(topology.get("dihedral_tags", ())) > 0
+    if has_bonds or has_angles or has_dihedrals:
         st.N, st.n_ghost = dom.N_local, dom.n_ghost
         for n in dom.names:
             setattr(st, n, dom.arrays[n])
@@ -342,6 +354,9 @@ def rank_simulation_from_snapshot(snap, n_global, decomp, rank, device, seed=1, 
         st.set_global_bonds(np.asarray(topology["bond_tags"], dtype=np.int64), topology["bond_typeid"], topology["bond_types"])
     if has_angles:
         st.set_global_angles(np.asarray(topology["angle_tags"], dtype=np.int64), topology["angle_typeid"], topology["angle_types"])
+    if has_dihedrals:
+        st.set_global_dihedrals(np.asarray(topology["dihedral_tags"], dtype=np.int64), topology["dihedral_typeid"],
+                                topology["dihedral_types"])
     sim.attach_domain(dom)
     return sim, dom
 
@@ -353,11 +368,11 @@ _WIRE = (("position", 3), ("typeid", 1), ("orientation", 4), ("velocity", 3), ("
 
 def distribute_snapshot(snap, decomp, root=0, device=None, group=None):
     """HOOMD's ``create_state_from_snapshot`` under MPI: only ``root`` holds the snapshot (the others pass ``None``),
-    every rank gets the particles its sub-box owns. Collective: the small things (box, type names, the bond and angle
-    topology by tag, the per-rank counts) are broadcast, the particle rows travel in ONE ``all_to_all_single`` in which only the root
+    every rank gets the particles its sub-box owns. Collective: the small things (box, type names, the bond, angle and
+    dihedral topology by tag, the per-rank counts) are broadcast, the particle rows travel in ONE ``all_to_all_single`` in which only the root
     sends (RCCL; gloo on CPU tensors in the tests). Returns ``(local_snapshot, n_global, topology)`` for
-    ``rank_simulation_from_snapshot``; ``topology`` is None without bonds and angles, and holds the ``angle_*`` keys only when there
-    are angles."""
+    ``rank_simulation_from_snapshot``; ``topology`` is None without bonds, angles and dihedrals, and holds the ``angle_*`` keys only
+    when there are angles and the ``dihedral_*`` keys only when there are dihedrals."""
     import torch
     import torch.distributed as dist
 

@@ -361,5 +361,7 @@ class DeviceDomain:
             state.relocalize_bonds()  # bond table and exclusions by local index: every index changed
         if getattr(state, "angle_tags", None) is not None:
             state.relocalize_angles()
+        if getattr(state, "dihedral_tags", None) is not None:
+            state.relocalize_dihedrals()
         state.position_generation += 1
         state.order_generation += 1  # every index changed: the list must be rebuilt

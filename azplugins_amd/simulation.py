@@ -213,6 +213,9 @@ class Simulation:
         if self.state.n_angles and self.state.angle_tags is None:
             raise _lib.AzpError("attach_domain: a system with angles needs its topology by tag (State.set_global_angles) -- "
                                 "the index-based angle table of a single-domain state does not survive a migration")
+        if self.state.n_dihedrals and self.state.dihedral_tags is None:
+            raise _lib.AzpError("attach_domain: a system with dihedrals needs its topology by tag (State.set_global_dihedrals) -- "
+                                "the index-based dihedral table of a single-domain state does not survive a migration")
         # every per-particle array that the integrator or a force touches must migrate with the particles
         # (an array left behind keeps its old size and order while N changes under it)
         need = ["pos", "vel", "tag", "image"]

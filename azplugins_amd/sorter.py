@@ -2,7 +2,7 @@
 ``hoomd.update.ParticleSorter``. Reorders the local particles along a Hilbert
 curve through small cells so that any 256 consecutive particles form a compact tile -- the order the
 tile plan (``pair_plan.hpp``) and the neighbor-list build rely on. Tags, images,
-velocities, orientations (and Langevin accelerations) travel with the particles; bonds and angles are re-indexed.
+velocities, orientations (and Langevin accelerations) travel with the particles; bonds, angles and dihedrals are re-indexed.
 
 Keys and the permutation are computed with torch ops on the device (this runs
 every few hundred steps, not on the per-step path)."""
@@ -65,7 +65,7 @@ class ParticleSorter:
         for name in names:
             a = getattr(st, name)
             a[:N] = a[:N].index_select(0, order)
-        if st.n_bonds or st.n_angles:
+        if st.n_bonds or st.n_angles or st.n_dihedrals:
             inv = torch.empty(N, dtype=torch.int64, device=st.device)
             inv[order] = torch.arange(N, dtype=torch.int64, device=st.device)
         if st.n_bonds:
@@ -75,6 +75,9 @@ class ParticleSorter:
         if st.n_angles:
             st.set_angle_group_device(inv[st.angle_group_device()])
             st._angle_table = None
+        if st.n_dihedrals:
+            st.set_dihedral_group_device(inv[st.dihedral_group_device()])
+            st._dihedral_table = None
         st.position_generation += 1
         st.order_generation += 1
         self.num_sorts += 1

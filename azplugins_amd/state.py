@@ -121,6 +121,24 @@ class _Angles:
         self.typeid = np.zeros(self._N, dtype=np.uint32)
 
 
+class _Dihedrals:
+    def __init__(self):
+        self._N = 0
+        self.types = []
+        self.group = np.zeros((0, 4), dtype=np.uint32)
+        self.typeid = np.zeros(0, dtype=np.uint32)
+
+    @property
+    def N(self):
+        return self._N
+
+    @N.setter
+    def N(self, n):
+        self._N = int(n)
+        self.group = np.zeros((self._N, 4), dtype=np.uint32)
+        self.typeid = np.zeros(self._N, dtype=np.uint32)
+
+
 class _Configuration:
     def __init__(self):
         self.box = Box(1.0)
@@ -131,18 +149,19 @@ class Snapshot:
     """Host-side system description with ``hoomd.Snapshot``'s attribute names
     (``particles.N/position/typeid/types/orientation/velocity/mass``,
     ``bonds.N/group/typeid/types``, ``angles.N/group/typeid/types`` with members ``a, b, c`` and ``b`` the vertex,
-    ``configuration.box``)."""
+    ``dihedrals.N/group/typeid/types`` with members ``a, b, c, d`` along the chain, ``configuration.box``)."""
 
     def __init__(self):
         self.particles = _Particles()
         self.bonds = _Bonds()
         self.angles = _Angles()
+        self.dihedrals = _Dihedrals()
         self.configuration = _Configuration()
 
     @classmethod
     def from_arrays(cls, xyz, box, typeid=None, types=("A",), orientation=None, velocity=None, tag=None, bonds=None,
                     bond_typeid=None, bond_types=("A-A",), moment_inertia=None, angmom=None, angles=None, angle_typeid=None,
-                    angle_types=("A-A-A",)):
+                    angle_types=("A-A-A",), dihedrals=None, dihedral_typeid=None, dihedral_types=("A-A-A-A",)):
         s = cls()
         xyz = np.asarray(xyz, dtype=np.float64)
         s.particles.N = xyz.shape[0]
@@ -175,6 +194,13 @@ class Snapshot:
             s.angles.types = list(angle_types)
             if angle_typeid is not None:
                 s.angles.typeid[:] = angle_typeid
+        if dihedrals is not None:
+            dihedrals = np.asarray(dihedrals, dtype=np.uint32).reshape(-1, 4)
+            s.dihedrals.N = dihedrals.shape[0]
+            s.dihedrals.group[:] = dihedrals
+            s.dihedrals.types = list(dihedral_types)
+            if dihedral_typeid is not None:
+                s.dihedrals.typeid[:] = dihedral_typeid
         return s
 
 
@@ -283,6 +309,59 @@ def build_angle_table(group, typeid, n_local):
     return dict(table=table, n_angles=na.to(torch.int32), pitch=N, width=width)
 
 
+def localize_dihedrals(tag, n_local, dihedral_tags, dihedral_typeid):
+    """``localize_angles`` for dihedrals (quadruples of particle tags in the order a, b, c, d): every dihedral with at
+    least one LOCAL member, as index quadruples over this rank's rows. All four members must be on the rank, as locals
+    or ghosts: the far end of a dihedral is three bonds away from a local end. Returns (dihedral_group uint32 (n, 4),
+    typeid)."""
+    tag = np.asarray(tag, dtype=np.int64)
+    dihedral_tags = np.asarray(dihedral_tags, dtype=np.int64).reshape(-1, 4)
+    n_glob = int(max(dihedral_tags.max() + 1 if dihedral_tags.size else 0, tag.max() + 1 if tag.size else 0))
+    rtag = np.full(n_glob + 1, -1, dtype=np.int64)
+    rtag[tag[::-1]] = np.arange(tag.size - 1, -1, -1)  # (the lowest row wins: local before ghost, as for bonds)
+    idx = rtag[dihedral_tags]
+    mine = np.any((idx >= 0) & (idx < n_local), axis=1)
+    if np.any(mine & np.any(idx < 0, axis=1)):
+        raise _lib.AzpError("a member of a dihedral with a local particle is neither local nor a ghost on this rank: the "
+                            "ghost shell (r_cut + buffer) is narrower than three bond lengths")
+    return idx[mine].astype(np.uint32).reshape(-1, 4), np.asarray(dihedral_typeid, dtype=np.uint32)[mine]
+
+
+def build_dihedral_table(group, typeid, n_local):
+    """The per-particle dihedral table from the dihedral members (``group``: integer tensor (n, 4), ``typeid``: integer
+    tensor (n,), below 2^30; any device, CPU included). Particle-major: entry ``s`` of local particle ``i`` is
+    ``table[s, i]`` = (the three other members in dihedral order, the dihedral type in the low 30 bits with ``i``'s
+    position 0 .. 3 in the dihedral in the top two), 16 bytes, for ``s < n_dihedrals[i]``. Only members with index
+    ``< n_local`` get entries; the entries of one particle are ordered by dihedral index (one stable sort), which fixes
+    the order of the kernel's sums."""
+    import torch
+
+    N = int(n_local)
+    dev = group.device
+    g = group.reshape(-1, 4).to(torch.int64)
+    n = g.shape[0]
+    # one candidate entry per (dihedral, member), dihedral-major
+    member = g.reshape(-1)
+    others = torch.stack([g[:, [1, 2, 3]], g[:, [0, 2, 3]], g[:, [0, 1, 3]], g[:, [0, 1, 2]]], dim=1).reshape(-1, 3)
+    which = torch.arange(4, dtype=torch.int64, device=dev).repeat(n)
+    dtype_ = typeid.to(torch.int64).reshape(-1).repeat_interleave(4)
+    keep = member < N
+    member, others, which, dtype_ = member[keep], others[keep], which[keep], dtype_[keep]
+    nd = torch.bincount(member, minlength=N)[:N] if member.numel() else torch.zeros(N, dtype=torch.int64, device=dev)
+    width = max(int(nd.max().item()) if (N and member.numel()) else 0, 1)
+    table = torch.zeros((width, N, 4), dtype=torch.int32, device=dev)
+    if member.numel():
+        order = torch.sort(member, stable=True).indices
+        m = member[order]
+        start = torch.cumsum(nd, 0) - nd
+        slot = torch.arange(m.numel(), device=dev) - start[m]
+        for k in range(3):
+            table[slot, m, k] = others[order, k].to(torch.int32)
+        word = dtype_[order] | (which[order] << 30)
+        table[slot, m, 3] = torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32)   # (the bits of a uint32)
+    return dict(table=table, n_dihedrals=nd.to(torch.int32), pitch=N, width=width)
+
+
 class State:
     """Device-resident particle data (HOOMD ``ParticleData`` + ``BondData``)."""
 
@@ -333,6 +412,14 @@ class State:
         self._angle_table = None
         self.angle_tags = None
         self.angle_tags_typeid = None
+        # dihedrals: once more (members a, b, c, d; set_global_dihedrals / relocalize_dihedrals)
+        dih = snapshot.dihedrals
+        self.dihedral_types = list(dih.types)
+        self.dihedral_group = np.ascontiguousarray(dih.group, dtype=np.uint32).reshape(-1, 4)
+        self.dihedral_typeid = np.ascontiguousarray(dih.typeid, dtype=np.uint32)
+        self._dihedral_table = None
+        self.dihedral_tags = None
+        self.dihedral_tags_typeid = None
         self.position_generation = 0  # bumped whenever positions change
         self.order_generation = 0     # bumped whenever the particles are re-indexed (sort, migration)
         self.type_generation = 0      # bumped whenever an updater may have changed the types in pos.w
@@ -406,6 +493,37 @@ class State:
         self._angle_group_dev = group.reshape(-1, 3)
         self._angle_group_host = None
 
+    # The dihedral members: a host array (uint32 (n, 4)) and a device tensor (int64 (n, 4)), kept as the bond members are.
+    @property
+    def dihedral_group(self):
+        if self._dihedral_group_host is None:
+            import torch
+
+            self._dihedral_group_host = self._dihedral_group_dev.to(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 4)
+        return self._dihedral_group_host
+
+    @dihedral_group.setter
+    def dihedral_group(self, group):
+        self._dihedral_group_host = np.ascontiguousarray(group, dtype=np.uint32).reshape(-1, 4)
+        self._dihedral_group_dev = None
+
+    @property
+    def n_dihedrals(self):
+        g = self._dihedral_group_host if self._dihedral_group_host is not None else self._dihedral_group_dev
+        return int(g.shape[0])
+
+    def dihedral_group_device(self):
+        """The dihedral members as an int64 (n, 4) tensor on the state's device."""
+        if self._dihedral_group_dev is None:
+            import torch
+
+            self._dihedral_group_dev = torch.from_numpy(self._dihedral_group_host.astype(np.int64)).to(self.device).reshape(-1, 4)
+        return self._dihedral_group_dev
+
+    def set_dihedral_group_device(self, group):
+        self._dihedral_group_dev = group.reshape(-1, 4)
+        self._dihedral_group_host = None
+
     @property
     def typeid_host(self):
         return self.pos[: self.N, 3].cpu().numpy().view(np.int64).astype(np.int64) & 0xFFFFFFFF
@@ -453,6 +571,32 @@ class State:
             self._angle_table = build_angle_table(self.angle_group_device(), at, self.N)
         return self._angle_table
 
+    def set_global_dihedrals(self, dihedral_tags, dihedral_typeid, dihedral_types):
+        """Domain-decomposed runs: the dihedrals of the WHOLE system as quadruples of particle tags, replicated on every
+        rank (as ``set_global_bonds``). ``relocalize_dihedrals`` turns them into this rank's index-based table."""
+        self.dihedral_tags = np.ascontiguousarray(dihedral_tags, dtype=np.int64).reshape(-1, 4)
+        self.dihedral_tags_typeid = np.ascontiguousarray(dihedral_typeid, dtype=np.uint32)
+        self.dihedral_types = list(dihedral_types)
+        self.relocalize_dihedrals()
+
+    def relocalize_dihedrals(self):
+        """(Re)build ``dihedral_group`` -- index quadruples over local + ghost rows -- from the tags now on this rank:
+        every dihedral with at least one LOCAL member, all four members on the rank (the ghost shell is at least three
+        bond lengths wide; ``AzpError`` if a member is missing)."""
+        tag = self.tag[: self.n_max].cpu().numpy().view(np.uint32).astype(np.int64)
+        self.dihedral_group, self.dihedral_typeid = localize_dihedrals(tag, self.N, self.dihedral_tags, self.dihedral_tags_typeid)
+        self._dihedral_table = None
+
+    def dihedral_table(self):
+        """The per-particle dihedral table the dihedral kernel walks (``build_dihedral_table`` on the state's device):
+        ``table`` int32 (width, N, 4), ``n_dihedrals`` int32 (N,), ``pitch`` = N. Rebuilt after a sort or a migration."""
+        import torch
+
+        if self._dihedral_table is None:
+            dt = torch.from_numpy(self.dihedral_typeid.astype(np.int64)).to(self.device)
+            self._dihedral_table = build_dihedral_table(self.dihedral_group_device(), dt, self.N)
+        return self._dihedral_table
+
     def bond_table(self):
         """HOOMD's per-particle GPU bond table (``BondData::getGPUTable``):
         column-major entries (partner index, bond type), the particle's position
@@ -492,7 +636,7 @@ class State:
 
     def exclusion_table(self):
         """Bonded partners as neighbor-list exclusions (HOOMD's default
-        ``exclusions=('bond',)``): (n_excl int32[N], excl int32[width, N]). Bond-only: angles add no exclusions (the
-        1-3 pair of an angle keeps its pair interaction)."""
+        ``exclusions=('bond',)``): (n_excl int32[N], excl int32[width, N]). Bond-only: angles and dihedrals add no exclusions
+        (the 1-3 pair of an angle and the 1-4 pair of a dihedral keep their pair interaction)."""
         t = self.bond_table()
         return t["n_bonds"], t["table"][:, :, 0].contiguous(), t["pitch"]

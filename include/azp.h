@@ -16,6 +16,7 @@
  *   azp_bond_forces_*            <- gpu_compute_bond_forces<E, 2>
  *                                   (src/PotentialBondGPUKernel.cu.inc:25-29)
  *   azp_angle_forces_*           (no counterpart in the reference: HOOMD's md.angle conventions, defined here)
+ *   azp_dihedral_forces_*        (no counterpart in the reference: md.dihedral's names, semantics defined here)
  *
  * Conventions (all restated from HOOMD-blue's ForceCompute data model):
  *   - Scalar = double. Scalar4 arrays are 4 consecutive doubles.
@@ -439,6 +440,78 @@ void azp_angle_cossq_params_unpack(const azp_angle_cossq_params* p, double* k, d
  * 256: AZP_ERROR_INVALID_ARGUMENT; parameters beyond 64 KiB of LDS: AZP_ERROR_TOO_MANY_TYPES. */
 int azp_angle_forces_harmonic(const azp_angle_args* args, const azp_angle_harmonic_params* d_params, void* stream);
 int azp_angle_forces_cosine_squared(const azp_angle_args* args, const azp_angle_cossq_params* d_params, void* stream);
+
+/* ---- dihedral forces ----
+ * Four-body torsion potentials over a per-particle dihedral table. The reference holds no dihedral code; the class
+ * names and parameter keys are HOOMD's md.dihedral.Periodic and md.dihedral.OPLS, the semantics are DEFINED HERE
+ * (DESIGN 4.17).
+ *
+ * A dihedral has members a, b, c, d. With b1 = r_b - r_a, b2 = r_c - r_b, b3 = r_d - r_c (each minimum image),
+ * n1 = b1 x b2 and n2 = b2 x b3:
+ *   phi = atan2(|b2| (b1 . n2), n1 . n2) in (-pi, pi]      (IUPAC: cis, a eclipsing d, is 0; trans is pi)
+ * An evaluator yields U and U' = dU/dphi:
+ *   periodic   U = 1/2 k (1 + d cos(n phi - phi0)),  d = +1 or -1, n an integer >= 1
+ *   OPLS       U = 1/2 [k1 (1 + cos phi) + k2 (1 - cos 2 phi) + k3 (1 + cos 3 phi) + k4 (1 - cos 4 phi)]
+ * Forces: F_m = -U' g_m with the gradient of phi (Blondel-Karplus form, no 1 / sin phi: phi = 0 and pi need no floor)
+ *   s = (b1 . b2) / |b2|^2,  t = (b3 . b2) / |b2|^2,
+ *   g_a = -(|b2| / |n1|^2) n1,   g_d = +(|b2| / |n2|^2) n2,
+ *   g_b = -(1 + s) g_a + t g_d,  g_c = -(1 + t) g_d + s g_a.
+ * The kernel takes cos phi = (n1 . n2) / (|n1||n2|) and sin phi = |b2| (b1 . n2) / (|n1||n2|) from the geometry and
+ * the multiples of phi from the angle-addition recurrence; cos phi0 and sin phi0 are folded on the host.
+ * Each member gets U / 4 and, when compute_virial is set, a quarter of
+ *   W = (-b1) (x) F_a + b2 (x) F_c + (b2 + b3) (x) F_d
+ * (the separations from b, composed from the three minimum-image vectors and not re-imaged), stored in the six rows
+ * xx, xy, xz, yy, yz, zz with the sign of the bond kernel; the trace of W is zero. a, b, c or b, c, d collinear
+ * (|n1| or |n2| equal to 0) and coincident members are undefined. No atomics: one lane per particle sums its entries
+ * in table order, so two calls give the same bits. A particle without dihedrals gets exact zeros. */
+
+/* One entry of the per-particle dihedral table (16 bytes, read as one load). */
+typedef struct azp_dihedral_entry
+    {
+    uint32_t idx[3];   /* indices of the three other members, in dihedral order (a, b, c, d without this particle) */
+    uint32_t type_pos; /* dihedral type in the low 30 bits; this particle's position 0 = a .. 3 = d in the top two  */
+    } azp_dihedral_entry;
+
+/* cos phi0 and sin phi0 are folded on the host */
+typedef struct azp_dihedral_periodic_params
+    {
+    double k, cos_phi0, sin_phi0;
+    int32_t d;  /* +1 or -1 */
+    uint32_t n; /* >= 1     */
+    } azp_dihedral_periodic_params;
+typedef struct azp_dihedral_opls_params { double k1, k2, k3, k4; } azp_dihedral_opls_params;
+
+/* Table entry s of particle i is d_gpu_dihedrallist[s * pitch + i], s < d_gpu_n_dihedrals[i]; only rows [0, N) have
+ * entries, their partners are rows of [0, n_max). */
+typedef struct azp_dihedral_args
+    {
+    double* d_force;         /* N x 4, overwritten */
+    double* d_virial;        /* 6 x virial_pitch, written when compute_virial is set */
+    uint64_t virial_pitch;
+    uint32_t N;
+    uint32_t n_max;
+    const double* d_pos;     /* n_max x 4 */
+    azp_box box;
+    const azp_dihedral_entry* d_gpu_dihedrallist;
+    const uint32_t* d_gpu_n_dihedrals;
+    uint64_t pitch;
+    uint32_t n_dihedral_types;
+    uint32_t compute_virial;
+    uint32_t block_size;     /* 0: 256; otherwise 64, 128 or 256 */
+    uint32_t _pad;
+    } azp_dihedral_args;
+
+void azp_dihedral_periodic_params_make(double k, int d, unsigned int n, double phi0, azp_dihedral_periodic_params* out);
+/* k, d and n come back exactly; phi0 as atan2(sin phi0, cos phi0): equal to what was given to rounding (for phi0 in
+ * (-pi, pi]), not to the bit */
+void azp_dihedral_periodic_params_unpack(const azp_dihedral_periodic_params* p, double* k, int* d, unsigned int* n, double* phi0);
+void azp_dihedral_opls_params_make(double k1, double k2, double k3, double k4, azp_dihedral_opls_params* out);
+void azp_dihedral_opls_params_unpack(const azp_dihedral_opls_params* p, double* k1, double* k2, double* k3, double* k4);
+/* No flag word: neither evaluator can reject its parameters. NULL args: AZP_ERROR_INVALID_ARGUMENT; N == 0: success,
+ * nothing launched; a missing array, pitch < N, n_dihedral_types == 0, a block size other than 64, 128 or 256:
+ * AZP_ERROR_INVALID_ARGUMENT; parameters beyond 64 KiB of LDS: AZP_ERROR_TOO_MANY_TYPES. */
+int azp_dihedral_forces_periodic(const azp_dihedral_args* args, const azp_dihedral_periodic_params* d_params, void* stream);
+int azp_dihedral_forces_opls(const azp_dihedral_args* args, const azp_dihedral_opls_params* d_params, void* stream);
 
 /* ---- neighbor-list build (the step before the path) ----
  * Cell list -> full Verlet list in the layout the force kernels consume.
