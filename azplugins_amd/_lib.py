@@ -356,6 +356,33 @@ class FlowMethodArgs(C.Structure):
     ]
 
 
+THERMOSTAT_BERENDSEN, THERMOSTAT_BUSSI, THERMOSTAT_MTTK = 0, 1, 2
+THERMOSTAT_NSTATE = 8
+(THERMOSTAT_ALPHA, THERMOSTAT_K, THERMOSTAT_ENERGY, THERMOSTAT_XI, THERMOSTAT_ETA, THERMOSTAT_ATTEMPTS) = range(6)
+
+
+class ThermostatArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_vel", C.c_void_p),
+        ("d_net_force", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_partials", C.c_void_p),
+        ("d_state", C.c_void_p),
+        ("partials_bytes", C.c_uint64),
+        ("box", Box),
+        ("dt", C.c_double),
+        ("kT", C.c_double),
+        ("tau", C.c_double),
+        ("ndof", C.c_double),
+        ("timestep", C.c_uint64),
+        ("seed", C.c_uint32),
+        ("kind", C.c_uint32),
+        ("N", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 class TypeUpdateArgs(C.Structure):
     _fields_ = [
         ("d_pos", C.c_void_p),
@@ -500,6 +527,11 @@ SYMBOLS = {
     "azp_integrate_langevin_flow_step_two": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
     "azp_integrate_langevin_flow_step_two_one": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
     "azp_integrate_brownian_flow_step": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
+    "azp_thermostat_partials_size": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
+    "azp_thermostat_kinetic": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
+    "azp_thermostat_step_two": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
+    "azp_thermostat_advance": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
+    "azp_thermostat_step_one": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
     "azp_type_update_region": (C.c_int, [C.POINTER(TypeUpdateArgs), _VP]),
     "azp_evaporate_scratch_size": (C.c_uint64, [C.c_uint32]),
     "azp_evaporate": (C.c_int, [C.POINTER(EvaporateArgs), _VP]),

@@ -78,15 +78,38 @@ class Periodic:
 
 class ConstantVolume:
     """NVE integration method (velocity Verlet) on all particles
-    (``hoomd.md.methods.ConstantVolume(filter=hoomd.filter.All())`` without a
-    thermostat, the dummy integrator of the reference's tests,
+    (``hoomd.md.methods.ConstantVolume(filter=hoomd.filter.All())``; without a
+    thermostat it is the dummy integrator of the reference's tests,
     src/pytest/test_pair.py:325-327). Any other filter is rejected: the kernels
-    integrate all N particles."""
+    integrate all N particles.
 
-    def __init__(self, filter=None):
+    ``thermostat``: None (NVE, the fused kernels) or one of ``azplugins_amd.thermostats`` (``Berendsen``, ``Bussi``,
+    ``MTTK``), which rescales the velocities of all particles once per step on the device. A
+    thermostatted method integrates translational degrees of freedom of a single-domain run only; out of scope:
+    rotational degrees of freedom, ``Type`` filters, decomposed runs, Nose-Hoover chains, ``ConstantPressure``."""
+
+    def __init__(self, filter=None, thermostat=None):
         if filter is not None and not isinstance(filter, All):
             raise _lib.AzpError("ConstantVolume: only filter=All() (or None) is supported, got %r" % (filter,))
         self.filter = All() if filter is None else filter
+        self._thermostat = None
+        self.thermostat = thermostat
+
+    @property
+    def thermostat(self):
+        return self._thermostat
+
+    @thermostat.setter
+    def thermostat(self, thermostat):
+        from .thermostats import _Thermostat
+
+        if thermostat is not None and not isinstance(thermostat, _Thermostat):
+            raise _lib.AzpError("ConstantVolume: thermostat must be None or one of azplugins_amd.thermostats, got %r" % (thermostat,))
+        if self._thermostat is not None:
+            self._thermostat._holders.discard(self)
+        if thermostat is not None:
+            thermostat._holders.add(self)
+        self._thermostat = thermostat
 
 
 class Integrator:
@@ -363,6 +386,8 @@ class Simulation:
             return self._run_flow(steps, flow_methods)
         if len(integ.methods) != 1 or not isinstance(integ.methods[0], ConstantVolume):
             raise _lib.AzpError("Integrator.methods must hold exactly one ConstantVolume (all particles); got %r" % (integ.methods,))
+        if integ.methods[0].thermostat is not None:
+            return self._run_thermostatted(steps, integ.methods[0])
         a = _lib.NVEArgs()
         a.box = st.box.to_c()
         a.dt = integ.dt
@@ -450,6 +475,75 @@ class Simulation:
         _lib.check(lib.azp_integrate_nve_step_two(C.byref(a), stream), "azp_integrate_nve_step_two")
         if rot is not None:
             rotational_step(False)
+        self._run_writers(self._writers_due())
+        for f in deferred:
+            f.defer_flag_check = False
+            f.check_flags(wait=True)
+
+    def _check_thermostat(self, integ, method):
+        """What a thermostatted ``ConstantVolume`` cannot do, each refused with its reason."""
+        th = method.thermostat
+        if not isinstance(method.filter, All):
+            raise _lib.AzpError("%s: a thermostat needs filter=All() (it rescales with the kinetic energy of all particles), "
+                                "got %r" % (th._name, method.filter))
+        if integ.integrate_rotational_dof:
+            raise _lib.AzpError("%s: rotational degrees of freedom are not thermostatted (integrate_rotational_dof=True)" % th._name)
+        if self.domain is not None:
+            raise _lib.AzpError("%s does not run decomposed (the kinetic energy would need a collective every step)" % th._name)
+        if self.state.N < 2:
+            raise _lib.AzpError("%s: fewer than 2 particles leave no degree of freedom (Nf = 3 N - 3), N = %d" % (th._name, self.state.N))
+        if th._kind == _lib.THERMOSTAT_BERENDSEN and th.tau < integ.dt:
+            raise _lib.AzpError("%s: tau = %r is below dt = %r (the rescaling factor's radicand can turn negative)"
+                                % (th._name, th.tau, integ.dt))
+        if any(m is not method for m in th._holders):
+            raise _lib.AzpError("%s: one thermostat object is held by two methods (its state belongs to one run)" % th._name)
+
+    def _run_thermostatted(self, steps, method):
+        """``steps`` steps of velocity Verlet with a thermostat. The thermostat needs the kinetic energy of
+        all particles between step two of one step and step one of the next, so the two are not fused here: step two
+        leaves the partial sums of K behind, one wave turns them into the scale factor alpha on the device, and step one
+        reads alpha from there. Nothing is read back."""
+        integ = self.operations.integrator
+        st = self.state
+        th = method.thermostat
+        self._check_thermostat(integ, method)
+        if th._kind == _lib.THERMOSTAT_BUSSI:
+            self._warn_if_seed_unset()
+        a = th._prepare(self)
+        a.box = st.box.to_c()
+        lib = _lib.lib()
+        stream = _lib.raw_stream(st.device)
+
+        def point_at_state():
+            # (the arrays are replaced when the particles are re-sorted)
+            a.d_pos = st.pos.data_ptr()
+            a.d_vel = st.vel.data_ptr()
+            a.d_net_force = st.net_force.data_ptr()
+            a.d_image = st.image.data_ptr()
+            a.N = st.N
+
+        # the velocities may have been changed between runs: K of the first step comes from a pass of its own
+        point_at_state()
+        _lib.check(lib.azp_thermostat_kinetic(C.byref(a), stream), "azp_thermostat_kinetic")
+        deferred = [f for f in integ.forces if hasattr(f, "defer_flag_check")]
+        for f in deferred:
+            f.defer_flag_check = True
+        for k in range(steps):
+            # writers see the full-step velocities v(t) before they are scaled, as HOOMD's do
+            if k:
+                self._run_writers(self._writers_due())
+            self._run_updaters()
+            point_at_state()
+            a.timestep = self.timestep
+            a.kT = th._last_kT = th._kT_at(self.timestep)
+            _lib.check(lib.azp_thermostat_advance(C.byref(a), stream), "azp_thermostat_advance")
+            _lib.check(lib.azp_thermostat_step_one(C.byref(a), stream), "azp_thermostat_step_one")
+            st.position_generation += 1
+            self.timestep += 1
+            self._run_tuners(integ)
+            self._compute_forces()
+            point_at_state()
+            _lib.check(lib.azp_thermostat_step_two(C.byref(a), stream), "azp_thermostat_step_two")
         self._run_writers(self._writers_due())
         for f in deferred:
             f.defer_flag_check = False

@@ -1,0 +1,188 @@
+"""Thermostats of ``ConstantVolume`` under the names and parameter keys of ``hoomd.md.methods.thermostats``:
+``Berendsen(kT, tau)``, ``Bussi(kT, tau=0.0)`` and ``MTTK(kT, tau)``, as in
+``ConstantVolume(filter=All(), thermostat=thermostats.Bussi(kT=1.0, tau=0.5))``. All three rescale the velocities of
+all particles by one factor per step, so the total momentum keeps its direction and a zero momentum stays zero: a
+canonical ensemble without the friction against a fixed frame that ``flow.Langevin`` adds.
+
+HOOMD-blue's source is not available to this project: the scheme is defined in ``include/azp.h`` and ``DESIGN.md``
+4.18 and runs in libazp (``csrc/thermostat.hip``). A thermostat acts once per step, at the start of step t, on the
+full-step velocities v(t): from K = sum 1/2 m |v|^2, Nf = 3 N - 3 and its own state it computes a scale factor alpha
+on the device, and step one does v <- alpha v ahead of the half kick. Nothing is read back inside ``run``.
+
+``kT``: a positive float or a callable of the timestep (evaluated on the host at the step's timestep, as
+``external.HarmonicBarrier.location``). ``energy`` (every thermostat) and ``MTTK.translational_dof`` can be read and
+set between runs; reading synchronises. The state lives in a small device tensor owned by the thermostat and persists
+across ``run`` calls: ``run(10); run(10)`` equals ``run(20)`` bit for bit.
+
+Out of scope: rotational degrees of freedom, ``Type`` filters, decomposed runs, Nose-Hoover chains longer than one,
+``ConstantPressure``, an ``_azplugins`` pybind class."""
+
+import math
+import weakref
+
+from . import _lib
+
+
+class _Thermostat:
+    _name = None
+    _kind = None
+    _tau_may_be_zero = False
+
+    def __init__(self, kT, tau):
+        self.kT = kT
+        self.tau = tau
+        self._holders = weakref.WeakSet()  # the ConstantVolume methods that hold this thermostat
+        self._state = None                 # AZP_THERMOSTAT_NSTATE doubles on the device, made at the first run
+        self._pending = [0.0] * _lib.THERMOSTAT_NSTATE  # what the state starts from (set before the first run)
+        self._partials = None
+        self._ndof = 0.0     # Nf of the last run
+        self._last_kT = 0.0  # kT of the last step run
+
+    @property
+    def kT(self):
+        return self._kT
+
+    @kT.setter
+    def kT(self, kT):
+        if not callable(kT):
+            kT = float(kT)
+            if not (math.isfinite(kT) and kT > 0.0):
+                raise _lib.AzpError("%s: kT must be a positive float or a callable of the timestep, got %r" % (self._name, kT))
+        self._kT = kT
+
+    @property
+    def tau(self):
+        return self._tau
+
+    @tau.setter
+    def tau(self, tau):
+        tau = float(tau)
+        ok = math.isfinite(tau) and (tau >= 0.0 if self._tau_may_be_zero else tau > 0.0)
+        if not ok:
+            raise _lib.AzpError("%s: tau must be %s, got %r" % (self._name, ">= 0" if self._tau_may_be_zero else "> 0", tau))
+        self._tau = tau
+
+    def _kT_at(self, timestep):
+        kT = float(self._kT(timestep)) if callable(self._kT) else self._kT
+        if not (math.isfinite(kT) and kT > 0.0):
+            raise _lib.AzpError("%s: kT must be > 0, got %r at timestep %d" % (self._name, kT, timestep))
+        return kT
+
+    # -- device-resident state -------------------------------------------------
+    def _slot(self, k):
+        """Slot k of the state; reading synchronises."""
+        if self._state is None:
+            return self._pending[k]
+        return float(self._state[k].item())
+
+    def _set_slot(self, k, value):
+        value = float(value)
+        if not math.isfinite(value):
+            raise _lib.AzpError("%s: state values must be finite, got %r" % (self._name, value))
+        if self._state is None:
+            self._pending[k] = value
+        else:
+            self._state[k] = value
+
+    def _prepare(self, sim):
+        """The argument struct of this run; the state tensor and the partials buffer on the state's device."""
+        import ctypes as C
+
+        import torch
+
+        st = sim.state
+        if self._state is None or self._state.device != st.vel.device:
+            start = self._pending if self._state is None else self._state.cpu().tolist()
+            self._state = torch.tensor(start, dtype=torch.float64, device=st.vel.device)
+        need = C.c_uint64(0)
+        _lib.check(_lib.lib().azp_thermostat_partials_size(st.N, C.byref(need)), "azp_thermostat_partials_size")
+        if self._partials is None or self._partials.numel() * 8 < need.value or self._partials.device != st.vel.device:
+            self._partials = torch.zeros(int(need.value) // 8, dtype=torch.float64, device=st.vel.device)
+        a = _lib.ThermostatArgs()
+        a.d_partials = self._partials.data_ptr()
+        a.partials_bytes = self._partials.numel() * 8
+        a.d_state = self._state.data_ptr()
+        a.dt = sim.operations.integrator.dt
+        a.tau = self._tau
+        a.ndof = float(3 * st.N - 3)
+        a.seed = int(sim.seed or 0) & 0xFFFF
+        a.kind = self._kind
+        self._ndof = a.ndof
+        return a
+
+    @property
+    def energy(self):
+        """The energy the thermostat has taken out of the particles: the running sum of K - alpha^2 K, so that
+        K + U + ``energy`` is conserved up to the integrator's error."""
+        return self._slot(_lib.THERMOSTAT_ENERGY)
+
+    @energy.setter
+    def energy(self, value):
+        self._set_slot(_lib.THERMOSTAT_ENERGY, value)
+
+    def __repr__(self):
+        return "%s(kT=%r, tau=%r)" % (type(self).__name__, self._kT, self._tau)
+
+
+class Berendsen(_Thermostat):
+    """Weak coupling: alpha = sqrt(1 + (dt / tau) (Kbar / K - 1)), Kbar = Nf kT / 2. It relaxes K towards Kbar with the
+    time constant ``tau`` but does not sample the canonical ensemble. ``tau`` > 0; ``tau`` < dt is rejected at ``run``
+    (the radicand can turn negative)."""
+
+    _name = "thermostats.Berendsen"
+    _kind = _lib.THERMOSTAT_BERENDSEN
+
+    def __init__(self, kT, tau):
+        super().__init__(kT, tau)
+
+
+class Bussi(_Thermostat):
+    """Stochastic velocity rescaling (Bussi, Donadio, Parrinello 2007): K is moved to K' = (sqrt(c K) + R1 sqrt((1 - c)
+    kT / 2))^2 + (1 - c)(kT / 2) S with c = exp(-dt / tau), R1 standard normal and S chi-square with Nf - 1 degrees of
+    freedom; alpha = sqrt(K' / K). Canonical. ``tau`` >= 0; ``tau`` = 0 (the default) draws K from its canonical
+    distribution every step. The random numbers come from ``sim.seed`` and the timestep."""
+
+    _name = "thermostats.Bussi"
+    _kind = _lib.THERMOSTAT_BUSSI
+    _tau_may_be_zero = True
+
+    def __init__(self, kT, tau=0.0):
+        super().__init__(kT, tau)
+
+
+class MTTK(_Thermostat):
+    """One Nose-Hoover degree of freedom (the equations of Martyna, Tobias, Tuckerman and Klein with a chain of one):
+    xi' = g(K) = (2 K / (Nf kT) - 1) / tau^2, eta' = xi, v' = a - xi v, integrated per step as xi += (dt / 2) g(K),
+    alpha = exp(-xi dt), eta += xi dt, xi += (dt / 2) g(alpha^2 K). Canonical and deterministic. ``tau`` > 0."""
+
+    _name = "thermostats.MTTK"
+    _kind = _lib.THERMOSTAT_MTTK
+
+    def __init__(self, kT, tau):
+        super().__init__(kT, tau)
+
+    @property
+    def translational_dof(self):
+        """(xi, eta): the thermostat's momentum and position."""
+        return self._slot(_lib.THERMOSTAT_XI), self._slot(_lib.THERMOSTAT_ETA)
+
+    @translational_dof.setter
+    def translational_dof(self, value):
+        xi, eta = value
+        self._set_slot(_lib.THERMOSTAT_XI, xi)
+        self._set_slot(_lib.THERMOSTAT_ETA, eta)
+
+    @property
+    def energy(self):
+        """Nf kT (tau^2 xi^2 / 2 + eta), which makes K + U + ``energy`` the conserved quantity of the equations, with
+        Nf and kT of the last step run (0 before the first). It follows from ``translational_dof`` and cannot be set
+        on its own."""
+        xi, eta = self.translational_dof
+        return (self._ndof * self._last_kT) * (0.5 * ((self._tau * self._tau) * (xi * xi)) + eta)
+
+    @energy.setter
+    def energy(self, value):
+        raise _lib.AzpError("thermostats.MTTK: energy = Nf kT (tau^2 xi^2 / 2 + eta) follows from translational_dof; set that")
+
+
+__all__ = ["Berendsen", "Bussi", "MTTK"]

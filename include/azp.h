@@ -784,6 +784,86 @@ int azp_integrate_langevin_flow_step_two(const azp_flow_method_args* args, void*
 int azp_integrate_langevin_flow_step_two_one(const azp_flow_method_args* args, void* stream);
 int azp_integrate_brownian_flow_step(const azp_flow_method_args* args, void* stream);
 
+/* ---- thermostats of the NVE step (azplugins_amd.thermostats: Berendsen, Bussi, MTTK) ----
+ * Names and parameter keys are hoomd.md.methods.thermostats'; HOOMD-blue's source is not available to this project,
+ * so the scheme is DEFINED HERE and pinned by tests/thermostat_ref.py.
+ *
+ * A thermostat acts once per step, at the start of step t, on the full-step velocities v(t): it is a scalar map
+ * (K, state, t) -> alpha; step one then does v <- alpha v, v += a dt/2, x += v dt, wrap. All N particles.
+ *   K    = sum_i 1/2 m_i |v_i|^2, each term 0.5 * (((m vx) vx + (m vy) vy) + (m vz) vz), summed in the reproducible
+ *          order of csrc/azp_reduce.hpp
+ *   Nf   = `ndof` (the driver passes 3 N - 3), Kbar = Nf kT / 2
+ *   Berendsen  alpha = sqrt(1 + (dt / tau) (Kbar / K - 1)); tau >= dt
+ *   Bussi      (Bussi, Donadio, Parrinello 2007) c = exp(-dt / tau), c = 0 for tau = 0; R1 standard normal;
+ *              S = 2 Gamma((Nf - 1) / 2); K' = (sqrt(c K) + R1 sqrt((1 - c) kT / 2))^2 + (1 - c) (kT / 2) S;
+ *              alpha = +sqrt(K' / K)
+ *   MTTK       one Nose-Hoover degree of freedom, g(K) = (2 K / (Nf kT) - 1) / tau^2:
+ *              xi += (dt / 2) g(K); alpha = exp(-xi dt); eta += xi dt; xi += (dt / 2) g(alpha^2 K)
+ *              (the equations xi' = g, eta' = xi, v' = a - xi v)
+ *   K == 0     Berendsen and Bussi: alpha = 1, state unchanged; MTTK integrates xi and eta with K = 0
+ *   energy     Berendsen and Bussi: the running sum of K - alpha^2 K; MTTK: Nf kT (tau^2 xi^2 / 2 + eta). K + U + energy
+ *              is conserved up to the integrator's error
+ * Random stream (Bussi): Philox4x32-10 with the flow methods' key layout and id 204, key {204 << 24 |
+ * (t >> 32 & 0xff) << 16 | seed, t & 0xffffffff}, counter {k, 0, 0, 0} for draw k, u01 = (u64 >> 11) 2^-53 + 2^-54. A
+ * normal is sqrt(-2 ln u_a) cos(2 pi u_b) from two consecutive draws; R1 uses draws 0 and 1. Gamma(a) is Marsaglia and
+ * Tsang's with d = a - 1/3, c = 1 / sqrt(9 d): attempt j takes its normal x from draws 2 + 3 j, 3 + 3 j and its uniform
+ * u from draw 4 + 3 j; with v = (1 + c x)^3 it returns d v when v > 0 and ln u < x^2 / 2 + d - d v + d ln v; after 32
+ * attempts (a guard: the acceptance rate exceeds 0.95 for a >= 1) the value d.
+ *
+ * d_state: AZP_THERMOSTAT_NSTATE doubles on the device, indexed by the AZP_THERMOSTAT_* slots below; it persists
+ * between calls and nothing reads it back. d_partials: azp_thermostat_partials_size(N) bytes.
+ *   azp_thermostat_kinetic    d_partials <- the per-workgroup partials of K of d_vel
+ *   azp_thermostat_step_two   v += (dt / 2) f / m, and d_partials <- the partials of K of the new v, in one pass
+ *   azp_thermostat_advance    folds d_partials (bit for bit the sum reduce_fold gives), computes alpha for the step that
+ *                             starts at `timestep`, updates xi / eta / energy and writes alpha, K and the number of
+ *                             Gamma attempts to d_state. One wave; kT, tau, dt, ndof, seed, timestep by value
+ *   azp_thermostat_step_one   reads alpha from d_state: v = alpha v, v += (dt / 2) f / m, x += dt v, wrap (image counters
+ *                             updated) as azp_integrate_nve_step_one does
+ * Plain IEEE arithmetic in the order written, no contraction, no atomics. Asynchronous on `stream`.
+ * AZP_ERROR_INVALID_ARGUMENT: NULL args, N == 0, a NULL array the call uses, too small a d_partials; for the advance
+ * also an unknown kind, dt <= 0, kT <= 0, ndof < 3, tau <= 0 (Bussi: tau < 0), Berendsen with tau < dt. */
+typedef enum azp_thermostat_kind
+    {
+    AZP_THERMOSTAT_BERENDSEN = 0,
+    AZP_THERMOSTAT_BUSSI = 1,
+    AZP_THERMOSTAT_MTTK = 2
+    } azp_thermostat_kind;
+
+#define AZP_THERMOSTAT_NSTATE 8
+#define AZP_THERMOSTAT_ALPHA 0    /* the scale factor of the last advance */
+#define AZP_THERMOSTAT_K 1        /* the kinetic energy it saw */
+#define AZP_THERMOSTAT_ENERGY 2
+#define AZP_THERMOSTAT_XI 3       /* MTTK */
+#define AZP_THERMOSTAT_ETA 4      /* MTTK */
+#define AZP_THERMOSTAT_ATTEMPTS 5 /* Bussi: attempts the Gamma sampler of the last advance took */
+
+typedef struct azp_thermostat_args
+    {
+    double* d_pos;             /* N x 4 (type in w is preserved); step one */
+    double* d_vel;             /* N x 4 (vx, vy, vz, mass) */
+    const double* d_net_force; /* N x 4; step one and step two */
+    int32_t* d_image;          /* N x 3 periodic image counters, may be NULL; step one */
+    double* d_partials;        /* azp_thermostat_partials_size(N) bytes */
+    double* d_state;           /* AZP_THERMOSTAT_NSTATE doubles */
+    uint64_t partials_bytes;
+    azp_box box;
+    double dt;
+    double kT;                 /* kT at `timestep` */
+    double tau;
+    double ndof;               /* Nf */
+    uint64_t timestep;
+    uint32_t seed;             /* low 16 bits used */
+    uint32_t kind;             /* azp_thermostat_kind */
+    uint32_t N;
+    uint32_t _pad;
+    } azp_thermostat_args;
+
+int azp_thermostat_partials_size(uint32_t N, uint64_t* bytes);
+int azp_thermostat_kinetic(const azp_thermostat_args* args, void* stream);
+int azp_thermostat_step_two(const azp_thermostat_args* args, void* stream);
+int azp_thermostat_advance(const azp_thermostat_args* args, void* stream);
+int azp_thermostat_step_one(const azp_thermostat_args* args, void* stream);
+
 /* ---- type updates: region type updater and particle evaporator ----
  * The reference's evaporation tools (HOOMD-2-era sources that its CMake no longer builds), restated. Both calls are
  * asynchronous on `stream`, touch rows [0, N) only (ghost rows follow their owner at the next exchange) and write
