@@ -383,6 +383,36 @@ class ThermostatArgs(C.Structure):
     ]
 
 
+FIRE_NSTATE = 16
+(FIRE_DT, FIRE_ALPHA, FIRE_KEEP, FIRE_MIX, FIRE_N_POS, FIRE_N_STEPS, FIRE_U, FIRE_U_PREV, FIRE_P, FIRE_VV, FIRE_FF, FIRE_CONVERGED,
+ FIRE_NONFINITE) = range(13)
+FIRE_NSLOTS = 4
+
+
+class FireArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_vel", C.c_void_p),
+        ("d_net_force", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_partials", C.c_void_p),
+        ("d_state", C.c_void_p),
+        ("partials_bytes", C.c_uint64),
+        ("box", Box),
+        ("dt_max", C.c_double),
+        ("force_tol", C.c_double),
+        ("energy_tol", C.c_double),
+        ("finc_dt", C.c_double),
+        ("fdec_dt", C.c_double),
+        ("alpha_start", C.c_double),
+        ("fdec_alpha", C.c_double),
+        ("min_steps_adapt", C.c_uint32),
+        ("min_steps_conv", C.c_uint32),
+        ("N", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 class TypeUpdateArgs(C.Structure):
     _fields_ = [
         ("d_pos", C.c_void_p),
@@ -532,6 +562,11 @@ SYMBOLS = {
     "azp_thermostat_step_two": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
     "azp_thermostat_advance": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
     "azp_thermostat_step_one": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
+    "azp_fire_partials_size": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
+    "azp_fire_measure": (C.c_int, [C.POINTER(FireArgs), _VP]),
+    "azp_fire_step_two": (C.c_int, [C.POINTER(FireArgs), _VP]),
+    "azp_fire_advance": (C.c_int, [C.POINTER(FireArgs), _VP]),
+    "azp_fire_step_one": (C.c_int, [C.POINTER(FireArgs), _VP]),
     "azp_type_update_region": (C.c_int, [C.POINTER(TypeUpdateArgs), _VP]),
     "azp_evaporate_scratch_size": (C.c_uint64, [C.c_uint32]),
     "azp_evaporate": (C.c_int, [C.POINTER(EvaporateArgs), _VP]),

@@ -376,6 +376,10 @@ class Simulation:
         self._attach_all()
         integ = self.operations.integrator
         st = self.state
+        from .minimize import FIRE
+
+        if isinstance(integ, FIRE):
+            return self._run_fire(steps)
         flow_methods = self._check_flow_methods(integ)
         if self.domain is not None:
             self._wire_domain()
@@ -544,6 +548,55 @@ class Simulation:
             self._compute_forces()
             point_at_state()
             _lib.check(lib.azp_thermostat_step_two(C.byref(a), stream), "azp_thermostat_step_two")
+        self._run_writers(self._writers_due())
+        for f in deferred:
+            f.defer_flag_check = False
+            f.check_flags(wait=True)
+
+    def _run_fire(self, steps):
+        """``steps`` steps of ``minimize.FIRE``: the thermostatted step's shape with a control state that
+        holds the time step itself. Step two leaves the partials of P = f . v, |v|^2, |f|^2 and U behind, one wave turns
+        them into the next step's time step and velocity coefficients on the device, and step one reads them from there.
+        Nothing is read back: once the state says converged the kernels return at once, and the loop only counts."""
+        integ = self.operations.integrator
+        st = self.state
+        integ._check(self)
+        self._compute_forces()
+        if steps == 0:
+            return
+        a = integ._prepare(self)
+        a.box = st.box.to_c()
+        lib = _lib.lib()
+        stream = _lib.raw_stream(st.device)
+
+        def point_at_state():
+            # (the arrays are replaced when the particles are re-sorted)
+            a.d_pos = st.pos.data_ptr()
+            a.d_vel = st.vel.data_ptr()
+            a.d_net_force = st.net_force.data_ptr()
+            a.d_image = st.image.data_ptr()
+            a.N = st.N
+
+        # the velocities may have been changed between runs: the sums of the first step come from a pass of their own
+        # (after a run that ended with step two it leaves the partials that step two left, bit for bit)
+        point_at_state()
+        _lib.check(lib.azp_fire_measure(C.byref(a), stream), "azp_fire_measure")
+        deferred = [f for f in integ.forces if hasattr(f, "defer_flag_check")]
+        for f in deferred:
+            f.defer_flag_check = True
+        for k in range(steps):
+            if k:
+                self._run_writers(self._writers_due())
+            self._run_updaters()
+            point_at_state()
+            _lib.check(lib.azp_fire_advance(C.byref(a), stream), "azp_fire_advance")
+            _lib.check(lib.azp_fire_step_one(C.byref(a), stream), "azp_fire_step_one")
+            st.position_generation += 1
+            self.timestep += 1
+            self._run_tuners(integ)
+            self._compute_forces()
+            point_at_state()
+            _lib.check(lib.azp_fire_step_two(C.byref(a), stream), "azp_fire_step_two")
         self._run_writers(self._writers_due())
         for f in deferred:
             f.defer_flag_check = False

@@ -864,6 +864,96 @@ int azp_thermostat_step_two(const azp_thermostat_args* args, void* stream);
 int azp_thermostat_advance(const azp_thermostat_args* args, void* stream);
 int azp_thermostat_step_one(const azp_thermostat_args* args, void* stream);
 
+/* ---- energy minimization (azplugins_amd.minimize.FIRE) ----
+ * Name and parameter keys are hoomd.md.minimize.FIRE's; HOOMD-blue's source is not available to this project, so the
+ * scheme is DEFINED HERE and pinned by tests/fire_ref.py. FIRE (Bitzek et al. 2006) is velocity Verlet
+ * whose velocities are steered towards the force and whose time step adapts: the control state, the time step
+ * included, lives in d_state on the device and nothing reads it back inside a run. All N particles, translational
+ * degrees of freedom only.
+ *
+ * Sums over all particles, f = d_net_force, v = d_vel, each term in the order written, summed in the reproducible
+ * order of csrc/azp_reduce.hpp (partials slot-major in d_partials, slots P, VV, FF, U):
+ *   P  = sum ((f.x v.x) + (f.y v.y)) + (f.z v.z)
+ *   VV = sum ((v.x v.x) + (v.y v.y)) + (v.z v.z)
+ *   FF = sum ((f.x f.x) + (f.y f.y)) + (f.z f.z)
+ *   U  = sum f.w   (net_force.w carries each particle's share of the potential energy)
+ * Masses do not enter the sums.
+ *
+ * d_state: AZP_FIRE_NSTATE doubles indexed by the AZP_FIRE_* slots below (unused slots stay 0). Initial values:
+ * DT = dt_max, ALPHA = alpha_start, KEEP = 1, MIX = 0, all others 0.
+ *
+ * One step at timestep t:
+ *   1. azp_fire_advance   one wave. Folds the four slots of d_partials (lane l adds the partials l, l + 64, ... in turn
+ *        from +0.0, then the butterfly: bit for bit what reduce_fold gives). Then lane 0:
+ *          CONVERGED or NONFINITE set: return.
+ *          any of the four sums not finite: NONFINITE = 1, KEEP = MIX = 0, return.
+ *          store P, VV, FF, U.
+ *          N_STEPS >= max(1, min_steps_conv) and sqrt(FF / (3 N)) < force_tol and |U - U_PREV| / N < energy_tol:
+ *            CONVERGED = 1, KEEP = MIX = 0, return.
+ *          KEEP = 1 - ALPHA; MIX = FF > 0 ? ALPHA * (sqrt(VV) / sqrt(FF)) : 0.
+ *          P > 0:  N_POS += 1; if N_POS > min_steps_adapt: DT = min(DT * finc_dt, dt_max), ALPHA = ALPHA * fdec_alpha.
+ *          else:   DT = DT * fdec_dt, ALPHA = alpha_start, N_POS = 0, KEEP = MIX = 0 (the velocities are dropped;
+ *                  DT has no floor).
+ *          U_PREV = U; N_STEPS += 1.
+ *   2. azp_fire_step_one  reads DT, KEEP, MIX and the flags from d_state. A flag set: the whole grid returns, nothing
+ *        moves. Otherwise v = (KEEP * v) + (MIX * f) per component, v += ((DT / 2) f) (1 / m), x += DT v, wrap (image
+ *        counters updated) as azp_integrate_nve_step_one does; pos.w and vel.w are preserved.
+ *   3. the forces at t + 1 (the caller's).
+ *   4. azp_fire_step_two  reads DT and the flags from d_state (the DT that step one used). A flag set: returns
+ *        without writing partials. Otherwise v += ((DT / 2) f) (1 / m) and, in the same pass, d_partials <- the
+ *        per-workgroup partials of the four sums of the new v and of f.
+ *   azp_fire_measure      d_partials <- the partials of v and f as they stand: the same terms in the same order, no
+ *        update, d_state not read. Called once at the start of a run (velocities may have been changed between runs);
+ *        after azp_fire_step_two it leaves the same partials bit for bit.
+ * Plain IEEE arithmetic in the order written, no contraction, no atomics. Asynchronous on `stream`.
+ * AZP_ERROR_INVALID_ARGUMENT: NULL args, N == 0, a NULL array the call uses (d_image may be NULL), a d_partials smaller
+ * than azp_fire_partials_size(N); for the advance also dt_max <= 0, force_tol <= 0, energy_tol <= 0, finc_dt <= 1,
+ * fdec_dt, alpha_start or fdec_alpha outside (0, 1), or any of them not finite. */
+#define AZP_FIRE_NSTATE 16
+#define AZP_FIRE_DT 0         /* the time step of the next step one */
+#define AZP_FIRE_ALPHA 1
+#define AZP_FIRE_KEEP 2       /* the two velocity coefficients of the next step one */
+#define AZP_FIRE_MIX 3
+#define AZP_FIRE_N_POS 4      /* steps since the last non-positive power */
+#define AZP_FIRE_N_STEPS 5    /* advances since reset */
+#define AZP_FIRE_U 6          /* the sums the last advance saw */
+#define AZP_FIRE_U_PREV 7
+#define AZP_FIRE_P 8
+#define AZP_FIRE_VV 9
+#define AZP_FIRE_FF 10
+#define AZP_FIRE_CONVERGED 11
+#define AZP_FIRE_NONFINITE 12
+#define AZP_FIRE_NSLOTS 4     /* slots of d_partials: P, VV, FF, U */
+
+typedef struct azp_fire_args
+    {
+    double* d_pos;             /* N x 4 (type in w is preserved); step one */
+    double* d_vel;             /* N x 4 (vx, vy, vz, mass) */
+    const double* d_net_force; /* N x 4 (fx, fy, fz, energy) */
+    int32_t* d_image;          /* N x 3 periodic image counters, may be NULL; step one */
+    double* d_partials;        /* azp_fire_partials_size(N) bytes */
+    double* d_state;           /* AZP_FIRE_NSTATE doubles */
+    uint64_t partials_bytes;
+    azp_box box;
+    double dt_max;
+    double force_tol;
+    double energy_tol;
+    double finc_dt;
+    double fdec_dt;
+    double alpha_start;
+    double fdec_alpha;
+    uint32_t min_steps_adapt;
+    uint32_t min_steps_conv;
+    uint32_t N;
+    uint32_t _pad;
+    } azp_fire_args;
+
+int azp_fire_partials_size(uint32_t N, uint64_t* bytes);
+int azp_fire_measure(const azp_fire_args* args, void* stream);
+int azp_fire_step_two(const azp_fire_args* args, void* stream);
+int azp_fire_advance(const azp_fire_args* args, void* stream);
+int azp_fire_step_one(const azp_fire_args* args, void* stream);
+
 /* ---- type updates: region type updater and particle evaporator ----
  * The reference's evaporation tools (HOOMD-2-era sources that its CMake no longer builds), restated. Both calls are
  * asynchronous on `stream`, touch rows [0, N) only (ghost rows follow their owner at the next exchange) and write
