@@ -23,7 +23,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .force import Force, TypeParameter
+from .bonded import BondedForce
+from .force import TypeParameter
 
 
 class _AngleParameter(TypeParameter):
@@ -38,27 +39,16 @@ class _AngleParameter(TypeParameter):
         return out
 
 
-class Angle(Force):
+class Angle(BondedForce):
     """Reduced ``hoomd.md.angle.Angle``: per-angle-type ``params``. ``block_size``: 0 (256) or 64, 128, 256."""
 
-    _entry = None
+    _kind = "angle"
     _make = None
     _unpack_entry = None
     _schema = dict(k=float, t0=float)
+    _parameter = _AngleParameter
+    _param_doubles = 2
     _cpp_class_name = None  # the reference's module.cc registers no angle class
-
-    def __init__(self):
-        super().__init__()
-        self.params = _AngleParameter("params", self._schema, 1, self._mark_dirty)
-        self._tables = None
-        self.block_size = 0
-
-    def _mark_dirty(self):
-        self._tables = None
-
-    def _attach(self, sim):
-        super()._attach(sim)
-        self._tables = None
 
     def _pack(self, d):
         """One type's dict folded into its two doubles by libazp."""
@@ -71,42 +61,6 @@ class Angle(Force):
         k, t0 = C.c_double(), C.c_double()
         getattr(_lib.lib(), self._unpack_entry)(raw.ctypes.data, C.byref(k), C.byref(t0))
         return dict(k=k.value, t0=t0.value)
-
-    def _build_tables(self):
-        import torch
-
-        types = self._state.angle_types
-        raw = np.zeros((max(len(types), 1), 2))
-        for i, t in enumerate(types):
-            d = self.params.get_raw(t)
-            if d is None:
-                raise _lib.AzpError("%s.params[%r] is not set" % (type(self).__name__, t))
-            raw[i] = self._pack(d)
-        self._tables = torch.from_numpy(raw).to(self._state.device)
-
-    def compute(self, timestep=None):
-        self._require()
-        st = self._state
-        self._ensure_buffers()
-        if self._tables is None or self._tables.shape[0] != max(len(st.angle_types), 1):
-            self._build_tables()
-        tab = st.angle_table()
-        a = _lib.AngleArgs()
-        a.d_force = self._force.data_ptr()
-        a.d_virial = self._virial.data_ptr()
-        a.virial_pitch = st.N
-        a.N = st.N
-        a.n_max = st.n_max
-        a.d_pos = st.pos.data_ptr()
-        a.box = st.box.to_c()
-        a.d_gpu_anglelist = tab["table"].data_ptr()
-        a.d_gpu_n_angles = tab["n_angles"].data_ptr()
-        a.pitch = tab["pitch"]
-        a.n_angle_types = max(len(st.angle_types), 1)
-        a.compute_virial = 1 if self.compute_virial else 0
-        a.block_size = self.block_size
-        _lib.check(getattr(_lib.lib(), self._entry)(C.byref(a), self._tables.data_ptr(), _lib.raw_stream(st.device)),
-                   self._entry)
 
 
 class Harmonic(Angle):

@@ -6,25 +6,17 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .force import Force, TypeParameter
+from .bonded import BondedForce
 
 
-class Bond(Force):
-    """Reduced ``hoomd.md.bond.Bond``: per-bond-type ``params``."""
+class Bond(BondedForce):
+    """Reduced ``hoomd.md.bond.Bond``: per-bond-type ``params``. Its own, around the shared launch: the ``_azplugins``
+    C++ object as the source of the parameter bytes and of what ``params[...]`` reads back, and the flag word of an
+    evaluator that rejected its parameters."""
 
+    _kind = "bond"
     _cpp_class_name = None
-    _entry = None
-    _schema = {}
     _param_doubles = 4
-
-    def __init__(self):
-        super().__init__()
-        self.params = TypeParameter("params", self._schema, 1, self._mark_dirty, self._readback)
-        self._tables = None
-        self.block_size = 0
-
-    def _mark_dirty(self):
-        self._tables = None
 
     def _readback(self, key):
         """After attaching, ``params[...]`` returns what the C++ object holds (HOOMD:
@@ -38,7 +30,6 @@ class Bond(Force):
         import torch
 
         super()._attach(sim)
-        self._tables = None
         self._cpp = None
         self._flags = torch.zeros(1, dtype=torch.int32, device=self._state.device)
 
@@ -52,57 +43,32 @@ class Bond(Force):
             if d is not None:
                 self._cpp.setParams(t, d)
 
-    def _build_tables(self):
-        import torch
-
-        types = self._state.bond_types
-        for t in types:
-            if self.params.get_raw(t) is None:
-                raise _lib.AzpError("%s.params[%r] is not set" % (type(self).__name__, t))
+    def _rows(self, types, values):
         self._sync_cpp()
         raw = np.frombuffer(self._cpp.params_bytes(), dtype=np.float64).reshape(max(len(types), 1), -1).copy()
         assert raw.shape[1] == self._param_doubles
-        self._tables = dict(params=torch.from_numpy(raw).to(self._state.device))
+        return raw
 
-    def compute(self, timestep=None):
+    def _build_tables(self):
+        super()._build_tables()
+        self._flags.zero_()  # (new parameters: the sticky "rejected" flag starts over, on the device and on the host)
+        self._flag_pending = None
+        if getattr(self, "_flag_host", None) is not None:
+            getattr(self, "_flag_side").synchronize()
+            self._flag_host.zero_()
+
+    def _launch(self, args, stream):
         import torch
 
-        self._require()
-        st = self._state
-        self._ensure_buffers()
-        if self._tables is None:
-            self._build_tables()
-            self._flags.zero_()  # (new parameters: the sticky "rejected" flag starts over, on the device and on the host)
-            self._flag_pending = None
-            if getattr(self, "_flag_host", None) is not None:
-                getattr(self, "_flag_side").synchronize()
-                self._flag_host.zero_()
-        tab = st.bond_table()
-        a = _lib.BondArgs()
-        a.d_force = self._force.data_ptr()
-        a.d_virial = self._virial.data_ptr()
-        a.virial_pitch = st.N
-        a.N = st.N
-        a.n_max = st.n_max
-        a.d_pos = st.pos.data_ptr()
-        a.box = st.box.to_c()
-        a.d_gpu_bondlist = tab["table"].data_ptr()
-        a.d_gpu_bond_pos = tab["bond_pos"].data_ptr()
-        a.d_gpu_n_bonds = tab["n_bonds"].data_ptr()
-        a.pitch = tab["pitch"]
-        a.n_bond_types = max(len(st.bond_types), 1)
-        a.compute_virial = 1 if self.compute_virial else 0
-        a.block_size = self.block_size
         # The evaluator's "rejected its parameters" flag (HOOMD: "bond.<name>: bond out of bounds") is sticky on the
         # device (the kernel only ever sets it) and travels to the host on a side stream behind each launch; it is
         # LOOKED AT when the next launch is queued, by which time it has long arrived -- a readback right behind
         # the launch would idle the GPU for a host round trip every step. check_flags() looks now.
         self.check_flags(wait=False)
-        stream = _lib.raw_stream(st.device)
         fn = getattr(_lib.lib(), self._entry)
-        _lib.check(fn(C.byref(a), self._tables["params"].data_ptr(), self._flags.data_ptr(), stream), self._entry)
+        _lib.check(fn(C.byref(args), self._tables.data_ptr(), self._flags.data_ptr(), stream), self._entry)
         if getattr(self, "_flag_side", None) is None:
-            self._flag_side = torch.cuda.Stream(device=st.device)
+            self._flag_side = torch.cuda.Stream(device=self._state.device)
             self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         done = torch.cuda.Event()
         done.record()

@@ -2,13 +2,11 @@
 // the semantics are HOOMD's documented md.angle.Harmonic and md.angle.CosineSquared conventions, defined in
 // include/azp.h ("angle forces") and DESIGN 4.16.
 //
-// One lane per particle, no atomics: the lane walks its table entries in order and keeps, of each angle, the force
-// on its own position, a third of the energy and a third of the virial. The three lanes of one angle evaluate the
-// same expression on the same operands, so their forces add to zero to rounding and two calls give the same bits.
-// Table columns are particle-major (entry s of particle i at s * pitch + i): every table read is one coalesced
-// 16-byte load; the two partner positions are the only gathers. Per-angle-type parameters are staged in LDS.
-#include "azp_device.hpp"
-#include "pair_kernel_host.hpp"
+// The outer kernel is bonded_forces_kernel (bonded_kernel.hpp); this file holds the evaluators and the angle geometry.
+// The lane keeps, of each angle, the force on its own position, a third of the energy and a third of the virial. The
+// three lanes of one angle evaluate the same expression on the same operands, so their forces add to zero to rounding.
+// Every table read is one 16-byte load.
+#include "bonded_kernel.hpp"
 
 namespace azp
 {
@@ -36,55 +34,49 @@ struct EvalAngleCosineSquared
         }
     };
 
-struct AngleKArgs
+struct AngleGeometry
     {
-    double* force;
-    double* virial;
-    uint64_t virial_pitch;
-    const double* pos;
-    const azp_angle_entry* anglelist;
-    const uint32_t* n_angles;
-    uint64_t pitch;
-    BoxDev box;
-    uint32_t N;
-    uint32_t n_angle_types;
-    uint32_t compute_virial;
-    uint32_t _pad;
-    };
+    typedef azp_angle_args Args;
+    typedef double3 Own;
+    typedef azp_angle_entry Entry;
+    static constexpr uint32_t PARTNERS = 2;
+    // An interior bead of a linear chain has 3 entries: BATCH = 3 holds it in one batch. The harmonic kernel takes 110
+    // VGPRs at 2, 3 and 4 alike (acos sets its peak), the cosine-squared one 75 / 89 / 103 (DESIGN 4.16).
+    static constexpr uint32_t BATCH = 3;
+    static constexpr bool FLAGS = false; // neither evaluator can reject its parameters
 
-__device__ __forceinline__ azp_angle_entry load_angle_entry(const azp_angle_entry* table, uint64_t at)
-    {
-    const uint4 w = reinterpret_cast<const uint4*>(table)[at];
-    azp_angle_entry e;
-    e.idx[0] = w.x; e.idx[1] = w.y; e.type = w.z; e.pos = w.w;
-    return e;
-    }
-
-// component-wise select (a ?: on the structs makes the compiler pick between addresses and park the batch in scratch)
-__device__ __forceinline__ double3 select3(bool take_first, const double3& x, const double3& y)
-    {
-    return make_double3(take_first ? x.x : y.x, take_first ? x.y : y.y, take_first ? x.z : y.z);
-    }
-
-template<class E>
-__global__ void __launch_bounds__(256) angle_forces_kernel(const AngleKArgs a, const typename E::Params* __restrict__ params)
-    {
-    typedef typename E::Params Params;
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    Params* s_params = reinterpret_cast<Params*>(s_raw);
-    for (uint32_t t = threadIdx.x; t < a.n_angle_types; t += blockDim.x)
-        s_params[t] = params[t];
-    __syncthreads();
-
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= a.N)
-        return;
-    const uint32_t na = a.n_angles[idx];
-    const double3 p = load_scalar3_of4(a.pos, idx);
-    double fx = 0.0, fy = 0.0, fz = 0.0, pe = 0.0;
-    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    auto one_angle = [&](const azp_angle_entry& ent, const double3& q0, const double3& q1)
+    static bool tables(const Args& args, BondedKArgs& k)
         {
+        k.table = args.d_gpu_anglelist;
+        k.counts = args.d_gpu_n_angles;
+        k.n_types = args.n_angle_types;
+        return k.table && k.counts;
+        }
+    static bool block_size_ok(uint32_t bs) { return bs % 64 == 0 && bs <= 256; }
+
+    static __device__ __forceinline__ Own own(const double* pos, uint32_t idx) { return load_scalar3_of4(pos, idx); }
+    static __device__ __forceinline__ Entry unused(uint32_t idx)
+        {
+        Entry e;
+        e.idx[0] = idx; e.idx[1] = idx; e.type = 0; e.pos = 0;
+        return e;
+        }
+    static __device__ __forceinline__ Entry load(const BondedKArgs& a, uint64_t at)
+        {
+        const uint4 w = static_cast<const uint4*>(a.table)[at];
+        Entry e;
+        e.idx[0] = w.x; e.idx[1] = w.y; e.type = w.z; e.pos = w.w;
+        return e;
+        }
+    static __device__ __forceinline__ uint32_t partner(const Entry& e, uint32_t k) { return e.idx[k]; }
+
+    template<class E>
+    static __device__ __forceinline__ void one(const BondedKArgs& a, const typename E::Params* s_params, const Own& p,
+                                               const Entry& ent, const double3 (&partners)[PARTNERS], BondedSums& sums, unsigned int*)
+        {
+        const double3 &q0 = partners[0], &q1 = partners[1];
+        double &fx = sums.fx, &fy = sums.fy, &fz = sums.fz, &pe = sums.pe;
+        double* v = sums.v;
         // members in angle order: this lane's own position goes into slot ent.pos, the partners fill the rest
         const bool is_a = ent.pos == 0, is_c = ent.pos == 2;
         const double3 ra = select3(is_a, p, q0);
@@ -118,91 +110,17 @@ __global__ void __launch_bounds__(256) angle_forces_kernel(const AngleKArgs a, c
             v[2] += third * (abx * faz + cbx * fcz); v[3] += third * (aby * fay + cby * fcy);
             v[4] += third * (aby * faz + cby * fcz); v[5] += third * (abz * faz + cbz * fcz);
             }
-        };
-    // As the bond kernel: the first BATCH table columns of every lane are loaded together, then their 2 * BATCH
-    // partner positions together -- two dependent round trips per particle instead of two per angle (an interior
-    // bead of a linear chain has 3 entries). BATCH = 3 holds that bead in one batch; the harmonic kernel takes 110
-    // VGPRs at 2, 3 and 4 alike (acos sets its peak), the cosine-squared one 75 / 89 / 103 (DESIGN 4.16).
-    constexpr uint32_t BATCH = 3;
-    azp_angle_entry ent[BATCH];
-#pragma unroll
-    for (uint32_t b = 0; b < BATCH; ++b)
-        {
-        ent[b].idx[0] = idx; ent[b].idx[1] = idx; ent[b].type = 0; ent[b].pos = 0;
-        if (b < na)
-            ent[b] = load_angle_entry(a.anglelist, (uint64_t)b * a.pitch + idx);
         }
-    double3 q0[BATCH], q1[BATCH];
-#pragma unroll
-    for (uint32_t b = 0; b < BATCH; ++b)
-        {
-        q0[b] = load_scalar3_of4(a.pos, ent[b].idx[0]); // unused slots re-read the lane's own (cached) row
-        q1[b] = load_scalar3_of4(a.pos, ent[b].idx[1]);
-        }
-#pragma unroll
-    for (uint32_t b = 0; b < BATCH; ++b)
-        if (b < na)
-            one_angle(ent[b], q0[b], q1[b]);
-    for (uint32_t b = BATCH; b < na; ++b)
-        {
-        const azp_angle_entry e = load_angle_entry(a.anglelist, (uint64_t)b * a.pitch + idx);
-        one_angle(e, load_scalar3_of4(a.pos, e.idx[0]), load_scalar3_of4(a.pos, e.idx[1]));
-        }
-    store_scalar4(a.force, idx, fx, fy, fz, pe);
-    if (a.compute_virial)
-        {
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-            a.virial[(uint64_t)c * a.virial_pitch + idx] = v[c];
-        }
-    }
-
-template<class E>
-static int launch_angle(const azp_angle_args* args, const typename E::Params* d_params, void* stream)
-    {
-    if (!args)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->N == 0)
-        return AZP_SUCCESS;
-    if (!d_params || !args->d_force || !args->d_pos || !args->d_gpu_anglelist || !args->d_gpu_n_angles
-        || args->pitch < args->N || args->n_angle_types == 0)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->compute_virial && (!args->d_virial || args->virial_pitch < args->N))
-        return AZP_ERROR_INVALID_ARGUMENT;
-    const uint32_t bs = args->block_size ? args->block_size : 256u;
-    if (bs % 64 || bs > 256)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    const size_t lds = sizeof(typename E::Params) * (size_t)args->n_angle_types;
-    if (lds > 64 * 1024)
-        return AZP_ERROR_TOO_MANY_TYPES;
-    AngleKArgs k;
-    k.force = args->d_force;
-    k.virial = args->d_virial;
-    k.virial_pitch = args->virial_pitch;
-    k.pos = args->d_pos;
-    k.anglelist = args->d_gpu_anglelist;
-    k.n_angles = args->d_gpu_n_angles;
-    k.pitch = args->pitch;
-    k.box = make_box_dev(args->box);
-    k.N = args->N;
-    k.n_angle_types = args->n_angle_types;
-    k.compute_virial = args->compute_virial;
-    k._pad = 0;
-    const uint32_t grid = (args->N + bs - 1) / bs;
-    LaunchInfo& li = last_launch();
-    li.block_size = bs; li.tpp = 1; li.grid = grid; li.lds_bytes = (uint32_t)lds;
-    hipLaunchKernelGGL(angle_forces_kernel<E>, dim3(grid), dim3(bs), lds, static_cast<hipStream_t>(stream), k, d_params);
-    return (int)hipGetLastError();
-    }
+    };
 } // namespace azp
 
 extern "C" int azp_angle_forces_harmonic(const azp_angle_args* args, const azp_angle_harmonic_params* d_params, void* stream)
     {
-    return azp::launch_angle<azp::EvalAngleHarmonic>(args, d_params, stream);
+    return azp::launch_bonded<azp::AngleGeometry, azp::EvalAngleHarmonic>(args, d_params, nullptr, stream);
     }
 
 extern "C" int azp_angle_forces_cosine_squared(const azp_angle_args* args, const azp_angle_cossq_params* d_params,
                                                void* stream)
     {
-    return azp::launch_angle<azp::EvalAngleCosineSquared>(args, d_params, stream);
+    return azp::launch_bonded<azp::AngleGeometry, azp::EvalAngleCosineSquared>(args, d_params, nullptr, stream);
     }

@@ -145,6 +145,12 @@ __device__ __forceinline__ void store_scalar4(double* base, uint32_t idx, double
     p[1] = make_double2(z, w);
     }
 
+// component-wise select (a ?: on the structs makes the compiler pick between addresses and park its operands in scratch)
+__device__ __forceinline__ double3 select3(bool take_first, const double3& x, const double3& y)
+    {
+    return make_double3(take_first ? x.x : y.x, take_first ? x.y : y.y, take_first ? x.z : y.z);
+    }
+
 // ---------------------------------------------------------------------------
 // Butterfly reduction inside a group of TPP consecutive lanes (TPP <= 64,
 // power of two). Steps 1/2/4/8 use DPP row operations (no LDS traffic);

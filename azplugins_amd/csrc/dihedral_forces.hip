@@ -2,17 +2,15 @@
 // code: the semantics (HOOMD's md.dihedral.Periodic and md.dihedral.OPLS class names and parameter keys, the IUPAC
 // angle) are defined in include/azp.h ("dihedral forces") and DESIGN 4.17.
 //
-// One lane per particle, no atomics: the lane walks its table entries in order and keeps, of each dihedral, the force
-// on its own position, a quarter of the energy and a quarter of the virial. The four lanes of one dihedral evaluate
-// the same expression on the same operands, so two calls give the same bits whatever the block size. Table columns
-// are particle-major (entry s of particle i at s * pitch + i): every table read is one coalesced 16-byte load; the
-// three partner positions are the only gathers. Per-dihedral-type parameters are staged in LDS.
+// The outer kernel is bonded_forces_kernel (bonded_kernel.hpp); this file holds the evaluators and the dihedral
+// geometry. The lane keeps, of each dihedral, the force on its own position, a quarter of the energy and a quarter of
+// the virial. The four lanes of one dihedral evaluate the same expression on the same operands. Every table read is
+// one 16-byte load.
 //
 // cos phi and sin phi come straight from the geometry (no atan2, no sincos): with n1 = b1 x b2, n2 = b2 x b3 and
 // q = 1 / (|n1||n2|), cos phi = (n1 . n2) q and sin phi = |b2| (b1 . n2) q. The multiples of phi follow from the
 // angle-addition recurrence, cos phi0 and sin phi0 are folded on the host.
-#include "azp_device.hpp"
-#include "pair_kernel_host.hpp"
+#include "bonded_kernel.hpp"
 
 #ifndef AZP_DIHEDRAL_BATCH
 #define AZP_DIHEDRAL_BATCH 3
@@ -53,61 +51,56 @@ struct EvalDihedralOPLS
         }
     };
 
-struct DihedralKArgs
+struct DihedralGeometry
     {
-    double* force;
-    double* virial;
-    uint64_t virial_pitch;
-    const double* pos;
-    const azp_dihedral_entry* dihedrallist;
-    const uint32_t* n_dihedrals;
-    uint64_t pitch;
-    BoxDev box;
-    uint32_t N;
-    uint32_t n_dihedral_types;
-    uint32_t compute_virial;
-    uint32_t _pad;
-    };
+    typedef azp_dihedral_args Args;
+    typedef double3 Own;
+    typedef azp_dihedral_entry Entry;
+    static constexpr uint32_t PARTNERS = 3;
+    // BATCH = 3 is the largest that keeps 4 waves per SIMD (124 VGPRs; 143 and 3 waves at 4). An interior bead of a
+    // linear chain has 4 entries and takes one turn of the tail loop; measured on C3, that still beats BATCH = 4 with
+    // its lost wave (DESIGN 4.17).
+    static constexpr uint32_t BATCH = AZP_DIHEDRAL_BATCH;
+    static constexpr bool FLAGS = false; // neither evaluator can reject its parameters
 
-__device__ __forceinline__ azp_dihedral_entry load_dihedral_entry(const azp_dihedral_entry* table, uint64_t at)
-    {
-    const uint4 w = reinterpret_cast<const uint4*>(table)[at];
-    azp_dihedral_entry e;
-    e.idx[0] = w.x; e.idx[1] = w.y; e.idx[2] = w.z; e.type_pos = w.w;
-    return e;
-    }
-
-// component-wise select (a ?: on the structs makes the compiler pick between addresses and park the batch in scratch)
-__device__ __forceinline__ double3 dihedral_select3(bool take_first, const double3& x, const double3& y)
-    {
-    return make_double3(take_first ? x.x : y.x, take_first ? x.y : y.y, take_first ? x.z : y.z);
-    }
-
-template<class E>
-__global__ void __launch_bounds__(256) dihedral_forces_kernel(const DihedralKArgs a, const typename E::Params* __restrict__ params)
-    {
-    typedef typename E::Params Params;
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    Params* s_params = reinterpret_cast<Params*>(s_raw);
-    for (uint32_t t = threadIdx.x; t < a.n_dihedral_types; t += blockDim.x)
-        s_params[t] = params[t];
-    __syncthreads();
-
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= a.N)
-        return;
-    const uint32_t nd = a.n_dihedrals[idx];
-    const double3 p = load_scalar3_of4(a.pos, idx);
-    double fx = 0.0, fy = 0.0, fz = 0.0, pe = 0.0;
-    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    auto one_dihedral = [&](const azp_dihedral_entry& ent, const double3& q0, const double3& q1, const double3& q2)
+    static bool tables(const Args& args, BondedKArgs& k)
         {
+        k.table = args.d_gpu_dihedrallist;
+        k.counts = args.d_gpu_n_dihedrals;
+        k.n_types = args.n_dihedral_types;
+        return k.table && k.counts;
+        }
+    static bool block_size_ok(uint32_t bs) { return bs == 64 || bs == 128 || bs == 256; }
+
+    static __device__ __forceinline__ Own own(const double* pos, uint32_t idx) { return load_scalar3_of4(pos, idx); }
+    static __device__ __forceinline__ Entry unused(uint32_t idx)
+        {
+        Entry e;
+        e.idx[0] = idx; e.idx[1] = idx; e.idx[2] = idx; e.type_pos = 0;
+        return e;
+        }
+    static __device__ __forceinline__ Entry load(const BondedKArgs& a, uint64_t at)
+        {
+        const uint4 w = static_cast<const uint4*>(a.table)[at];
+        Entry e;
+        e.idx[0] = w.x; e.idx[1] = w.y; e.idx[2] = w.z; e.type_pos = w.w;
+        return e;
+        }
+    static __device__ __forceinline__ uint32_t partner(const Entry& e, uint32_t k) { return e.idx[k]; }
+
+    template<class E>
+    static __device__ __forceinline__ void one(const BondedKArgs& a, const typename E::Params* s_params, const Own& p,
+                                               const Entry& ent, const double3 (&partners)[PARTNERS], BondedSums& sums, unsigned int*)
+        {
+        const double3 &q0 = partners[0], &q1 = partners[1], &q2 = partners[2];
+        double &fx = sums.fx, &fy = sums.fy, &fz = sums.fz, &pe = sums.pe;
+        double* v = sums.v;
         // members in dihedral order: this lane's own position goes into slot m, the partners fill the rest
         const uint32_t m = ent.type_pos >> 30;
-        const double3 ra = dihedral_select3(m == 0, p, q0);
-        const double3 rb = dihedral_select3(m == 0, q0, dihedral_select3(m == 1, p, q1));
-        const double3 rc = dihedral_select3(m <= 1, q1, dihedral_select3(m == 2, p, q2));
-        const double3 rd = dihedral_select3(m == 3, p, q2);
+        const double3 ra = select3(m == 0, p, q0);
+        const double3 rb = select3(m == 0, q0, select3(m == 1, p, q1));
+        const double3 rc = select3(m <= 1, q1, select3(m == 2, p, q2));
+        const double3 rd = select3(m == 3, p, q2);
         double b1x = rb.x - ra.x, b1y = rb.y - ra.y, b1z = rb.z - ra.z;
         double b2x = rc.x - rb.x, b2y = rc.y - rb.y, b2z = rc.z - rb.z;
         double b3x = rd.x - rc.x, b3y = rd.y - rc.y, b3z = rd.z - rc.z;
@@ -148,93 +141,17 @@ __global__ void __launch_bounds__(256) dihedral_forces_kernel(const DihedralKArg
             v[2] += 0.25 * (b2x * fcz + dx * fdz - b1x * faz); v[3] += 0.25 * (b2y * fcy + dy * fdy - b1y * fay);
             v[4] += 0.25 * (b2y * fcz + dy * fdz - b1y * faz); v[5] += 0.25 * (b2z * fcz + dz * fdz - b1z * faz);
             }
-        };
-    // As the angle and bond kernels: the first BATCH table columns of every lane are loaded together, then their
-    // 3 * BATCH partner positions together -- two dependent round trips for the batch instead of two per dihedral.
-    // BATCH = 3 is the largest that keeps 4 waves per SIMD (124 VGPRs; 143 and 3 waves at 4). An interior bead of a
-    // linear chain has 4 entries and takes one turn of the tail loop; measured on C3, that still beats BATCH = 4 with
-    // its lost wave (DESIGN 4.17).
-    constexpr uint32_t BATCH = AZP_DIHEDRAL_BATCH;
-    azp_dihedral_entry ent[BATCH];
-#pragma unroll
-    for (uint32_t b = 0; b < BATCH; ++b)
-        {
-        ent[b].idx[0] = idx; ent[b].idx[1] = idx; ent[b].idx[2] = idx; ent[b].type_pos = 0;
-        if (b < nd)
-            ent[b] = load_dihedral_entry(a.dihedrallist, (uint64_t)b * a.pitch + idx);
         }
-    double3 q0[BATCH], q1[BATCH], q2[BATCH];
-#pragma unroll
-    for (uint32_t b = 0; b < BATCH; ++b)
-        {
-        q0[b] = load_scalar3_of4(a.pos, ent[b].idx[0]); // unused slots re-read the lane's own (cached) row
-        q1[b] = load_scalar3_of4(a.pos, ent[b].idx[1]);
-        q2[b] = load_scalar3_of4(a.pos, ent[b].idx[2]);
-        }
-#pragma unroll
-    for (uint32_t b = 0; b < BATCH; ++b)
-        if (b < nd)
-            one_dihedral(ent[b], q0[b], q1[b], q2[b]);
-    for (uint32_t b = BATCH; b < nd; ++b)
-        {
-        const azp_dihedral_entry e = load_dihedral_entry(a.dihedrallist, (uint64_t)b * a.pitch + idx);
-        one_dihedral(e, load_scalar3_of4(a.pos, e.idx[0]), load_scalar3_of4(a.pos, e.idx[1]), load_scalar3_of4(a.pos, e.idx[2]));
-        }
-    store_scalar4(a.force, idx, fx, fy, fz, pe);
-    if (a.compute_virial)
-        {
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-            a.virial[(uint64_t)c * a.virial_pitch + idx] = v[c];
-        }
-    }
-
-template<class E>
-static int launch_dihedral(const azp_dihedral_args* args, const typename E::Params* d_params, void* stream)
-    {
-    if (!args)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->N == 0)
-        return AZP_SUCCESS;
-    if (!d_params || !args->d_force || !args->d_pos || !args->d_gpu_dihedrallist || !args->d_gpu_n_dihedrals
-        || args->pitch < args->N || args->n_dihedral_types == 0)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    if (args->compute_virial && (!args->d_virial || args->virial_pitch < args->N))
-        return AZP_ERROR_INVALID_ARGUMENT;
-    const uint32_t bs = args->block_size ? args->block_size : 256u;
-    if (bs != 64 && bs != 128 && bs != 256)
-        return AZP_ERROR_INVALID_ARGUMENT;
-    const size_t lds = sizeof(typename E::Params) * (size_t)args->n_dihedral_types;
-    if (lds > 64 * 1024)
-        return AZP_ERROR_TOO_MANY_TYPES;
-    DihedralKArgs k;
-    k.force = args->d_force;
-    k.virial = args->d_virial;
-    k.virial_pitch = args->virial_pitch;
-    k.pos = args->d_pos;
-    k.dihedrallist = args->d_gpu_dihedrallist;
-    k.n_dihedrals = args->d_gpu_n_dihedrals;
-    k.pitch = args->pitch;
-    k.box = make_box_dev(args->box);
-    k.N = args->N;
-    k.n_dihedral_types = args->n_dihedral_types;
-    k.compute_virial = args->compute_virial;
-    k._pad = 0;
-    const uint32_t grid = (args->N + bs - 1) / bs;
-    LaunchInfo& li = last_launch();
-    li.block_size = bs; li.tpp = 1; li.grid = grid; li.lds_bytes = (uint32_t)lds;
-    hipLaunchKernelGGL(dihedral_forces_kernel<E>, dim3(grid), dim3(bs), lds, static_cast<hipStream_t>(stream), k, d_params);
-    return (int)hipGetLastError();
-    }
+    };
 } // namespace azp
 
 extern "C" int azp_dihedral_forces_periodic(const azp_dihedral_args* args, const azp_dihedral_periodic_params* d_params,
                                             void* stream)
     {
-    return azp::launch_dihedral<azp::EvalDihedralPeriodic>(args, d_params, stream);
+    return azp::launch_bonded<azp::DihedralGeometry, azp::EvalDihedralPeriodic>(args, d_params, nullptr, stream);
     }
 
 extern "C" int azp_dihedral_forces_opls(const azp_dihedral_args* args, const azp_dihedral_opls_params* d_params, void* stream)
     {
-    return azp::launch_dihedral<azp::EvalDihedralOPLS>(args, d_params, stream);
+    return azp::launch_bonded<azp::DihedralGeometry, azp::EvalDihedralOPLS>(args, d_params, nullptr, stream);
     }

@@ -20,6 +20,8 @@ The same code runs under ``gloo`` with CPU tensors (tests/test_decomposition.py)
 
 import numpy as np
 
+from .state import ARITY, KINDS
+
 
 def choose_grid(world, L):
     """Regular grid (nx, ny, nz) with nx*ny*nz == world minimising the ghost
@@ -263,18 +265,20 @@ def _snapshot_topology(snap):
     snapshot has angles, ``angle_tags`` / ``angle_typeid`` / ``angle_types`` (absent without angles; a snapshot with
     angles but no bonds carries an empty bond list), and ``dihedral_tags`` / ``dihedral_typeid`` / ``dihedral_types`` in
     the same way, only when it has dihedrals. None when there are neither bonds nor angles nor dihedrals."""
-    if not (snap.bonds.N or snap.angles.N or snap.dihedrals.N):
+    if not any(getattr(snap, kind + "s").N for kind in KINDS):
         return None
     tag = snap.particles.tag.astype(np.int64)
-    topo = dict(bond_tags=tag[snap.bonds.group.astype(np.int64)].reshape(-1, 2), bond_typeid=snap.bonds.typeid.copy(),
-                bond_types=tuple(snap.bonds.types))
-    if snap.angles.N:
-        topo.update(angle_tags=tag[snap.angles.group.astype(np.int64)].reshape(-1, 3), angle_typeid=snap.angles.typeid.copy(),
-                    angle_types=tuple(snap.angles.types))
-    if snap.dihedrals.N:
-        topo.update(dihedral_tags=tag[snap.dihedrals.group.astype(np.int64)].reshape(-1, 4), dihedral_typeid=snap.dihedrals.typeid.copy(),
-                    dihedral_types=tuple(snap.dihedrals.types))
+    topo = {}
+    for kind in KINDS:
+        g = getattr(snap, kind + "s")
+        if g.N or kind == "bond":
+            topo.update(_topology_of(kind, tag[g.group.astype(np.int64)], g.typeid.copy(), tuple(g.types)))
     return topo
+
+
+def _topology_of(kind, tags, typeid, types):
+    """One kind's three keys of a topology dict: ``<kind>_tags`` (n, arity), ``<kind>_typeid``, ``<kind>_types``."""
+    return {kind + "_tags": np.asarray(tags, dtype=np.int64).reshape(-1, ARITY[kind]), kind + "_typeid": typeid, kind + "_types": types}
 
 
 def build_rank_state(cfg, decomp, rank, device):
@@ -306,28 +310,18 @@ def rank_simulation(cfg, decomp, rank, device, seed=1):
         snap.particles.moment_inertia[:] = cfg["inertia"][mine]
     if "angmom" in cfg:
         snap.particles.angmom[:] = cfg["angmom"][mine]
-    topology = None
-    if cfg.get("bonds") is not None and len(cfg["bonds"]):
-        # the topology by tag, replicated (tags = indices of the global configuration unless cfg carries its own)
-        gtag = np.asarray(cfg["tag"], dtype=np.int64) if "tag" in cfg else np.arange(xyz.shape[0], dtype=np.int64)
-        b = np.asarray(cfg["bonds"], dtype=np.int64).reshape(-1, 2)
-        topology = dict(bond_tags=gtag[b], bond_typeid=cfg.get("bond_typeid", np.zeros(b.shape[0], dtype=np.uint32)),
-                        bond_types=cfg.get("bond_types", ("A-A",)))
-    if cfg.get("angles") is not None and len(cfg["angles"]):
-        gtag = np.asarray(cfg["tag"], dtype=np.int64) if "tag" in cfg else np.arange(xyz.shape[0], dtype=np.int64)
-        g = np.asarray(cfg["angles"], dtype=np.int64).reshape(-1, 3)
-        if topology is None:
-            topology = dict(bond_tags=np.zeros((0, 2), dtype=np.int64), bond_typeid=np.zeros(0, dtype=np.uint32), bond_types=())
-        topology.update(angle_tags=gtag[g], angle_typeid=cfg.get("angle_typeid", np.zeros(g.shape[0], dtype=np.uint32)),
-                        angle_types=cfg.get("angle_types", ("A-A-A",)))
-    if cfg.get("dihedrals") is not None and len(cfg["dihedrals"]):
-        gtag = np.asarray(cfg["tag"], dtype=np.int64) if "tag" in cfg else np.arange(xyz.shape[0], dtype=np.int64)
-        g = np.asarray(cfg["dihedrals"], dtype=np.int64).reshape(-1, 4)
-        if topology is None:
-            topology = dict(bond_tags=np.zeros((0, 2), dtype=np.int64), bond_typeid=np.zeros(0, dtype=np.uint32), bond_types=())
-        topology.update(dihedral_tags=gtag[g], dihedral_typeid=cfg.get("dihedral_typeid", np.zeros(g.shape[0], dtype=np.uint32)),
-                        dihedral_types=cfg.get("dihedral_types", ("A-A-A-A",)))
-    return rank_simulation_from_snapshot(snap, xyz.shape[0], decomp, rank, device, seed=seed, topology=topology)
+    # the topology by tag, replicated (tags = indices of the global configuration unless cfg carries its own); with
+    # angles or dihedrals and no bonds it carries an empty bond list
+    gtag = np.asarray(cfg["tag"], dtype=np.int64) if "tag" in cfg else np.arange(xyz.shape[0], dtype=np.int64)
+    topology = {}
+    for kind in KINDS:
+        if cfg.get(kind + "s") is not None and len(cfg[kind + "s"]):
+            g = np.asarray(cfg[kind + "s"], dtype=np.int64).reshape(-1, ARITY[kind])
+            topology.update(_topology_of(kind, gtag[g], cfg.get(kind + "_typeid", np.zeros(g.shape[0], dtype=np.uint32)),
+                                         cfg.get(kind + "_types", ("-".join("A" * ARITY[kind]),))))
+    if topology and "bond_tags" not in topology:
+        topology.update(_topology_of("bond", np.zeros((0, 2), dtype=np.int64), np.zeros(0, dtype=np.uint32), ()))
+    return rank_simulation_from_snapshot(snap, xyz.shape[0], decomp, rank, device, seed=seed, topology=topology or None)
 
 
 def rank_simulation_from_snapshot(snap, n_global, decomp, rank, device, seed=1, topology=None):
@@ -343,20 +337,13 @@ def rank_simulation_from_snapshot(snap, n_global, decomp, rank, device, seed=1, 
     arrays = dict(pos=st.pos, vel=st.vel, orientation=st.orientation, tag=st.tag, image=st.image, angmom=st.angmom, inertia=st.inertia)
     dom = DeviceDomain(decomp, rank, arrays, density=n_global / float(np.prod(decomp.L)))
     dom.rebuild()
-    has_bonds = topology is not None and len(topology["bond_tags"]) > 0
-    has_angles = topology is not None and len(topology.get("angle_tags", ())) > 0
-    has_dihedrals = topology is not None and len(topology.get("dihedral_tags", ())) > 0
-    if has_bonds or has_angles or has_dihedrals:
+    present = [kind for kind in KINDS if topology is not None and len(topology.get(kind + "_tags", ())) > 0]
+    if present:
         st.N, st.n_ghost = dom.N_local, dom.n_ghost
         for n in dom.names:
             setattr(st, n, dom.arrays[n])
-    if has_bonds:
-        st.set_global_bonds(np.asarray(topology["bond_tags"], dtype=np.int64), topology["bond_typeid"], topology["bond_types"])
-    if has_angles:
-        st.set_global_angles(np.asarray(topology["angle_tags"], dtype=np.int64), topology["angle_typeid"], topology["angle_types"])
-    if has_dihedrals:
-        st.set_global_dihedrals(np.asarray(topology["dihedral_tags"], dtype=np.int64), topology["dihedral_typeid"],
-                                topology["dihedral_types"])
+    for kind in present:
+        st.set_global(kind, topology[kind + "_tags"], topology[kind + "_typeid"], topology[kind + "_types"])
     sim.attach_domain(dom)
     return sim, dom
 

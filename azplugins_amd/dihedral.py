@@ -26,71 +26,16 @@ import math
 import numpy as np
 
 from . import _lib
-from .force import Force, TypeParameter
+from .bonded import BondedForce
+from .force import TypeParameter
 
 
-class Dihedral(Force):
-    """Reduced ``hoomd.md.dihedral.Dihedral``: per-dihedral-type ``params``. ``block_size``: 0 (256) or 64, 128, 256."""
+class Dihedral(BondedForce):
+    """Reduced ``hoomd.md.dihedral.Dihedral``: per-dihedral-type ``params``. ``block_size``: 0 (256) or 64, 128, 256.
+    One type's parameter row is 32 bytes, handled as four float64 words."""
 
-    _entry = None
-    _schema = None
-    _parameter = TypeParameter
-
-    def __init__(self):
-        super().__init__()
-        self.params = self._parameter("params", self._schema, 1, self._mark_dirty)
-        self._tables = None
-        self.block_size = 0
-
-    def _mark_dirty(self):
-        self._tables = None
-
-    def _attach(self, sim):
-        super()._attach(sim)
-        self._tables = None
-
-    def _pack(self, d):
-        """One type's dict folded into its 32-byte parameter row by libazp (returned as four float64 words)."""
-        raise NotImplementedError
-
-    def _unpack(self, raw):
-        raise NotImplementedError
-
-    def _build_tables(self):
-        import torch
-
-        types = self._state.dihedral_types
-        raw = np.zeros((max(len(types), 1), 4))
-        for i, t in enumerate(types):
-            d = self.params.get_raw(t)
-            if d is None:
-                raise _lib.AzpError("%s.params[%r] is not set" % (type(self).__name__, t))
-            raw[i] = self._pack(d)
-        self._tables = torch.from_numpy(raw).to(self._state.device)
-
-    def compute(self, timestep=None):
-        self._require()
-        st = self._state
-        self._ensure_buffers()
-        if self._tables is None or self._tables.shape[0] != max(len(st.dihedral_types), 1):
-            self._build_tables()
-        tab = st.dihedral_table()
-        a = _lib.DihedralArgs()
-        a.d_force = self._force.data_ptr()
-        a.d_virial = self._virial.data_ptr()
-        a.virial_pitch = st.N
-        a.N = st.N
-        a.n_max = st.n_max
-        a.d_pos = st.pos.data_ptr()
-        a.box = st.box.to_c()
-        a.d_gpu_dihedrallist = tab["table"].data_ptr()
-        a.d_gpu_n_dihedrals = tab["n_dihedrals"].data_ptr()
-        a.pitch = tab["pitch"]
-        a.n_dihedral_types = max(len(st.dihedral_types), 1)
-        a.compute_virial = 1 if self.compute_virial else 0
-        a.block_size = self.block_size
-        _lib.check(getattr(_lib.lib(), self._entry)(C.byref(a), self._tables.data_ptr(), _lib.raw_stream(st.device)),
-                   self._entry)
+    _kind = "dihedral"
+    _param_doubles = 4
 
 
 class _PeriodicParameter(TypeParameter):

@@ -357,11 +357,8 @@ class DeviceDomain:
             setattr(state, n, self.arrays[n])
         # (Simulation.attach_domain insists on every array the integrator and the forces use being in self.names:
         # an array that does not migrate would keep its old size and order)
-        if getattr(state, "bond_tags", None) is not None:
-            state.relocalize_bonds()  # bond table and exclusions by local index: every index changed
-        if getattr(state, "angle_tags", None) is not None:
-            state.relocalize_angles()
-        if getattr(state, "dihedral_tags", None) is not None:
-            state.relocalize_dihedrals()
+        for kind, g in getattr(state, "groups", {}).items():
+            if g.tags is not None:
+                state.relocalize(kind)  # tables and exclusions by local index: every index changed
         state.position_generation += 1
         state.order_generation += 1  # every index changed: the list must be rebuilt

@@ -230,15 +230,11 @@ class Simulation:
         any rank's distance check asks for a neighbor-list rebuild, all ranks migrate their
         particles and re-select their ghosts first (HOOMD: Communicator::migrateParticles /
         exchangeGhosts ahead of NeighborList::compute)."""
-        if self.state.n_bonds and self.state.bond_tags is None:
-            raise _lib.AzpError("attach_domain: a bonded system needs its topology by tag (State.set_global_bonds) -- the "
-                                "index-based bond table of a single-domain state does not survive a migration")
-        if self.state.n_angles and self.state.angle_tags is None:
-            raise _lib.AzpError("attach_domain: a system with angles needs its topology by tag (State.set_global_angles) -- "
-                                "the index-based angle table of a single-domain state does not survive a migration")
-        if self.state.n_dihedrals and self.state.dihedral_tags is None:
-            raise _lib.AzpError("attach_domain: a system with dihedrals needs its topology by tag (State.set_global_dihedrals) -- "
-                                "the index-based dihedral table of a single-domain state does not survive a migration")
+        for kind, g in self.state.groups.items():
+            if g.n and g.tags is None:
+                raise _lib.AzpError("attach_domain: a %s needs its topology by tag (State.set_global_%ss) -- the index-based "
+                                    "%s table of a single-domain state does not survive a migration"
+                                    % ("bonded system" if kind == "bond" else "system with %ss" % kind, kind, kind))
         # every per-particle array that the integrator or a force touches must migrate with the particles
         # (an array left behind keeps its old size and order while N changes under it)
         need = ["pos", "vel", "tag", "image"]

@@ -65,19 +65,12 @@ class ParticleSorter:
         for name in names:
             a = getattr(st, name)
             a[:N] = a[:N].index_select(0, order)
-        if st.n_bonds or st.n_angles or st.n_dihedrals:
+        if any(g.n for g in st.groups.values()):
             inv = torch.empty(N, dtype=torch.int64, device=st.device)
             inv[order] = torch.arange(N, dtype=torch.int64, device=st.device)
-        if st.n_bonds:
-            # (the 10^6-entry lookup on the device, and the result stays there: State.bond_group fetches it when asked)
-            st.set_bond_group_device(inv[st.bond_group_device()])
-            st._bond_table = None
-        if st.n_angles:
-            st.set_angle_group_device(inv[st.angle_group_device()])
-            st._angle_table = None
-        if st.n_dihedrals:
-            st.set_dihedral_group_device(inv[st.dihedral_group_device()])
-            st._dihedral_table = None
+            for g in st.groups.values():
+                # (the 10^6-entry lookup on the device, and the result stays there: State.bond_group fetches it when asked)
+                g.reindex(inv)
         st.position_generation += 1
         st.order_generation += 1
         self.num_sorts += 1
