@@ -507,6 +507,9 @@ SYMBOLS = {
     "azp_pair_plan_tile_stage": (C.c_int, [_VP, C.POINTER(C.c_uint32), C.c_uint32]),
     "azp_pair_plan_query": (C.c_int, [_VP, C.POINTER(PlanInfo)]),
     "azp_pair_plan_phase_chunks": (C.c_int, [_VP, C.POINTER(C.c_float)]),
+    "azp_pair_plan_shells": (C.c_uint32, []),
+    "azp_pair_plan_shells_for": (C.c_uint32, [_D, C.c_int, _D]),
+    "azp_pair_plan_row_batches": (C.c_int, [_VP, C.POINTER(C.c_uint32), C.c_uint32, _PD]),
     "azp_sum_forces": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), _VP, _VP]),
     "azp_pair_auto_plan_get_stats": (None, [C.POINTER(AutoPlanStats)]),
     "azp_pair_auto_plan_clear": (None, []),
@@ -704,6 +707,19 @@ class PairPlan:
         out = (C.c_float * 3)()
         check(lib().azp_pair_plan_phase_chunks(self._h, out), "azp_pair_plan_phase_chunks")
         return [float(x) for x in out]
+
+    def row_batches(self):
+        """Row ends of the last build: (counts, shell width). counts[slice, 0] batches of 4 entries per lane covering
+        the in-range entries, counts[slice, 1 + s] up to the end of buffer shell s; the last column is the whole row."""
+        import numpy as np
+
+        cols = int(lib().azp_pair_plan_shells()) + 1
+        out = np.zeros(max(4 * self.info()["n_tiles"], 1) * cols, dtype=np.uint32)
+        w = C.c_double(0.0)
+        m = lib().azp_pair_plan_row_batches(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(w))
+        if m < 0:
+            check(m, "azp_pair_plan_row_batches")
+        return out[:m].reshape(-1, cols), w.value
 
     @property
     def handle(self):

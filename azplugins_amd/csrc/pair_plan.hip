@@ -8,10 +8,11 @@
 //           set exceeds PLAN_MAX_STAGE particles -- e.g. unsorted particle order --
 //           invalidates the plan); the staged positions are loaded into LDS; every
 //           row entry is translated (hash lookup) to a u16 byte offset, classified
-//           core / near / buffer shell 0 .. PLAN_SHELLS - 1, placed bank-aware inside
+//           core / sure / near / buffer shell class 0 .. PLAN_SHELL_CLASSES - 1, placed bank-aware inside
 //           its class, and the row is written as 16-byte chunks in the force
-//           kernel's own lane order; per slice the chunk counts up to the end of the
-//           in-range entries and of every shell are kept for the displacement bound.
+//           kernel's own lane order; per slice the batch counts (4 entries per lane: half a
+//           chunk) up to the end of the in-range entries and of every shell are kept
+//           for the displacement bound.
 // The host-side scan makes plan build a sync point, like HOOMD's own
 // neighbor-list overflow check.
 #include <algorithm>
@@ -30,7 +31,7 @@ struct PlanKArgs
     const uint64_t* head_list;
     const double* rcutsq;
     const double* rinnersq; // optional (may be null): "core" class radius^2 per type pair
-    uint32_t* slice_Kend;   // PLAN_SHELLS + 1 per slice, zeroed before the build kernel
+    uint32_t* slice_Kend;   // PLAN_SHELLS + 1 per slice, in batches of 4 entries per lane; zeroed before the build kernel
     uint32_t* slice_Kphase; // [2][n_slices]: core chunks (zeroed before the build kernel), sure chunks (set to ~0 before it);
                             // diagnostic, no kernel consumes the phase counts
     uint32_t n_slices;
@@ -354,7 +355,7 @@ __global__ void __launch_bounds__(PLAN_BUILD_THREADS) plan_build_kernel(const Pl
         const uint32_t iters = (n + 63u) >> 6;
         // pass A: translate + classify. Classes: 0 core (inside the evaluator's inner
         // radius hint, e.g. the WCA core of PerturbedLJ), 1 near (inside the cutoff
-        // now), 2 + s: buffer shell s (r_cut + s w <= r, s < PLAN_SHELLS). Rows are
+        // now), 3 + s: buffer shell s (r_cut + s w <= r; the shells from PLAN_SHELL_CLASSES - 1 on share the last class). Rows are
         // written core | near | shell 0 | shell 1 | ... The core / near split is an
         // ordering hint; the near / shell splits let the force kernel stop early when
         // the caller bounds the displacement since this build, so they must be
@@ -404,7 +405,7 @@ __global__ void __launch_bounds__(PLAN_BUILD_THREADS) plan_build_kernel(const Pl
                         // r is shortened by 5e-5 (its own error is < 1e-5) before it is binned
                         const float rc = rc_cached ? s_rcut[tp] : sqrtf(fmaxf(rcsq, 0.f));
                         const float sh = floorf((sqrtf(rsq) * 0.99995f - rc) * shell_winv);
-                        cls = PLAN_CLS_SHELL0 + (uint32_t)fminf(fmaxf(sh, 0.f), (float)(PLAN_SHELLS - 1)); // NaN (w = 0) -> shell 0
+                        cls = PLAN_CLS_SHELL0 + (uint32_t)fminf(fmaxf(sh, 0.f), (float)(PLAN_SHELL_CLASSES - 1)); // NaN (w = 0) -> shell 0
                         }
                     enc[it] = (((sidx + 1u) * 8u) << 4) | cls;
                     }
@@ -420,11 +421,11 @@ __global__ void __launch_bounds__(PLAN_BUILD_THREADS) plan_build_kernel(const Pl
             seg[cidx + 1] = seg[cidx] + cnt_cls[cidx];
         if (lane == 0 && p < count)
             {
-            // chunks a force-kernel wave must process to cover every in-range entry [0] / every
-            // entry up to the end of shell s [1 + s], over the rows of its slice
+            // batches (half chunks) a force-kernel wave must process to cover every in-range entry [0] /
+            // every entry up to the end of shell s [1 + s], over the rows of its slice
 #pragma unroll
             for (uint32_t sh = 0; sh <= PLAN_SHELLS; ++sh)
-                atomicMax(&a.slice_Kend[(PLAN_SHELLS + 1) * slice + sh], (seg[PLAN_CLS_SHELL0 + sh] + 8u * TPP - 1u) / (8u * TPP));
+                atomicMax(&a.slice_Kend[(PLAN_SHELLS + 1) * slice + sh], plan_row_batches(seg[PLAN_CLS_SHELL0 + (sh < PLAN_SHELL_CLASSES ? sh : PLAN_SHELL_CLASSES)], TPP));
             // ordering class and diagnostic (no kernel consumes the phase counts): chunks that cover the core entries,
             // chunks made of core / sure entries alone
             atomicMax(&a.slice_Kphase[slice], (seg[PLAN_CLS_SURE] + 8u * TPP - 1u) / (8u * TPP));
@@ -599,7 +600,7 @@ template<int TPP, uint32_t HC> static hipError_t launch_plan_build(const PlanKAr
     {
     const size_t lds = plan_lds_bytes(HC, k.stage_stride);
     auto kern = plan_build_kernel<TPP, HC>;
-    if (lds + 16 * 1024 > 64 * 1024) // + the kernel's static LDS (bank counters, hole lists: ~14.5 KiB)
+    if (lds + 18 * 1024 > 64 * 1024) // + the kernel's static LDS (bank counters of 16 row classes, hole lists: 17.3 KiB)
         {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -893,4 +894,33 @@ extern "C" int azp_pair_plan_phase_chunks(const azp_pair_plan* plan, float out[3
     out[1] = (float)(s1 / p->n_slices);
     out[2] = (float)(s2 / p->n_slices);
     return AZP_SUCCESS;
+    }
+
+extern "C" uint32_t azp_pair_plan_shells(void)
+    {
+    return azp::PLAN_SHELLS;
+    }
+
+extern "C" uint32_t azp_pair_plan_shells_for(double shell_width, int has_bound, double bound)
+    {
+    return azp::plan_shells_for_width(shell_width, has_bound != 0, bound);
+    }
+
+extern "C" int azp_pair_plan_row_batches(const azp_pair_plan* plan, uint32_t* out, uint32_t n, double* shell_width)
+    {
+    if (!plan || (!out && n))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    const azp::PairPlan* p = reinterpret_cast<const azp::PairPlan*>(plan);
+    if (shell_width)
+        *shell_width = p->shell_width;
+    if (!p->valid || !p->d_slice_Kend)
+        return 0;
+    const size_t have = (azp::PLAN_SHELLS + 1) * (size_t)p->n_slices;
+    const uint32_t m = (uint32_t)std::min<size_t>(n, have);
+    if (m)
+        {
+        if (hipMemcpy(out, p->d_slice_Kend, sizeof(uint32_t) * m, hipMemcpyDeviceToHost) != hipSuccess)
+            return AZP_ERROR_INVALID_ARGUMENT;
+        }
+    return (int)m;
     }

@@ -38,15 +38,34 @@ constexpr uint32_t PLAN_BITMAP_WORDS = 80;    // 2560 slots / 32
 constexpr uint32_t PLAN_ROWBUF = 512;         // compiled entries per row the builder can hold (rows longer than
                                               // this invalidate the plan)
 constexpr double PLAN_FAR = 1.0e30;          // coordinate of the dummy slot
-constexpr uint32_t PLAN_SHELLS = 8;          // the Verlet-buffer entries of every row are ordered into this many shells
-                                              // of equal width by their separation when the plan is built
-constexpr uint32_t PLAN_CLASSES = PLAN_SHELLS + 3; // row order: core | sure | near | shell 0 | ... | shell PLAN_SHELLS - 1
-                                                   // (the order fixes the summation order, hence the bits of every force)
+// The one constant the shell tables derive from (the plan compilers, plan_shells_for, tile_shells_for, the TileDyn clamp,
+// the list check of pair_auto.hip, azp_pair_plan_shells): the Verlet buffer is cut into this many shells of equal width
+// w = r_buff / PLAN_SHELLS by the separation when the plan is built.
+constexpr uint32_t PLAN_SHELLS = 16;
+// Shell classes a row is ordered by: shells 0 .. PLAN_SHELL_CLASSES - 2 each have their own, the last class holds every
+// shell from PLAN_SHELL_CLASSES - 1 on (a shell is a lower bound on the separation: filing an entry lower is
+// conservative). 13 + core, sure, near = 16 row classes: the 4 bits both compilers have for the class of an entry (and
+// the LDS the cell compiler has for its per-class counters, pair_plan_cells.hip). A launch that needs more than
+// PLAN_SHELL_CLASSES - 1 shells walks whole rows; an MD cycle gets there in its last step or two before the rebuild.
+constexpr uint32_t PLAN_SHELL_CLASSES = 13;
+constexpr uint32_t PLAN_CLASSES = PLAN_SHELL_CLASSES + 3; // row order: core | sure | near | shell class 0 | ... | PLAN_SHELL_CLASSES - 1
+                                                          // (the order fixes the summation order, hence the bits of every force)
+static_assert(PLAN_CLASSES <= 16 && PLAN_SHELL_CLASSES <= PLAN_SHELLS, "an entry's class is kept in 4 bits");
 constexpr uint32_t PLAN_CLS_CORE = 0;  // closer than the evaluator's inner radius hint (azp_pair_args.d_rinnersq) at build time
 constexpr uint32_t PLAN_CLS_SURE = 1;  // certainly closer than r_cut - r_buff at build time (one particle type only): such a pair
                                        // stays inside the cutoff while no particle has moved farther than r_buff / 2
 constexpr uint32_t PLAN_CLS_NEAR = 2;  // inside the cutoff at build time, or too close to call
-constexpr uint32_t PLAN_CLS_SHELL0 = 3; // + s: certainly >= r_cut + s w away at build time
+constexpr uint32_t PLAN_CLS_SHELL0 = 3; // + s: certainly >= r_cut + s w away at build time (s < PLAN_SHELL_CLASSES)
+
+// Row ends are counted in batches of 4 entries per lane (half a 16-byte chunk: what the tile kernel gathers and
+// evaluates at a time), not in whole chunks. Batches a wave has to walk to cover the first n entries of a row that
+// tpp lanes share: entry q sits in chunk q / 8 of the row, chunk c in iteration c / tpp, and only the first lane's
+// first half counts as a half iteration. One lane per particle: ceil(n / 4).
+__host__ __device__ inline uint32_t plan_row_batches(uint32_t n, uint32_t tpp)
+    {
+    const uint32_t per = 8u * tpp, r = n % per;
+    return 2u * (n / per) + (r == 0u ? 0u : (r <= 4u ? 1u : 2u));
+    }
 
 struct PairPlan
     {
@@ -69,9 +88,9 @@ struct PairPlan
     uint32_t* d_tile_nstage = nullptr;     // n_tiles
     uint64_t* d_tile_head = nullptr;       // n_tiles
     uint32_t* d_stage_idx = nullptr;       // total_stage
-    uint32_t* d_slice_K = nullptr;         // n_slices
-    uint32_t* d_slice_Kend = nullptr;      // (PLAN_SHELLS + 1) x n_slices: chunks up to the end of the in-range entries [0] /
-                                           // of buffer shell s [1 + s]
+    uint32_t* d_slice_K = nullptr;         // n_slices: chunks of the slice's rectangle (layout of d_cnl; no force kernel reads it)
+    uint32_t* d_slice_Kend = nullptr;      // (PLAN_SHELLS + 1) x n_slices: batches of 4 entries (plan_row_batches) up to the end of
+                                           // the in-range entries [0] / of buffer shell s [1 + s]; [PLAN_SHELLS] = whole rows
     uint32_t* d_slice_Kphase = nullptr;    // [2][n_slices]: chunks covering every entry of class core [0][slice]; chunks up to which
                                            // every row of the slice holds only entries of the classes core and sure [1][slice].
                                            // Ordering class and diagnostic (azp_pair_plan_phase_chunks); no kernel consumes the
@@ -114,16 +133,21 @@ struct PairPlan
 // Buffer shells a launch has to walk, from the caller's displacement bound: an entry of
 // shell s was at least r_cut + s w away when the plan was built, so it cannot be in range
 // while 2 x bound <= s w. Exact, not a heuristic.
+inline uint32_t plan_shells_for_width(double shell_width, bool has_bound, double bound)
+    {
+    if (!has_bound || !(bound >= 0.0))
+        return PLAN_SHELLS; // unknown: whole rows
+    if (bound == 0.0)
+        return 0;
+    if (!(shell_width > 0.0))
+        return PLAN_SHELLS;
+    const double n = std::ceil(2.0 * bound * (1.0 + 1e-12) / shell_width);
+    return n >= (double)PLAN_SHELLS ? PLAN_SHELLS : (uint32_t)n;
+    }
+
 inline uint32_t plan_shells_for(const PairPlan& plan, const azp_pair_args& args)
     {
-    if (!args.has_displacement_bound || !(args.displacement_bound >= 0.0))
-        return PLAN_SHELLS; // unknown: whole rows
-    if (args.displacement_bound == 0.0)
-        return 0;
-    if (!(plan.shell_width > 0.0))
-        return PLAN_SHELLS;
-    const double n = std::ceil(2.0 * args.displacement_bound * (1.0 + 1e-12) / plan.shell_width);
-    return n >= (double)PLAN_SHELLS ? PLAN_SHELLS : (uint32_t)n;
+    return plan_shells_for_width(plan.shell_width, args.has_displacement_bound != 0, args.displacement_bound);
     }
 
 int plan_build(PairPlan& p, const azp_pair_args& args, hipStream_t s); // pair_plan.hip

@@ -22,7 +22,7 @@
 //      of the force kernel; the stage list is written;
 //   4. every thread turns its raw row into the force kernel's compiled row: entries ordered
 //      class by class (a running cursor per class, seeded with the class totals of phase 2),
-//      slot byte offsets, 16-byte chunks in the kernel's lane order, chunk counts per class
+//      slot byte offsets, 16-byte chunks in the kernel's lane order, batch counts (half chunks) per class
 //      boundary for the displacement bound.
 //
 // No hash set of particles, no sort, no u32 rows, no host scan (slices have a fixed chunk
@@ -168,6 +168,13 @@ __device__ __forceinline__ uint32_t pair_class(float rsq, float rcsq_m, float ri
     return !(rsq >= rcsq_m) ? ((rsq < rin) ? PLAN_CLS_CORE : PLAN_CLS_NEAR) : shell;
     }
 
+// Per-thread class counters / cursors: a row holds at most PC_ROWMAX = 512 entries, so 10 bits each, three to a word
+// (16 classes in 6 words per thread; 16-bit counters would cost the kernel its fourth workgroup per CU).
+constexpr uint32_t PC_CUR_WORDS = (PLAN_CLASSES + 2) / 3;
+static_assert(PLAN_CLASSES <= 32, "cur_word divides by 3 with a multiply that is exact below 32");
+__device__ __forceinline__ uint32_t cur_word(uint32_t cls) { return (cls * 11u) >> 5; } // cls / 3
+__device__ __forceinline__ uint32_t cur_shift(uint32_t cls) { return 10u * (cls - 3u * cur_word(cls)); }
+
 // SINGLE: one particle type (cutoffs are constants, classes come from a table). HALF: cells of half the list radius
 // (local grid, per-member runs); else cells of the full list radius (27 cells around each member cell).
 template<bool SINGLE, bool HALF>
@@ -181,7 +188,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
     constexpr uint32_t BATCH = HALF ? PC_BATCH_H : PC_BATCH;
     constexpr uint32_t CSTRIDE = BATCH + 4;                  // pad entries: candidates are read two / four at a time
     constexpr uint32_t CAND_BYTES = (CSTRIDE * 16 + BATCH + 32 + 15) / 16 * 16; // x | y | z | particle index | types
-    constexpr uint32_t CUR_BYTES = PLAN_CLASSES * PC_THREADS * 2;
+    constexpr uint32_t CUR_BYTES = PC_CUR_WORDS * PC_THREADS * 4;
     constexpr uint32_t RUNG_OFF = CAND_BYTES;                                  // HALF: u16 [run][thread], first candidate
     constexpr uint32_t RUNL_OFF = RUNG_OFF + PC_RUNS_H * PC_THREADS * 2;       // HALF: u8 [run][thread], candidates in the run
     constexpr uint32_t PRE_OFF = RUNL_OFF + PC_RUNS_H * PC_THREADS;            // HALF: u16 [PC_MAXGRID + 1] candidates before each cell
@@ -189,7 +196,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
     constexpr uint32_t USED_OFF = CUR_OFF + CUR_BYTES;                         // HALF: bitmap, word bases, sort keys of balanced plans
     constexpr uint32_t WBASE_OFF = USED_OFF + PC_MAXCAND / 8;
     constexpr uint32_t KEY_OFF = WBASE_OFF + (PC_MAXCAND / 32 + 4) * 4;
-    constexpr uint32_t REGION = HALF ? PRE_OFF + (PC_MAXGRID + 8) * 2 : CUR_OFF + CUR_BYTES; // 22,592 (full) / 36,448 (half)
+    constexpr uint32_t REGION = HALF ? PRE_OFF + (PC_MAXGRID + 8) * 2 : CUR_OFF + CUR_BYTES; // 23,104 (full) / 36,448 (half)
     static_assert(HALF || CAND_BYTES >= 2 * PC_MAXCAND, "slot table does not fit");
     static_assert(HALF || CAND_BYTES >= (PC_SETA + PC_SETB + PC_MAXCELLS) * 4, "hash sets do not fit");
     static_assert(!HALF || KEY_OFF + PC_THREADS * 4 <= PRE_OFF, "half-width cells: the late tables overlap the grid prefix");
@@ -204,7 +211,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
     uint32_t* setB = setA + PC_SETA;
     uint32_t* s_tmp = setB + PC_SETB;
     uint16_t* s_slot = reinterpret_cast<uint16_t*>(s_region);
-    uint16_t* s_cur = reinterpret_cast<uint16_t*>(s_region + CUR_OFF); // [class][thread]
+    uint32_t* s_cur = reinterpret_cast<uint32_t*>(s_region + CUR_OFF); // [word][thread]: three 10-bit class counters per word
     __shared__ uint32_t s_used_f[HALF ? 1 : PC_MAXCAND / 32];
     __shared__ uint32_t s_wordbase_f[HALF ? 1 : PC_MAXCAND / 32 + 1];
     uint32_t* s_used = HALF ? reinterpret_cast<uint32_t*>(s_region + USED_OFF) : s_used_f;
@@ -604,11 +611,21 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
             }
         return;
         }
-    // a raw entry: candidate number | class. 4 bits of class (core, sure, near, 8 shells) when 12 bits hold the
-    // candidate number; else 3 (shells 4 .. 7 are filed under 4 -- conservative, a shell is a lower bound)
+    // a raw entry: candidate number | class. 4 bits of class (the PLAN_CLASSES row classes) when 12 bits hold the
+    // candidate number; else 3: core, sure, near and five shell classes of twice the width, the last one open-ended
+    // (stored 3 + j = row class 3 + 2 j -- conservative, a shell is a lower bound)
     const uint32_t cbits = (NC <= 4096u) ? 4u : 3u;
     const uint32_t cmask = (1u << cbits) - 1u;
-    const float fmax_shell = (cbits == 4u) ? (float)(PLAN_SHELLS - 1u) : 4.f;
+    const uint32_t csh = (cbits == 4u) ? 0u : 1u;
+    const float cscale = csh ? 0.5f : 1.f; // (exact: floor((r rscale - rcw) / 2))
+    const float fmax_shell = csh ? 4.f : (float)(PLAN_SHELL_CLASSES - 1u);
+    const float rscale_c = rscale * cscale;
+    static_assert(PLAN_CLS_SHELL0 + 2u * 4u < PLAN_CLASSES, "the double-width shell classes are row classes too");
+    auto row_class = [&](uint32_t e) -> uint32_t
+        {
+        const uint32_t c = e & cmask;
+        return c <= PLAN_CLS_SHELL0 ? c : PLAN_CLS_SHELL0 + ((c - PLAN_CLS_SHELL0) << csh);
+        };
     // Acceptance test in single precision: r^2 <= r_list^2 (1 + 1e-5) + e, where e bounds what rounding the
     // staged coordinates (|coordinate| <= cmax: the members' extent + two cells) to FP32 can do to r^2:
     // 2 sqrt(3) r cmax 2^-23 = 4.2e-7 r cmax; taken as 1e-6 r_list cmax. A superset of the exact list, never less.
@@ -707,8 +724,8 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
         {
         // r^2 -> class, at the lower edge of each bin (classes grow with r: never too high a class)
         const float rcsq_m = (float)a.rcutsq[0] * 1.0001f, rin = a.rinnersq ? (float)a.rinnersq[0] : 0.f;
-        const float rcw = sqrtf(fmaxf((float)a.rcutsq[0], 0.f)) * shell_winv;
-        // class sure: certainly closer than r_cut - r_buff (r_buff = PLAN_SHELLS shell widths): the UPPER edge of the bin has
+        const float rcw = sqrtf(fmaxf((float)a.rcutsq[0], 0.f)) * shell_winv * cscale;
+        // class sure: certainly closer than r_cut - r_buff (r_buff = PLAN_SHELLS shell widths of the full resolution): the UPPER edge of the bin has
         // to clear the radius, which itself is taken 2e-4 short (the single-precision separation is good to ~2e-6)
         const float r_sure = (shell_w > 0.f) ? sqrtf(fmaxf((float)a.rcutsq[0], 0.f)) - (float)PLAN_SHELLS * shell_w - 2e-4f : 0.f;
         const float sure_sq = r_sure > 0.f ? r_sure * r_sure : 0.f;
@@ -716,7 +733,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
             {
             const float lo = (float)t * (rl1 * (1.0f / PC_CTAB)) * 0.999999f;
             const float hi = (float)(t + 1u) * (rl1 * (1.0f / PC_CTAB)) * 1.000001f;
-            uint32_t cls = pair_class(lo, rcsq_m, rin, rcw, rscale, fmax_shell);
+            uint32_t cls = pair_class(lo, rcsq_m, rin, rcw, rscale_c, fmax_shell);
             if (cls == PLAN_CLS_NEAR && hi < sure_sq)
                 cls = PLAN_CLS_SURE;
             s_ctab[t] = (unsigned char)cls;
@@ -756,7 +773,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
     // ---- phase 2: stage a batch of candidates; every thread walks its member's runs through it ----
     uint32_t cnt = 0;
     if (!HALF) // (half-width cells: the counters take the place of the run tables once the tests are done)
-        for (uint32_t t = 0; t < PLAN_CLASSES; ++t)
+        for (uint32_t t = 0; t < PC_CUR_WORDS; ++t)
             s_cur[t * PC_THREADS + tid] = 0;
     // run q of my member: candidates [first, end)
     auto fetch_run = [&](uint32_t q, uint32_t& first_c, uint32_t& end_c)
@@ -876,10 +893,10 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
                         {
                         clsa = pair_class(rsq.x, rc_cached ? s_rcutsq[tpa] : (float)a.rcutsq[tpa] * 1.0001f,
                                           rc_cached ? s_rinnersq[tpa] : (a.rinnersq ? (float)a.rinnersq[tpa] : 0.f),
-                                          rc_cached ? s_rcw[tpa] : sqrtf(fmaxf((float)a.rcutsq[tpa], 0.f)) * shell_winv, rscale, fmax_shell);
+                                          (rc_cached ? s_rcw[tpa] : sqrtf(fmaxf((float)a.rcutsq[tpa], 0.f)) * shell_winv) * cscale, rscale_c, fmax_shell);
                         clsb = pair_class(rsq.y, rc_cached ? s_rcutsq[tpb] : (float)a.rcutsq[tpb] * 1.0001f,
                                           rc_cached ? s_rinnersq[tpb] : (a.rinnersq ? (float)a.rinnersq[tpb] : 0.f),
-                                          rc_cached ? s_rcw[tpb] : sqrtf(fmaxf((float)a.rcutsq[tpb], 0.f)) * shell_winv, rscale, fmax_shell);
+                                          (rc_cached ? s_rcw[tpb] : sqrtf(fmaxf((float)a.rcutsq[tpb], 0.f)) * shell_winv) * cscale, rscale_c, fmax_shell);
                         }
                     if (acca)
                         {
@@ -966,7 +983,7 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
     if (HALF)
         {
         // (batch and run tables are done with: counters and bitmap move in)
-        for (uint32_t t = 0; t < PLAN_CLASSES; ++t)
+        for (uint32_t t = 0; t < PC_CUR_WORDS; ++t)
             s_cur[t * PC_THREADS + tid] = 0;
         for (uint32_t t = tid; t < PC_MAXCAND / 32; t += PC_THREADS)
             s_used[t] = 0;
@@ -985,7 +1002,8 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
             for (uint32_t u = 0; u < PC_WALK; ++u)
                 if (e[u] != 0xffffffffu)
                     {
-                    ++s_cur[(e[u] & cmask) * PC_THREADS + tid];
+                    const uint32_t cls = row_class(e[u]);
+                    s_cur[cur_word(cls) * PC_THREADS + tid] += 1u << cur_shift(cls);
                     const uint32_t g = e[u] >> cbits;
                     atomicOr(&s_used[g >> 5], 1u << (g & 31u));
                     }
@@ -1014,7 +1032,8 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
     if (a.perm)
         {
         uint32_t* s_key = HALF ? reinterpret_cast<uint32_t*>(s_region + KEY_OFF) : &s_runs[0][0]; // (the run table is not needed any more)
-        const uint32_t nin = member ? min((uint32_t)s_cur[tid] + (uint32_t)s_cur[PC_THREADS + tid] + (uint32_t)s_cur[2 * PC_THREADS + tid], 1023u) : 0u;
+        const uint32_t w0 = s_cur[tid]; // core | sure | near
+        const uint32_t nin = member ? min((w0 & 1023u) + ((w0 >> 10) & 1023u) + ((w0 >> 20) & 1023u), 1023u) : 0u;
         const uint32_t key = ((1023u - nin) << 8) | tid;
         s_key[tid] = key;
         __syncthreads();
@@ -1080,21 +1099,32 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
             stage[slot] = cand_particle(g);
             }
         }
-    // class totals -> first row position of each class (the cursors of phase 4); chunk counts per class boundary
+    // class totals -> first row position of each class (the cursors of phase 4); batch counts (4 entries) per class boundary
     const uint32_t n = member ? cnt : 0u;
     uint32_t before = 0;
-    for (uint32_t c = 0; c < PLAN_CLASSES; ++c)
+    for (uint32_t wd = 0; wd < PC_CUR_WORDS; ++wd)
         {
-        const uint32_t v = s_cur[c * PC_THREADS + tid];
-        s_cur[c * PC_THREADS + tid] = (uint16_t)before;
-        before += v;
-        if (c >= PLAN_CLS_NEAR && member)
-            atomicMax(&s_kend[pw][c - PLAN_CLS_NEAR], (before + 7u) / 8u); // [0]: through "near", [1 + s]: through shell s
-        if (c == PLAN_CLS_CORE && member)
-            atomicMax(&s_kcore[pw], (before + 7u) / 8u);
-        if (c == PLAN_CLS_SURE && member)
-            atomicMin(&s_ksure[pw], before / 8u);
+        const uint32_t counts = s_cur[wd * PC_THREADS + tid];
+        uint32_t cursors = 0;
+#pragma unroll
+        for (uint32_t f = 0; f < 3u; ++f)
+            {
+            const uint32_t c = 3u * wd + f;
+            cursors |= before << (10u * f); // (before <= row_cap < 1024)
+            before += (counts >> (10u * f)) & 1023u;
+            // batches of 4: [0] through "near", [1 + s] through shell s (the shells of the last class: whole rows, below)
+            if (c >= PLAN_CLS_NEAR && c - PLAN_CLS_NEAR < PLAN_SHELL_CLASSES && member)
+                atomicMax(&s_kend[pw][c - PLAN_CLS_NEAR], plan_row_batches(before, 1u));
+            if (c == PLAN_CLS_CORE && member)
+                atomicMax(&s_kcore[pw], (before + 7u) / 8u);
+            if (c == PLAN_CLS_SURE && member)
+                atomicMin(&s_ksure[pw], before / 8u);
+            }
+        s_cur[wd * PC_THREADS + tid] = cursors;
         }
+    if (member)
+        for (uint32_t sh = PLAN_SHELL_CLASSES; sh <= PLAN_SHELLS; ++sh)
+            atomicMax(&s_kend[pw][sh], plan_row_batches(before, 1u));
     __syncthreads();
 #ifdef AZP_PLAN_CELLS_PROFILE
     if ((a.stop_after & 255u) == 4u)
@@ -1119,9 +1149,10 @@ __global__ void __launch_bounds__(PC_THREADS) plan_cells_kernel(const PlanCellsK
         for (uint32_t u = 0; u < PC_WALK; ++u)
             if (e[u] != 0xffffffffu)
                 {
-                const uint32_t cls = e[u] & cmask;
-                const uint32_t posn = s_cur[cls * PC_THREADS + tid];
-                s_cur[cls * PC_THREADS + tid] = (uint16_t)(posn + 1u);
+                const uint32_t cls = row_class(e[u]);
+                const uint32_t word = s_cur[cur_word(cls) * PC_THREADS + tid];
+                const uint32_t posn = (word >> cur_shift(cls)) & 1023u;
+                s_cur[cur_word(cls) * PC_THREADS + tid] = word + (1u << cur_shift(cls));
                 *reinterpret_cast<uint16_t*>(out + (posn >> 3) * 1024u + (posn & 7u) * 2u) = (uint16_t)off[u];
                 }
         }

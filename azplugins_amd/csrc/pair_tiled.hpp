@@ -10,11 +10,13 @@
 //      neighbors three LDS gathers and the evaluator, software-pipelined in
 //      batches of 4 pairs. No global gathers, no minimum image (unless the tile
 //      is wide compared with the box), no row-length test (rows are padded with
-//      the dummy). Rows are ordered core | sure | near | buffer shell 0 .. 7
-//      (pair_plan.hpp): a batch with no pair in range is skipped after the
+//      the dummy). Rows are ordered core | sure | near | buffer shell classes
+//      (pair_plan.hpp: 16 shells, the outer ones filed together): a batch with no pair in range is skipped after the
 //      separations, and a batch with no pair in the evaluator's core uses the
 //      cheaper tail form (PerturbedLJ); both are tested on the actual
-//      separations. The row ends after the buffer shells that the displacement
+//      separations. Rows end at a batch, not at a chunk: a slice whose walked
+//      entries end in the first half of a chunk gets one final half iteration
+//      after the loop. The row ends after the buffer shells that the displacement
 //      since the plan was built can have brought into range (n_shells): from
 //      the caller's bound, from the words of the list's distance check, or per
 //      tile from per-particle displacements.
@@ -54,9 +56,9 @@ struct TiledKArgs
     const uint32_t* tile_nstage;
     const uint64_t* tile_head;
     const uint32_t* stage_idx;
-    const uint32_t* slice_K;
-    const uint32_t* slice_Kend;  // PLAN_SHELLS + 1 per slice: chunks covering the in-range entries [0] / the entries up to
-                                 // the end of buffer shell s [1 + s]
+    const uint32_t* slice_Kend;  // PLAN_SHELLS + 1 per slice: batches of 4 entries per lane (half chunks, plan_row_batches)
+                                 // covering the in-range entries [0] / the entries up to the end of buffer shell s [1 + s];
+                                 // [PLAN_SHELLS]: whole rows
     uint32_t n_shells;           // buffer shells this launch has to walk: 0 = none (positions as at plan build) ...
                                  // PLAN_SHELLS = whole rows
     const uint64_t* slice_head;
@@ -255,7 +257,10 @@ __device__ __forceinline__ void tile_compute(const TileBatch& b, const TiledKArg
 
 // Inner loop over this lane's chunks, software-pipelined at half-chunk
 // granularity: while the arithmetic of one half (4 pairs) runs, the 12 LDS gathers
-// of the next half and the index load of the next chunk are in flight. WRAP = true
+// of the next half and the index load of the next chunk are in flight. The row is
+// Kb batches (half chunks) long: Kb / 2 whole iterations, and for an odd Kb the first
+// half of one more chunk, peeled off behind the loop (its gathers are the ones the
+// last iteration -- or the prologue -- issued anyway; nothing is loaded for it). WRAP = true
 // re-applies the minimum image to every pair (tiles that are wide compared with the
 // box, triclinic boxes, or no r_list_max hint); WRAP = false trusts the staged
 // image (the common case).
@@ -263,7 +268,7 @@ template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR, bool W
 __device__ __forceinline__ void tiled_loop(const TiledKArgs& a, const char* bx, const char* bt,
                                            const typename E::Coeff* __restrict__ s_coeff,
                                            const double* __restrict__ s_ronsq, const typename E::Coeff& c0, double ronsq0,
-                                           double rcutsq_max, const char* __restrict__ slice_base, uint32_t lane_off, uint32_t K,
+                                           double rcutsq_max, const char* __restrict__ slice_base, uint32_t lane_off, uint32_t Kb,
                                            double3 pi, int typei, double& fx, double& fy, double& fz, double& pe, double (&v)[6], uint32_t& n_core,
                                            uint32_t& n_in, double (&es)[2])
     {
@@ -273,8 +278,10 @@ __device__ __forceinline__ void tiled_loop(const TiledKArgs& a, const char* bx, 
         { return *reinterpret_cast<const uint4*>(slice_base + (uint64_t)kk * 1024u + lane_off); };
     // (prefetching the chunk indices two iterations ahead instead of one costs 9 more
     // spilled registers and measures 3 % slower)
-    uint4 u = (K > 0) ? chunk_at(0) : zero4;
-    uint4 un = (K > 1) ? chunk_at(1) : u;
+    const uint32_t K = Kb >> 1;         // whole iterations
+    const uint32_t Kc = (Kb + 1u) >> 1; // chunks this lane reads (the last one only its first half when Kb is odd)
+    uint4 u = (Kc > 0) ? chunk_at(0) : zero4;
+    uint4 un = (Kc > 1) ? chunk_at(1) : u;
     TileBatch A, B;
     tile_gather<CAP, 0>(A, u, bx);
     for (uint32_t kk = 0; kk < K; ++kk)
@@ -283,18 +290,20 @@ __device__ __forceinline__ void tiled_loop(const TiledKArgs& a, const char* bx, 
         // does not always cover an HBM round trip); past the end the last chunk is
         // reloaded (an unconditional 16-byte load: a predicated one is split into
         // four 4-byte loads)
-        const uint4 un2 = chunk_at((kk + 2 < K) ? kk + 2 : K - 1);
+        const uint4 un2 = chunk_at((kk + 2 < Kc) ? kk + 2 : Kc - 1);
         tile_gather<CAP, 1>(B, u, bx);
         __builtin_amdgcn_sched_barrier(0);
         tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP>(A, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
         __builtin_amdgcn_sched_barrier(0);
-        tile_gather<CAP, 0>(A, un, bx); // when kk + 1 == K: gathered, never used
+        tile_gather<CAP, 0>(A, un, bx); // when kk + 1 == Kc: gathered, never used
         __builtin_amdgcn_sched_barrier(0);
         tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP>(B, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
         __builtin_amdgcn_sched_barrier(0);
         u = un;
         un = un2;
         }
+    if (Kb & 1u) // A holds the first half of chunk K
+        tile_compute<E, CAP, VIRIAL, SINGLE, XPLOR, WRAP>(A, a, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
     }
 
 template<class E, int TPP, int CAP, bool VIRIAL, bool SINGLE, bool XPLOR>
@@ -501,10 +510,10 @@ __global__ void __launch_bounds__(256, E::kTileWaves) pair_forces_tiled_kernel(c
         }
 
     const uint32_t slice = tile * 4 + wave;
-    // scalar trip count (the loop counter and the chunk address stay in SGPRs). With a
-    // displacement bound from the caller the row ends early: entries that were at
+    // scalar trip count, in batches of 4 pairs (the loop counter and the chunk address stay in SGPRs).
+    // With a displacement bound from the caller the row ends early: entries that were at
     // least 2 x bound outside the cutoff when the plan was built cannot be in range.
-    const uint32_t K = to_uniform(n_shells >= PLAN_SHELLS ? a.slice_K[slice] : a.slice_Kend[(PLAN_SHELLS + 1) * slice + n_shells]);
+    const uint32_t Kb = to_uniform(a.slice_Kend[(PLAN_SHELLS + 1) * slice + min(n_shells, PLAN_SHELLS)]);
     // wave-uniform slice base (SGPRs) + lane: the loads use scalar-base addressing
     const uint64_t slice_head = to_uniform(a.slice_head[slice]);
     const char* __restrict__ slice_base = reinterpret_cast<const char*>(a.cnl + slice_head * 64ull);
@@ -517,10 +526,10 @@ __global__ void __launch_bounds__(256, E::kTileWaves) pair_forces_tiled_kernel(c
     const char* bx = reinterpret_cast<const char*>(s_x);
     const char* bt = reinterpret_cast<const char*>(s_t);
     if (wide)
-        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, true>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, K, pi,
+        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, true>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, Kb, pi,
                                                             typei, fx, fy, fz, pe, v, n_core, n_in, es);
     else
-        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, false>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, K, pi,
+        tiled_loop<E, TPP, CAP, VIRIAL, SINGLE, XPLOR, false>(a, bx, bt, s_coeff, s_ronsq, c0, ronsq0, rcutsq_max, slice_base, lane_off, Kb, pi,
                                                              typei, fx, fy, fz, pe, v, n_core, n_in, es);
     if constexpr (SINGLE && !XPLOR && E::kSplitEnergy)
         pe = E::finish_split(c0, pe, es[0], es[1], n_core, n_in);
@@ -570,7 +579,6 @@ inline TiledKArgs make_tiled_kargs(const PairPlan& plan, const azp_pair_args& ar
     k.tile_head = plan.d_tile_head;
     k.stage_idx = plan.d_stage_idx;
     k.perm = plan.balanced ? plan.d_perm : nullptr;
-    k.slice_K = plan.d_slice_K;
     k.slice_Kend = plan.d_slice_Kend;
     k.n_shells = plan_shells_for(plan, args);
     fill_local_bound(k, plan, args);

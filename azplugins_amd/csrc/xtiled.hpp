@@ -175,7 +175,8 @@ __global__ void __launch_bounds__(256, X::kMinWaves) xtiled_kernel(const TiledKA
         n_shells = tile_shells_for(to_uniform((double)fmaxf(fmaxf(s_dmax[0], s_dmax[1]), fmaxf(s_dmax[2], s_dmax[3])) + a.bound_extra), a.shell_winv);
 
     const uint32_t slice = tile * 4 + wave;
-    const uint32_t K = to_uniform(n_shells >= PLAN_SHELLS ? a.slice_K[slice] : a.slice_Kend[(PLAN_SHELLS + 1) * slice + n_shells]);
+    // (the plan counts row ends in batches of 4 entries; this kernel walks whole chunks of 8)
+    const uint32_t K = (to_uniform(a.slice_Kend[(PLAN_SHELLS + 1) * slice + min(n_shells, PLAN_SHELLS)]) + 1u) >> 1;
     const uint64_t slice_head = to_uniform(a.slice_head[slice]);
     const uint4* __restrict__ rows = a.cnl + slice_head * 64ull + lane;
 

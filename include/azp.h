@@ -287,6 +287,17 @@ int azp_pair_plan_query(const azp_pair_plan* plan, azp_pair_plan_info* info);
  * last build as means over the slices -- out[0] chunks that cover the core entries, out[1] chunks up to the end of
  * the all-sure part of the rows, out[2] chunks of the whole rows. */
 int azp_pair_plan_phase_chunks(const azp_pair_plan* plan, float out[3]);
+/* Row ends of a plan. The Verlet-buffer entries of every row are ordered into azp_pair_plan_shells() shells of equal
+ * width by their separation at build time; per slice (one wave of the force kernel: 4 per tile) the plan keeps
+ * shells + 1 counts of BATCHES -- 4 entries per lane, half a 16-byte chunk -- that cover the in-range entries [0] and
+ * the entries up to the end of shell s [1 + s]; the last one is the whole row. A launch that has to walk n shells
+ * (azp_pair_plan_shells_for: the smallest n with n x width >= 2 x bound, all of them without a bound, with a NaN or
+ * negative one, or without a width) runs count / 2 whole iterations and, for an odd count, one half iteration.
+ * azp_pair_plan_row_batches copies the first n counts of the last build from the device (synchronises), stores the
+ * shell width (optional) and returns the number of counts written (0: no valid plan). Diagnostics and tests. */
+uint32_t azp_pair_plan_shells(void);
+uint32_t azp_pair_plan_shells_for(double shell_width, int has_bound, double bound);
+int azp_pair_plan_row_batches(const azp_pair_plan* plan, uint32_t* out, uint32_t n, double* shell_width);
 
 /* The plan cache behind azp_pair_forces_* (diagnostics and tests). */
 typedef struct azp_auto_plan_stats
