@@ -102,7 +102,7 @@ def advance(sums, state, N, dt_max, force_tol, energy_tol, min_steps_adapt=5, fi
     return s
 
 
-def step_one(pos, vel, mass, force, image, L, state):
+def step_one(pos, vel, mass, force, image, L, state, tilt=(0.0, 0.0, 0.0), periodic=(1, 1, 1)):
     """v = (KEEP v) + (MIX f); v += ((DT / 2) f) (1 / m); x += DT v; wrap. Returns (pos, vel, image); untouched when a
     flag is set."""
     if state["converged"] or state["nonfinite"]:
@@ -112,7 +112,7 @@ def step_one(pos, vel, mass, force, image, L, state):
     minv = 1.0 / np.asarray(mass, dtype=np.float64)
     v = (state["keep"] * vel) + (state["mix"] * force)
     v = v + (hdt * force) * minv[:, None]
-    p, im = flow_ref.wrap(pos + dt * v, image, L)
+    p, im = flow_ref.wrap(pos + dt * v, image, L, tilt, periodic)
     return p, v, im
 
 

@@ -6,6 +6,8 @@ pos (N, 3), vel (N, 3), mass (N,), accel (N, 3), force (N, 3), image (N, 3) int,
 
 import numpy as np
 
+import box_ref
+
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 W0, W1 = np.uint32(0x9E3779B9), np.uint32(0xBB67AE85)
 MASK32 = np.uint64(0xFFFFFFFF)
@@ -66,22 +68,15 @@ def flow_velocity(flow, pos):
     return u
 
 
-def wrap(pos, image, L):
-    """Orthorhombic periodic box of edges L centred on the origin, one shift per axis (wrap_into_box)."""
-    pos, image = pos.copy(), image.copy()
-    for d in range(3):
-        hi = pos[:, d] >= 0.5 * L[d]
-        lo = pos[:, d] < -0.5 * L[d]
-        pos[hi, d] -= L[d]
-        pos[lo, d] += L[d]
-        image[:, d] += hi.astype(image.dtype) - lo.astype(image.dtype)
-    return pos, image
+def wrap(pos, image, L, tilt=(0.0, 0.0, 0.0), periodic=(1, 1, 1)):
+    """Box of edges L centred on the origin, one shift per axis (wrap_into_box): tests/box_ref.py."""
+    return box_ref.wrap(pos, image, L, tilt, periodic)
 
 
-def langevin_step_one(pos, vel, accel, image, L, dt, sel):
+def langevin_step_one(pos, vel, accel, image, L, dt, sel, tilt=(0.0, 0.0, 0.0), periodic=(1, 1, 1)):
     hdt = 0.5 * dt
     p = pos + (vel + hdt * accel) * dt
-    p, im = wrap(p, image, L)
+    p, im = wrap(p, image, L, tilt, periodic)
     v = vel + hdt * accel
     return (np.where(sel[:, None], p, pos), np.where(sel[:, None], v, vel), np.where(sel[:, None], im, image))
 
@@ -100,12 +95,13 @@ def langevin_step_two(pos, vel, mass, accel, force, tag, gamma, kT, dt, seed, ti
     return np.where(sel[:, None], v, vel), np.where(sel[:, None], a, accel)
 
 
-def brownian_step(pos, image, force, tag, gamma, kT, dt, seed, timestep, flow, noiseless, L, sel):
+def brownian_step(pos, image, force, tag, gamma, kT, dt, seed, timestep, flow, noiseless, L, sel, tilt=(0.0, 0.0, 0.0),
+                  periodic=(1, 1, 1)):
     u = flow_velocity(flow, pos)
     c = np.sqrt(6.0 * gamma * kT / dt)
     if noiseless:
         c = np.zeros_like(c)
     R = uniform3(BROWNIAN_ID, seed, tag, timestep, c)
     p = pos + (u + (force + R) / gamma[:, None]) * dt
-    p, im = wrap(p, image, L)
+    p, im = wrap(p, image, L, tilt, periodic)
     return np.where(sel[:, None], p, pos), np.where(sel[:, None], im, image)

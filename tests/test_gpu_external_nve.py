@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import azplugins_amd as azp
+import box_cases
+import box_ref
 from azplugins_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -113,6 +115,46 @@ def test_barrier_parity_large(oracle):
         got = np.c_[b.forces, b.energies]
         assert np.abs(got - ref).max() <= 1e-13 * np.abs(ref).max()
         assert (ref[:, 3] > 0).sum() > 1000
+
+
+@pytest.mark.parametrize("box_id", ["tilt3", "tilt3_open_y"])
+def test_barrier_parity_tilted(oracle, box_id):
+    """The recipe of test_barrier_parity_large in a tilted box, fully periodic and open in y: N = 4096, positions scaled
+    by 1.08 in fractional coordinates, so that about 8 % lie one image outside along each lattice direction and
+    wrap_into_box takes its tilted branches (with y open, the z shift still carries Lz yz into y, which the planar
+    barrier reads). Same oracle, same 1e-13; the guard is the large test's 1000 of 32,768, scaled to N."""
+    L, tilt, periodic = box_cases.BOXES[box_id]
+    n = 4096
+    frac = np.random.default_rng(3).uniform(-0.5, 0.5, (n, 3)) * 1.08
+    outside = np.abs(frac) >= 0.5
+    assert np.all(outside.sum(axis=0) > 0.05 * n) and (outside.sum(axis=1) >= 2).sum() > 20
+    xyz = frac @ box_ref.box_matrix(L, tilt).T
+    # (no particle where the kernel's FMA and the oracle's product and sum could decide differently)
+    assert box_cases.face_distance(xyz, L, tilt, periodic) > box_cases.FACE_MARGIN
+    typeid = np.arange(n) % 3
+    params = [[50.0, 0.1], [200.0, -0.4], [0.0, 0.0]]
+    pos = syn.pos4(xyz, typeid)
+    box = azp.Box(L[0], L[1], L[2], *tilt, periodic=tuple(bool(p) for p in periodic))
+    snap = azp.Snapshot.from_arrays(xyz, box, typeid=typeid, types=("A", "B", "C"))
+    obox = oracle.make_box(L, tilt=tilt, periodic=periodic)
+    # (the planar barrier has to lie inside the box in y, the sphere inside the nearest planes: 1.9 and 2.45 here)
+    for kind, cls, loc in (("planar", azp.external.PlanarHarmonicBarrier, 1.0), ("spherical", azp.external.SphericalHarmonicBarrier, 2.0)):
+        sim = azp.Simulation(device="cuda:0", seed=1)
+        sim.create_state_from_snapshot(snap)
+        sim.operations.tuners.clear()
+        b = cls(location=loc)
+        for t, (k, off) in zip("ABC", params):
+            b.params[t] = dict(k=k, offset=off)
+        sim.operations.integrator = azp.Integrator(dt=0.0, forces=[b])
+        sim.run(0)
+        ref = oracle.barrier_forces(kind, pos, obox, params, loc)
+        got = np.c_[b.forces, b.energies]
+        print("%s barrier in %s: largest deviation %.3e of the largest entry" % (kind, box_id, np.abs(got - ref).max() / np.abs(ref).max()))
+        assert np.abs(got - ref).max() <= 1e-13 * np.abs(ref).max()
+        assert (ref[:, 3] > 0).sum() > 1000 * n // 32768
+        # the wrap matters to the answer: the unwrapped positions give other forces
+        far = oracle.barrier_forces(kind, pos, oracle.make_box(L, tilt=tilt, periodic=(0, 0, 0)), params, loc)
+        assert np.abs(far - ref).max() > 1e-3 * np.abs(ref).max()
 
 
 def test_nve_steps_match_oracle(oracle):

@@ -50,10 +50,10 @@ def step_two(vel, mass, force, dt):
     return vel + (hdt * force) * minv[:, None]
 
 
-def step_one(pos, vel, mass, force, image, L, dt, alpha):
+def step_one(pos, vel, mass, force, image, L, dt, alpha, tilt=(0.0, 0.0, 0.0), periodic=(1, 1, 1)):
     """v = alpha v; v += ((dt / 2) f) (1 / m); x += dt v; wrap. Returns (pos, vel, image)."""
     v = step_two(alpha * vel, mass, force, dt)
-    p, im = flow_ref.wrap(pos + dt * v, image, L)
+    p, im = flow_ref.wrap(pos + dt * v, image, L, tilt, periodic)
     return p, v, im
 
 

@@ -6,26 +6,11 @@ momentum / mass per bin, 0 where the mass is 0."""
 
 import numpy as np
 
+import box_ref
+
 
 def wrap(xyz, L, tilt=(0.0, 0.0, 0.0), periodic=(True, True, True)):
-    x, y, z = (np.array(xyz[:, k], dtype=np.float64) for k in range(3))
-    Lx, Ly, Lz = (float(v) for v in L)
-    xy, xz, yz = (float(v) for v in tilt)
-    if periodic[2]:
-        h = 0.5 * Lz
-        up, dn = z >= h, z < -h
-        z = np.where(up, z - Lz, np.where(dn, z + Lz, z))
-        y = np.where(up, y - Lz * yz, np.where(dn, y + Lz * yz, y))
-        x = np.where(up, x - Lz * xz, np.where(dn, x + Lz * xz, x))
-    if periodic[1]:
-        h, s = 0.5 * Ly, z * yz
-        up, dn = y >= h + s, y < -h + s
-        y = np.where(up, y - Ly, np.where(dn, y + Ly, y))
-        x = np.where(up, x - Ly * xy, np.where(dn, x + Ly * xy, x))
-    if periodic[0]:
-        h, s = 0.5 * Lx, y * xy + z * (xz - xy * yz)
-        x = np.where(x >= h + s, x - Lx, np.where(x < -h + s, x + Lx, x))
-    return np.stack([x, y, z], axis=1)
+    return box_ref.wrap(xyz, None, L, tilt, periodic)[0]
 
 
 def _bin_1d(x, lo, hi, n):

@@ -10,6 +10,8 @@ import math
 
 import numpy as np
 
+import box_ref
+
 
 def _ln(x):
     # (scalars go through libm, as the C fold does; arrays through numpy)
@@ -60,17 +62,9 @@ def fold(kind, p, mode):
     return c, e, shift, Ve, Fe
 
 
-def wrap(pos, L):
-    """BoxDim::wrap for one shift per axis, orthorhombic box."""
-    x = np.array(pos, dtype=np.float64, copy=True)
-    L = np.broadcast_to(np.asarray(L, dtype=np.float64), (3,))
-    for k in (2, 1, 0):
-        h = 0.5 * L[k]
-        hi = x[:, k] >= h
-        lo = x[:, k] < -h
-        x[hi, k] -= L[k]
-        x[lo, k] += L[k]
-    return x
+def wrap(pos, L, tilt=(0.0, 0.0, 0.0), periodic=(1, 1, 1)):
+    """BoxDim::wrap for one shift per axis: tests/box_ref.py."""
+    return box_ref.wrap(pos, None, L, tilt, periodic)[0]
 
 
 def unit(v):
@@ -102,10 +96,10 @@ def distance(wall, x):
     return rho - wall["radius"], radial
 
 
-def evaluate(kind, walls, params, mode, pos, typeid, L):
+def evaluate(kind, walls, params, mode, pos, typeid, L, tilt=(0.0, 0.0, 0.0), periodic=(1, 1, 1)):
     """Per-wall forces (W, N, 3), energies (W, N) and distances (W, N); ``params`` is a list indexed by type id.
     The sums over the walls, in list order, are ``forces.sum`` taken wall by wall: see ``total``."""
-    x = wrap(pos, L)
+    x = wrap(pos, L, tilt, periodic)
     typeid = np.asarray(typeid)
     N = x.shape[0]
     F = np.zeros((len(walls), N, 3))
