@@ -156,11 +156,23 @@ class _FlowMethod:
         """kT at ``timestep``, evaluated on the host (passed to the kernel by value)."""
         return float(self.kT(timestep)) if callable(self.kT) else float(self.kT)
 
-    def _prepare(self, sim):
-        """Upload the gamma table and the type mask; build the argument struct for this run."""
+    # -- the stepper (DESIGN 4.20) -----------------------------------------------
+    _fusable = True
+    # a method filtered by type reads the types when its kernel runs: where an updater is due, step two of the previous
+    # step runs on its own ahead of the updater, as in HOOMD (the fused kernel is bit-identical to the two halves)
+    _updaters_split = True
+
+    def _begin(self, sim):
+        """The seed warning; the accelerations of a first run; the gamma table and the type mask on the device; the
+        argument struct of this run."""
         import torch
 
         st = sim.state
+        sim._warn_if_seed_unset()
+        if self._uses_accel and (st.accel is None or st.accel.shape[0] != st.n_max):
+            # HOOMD computeAccelerations (prepRun): a = F_net / m on the first run of an integrator that needs it
+            st.accel = torch.zeros((st.n_max, 4), dtype=torch.float64, device=st.device)
+            st.accel[: st.N, :3] = st.net_force[: st.N, :3] / st.vel[: st.N, 3:4]
         key = (tuple(st.types), tuple(self.gamma.table(st.types)), self.filter)
         if self._tables is None or self._tables[0] != key:
             g = torch.from_numpy(self.gamma.table(st.types)).to(st.device)
@@ -176,8 +188,11 @@ class _FlowMethod:
         a.ntypes = len(st.types)
         a.flow = self.flow_field._c()
         self._args = a
+        self._stream = _lib.raw_stream(st.device)
 
-    def _point_at_state(self, st, timestep):
+    def _launch(self, name, st, timestep):
+        """Queue the libazp entry ``name`` with the struct pointed at the state's arrays and at ``timestep`` (random
+        numbers and kT)."""
         a = self._args
         a.d_pos = st.pos.data_ptr()
         a.d_vel = st.vel.data_ptr()
@@ -189,7 +204,7 @@ class _FlowMethod:
         a.N = st.N
         a.timestep = int(timestep)
         a.kT = self._kT(timestep)
-        return a
+        _lib.check(getattr(_lib.lib(), name)(C.byref(a), self._stream), name)
 
 
 class Langevin(_FlowMethod):
@@ -206,17 +221,16 @@ class Langevin(_FlowMethod):
             raise _lib.AzpError("flow.Langevin: gamma must be >= 0, got %r" % (g,))
         return g
 
-    def _step(self, st, timestep, stream, fused):
+    def _step_one(self, sim, timestep, fused):
         """Step one of the step starting at ``timestep`` (fused: preceded by step two of the previous step, whose
         random numbers and kT belong to ``timestep - 1``; step one itself draws nothing)."""
-        lib = _lib.lib()
-        a = self._point_at_state(st, timestep - 1 if fused else timestep)
-        fn = lib.azp_integrate_langevin_flow_step_two_one if fused else lib.azp_integrate_langevin_flow_step_one
-        _lib.check(fn(C.byref(a), stream), "azp_integrate_langevin_flow_step")
+        if fused:
+            self._launch("azp_integrate_langevin_flow_step_two_one", sim.state, timestep - 1)
+        else:
+            self._launch("azp_integrate_langevin_flow_step_one", sim.state, timestep)
 
-    def _step_two(self, st, timestep, stream):
-        a = self._point_at_state(st, timestep)
-        _lib.check(_lib.lib().azp_integrate_langevin_flow_step_two(C.byref(a), stream), "azp_integrate_langevin_flow_step_two")
+    def _step_two(self, sim, timestep):
+        self._launch("azp_integrate_langevin_flow_step_two", sim.state, timestep)
 
 
 class Brownian(_FlowMethod):
@@ -233,10 +247,9 @@ class Brownian(_FlowMethod):
             raise _lib.AzpError("flow.Brownian: gamma must be > 0 (the step divides by it), got %r" % (g,))
         return g
 
-    def _step(self, st, timestep, stream, fused):
+    def _step_one(self, sim, timestep, fused):
         """The whole step starting at ``timestep``."""
-        a = self._point_at_state(st, timestep)
-        _lib.check(_lib.lib().azp_integrate_brownian_flow_step(C.byref(a), stream), "azp_integrate_brownian_flow_step")
+        self._launch("azp_integrate_brownian_flow_step", sim.state, timestep)
 
-    def _step_two(self, st, timestep, stream):
+    def _step_two(self, sim, timestep):
         pass  # Brownian dynamics has no second half

@@ -30,7 +30,7 @@ import math
 import weakref
 
 from . import _lib
-from .simulation import All, ConstantVolume, Integrator
+from .simulation import All, ConstantVolume, Integrator, _launch
 
 
 def _positive(name, value):
@@ -102,8 +102,17 @@ class FIRE(Integrator):
         if sim.state.N == 0:
             raise _lib.AzpError("minimize.FIRE: the state holds no particles (N = 0)")
 
-    def _prepare(self, sim):
-        """The argument struct of this run; the state tensor and the partials buffer on the state's device."""
+    # The stepper: the thermostatted step's shape with a control state that holds the time step itself.
+    # Step two leaves the partials of P = f . v, |v|^2, |f|^2 and U behind, one wave turns them into the next step's time
+    # step and velocity coefficients on the device, and step one reads them from there. Nothing is read back: once the
+    # state says converged the kernels return at once, and the loop only counts.
+    _fusable = False
+    _updaters_split = False
+
+    def _begin(self, sim):
+        """The argument struct of this run, the state tensor and the partials buffer on the state's device, and the sums
+        of the first step from a pass of their own: the velocities may have been changed between runs (after a run that
+        ended with step two it leaves the partials that step two left, bit for bit)."""
         import ctypes as C
 
         import torch
@@ -116,16 +125,24 @@ class FIRE(Integrator):
         _lib.check(_lib.lib().azp_fire_partials_size(st.N, C.byref(need)), "azp_fire_partials_size")
         if self._partials is None or self._partials.numel() * 8 < need.value or self._partials.device != st.vel.device:
             self._partials = torch.zeros(int(need.value) // 8, dtype=torch.float64, device=st.vel.device)
-        a = _lib.FireArgs()
+        a = self._args = _lib.FireArgs()
         a.d_partials = self._partials.data_ptr()
         a.partials_bytes = self._partials.numel() * 8
         a.d_state = self._state.data_ptr()
+        a.box = st.box.to_c()
         a.dt_max, a.force_tol, a.energy_tol = self.dt, self.force_tol, self.energy_tol
         a.finc_dt, a.fdec_dt, a.alpha_start, a.fdec_alpha = self.finc_dt, self.fdec_dt, self.alpha_start, self.fdec_alpha
         a.min_steps_adapt, a.min_steps_conv = self.min_steps_adapt, self.min_steps_conv
         self._n = st.N
         self._sim = weakref.ref(sim)
-        return a
+        self._stream = _lib.raw_stream(st.device)
+        _launch(a, st, self._stream, "azp_fire_measure")
+
+    def _step_one(self, sim, timestep, fused):
+        _launch(self._args, sim.state, self._stream, "azp_fire_advance", "azp_fire_step_one")
+
+    def _step_two(self, sim, timestep):
+        _launch(self._args, sim.state, self._stream, "azp_fire_step_two")
 
     # -- results ----------------------------------------------------------------
     def _read(self):

@@ -76,6 +76,19 @@ class Periodic:
         return "Periodic(period=%d, phase=%d)" % (self.period, self.phase)
 
 
+def _launch(a, st, stream, *names):
+    """Queue the libazp integration entries ``names`` with their argument struct ``a`` pointed at the state's arrays of
+    this moment (they are replaced when particles migrate between ranks or are re-sorted)."""
+    a.d_pos = st.pos.data_ptr()
+    a.d_vel = st.vel.data_ptr()
+    a.d_net_force = st.net_force.data_ptr()
+    a.d_image = st.image.data_ptr()
+    a.N = st.N
+    lib = _lib.lib()
+    for name in names:
+        _lib.check(getattr(lib, name)(C.byref(a), stream), name)
+
+
 class ConstantVolume:
     """NVE integration method (velocity Verlet) on all particles
     (``hoomd.md.methods.ConstantVolume(filter=hoomd.filter.All())``; without a
@@ -110,6 +123,53 @@ class ConstantVolume:
         if thermostat is not None:
             thermostat._holders.add(self)
         self._thermostat = thermostat
+
+    # -- the stepper of the NVE path; with a thermostat the thermostat steps --------
+    _fusable = True
+    _updaters_split = False  # (an updater changes types alone, which these kernels do not read)
+
+    def _begin(self, sim):
+        integ = sim.operations.integrator
+        a = self._args = _lib.NVEArgs()
+        a.box = sim.state.box.to_c()
+        a.dt = integ.dt
+        self._stream = _lib.raw_stream(sim.state.device)
+        self._rot = None
+        if integ.integrate_rotational_dof:
+            if sim.domain is not None and not all(n in sim.domain.names for n in ("orientation", "angmom", "inertia")):
+                raise _lib.AzpError("integrate_rotational_dof in a decomposed run: the domain must carry orientation, angmom "
+                                    "and inertia (they migrate with the particles)")
+            self._rot = _lib.NVERotArgs()
+            self._rot.dt = integ.dt
+
+    def _rotational_step(self, sim, one):
+        st, rot, forces = sim.state, self._rot, sim.operations.integrator.forces
+        torque = forces[0].torque_tensor  # the net torque, kept alive until the kernel is queued
+        if len(forces) > 1:
+            torque = torque.clone()
+            for f in forces[1:]:
+                torque += f.torque_tensor
+        rot.d_orientation = st.orientation.data_ptr()
+        rot.d_angmom = st.angmom.data_ptr()
+        rot.d_inertia = st.inertia.data_ptr()
+        rot.d_net_torque = torque.data_ptr()
+        rot.N = st.N
+        fn = _lib.lib().azp_integrate_nve_rot_step_one if one else _lib.lib().azp_integrate_nve_rot_step_two
+        _lib.check(fn(C.byref(rot), self._stream), "azp_integrate_nve_rot_step")
+
+    def _step_one(self, sim, timestep, fused):
+        """Velocity Verlet (libazp kernels): v += a dt/2, x += v dt, wrap | forces | v += a dt/2; ``fused``: behind step
+        two of the previous step, in one kernel."""
+        _launch(self._args, sim.state, self._stream, "azp_integrate_nve_step_two_one" if fused else "azp_integrate_nve_step_one")
+        if self._rot is not None:
+            if fused:
+                self._rotational_step(sim, False)  # (step two of the previous step: the torques are still its own)
+            self._rotational_step(sim, True)
+
+    def _step_two(self, sim, timestep):
+        _launch(self._args, sim.state, self._stream, "azp_integrate_nve_step_two")
+        if self._rot is not None:
+            self._rotational_step(sim, False)
 
 
 class Integrator:
@@ -368,116 +428,78 @@ class Simulation:
             _lib.check(_lib.lib().azp_sum_forces(st.N, len(ptrs), arr, st.net_force.data_ptr(), _lib.raw_stream(st.device)), "azp_sum_forces")
 
     def run(self, steps):
+        """``steps`` steps of the integrator's methods (HOOMD IntegratorTwoStep::update): every stepper's step one at the
+        step's timestep t, the forces at t + 1, every stepper's step two at t. The one loop of all paths."""
+        from .minimize import FIRE
+
         self._check_writers()
         self._attach_all()
         integ = self.operations.integrator
         st = self.state
-        from .minimize import FIRE
-
-        if isinstance(integ, FIRE):
-            return self._run_fire(steps)
-        flow_methods = self._check_flow_methods(integ)
+        # (refused even where nothing is stepped, and ahead of the forces: what the minimizer and the flow methods cannot do)
+        fire = isinstance(integ, FIRE)
+        if fire:
+            integ._check(self)
+        flow_methods = [] if fire else self._check_flow_methods(integ)
         if self.domain is not None:
             self._wire_domain()
         self._compute_forces()
         if steps == 0 or not integ.methods:
             return
-        if flow_methods:
-            return self._run_flow(steps, flow_methods)
-        if len(integ.methods) != 1 or not isinstance(integ.methods[0], ConstantVolume):
+        # what moves the particles, each with the stepper interface (DESIGN 4.20): the minimizer, the flow methods, or
+        # the one ConstantVolume (its thermostat where it has one)
+        if fire:
+            steppers = [integ]
+        elif flow_methods:
+            steppers = flow_methods
+        elif len(integ.methods) != 1 or not isinstance(integ.methods[0], ConstantVolume):
             raise _lib.AzpError("Integrator.methods must hold exactly one ConstantVolume (all particles); got %r" % (integ.methods,))
-        if integ.methods[0].thermostat is not None:
-            return self._run_thermostatted(steps, integ.methods[0])
-        a = _lib.NVEArgs()
-        a.box = st.box.to_c()
-        a.dt = integ.dt
-        lib = _lib.lib()
-        stream = _lib.raw_stream(st.device)
-
-        rot = None
-        if integ.integrate_rotational_dof:
-            if self.domain is not None and not all(n in self.domain.names for n in ("orientation", "angmom", "inertia")):
-                raise _lib.AzpError("integrate_rotational_dof in a decomposed run: the domain must carry orientation, angmom "
-                                    "and inertia (they migrate with the particles)")
-            rot = _lib.NVERotArgs()
-            rot.dt = integ.dt
-
-        def net_torque():
-            forces = integ.forces
-            if len(forces) == 1:
-                return forces[0].torque_tensor
-            t = forces[0].torque_tensor.clone()
-            for f in forces[1:]:
-                t += f.torque_tensor
-            return t
-
-        def point_at_state():
-            # (the arrays are replaced when particles migrate between ranks or are re-sorted)
-            a.d_pos = st.pos.data_ptr()
-            a.d_vel = st.vel.data_ptr()
-            a.d_net_force = st.net_force.data_ptr()
-            a.d_image = st.image.data_ptr()
-            a.N = st.N
-
-        def rotational_step(one):
-            torque = net_torque()  # kept alive until the kernel is queued
-            rot.d_orientation = st.orientation.data_ptr()
-            rot.d_angmom = st.angmom.data_ptr()
-            rot.d_inertia = st.inertia.data_ptr()
-            rot.d_net_torque = torque.data_ptr()
-            rot.N = st.N
-            fn = lib.azp_integrate_nve_rot_step_one if one else lib.azp_integrate_nve_rot_step_two
-            _lib.check(fn(C.byref(rot), stream), "azp_integrate_nve_rot_step")
-            return torque
-
+        else:
+            steppers = [integ.methods[0].thermostat or integ.methods[0]]
+        for s in steppers:
+            s._begin(self)
+        # Inside a run nothing reads the velocities between step two of one step and step one of the next: where the
+        # stepper can (_fusable) they are one kernel (same arithmetic, one pass over the arrays). Where a writer is due,
+        # the full-step velocities of the previous step have to exist: its step two runs on its own (the same arithmetic,
+        # bit for bit), the writer records, and this step starts with a plain step one. An updater changes types alone:
+        # it splits the fusion only for kernels that read them (_updaters_split: a flow method filtered by type)
+        fusable, updaters_split = steppers[0]._fusable, steppers[0]._updaters_split
         # (a bond force examines the "evaluator rejected its parameters" flag of step k when step k + 1 is queued, and
         # once more after the loop: no host round trip behind every launch)
         deferred = [f for f in integ.forces if hasattr(f, "defer_flag_check")]
+        try:
+            for f in deferred:
+                f.defer_flag_check = True
+            for k in range(steps):
+                writers = self._writers_due() if k else []
+                updaters = self._updaters_due()
+                split = k > 0 and bool(not fusable or writers or (updaters and updaters_split))
+                if split:
+                    for s in steppers:
+                        s._step_two(self, self.timestep - 1)
+                self._run_writers(writers)  # (the state after self.timestep complete steps)
+                self._run_updaters(updaters)
+                for s in steppers:
+                    s._step_one(self, self.timestep, fused=k > 0 and not split)
+                if self.domain is not None:
+                    self.domain.exchange(self._halo_fields())  # ghost rows follow their owners' particles
+                st.position_generation += 1
+                self.timestep += 1
+                # re-index the particles between the position update and the force
+                # evaluation: every per-particle array that survives the step is permuted,
+                # the forces are recomputed in the new order
+                # (also when a tile plan could not be compiled from the cells because the members of some tile have drifted
+                # apart -- a DPD fluid diffuses a cell width in ~200 steps: sorting now costs 0.5 ms, the list-based rebuilds
+                # that would follow until the sorter's next period 2.5 ms each; at most once per 20 steps)
+                self._run_tuners(integ)
+                self._compute_forces()
+            for s in steppers:
+                s._step_two(self, self.timestep - 1)
+            self._run_writers(self._writers_due())
+        finally:
+            for f in deferred:
+                f.defer_flag_check = False
         for f in deferred:
-            f.defer_flag_check = True
-        for k in range(steps):
-            # velocity Verlet (libazp kernels): v += a dt/2, x += v dt, wrap | forces | v += a dt/2. Inside a run
-            # nothing reads the velocities between step two of one step and step one of the next: they are one
-            # kernel (same arithmetic, one pass over the arrays); the last step two comes after the loop. An updater
-            # changes types alone, which these kernels do not read: they stay fused. Where a writer is due, the
-            # full-step velocities of the previous step have to exist: its step two runs on its own (the same arithmetic,
-            # bit for bit), the writer records, and this step starts with a plain step one
-            writers = self._writers_due() if k else []
-            if writers:
-                point_at_state()
-                _lib.check(lib.azp_integrate_nve_step_two(C.byref(a), stream), "azp_integrate_nve_step_two")
-                if rot is not None:
-                    rotational_step(False)
-                self._run_writers(writers)
-            self._run_updaters()
-            point_at_state()
-            if k == 0 or writers:
-                _lib.check(lib.azp_integrate_nve_step_one(C.byref(a), stream), "azp_integrate_nve_step_one")
-            else:
-                _lib.check(lib.azp_integrate_nve_step_two_one(C.byref(a), stream), "azp_integrate_nve_step_two_one")
-            if rot is not None:
-                if k and not writers:
-                    rotational_step(False)  # (step two of the previous step: the torques are still its own)
-                rotational_step(True)
-            if self.domain is not None:
-                self.domain.exchange(self._halo_fields())  # ghost rows follow their owners' particles
-            st.position_generation += 1
-            self.timestep += 1
-            # re-index the particles between the position update and the force
-            # evaluation: every per-particle array that survives the step is permuted,
-            # the forces are recomputed in the new order
-            # (also when a tile plan could not be compiled from the cells because the members of some tile have drifted
-            # apart -- a DPD fluid diffuses a cell width in ~200 steps: sorting now costs 0.5 ms, the list-based rebuilds
-            # that would follow until the sorter's next period 2.5 ms each; at most once per 20 steps)
-            self._run_tuners(integ)
-            self._compute_forces()
-        point_at_state()
-        _lib.check(lib.azp_integrate_nve_step_two(C.byref(a), stream), "azp_integrate_nve_step_two")
-        if rot is not None:
-            rotational_step(False)
-        self._run_writers(self._writers_due())
-        for f in deferred:
-            f.defer_flag_check = False
             f.check_flags(wait=True)
 
     def _check_thermostat(self, integ, method):
@@ -498,115 +520,14 @@ class Simulation:
         if any(m is not method for m in th._holders):
             raise _lib.AzpError("%s: one thermostat object is held by two methods (its state belongs to one run)" % th._name)
 
-    def _run_thermostatted(self, steps, method):
-        """``steps`` steps of velocity Verlet with a thermostat. The thermostat needs the kinetic energy of
-        all particles between step two of one step and step one of the next, so the two are not fused here: step two
-        leaves the partial sums of K behind, one wave turns them into the scale factor alpha on the device, and step one
-        reads alpha from there. Nothing is read back."""
-        integ = self.operations.integrator
-        st = self.state
-        th = method.thermostat
-        self._check_thermostat(integ, method)
-        if th._kind == _lib.THERMOSTAT_BUSSI:
-            self._warn_if_seed_unset()
-        a = th._prepare(self)
-        a.box = st.box.to_c()
-        lib = _lib.lib()
-        stream = _lib.raw_stream(st.device)
-
-        def point_at_state():
-            # (the arrays are replaced when the particles are re-sorted)
-            a.d_pos = st.pos.data_ptr()
-            a.d_vel = st.vel.data_ptr()
-            a.d_net_force = st.net_force.data_ptr()
-            a.d_image = st.image.data_ptr()
-            a.N = st.N
-
-        # the velocities may have been changed between runs: K of the first step comes from a pass of its own
-        point_at_state()
-        _lib.check(lib.azp_thermostat_kinetic(C.byref(a), stream), "azp_thermostat_kinetic")
-        deferred = [f for f in integ.forces if hasattr(f, "defer_flag_check")]
-        for f in deferred:
-            f.defer_flag_check = True
-        for k in range(steps):
-            # writers see the full-step velocities v(t) before they are scaled, as HOOMD's do
-            if k:
-                self._run_writers(self._writers_due())
-            self._run_updaters()
-            point_at_state()
-            a.timestep = self.timestep
-            a.kT = th._last_kT = th._kT_at(self.timestep)
-            _lib.check(lib.azp_thermostat_advance(C.byref(a), stream), "azp_thermostat_advance")
-            _lib.check(lib.azp_thermostat_step_one(C.byref(a), stream), "azp_thermostat_step_one")
-            st.position_generation += 1
-            self.timestep += 1
-            self._run_tuners(integ)
-            self._compute_forces()
-            point_at_state()
-            _lib.check(lib.azp_thermostat_step_two(C.byref(a), stream), "azp_thermostat_step_two")
-        self._run_writers(self._writers_due())
-        for f in deferred:
-            f.defer_flag_check = False
-            f.check_flags(wait=True)
-
-    def _run_fire(self, steps):
-        """``steps`` steps of ``minimize.FIRE``: the thermostatted step's shape with a control state that
-        holds the time step itself. Step two leaves the partials of P = f . v, |v|^2, |f|^2 and U behind, one wave turns
-        them into the next step's time step and velocity coefficients on the device, and step one reads them from there.
-        Nothing is read back: once the state says converged the kernels return at once, and the loop only counts."""
-        integ = self.operations.integrator
-        st = self.state
-        integ._check(self)
-        self._compute_forces()
-        if steps == 0:
-            return
-        a = integ._prepare(self)
-        a.box = st.box.to_c()
-        lib = _lib.lib()
-        stream = _lib.raw_stream(st.device)
-
-        def point_at_state():
-            # (the arrays are replaced when the particles are re-sorted)
-            a.d_pos = st.pos.data_ptr()
-            a.d_vel = st.vel.data_ptr()
-            a.d_net_force = st.net_force.data_ptr()
-            a.d_image = st.image.data_ptr()
-            a.N = st.N
-
-        # the velocities may have been changed between runs: the sums of the first step come from a pass of their own
-        # (after a run that ended with step two it leaves the partials that step two left, bit for bit)
-        point_at_state()
-        _lib.check(lib.azp_fire_measure(C.byref(a), stream), "azp_fire_measure")
-        deferred = [f for f in integ.forces if hasattr(f, "defer_flag_check")]
-        for f in deferred:
-            f.defer_flag_check = True
-        for k in range(steps):
-            if k:
-                self._run_writers(self._writers_due())
-            self._run_updaters()
-            point_at_state()
-            _lib.check(lib.azp_fire_advance(C.byref(a), stream), "azp_fire_advance")
-            _lib.check(lib.azp_fire_step_one(C.byref(a), stream), "azp_fire_step_one")
-            st.position_generation += 1
-            self.timestep += 1
-            self._run_tuners(integ)
-            self._compute_forces()
-            point_at_state()
-            _lib.check(lib.azp_fire_step_two(C.byref(a), stream), "azp_fire_step_two")
-        self._run_writers(self._writers_due())
-        for f in deferred:
-            f.defer_flag_check = False
-            f.check_flags(wait=True)
-
     def _updaters_due(self):
         return [u for u in self.operations.updaters if u.trigger(self.timestep)]
 
-    def _run_updaters(self, due=None):
+    def _run_updaters(self, due):
         """The updaters whose trigger fires at this timestep (HOOMD runs its updaters ahead of the integrator's
         step). They change particle types: every neighbor list and tile plan is rebuilt before the next force
         evaluation (the reference: notifyParticleSort(), src/TypeUpdater.cc:86-87) -- whether or not a type really
         changed, so that nothing is read back from the device."""
-        due = self._updaters_due() if due is None else due
         for u in due:
             u._update(self, self.timestep)
         if due:
@@ -654,51 +575,6 @@ class Simulation:
                 raise _lib.AzpError("Integrator.methods: the filters of the flow methods overlap (types %s)" % sorted(overlap))
             seen |= set(m.filter.types)
         return flow_methods
-
-    def _run_flow(self, steps, methods):
-        """``steps`` steps of Langevin / Brownian dynamics (HOOMD IntegratorTwoStep::update): every method's step one
-        at the step's timestep t, the forces at t + 1, every method's step two at t. Inside the run step two of one
-        step and step one of the next are one kernel; the last step two comes after the loop."""
-        import torch
-
-        integ = self.operations.integrator
-        st = self.state
-        self._warn_if_seed_unset()
-        if any(m._uses_accel for m in methods) and (st.accel is None or st.accel.shape[0] != st.n_max):
-            # HOOMD computeAccelerations (prepRun): a = F_net / m on the first run of an integrator that needs it
-            st.accel = torch.zeros((st.n_max, 4), dtype=torch.float64, device=st.device)
-            st.accel[: st.N, :3] = st.net_force[: st.N, :3] / st.vel[: st.N, 3:4]
-        for m in methods:
-            m._prepare(self)
-        stream = _lib.raw_stream(st.device)
-        deferred = [f for f in integ.forces if hasattr(f, "defer_flag_check")]
-        for f in deferred:
-            f.defer_flag_check = True
-        for k in range(steps):
-            # a method filtered by type reads the types when its kernel runs: where an updater is due, step two of the
-            # previous step runs on its own ahead of the updater, as in HOOMD (the fused kernel is bit-identical to
-            # the two halves)
-            due = self._updaters_due()
-            writers = self._writers_due() if k else []
-            if due or writers:
-                if k > 0:
-                    for m in methods:
-                        m._step_two(st, self.timestep - 1, stream)
-                self._run_writers(writers)  # (the state after self.timestep complete steps)
-                self._run_updaters(due)
-            for m in methods:
-                # (k > 0: step two of the previous step, at its timestep, fused with this step one)
-                m._step(st, self.timestep, stream, fused=k > 0 and not due and not writers)
-            st.position_generation += 1
-            self.timestep += 1
-            self._run_tuners(integ)
-            self._compute_forces()
-        for m in methods:
-            m._step_two(st, self.timestep - 1, stream)
-        self._run_writers(self._writers_due())
-        for f in deferred:
-            f.defer_flag_check = False
-            f.check_flags(wait=True)
 
     def kinetic_temperature(self):
         """Instantaneous kT = 2 KE / (3 N - 3) (HOOMD ThermodynamicQuantities)."""

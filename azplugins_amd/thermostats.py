@@ -21,6 +21,7 @@ import math
 import weakref
 
 from . import _lib
+from .simulation import _launch
 
 
 class _Thermostat:
@@ -84,13 +85,24 @@ class _Thermostat:
         else:
             self._state[k] = value
 
-    def _prepare(self, sim):
-        """The argument struct of this run; the state tensor and the partials buffer on the state's device."""
+    # -- the stepper of a thermostatted ConstantVolume ---------------
+    # The thermostat needs the kinetic energy of all particles between step two of one step and step one of the next,
+    # so the two are never fused: step two leaves the partial sums of K behind, one wave turns them into the scale
+    # factor alpha on the device, and step one reads alpha from there. Nothing is read back.
+    _fusable = False
+    _updaters_split = False
+
+    def _begin(self, sim):
+        """The refusals, the argument struct of this run, the state tensor and the partials buffer on the state's device,
+        and K of the first step from a pass of its own (the velocities may have been changed between runs)."""
         import ctypes as C
 
         import torch
 
-        st = sim.state
+        integ, st = sim.operations.integrator, sim.state
+        sim._check_thermostat(integ, integ.methods[0])
+        if self._kind == _lib.THERMOSTAT_BUSSI:
+            sim._warn_if_seed_unset()
         if self._state is None or self._state.device != st.vel.device:
             start = self._pending if self._state is None else self._state.cpu().tolist()
             self._state = torch.tensor(start, dtype=torch.float64, device=st.vel.device)
@@ -98,17 +110,28 @@ class _Thermostat:
         _lib.check(_lib.lib().azp_thermostat_partials_size(st.N, C.byref(need)), "azp_thermostat_partials_size")
         if self._partials is None or self._partials.numel() * 8 < need.value or self._partials.device != st.vel.device:
             self._partials = torch.zeros(int(need.value) // 8, dtype=torch.float64, device=st.vel.device)
-        a = _lib.ThermostatArgs()
+        a = self._args = _lib.ThermostatArgs()
         a.d_partials = self._partials.data_ptr()
         a.partials_bytes = self._partials.numel() * 8
         a.d_state = self._state.data_ptr()
-        a.dt = sim.operations.integrator.dt
+        a.box = st.box.to_c()
+        a.dt = integ.dt
         a.tau = self._tau
         a.ndof = float(3 * st.N - 3)
         a.seed = int(sim.seed or 0) & 0xFFFF
         a.kind = self._kind
         self._ndof = a.ndof
-        return a
+        self._stream = _lib.raw_stream(st.device)
+        _launch(a, st, self._stream, "azp_thermostat_kinetic")
+
+    def _step_one(self, sim, timestep, fused):
+        a = self._args
+        a.timestep = timestep
+        a.kT = self._last_kT = self._kT_at(timestep)
+        _launch(a, sim.state, self._stream, "azp_thermostat_advance", "azp_thermostat_step_one")
+
+    def _step_two(self, sim, timestep):
+        _launch(self._args, sim.state, self._stream, "azp_thermostat_step_two")
 
     @property
     def energy(self):
