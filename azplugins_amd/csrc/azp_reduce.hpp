@@ -1,4 +1,5 @@
-// azp_reduce.hpp -- the reproducible two-stage sum of double slots over the particles (thermo.hip, wall_forces.hip).
+// azp_reduce.hpp -- the reproducible two-stage sum of double slots over the particles (thermo.hip, wall_forces.hip,
+// and through controlled_verlet.hpp thermostat.hip and fire.hip).
 // Nothing is atomic and every order is fixed by N alone, so two calls on the same state give bit-identical sums, and
 // a host restatement of the order (tests/reduction_ref.py) reproduces them bit for bit from the per-particle terms.
 //
@@ -11,8 +12,9 @@
 //                      s = 1, 2, 4, 8, 16, 32); lane 0 of each wave writes to LDS; the four waves are added in wave
 //                      order, starting from wave 0's value; one partial per workgroup and slot goes to the scratch
 //                      buffer, slot-major (scratch[slot * n_blocks + b]).
-//   reduce_fold        one wave per slot: lane l adds the partials l, l + 64, ... in turn from +0.0, then the
-//                      butterfly; lane 0 writes out[slot] (any device address).
+//   fold_partials      one wave per slot: lane l adds the partials l, l + 64, ... in turn from +0.0, then the
+//                      butterfly. reduce_fold: lane 0 writes out[slot] (any device address); cv_advance_kernel
+//                      (controlled_verlet.hpp) keeps the sums in registers.
 //
 // Addition depth (the longest chain of additions a term passes through), for a caller that makes A additions per
 // particle before the term reaches its lane's accumulator: A + per_lane + 6 + 3 + ceil(n_blocks / 64) + 6.
@@ -75,20 +77,25 @@ __device__ __forceinline__ void reduce_block_store(const double (&acc)[NS], doub
         }
     }
 
-// One wave per slot (grid = the number of slots, workgroups of one wave). NEG3OF4: the slots with slot % 4 != 3 are
-// stored with their sign changed (wall_forces.hip: the force ON the wall and, fourth, its energy). The sign changes
-// after the sum: a sum of no terms is +0.0 and leaves as -0.0, which negated terms would not give.
-template<bool NEG3OF4> __global__ void __launch_bounds__(WAVE) reduce_fold(const double* scratch, uint32_t n_blocks, double* out)
+// Every lane of one wave calls it with the n_blocks partials of one slot; all lanes return the slot's sum.
+__device__ __forceinline__ double fold_partials(const double* row, uint32_t n_blocks, uint32_t lane)
     {
-    const uint32_t slot = blockIdx.x, lane = threadIdx.x;
-    const double* row = scratch + (uint64_t)slot * n_blocks;
     double s = 0.0;
     // (unrolled: eight independent loads in flight per lane; the adds keep their order)
 #pragma unroll 8
     for (uint32_t b = lane; b < n_blocks; b += WAVE)
         s += row[b];
-    s = group_sum<WAVE>(s);
-    if (lane == 0)
+    return group_sum<WAVE>(s);
+    }
+
+// One wave per slot (grid = the number of slots, workgroups of one wave). NEG3OF4: the slots with slot % 4 != 3 are
+// stored with their sign changed (wall_forces.hip: the force ON the wall and, fourth, its energy). The sign changes
+// after the sum: a sum of no terms is +0.0 and leaves as -0.0, which negated terms would not give.
+template<bool NEG3OF4> __global__ void __launch_bounds__(WAVE) reduce_fold(const double* scratch, uint32_t n_blocks, double* out)
+    {
+    const uint32_t slot = blockIdx.x;
+    const double s = fold_partials(scratch + (uint64_t)slot * n_blocks, n_blocks, threadIdx.x);
+    if (threadIdx.x == 0)
         out[slot] = (NEG3OF4 && (slot & 3u) != 3u) ? -s : s;
     }
 

@@ -487,18 +487,28 @@ __device__ __forceinline__ void philox4x32_10(uint32_t& c0, uint32_t& c1, uint32
         }
     }
 
+// the first key word of HOOMD's Seed(id, timestep, seed): id << 24 | t[39:32] << 16 | seed16 (the second is t[31:0])
+__host__ __device__ __forceinline__ uint32_t philox_key0(uint32_t id, uint64_t t, uint32_t seed)
+    {
+    return (id << 24) | ((uint32_t)((t >> 32) & 0xffu) << 16) | (seed & 0xffffu);
+    }
+
+// One block of the stream as a double in (0, 1): the upper 53 bits of c0:c1, centred in their cell. The product is
+// exact (53 bits times a power of two), so a fused and an unfused add round the same value: the contraction setting
+// of the caller does not matter.
+__device__ __forceinline__ double philox_u01(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3)
+    {
+    philox4x32_10(c0, c1, c2, c3, k0, k1);
+    const uint64_t u = ((uint64_t)c0 << 32) | (uint64_t)c1;
+    return (double)(u >> 11) * (1.0 / 9007199254740992.0) + (0.5 / 9007199254740992.0);
+    }
+
 __device__ __forceinline__ double dpd_alpha(uint16_t seed, uint32_t tag_i, uint32_t tag_j, uint64_t timestep)
     {
     const uint32_t oi = tag_i > tag_j ? tag_j : tag_i;
     const uint32_t oj = tag_i > tag_j ? tag_i : tag_j;
-    const uint64_t ts = (uint64_t)(uint32_t)timestep; // reference passes unsigned int (:130-137)
-    const uint32_t k0 = (200u << 24) | ((uint32_t)((ts >> 32) & 0xffu) << 16) | (uint32_t)seed;
-    const uint32_t k1 = (uint32_t)(ts & 0xffffffffu);
-    uint32_t c0 = 0, c1 = oi, c2 = oj, c3 = 0;
-    philox4x32_10(c0, c1, c2, c3, k0, k1);
-    const uint64_t u = ((uint64_t)c0 << 32) | (uint64_t)c1;
-    const double u01 = (double)(u >> 11) * (1.0 / 9007199254740992.0) + (0.5 / 9007199254740992.0);
-    return -1.0 + 2.0 * u01;
+    const uint32_t ts = (uint32_t)timestep; // reference passes unsigned int (:130-137)
+    return -1.0 + 2.0 * philox_u01(philox_key0(200u, ts, seed), ts, 0, oi, oj, 0);
     }
 
 // ---------------------------------------------------------------------------

@@ -6,8 +6,8 @@
 // One thread per particle, Scalar4 rows as two 16-byte loads. The flow kind is a template parameter. No atomics.
 //
 // Random stream: HOOMD-5's RandomGenerator(Seed(id, timestep, seed), Counter(tag)) as the DPD thermostat restates
-// it (evaluators.hpp, dpd_alpha): key = {id << 24 | (t >> 32 & 0xff) << 16 | seed16, t & 0xffffffff}, counter
-// {k, tag, 0, 0} for draw k. HOOMD-blue's own source is not available to this project, so this bit layout is
+// it (evaluators.hpp: philox_key0, philox_u01): key = {id << 24 | (t >> 32 & 0xff) << 16 | seed16, t & 0xffffffff},
+// counter {k, tag, 0, 0} for draw k. HOOMD-blue's own source is not available to this project, so this bit layout is
 // NOT checked against HOOMD; the Philox core is checked by the golden known answers (philox4x32_10_kat).
 #include "azp_device.hpp"
 #include "evaluators.hpp"
@@ -50,18 +50,11 @@ template<int KIND> __device__ __forceinline__ double3 flow_velocity(const FlowKA
 // the three uniform(-c, c) draws of one particle (UniformDistribution: a + (b - a) u01)
 __device__ __forceinline__ double3 uniform3(uint32_t id, uint32_t seed, uint32_t tag, uint64_t t, double c)
     {
-    const uint32_t k0 = (id << 24) | ((uint32_t)((t >> 32) & 0xffu) << 16) | (seed & 0xffffu);
-    const uint32_t k1 = (uint32_t)(t & 0xffffffffu);
+    const uint32_t k0 = philox_key0(id, t, seed), k1 = (uint32_t)t;
     double r[3];
 #pragma unroll
     for (uint32_t k = 0; k < 3; ++k)
-        {
-        uint32_t c0 = k, c1 = tag, c2 = 0, c3 = 0;
-        philox4x32_10(c0, c1, c2, c3, k0, k1);
-        const uint64_t u = ((uint64_t)c0 << 32) | (uint64_t)c1;
-        const double u01 = (double)(u >> 11) * (1.0 / 9007199254740992.0) + (0.5 / 9007199254740992.0);
-        r[k] = -c + 2.0 * c * u01;
-        }
+        r[k] = -c + 2.0 * c * philox_u01(k0, k1, k, tag, 0, 0);
     return make_double3(r[0], r[1], r[2]);
     }
 

@@ -369,9 +369,8 @@ static EvapKArgs kernel_args(const azp_evaporate_args* args)
     k.z_lo = args->z_lo;
     k.z_hi = args->z_hi;
     k.threshold = 0;
-    const uint64_t t = args->timestep;
-    k.k0 = (RNG_EVAPORATOR << 24) | ((uint32_t)((t >> 32) & 0xffu) << 16) | (args->seed & 0xffffu);
-    k.k1 = (uint32_t)(t & 0xffffffffu);
+    k.k0 = philox_key0(RNG_EVAPORATOR, args->timestep, args->seed);
+    k.k1 = (uint32_t)args->timestep;
     k.N = args->N;
     k.solvent = args->solvent_type;
     k.evaporated = args->evaporated_type;

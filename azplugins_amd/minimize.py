@@ -30,7 +30,7 @@ import math
 import weakref
 
 from . import _lib
-from .simulation import All, ConstantVolume, Integrator, _launch
+from .simulation import All, ConstantVolume, Integrator, _DeviceControlled, _launch
 
 
 def _positive(name, value):
@@ -55,7 +55,7 @@ def _count(name, value):
     return int(value)
 
 
-class FIRE(Integrator):
+class FIRE(Integrator, _DeviceControlled):
     """``hoomd.md.minimize.FIRE`` reduced to translational degrees of freedom of all particles of a single-domain run.
 
     ``dt``: the largest time step, and the one the minimization starts from (``sim.dt`` keeps returning it; the step in
@@ -76,12 +76,11 @@ class FIRE(Integrator):
         self.fdec_alpha = _in_unit_interval("fdec_alpha", fdec_alpha)
         self.min_steps_adapt = _count("min_steps_adapt", min_steps_adapt)
         self.min_steps_conv = _count("min_steps_conv", min_steps_conv)
-        self._state = None     # AZP_FIRE_NSTATE doubles on the device, made at the first run
-        self._partials = None
         self._n = 0            # N of the last run
         self._sim = None       # (weak) the simulation of the last run
 
     def _initial(self):
+        """What the control state (AZP_FIRE_NSTATE doubles) starts from."""
         start = [0.0] * _lib.FIRE_NSTATE
         start[_lib.FIRE_DT] = self.dt
         start[_lib.FIRE_ALPHA] = self.alpha_start
@@ -113,23 +112,9 @@ class FIRE(Integrator):
         """The argument struct of this run, the state tensor and the partials buffer on the state's device, and the sums
         of the first step from a pass of their own: the velocities may have been changed between runs (after a run that
         ended with step two it leaves the partials that step two left, bit for bit)."""
-        import ctypes as C
-
-        import torch
-
         st = sim.state
-        if self._state is None or self._state.device != st.vel.device:
-            start = self._initial() if self._state is None else self._state.cpu().tolist()
-            self._state = torch.tensor(start, dtype=torch.float64, device=st.vel.device)
-        need = C.c_uint64(0)
-        _lib.check(_lib.lib().azp_fire_partials_size(st.N, C.byref(need)), "azp_fire_partials_size")
-        if self._partials is None or self._partials.numel() * 8 < need.value or self._partials.device != st.vel.device:
-            self._partials = torch.zeros(int(need.value) // 8, dtype=torch.float64, device=st.vel.device)
         a = self._args = _lib.FireArgs()
-        a.d_partials = self._partials.data_ptr()
-        a.partials_bytes = self._partials.numel() * 8
-        a.d_state = self._state.data_ptr()
-        a.box = st.box.to_c()
+        self._bind_control(a, st, self._initial(), "azp_fire_partials_size")
         a.dt_max, a.force_tol, a.energy_tol = self.dt, self.force_tol, self.energy_tol
         a.finc_dt, a.fdec_dt, a.alpha_start, a.fdec_alpha = self.finc_dt, self.fdec_dt, self.alpha_start, self.fdec_alpha
         a.min_steps_adapt, a.min_steps_conv = self.min_steps_adapt, self.min_steps_conv

@@ -89,6 +89,33 @@ def _launch(a, st, stream, *names):
         _lib.check(getattr(lib, name)(C.byref(a), stream), name)
 
 
+class _DeviceControlled:
+    """A stepper whose step is controlled on the device (the thermostats, ``minimize.FIRE``) and the buffers it owns: the
+    control state, float64 doubles made at the first run, which persist across runs and follow the particles to their
+    device, and the partials that its sums pass through."""
+
+    _state = None
+    _partials = None
+
+    def _bind_control(self, a, st, start, size_entry):
+        """Make the state from the list ``start`` (first run) or move it to the device of ``st``, size the partials with
+        libazp's ``size_entry``, and point the argument struct ``a`` at both and at the box."""
+        import torch
+
+        dev = st.vel.device
+        if self._state is None or self._state.device != dev:
+            start = start if self._state is None else self._state.cpu().tolist()
+            self._state = torch.tensor(start, dtype=torch.float64, device=dev)
+        need = C.c_uint64(0)
+        _lib.check(getattr(_lib.lib(), size_entry)(st.N, C.byref(need)), size_entry)
+        if self._partials is None or self._partials.numel() * 8 < need.value or self._partials.device != dev:
+            self._partials = torch.zeros(int(need.value) // 8, dtype=torch.float64, device=dev)
+        a.d_partials = self._partials.data_ptr()
+        a.partials_bytes = self._partials.numel() * 8
+        a.d_state = self._state.data_ptr()
+        a.box = st.box.to_c()
+
+
 class ConstantVolume:
     """NVE integration method (velocity Verlet) on all particles
     (``hoomd.md.methods.ConstantVolume(filter=hoomd.filter.All())``; without a

@@ -21,10 +21,10 @@ import math
 import weakref
 
 from . import _lib
-from .simulation import _launch
+from .simulation import _DeviceControlled, _launch
 
 
-class _Thermostat:
+class _Thermostat(_DeviceControlled):
     _name = None
     _kind = None
     _tau_may_be_zero = False
@@ -33,9 +33,7 @@ class _Thermostat:
         self.kT = kT
         self.tau = tau
         self._holders = weakref.WeakSet()  # the ConstantVolume methods that hold this thermostat
-        self._state = None                 # AZP_THERMOSTAT_NSTATE doubles on the device, made at the first run
-        self._pending = [0.0] * _lib.THERMOSTAT_NSTATE  # what the state starts from (set before the first run)
-        self._partials = None
+        self._pending = [0.0] * _lib.THERMOSTAT_NSTATE  # what the state (AZP_THERMOSTAT_NSTATE doubles) starts from
         self._ndof = 0.0     # Nf of the last run
         self._last_kT = 0.0  # kT of the last step run
 
@@ -95,26 +93,12 @@ class _Thermostat:
     def _begin(self, sim):
         """The refusals, the argument struct of this run, the state tensor and the partials buffer on the state's device,
         and K of the first step from a pass of its own (the velocities may have been changed between runs)."""
-        import ctypes as C
-
-        import torch
-
         integ, st = sim.operations.integrator, sim.state
         sim._check_thermostat(integ, integ.methods[0])
         if self._kind == _lib.THERMOSTAT_BUSSI:
             sim._warn_if_seed_unset()
-        if self._state is None or self._state.device != st.vel.device:
-            start = self._pending if self._state is None else self._state.cpu().tolist()
-            self._state = torch.tensor(start, dtype=torch.float64, device=st.vel.device)
-        need = C.c_uint64(0)
-        _lib.check(_lib.lib().azp_thermostat_partials_size(st.N, C.byref(need)), "azp_thermostat_partials_size")
-        if self._partials is None or self._partials.numel() * 8 < need.value or self._partials.device != st.vel.device:
-            self._partials = torch.zeros(int(need.value) // 8, dtype=torch.float64, device=st.vel.device)
         a = self._args = _lib.ThermostatArgs()
-        a.d_partials = self._partials.data_ptr()
-        a.partials_bytes = self._partials.numel() * 8
-        a.d_state = self._state.data_ptr()
-        a.box = st.box.to_c()
+        self._bind_control(a, st, self._pending, "azp_thermostat_partials_size")
         a.dt = integ.dt
         a.tau = self._tau
         a.ndof = float(3 * st.N - 3)

@@ -14,7 +14,9 @@ from azplugins_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1000, 2048 * 256 + 1]  # the last: two particles per lane, 1025 partials per slot
+# 63 * 256 to 64 * 256 + 1: 63, 64 and 65 partials, the fold's step from one round of a wave to two; the last: two
+# particles per lane, 1025 partials per slot
+SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1000, 63 * 256, 64 * 256, 64 * 256 + 1, 2048 * 256 + 1]
 L_BOX = (6.0, 7.0, 8.0)
 PARAMS = dict(dt_max=0.05, force_tol=1e-3, energy_tol=1e-7, finc_dt=1.1, fdec_dt=0.5, alpha_start=0.1, fdec_alpha=0.99,
               min_steps_adapt=5, min_steps_conv=10)

@@ -18,7 +18,9 @@ from azplugins_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [2, 63, 64, 65, 255, 256, 257, 1000, 2048 * 256 + 1]  # the last: two particles per lane, 1025 partials
+# 63 * 256 to 64 * 256 + 1: 63, 64 and 65 partials, the fold's step from one round of a wave to two; the last: two
+# particles per lane, 1025 partials
+SIZES = [2, 63, 64, 65, 255, 256, 257, 1000, 63 * 256, 64 * 256, 64 * 256 + 1, 2048 * 256 + 1]
 L_BOX = (6.0, 7.0, 8.0)
 
 
