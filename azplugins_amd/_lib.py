@@ -59,6 +59,10 @@ class PairArgs(C.Structure):
     ]
 
 
+class TableParams(C.Structure):
+    _fields_ = [("r_min", C.c_double), ("r_max", C.c_double), ("d_rows", C.c_void_p), ("n", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class DPDArgs(C.Structure):
     _fields_ = [
         ("pair", PairArgs),
@@ -493,6 +497,10 @@ SYMBOLS = {
     "azp_dw_params_unpack": (None, [_VP] + [_PD] * 4),
     "azp_quartic_params_make": (None, [_D] * 8 + [_VP]),
     "azp_quartic_params_unpack": (None, [_VP] + [_PD] * 8),
+    "azp_table_pack": (C.c_int, [_D, _D, _VP, _VP, C.c_uint32, C.c_int, _VP]),
+    "azp_pair_forces_table": (C.c_int, [C.POINTER(PairArgs), _VP, _VP]),
+    "azp_pair_forces_planned_table": (C.c_int, [_VP, C.POINTER(PairArgs), _VP, _VP]),
+    "azp_bond_forces_table": (C.c_int, [C.POINTER(BondArgs), _VP, _VP, _VP]),
     "azp_pair_forces_perturbed_lennard_jones": (C.c_int, [C.POINTER(PairArgs), _VP, _VP]),
     "azp_pair_forces_hertz": (C.c_int, [C.POINTER(PairArgs), _VP, _VP]),
     "azp_pair_forces_expanded_yukawa": (C.c_int, [C.POINTER(PairArgs), _VP, _VP]),
@@ -642,6 +650,31 @@ def check(rc, what="libazp call"):
     if rc != 0:
         msg = lib().azp_status_string(rc).decode()
         raise AzpError("%s failed: status %d (%s)" % (what, rc, msg))
+
+
+def table_pack(r_min, r_end, U, F, closed):
+    """azp_table_pack: the rows {U_k, U_{k+1} - U_k, F_k, F_{k+1} - F_k} of one table (numpy, n x 4), or None for
+    input the library refuses."""
+    import numpy as np
+
+    U = np.ascontiguousarray(U, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.float64)
+    if U.ndim != 1 or U.shape != F.shape:
+        return None
+    rows = np.zeros((max(len(U) - (1 if closed else 0), 0), 4))
+    rc = lib().azp_table_pack(float(r_min), float(r_end), U.ctypes.data, F.ctypes.data, len(U), 1 if closed else 0, rows.ctypes.data)
+    return rows if rc == 0 else None
+
+
+def table_params_rows(entries):
+    """The azp_table_params structs ``(r_min, r_max, device address of the rows, n)`` of ``entries`` as float64 words
+    (len(entries) x 4), the form the parameter tables are uploaded in."""
+    import numpy as np
+
+    arr = (TableParams * max(len(entries), 1))()
+    for p, (r_min, r_max, ptr, n) in zip(arr, entries):
+        p.r_min, p.r_max, p.d_rows, p.n = r_min, r_max, ptr, n
+    return np.frombuffer(bytes(arr), dtype=np.float64).reshape(-1, 4).copy()
 
 
 def raw_stream(device):

@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _lib
 from .bonded import BondedForce
+from .force import TableTypeParameter
 
 
 class Bond(BondedForce):
@@ -137,4 +138,39 @@ class Quartic(Bond):
         return {k: x.value for k, x in zip(keys, v)}
 
 
-__all__ = ["DoubleWell", "Quartic"]
+class Table(Bond):
+    """Tabulated bond potential (``hoomd.md.bond.Table``'s name; the reference has none, the semantics are defined in
+    ``include/azp.h`` and DESIGN 4.21). ``params[type] = dict(r_min=float, r_max=float, U=array, F=array)``:
+    ``width = len(U) >= 2`` samples of the energy and of ``F = -dU/dr`` at ``r_min + k (r_max - r_min) / (width - 1)``,
+    both end points included, interpolated linearly in between. A bond shorter than ``r_min`` or of length ``r_max`` or
+    more is an error ("bond out of bounds"), found by the kernel before it reads the table.
+
+    There is no ``_azplugins`` class behind it: the tables of all bond types live in one device tensor this object owns."""
+
+    _entry = "azp_bond_forces_table"
+    _schema = dict(r_min=float, r_max=float, U=np.ndarray, F=np.ndarray)
+    _parameter = TableTypeParameter
+
+    def _readback(self, key):
+        return None  # (params[...] hands back what was set: there is no C++ object that could hold anything else)
+
+    def _rows(self, types, values):
+        import torch
+
+        packed = []
+        for t, d in zip(types, values):
+            rows = _lib.table_pack(d["r_min"], d["r_max"], d["U"], d["F"], closed=True)
+            if rows is None:
+                raise _lib.AzpError("%s.params[%r]: needs 0 <= r_min < r_max and at least 2 finite samples in U and F"
+                                    % (type(self).__name__, t))
+            packed.append(rows)
+        self._table_rows = torch.from_numpy(np.concatenate(packed + [np.zeros((1, 4))])).to(self._state.device)
+        assert self._table_rows.data_ptr() % 32 == 0
+        entries, first = [], 0
+        for d, rows in zip(values, packed):
+            entries.append((d["r_min"], d["r_max"], self._table_rows.data_ptr() + 32 * first, len(rows)))
+            first += len(rows)
+        return _lib.table_params_rows(entries)
+
+
+__all__ = ["DoubleWell", "Quartic", "Table"]

@@ -246,6 +246,31 @@ int azp_wall_colloid_params_make(double A, double sigma, double a, double r_cut,
     return AZP_SUCCESS;
     }
 
+// ---- tabulated potentials (include/azp.h, azp_table_params): samples -> rows {U_k, U_{k+1} - U_k, F_k, F_{k+1} - F_k} ----
+// Each difference is ONE IEEE subtraction (tests/table_ref.py restates it bit for bit); the pair form's implicit zero at
+// r_end is the minuend of the last row.
+int azp_table_pack(double r_min, double r_end, const double* U, const double* F, uint32_t width, int closed, double* out_rows)
+    {
+    if (!U || !F || !out_rows || width < (closed ? 2u : 1u))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    if (!std::isfinite(r_min) || !std::isfinite(r_end) || !(r_min >= 0.0) || !(r_end > r_min))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    for (uint32_t k = 0; k < width; ++k)
+        if (!std::isfinite(U[k]) || !std::isfinite(F[k]))
+            return AZP_ERROR_INVALID_ARGUMENT;
+    const uint32_t n = closed ? width - 1 : width;
+    for (uint32_t k = 0; k < n; ++k)
+        {
+        const double U1 = (k + 1 < width) ? U[k + 1] : 0.0, F1 = (k + 1 < width) ? F[k + 1] : 0.0;
+        double* row = out_rows + 4 * (size_t)k;
+        row[0] = U[k];
+        row[1] = U1 - U[k];
+        row[2] = F[k];
+        row[3] = F1 - F[k];
+        }
+    return AZP_SUCCESS;
+    }
+
 int azp_version(void)
     {
     return AZP_VERSION_MAJOR * 1000 + AZP_VERSION_MINOR;

@@ -100,3 +100,11 @@ extern "C" int azp_bond_forces_quartic(const azp_bond_args* args, const azp_quar
     {
     return azp::launch_bonded<azp::BondGeometry, azp::EvalQuartic>(args, d_params, d_flags, stream);
     }
+
+// Tabulated bond (include/azp.h, azp_table_params): no counterpart in the reference. The flag word here means a bond
+// outside its table's [r_min, r_max), found before the table is read.
+extern "C" int azp_bond_forces_table(const azp_bond_args* args, const azp_table_params* d_params,
+                                     unsigned int* d_flags, void* stream)
+    {
+    return azp::launch_bonded<azp::BondGeometry, azp::EvalTable>(args, d_params, d_flags, stream);
+    }

@@ -442,6 +442,91 @@ struct EvalDPDConservative
     };
 
 // ---------------------------------------------------------------------------
+// Tabulated potential -- no counterpart in the reference; semantics in include/azp.h (azp_table_params) and DESIGN 4.21.
+// One evaluator for pair.Table (prepare + eval on a Coeff) and bond.Table (eval on the raw Params). A row of the table is
+// {U_k, U_{k+1} - U_k, F_k, F_{k+1} - F_k}, 32-byte aligned: one gather of two 16-byte loads from one 32-byte segment and
+// two FMAs per evaluation; row k + 1 is never read and the last interval needs no branch (the pair form's zero at the
+// cutoff is folded into row n - 1 by azp_table_pack). The rows are read through ordinary global loads: the hot part of a
+// table (a few hundred rows around the first neighbor shells) stays in a CU's L1 / the L2.
+// ---------------------------------------------------------------------------
+struct EvalTable
+    {
+    typedef azp_table_params Params;
+    static constexpr bool kSplitEnergy = false;
+    // Tile kernel instances (--save-temps, profiles/pair_table.md): at 4 waves per SIMD all take the 128 VGPRs and park 24-64
+    // of them in scratch (60-168 bytes per lane; Hertz at 4 waves: 25-54 VGPRs); at 3 waves they need 144-167 VGPRs and no
+    // scratch. Measured on the north-star liquid, 4 waves are faster at every table width (width 256: 0.214 against 0.249 ms
+    // per launch, width 4096: 0.293 against 0.303): the row gathers are latency the fourth wave hides.
+#ifndef AZP_TW_TABLE
+#define AZP_TW_TABLE 4
+#endif
+    static constexpr int kTileWaves = AZP_TW_TABLE; // waves per SIMD of the tile kernel (register budget)
+    struct Coeff
+        {
+        double rcutsq, r_min, inv_dr;
+        const double* rows;
+        uint32_t last, _pad; // n - 1: the index is clamped to it BEFORE the load
+        };
+    static __device__ __forceinline__ Coeff prepare(const Params& p, double rcutsq, bool)
+        {
+        Coeff c;
+        const bool live = rcutsq > 0.0 && p.n > 0 && p.d_rows != nullptr; // r_cut = 0: the pair never interacts
+        const double width = live ? sqrt(rcutsq) - p.r_min : 1.0;
+        c.rcutsq = (live && width > 0.0) ? rcutsq : -1.0;
+        c.r_min = p.r_min;
+        c.inv_dr = (double)p.n / width;
+        c.rows = p.d_rows;
+        c.last = live ? p.n - 1 : 0;
+        c._pad = 0;
+        return c;
+        }
+    // s >= 0 (the caller has tested r >= r_min); v_cvt_u32_f64 saturates, and the clamp keeps a rounded-up s of the last
+    // interval (s == n) inside the table: f is then 1 and the row gives the value at its right knot.
+    static __device__ __forceinline__ void interpolate(const double* __restrict__ rows, uint32_t last, double s, double& U, double& F)
+        {
+        uint32_t k = (uint32_t)s;
+        k = k < last ? k : last;
+        const double f = s - (double)k;
+        const double2* row = reinterpret_cast<const double2*>(rows) + 2 * (size_t)k;
+        const double2 u = row[0], g = row[1];
+        U = __builtin_fma(f, u.y, u.x);
+        F = __builtin_fma(f, g.y, g.x);
+        }
+    // pair form: r = rsq / sqrt(rsq) and 1 / r from one reciprocal square root, as Hertz
+    static __device__ __forceinline__ bool eval(const Coeff& c, double rsq, double& force_divr, double& pair_eng)
+        {
+        force_divr = 0.0;
+        pair_eng = 0.0;
+        if (rsq < c.rcutsq)
+            {
+            const double rinv = fast_rsqrt(rsq);
+            const double r = rsq * rinv;
+            if (r >= c.r_min) // (false for the NaN of rsq = 0 too)
+                {
+                double F;
+                interpolate(c.rows, c.last, (r - c.r_min) * c.inv_dr, pair_eng, F);
+                force_divr = F * rinv;
+                return true;
+                }
+            }
+        return false;
+        }
+    // bond form: a bond outside [r_min, r_max) -- or a type without a table -- is rejected BEFORE any table read
+    static __device__ __forceinline__ bool eval(const Params& p, double rsq, double& force_divr, double& bond_eng)
+        {
+        force_divr = 0.0;
+        bond_eng = 0.0;
+        const double r = sqrt(rsq);
+        if (!(r >= p.r_min && r < p.r_max) || p.n == 0 || p.d_rows == nullptr)
+            return false;
+        double F;
+        interpolate(p.d_rows, p.n - 1, (r - p.r_min) * ((double)p.n / (p.r_max - p.r_min)), bond_eng, F);
+        force_divr = F / r;
+        return true;
+        }
+    };
+
+// ---------------------------------------------------------------------------
 // XPLOR smoothing applied around any isotropic evaluator (HOOMD PotentialPair
 // restated; not pinned by a reference test).
 // ---------------------------------------------------------------------------

@@ -98,6 +98,67 @@ class _ParamView(dict):
         self.update({k: v})
 
 
+class TableTypeParameter(TypeParameter):
+    """``params`` of the tabulated potentials (``pair.Table``, ``bond.Table``): ``r_min``, for bonds ``r_max``, and the
+    samples ``U`` and ``F = -dU/dr`` as equally long one-dimensional arrays. What can be judged when a value is set
+    raises ``ValueError`` there: unequal lengths, too few samples, non-finite entries, a range that is empty, and, for
+    pairs, a table for ``(b, a)`` that differs from the one set for ``(a, b)`` (both orders name the same rows)."""
+
+    def __init__(self, name, schema, len_keys, on_change=None, readback=None):
+        super().__init__(name, schema, len_keys, on_change, readback)
+        self.closed = "r_max" in self.schema   # bond form: both end points stored
+        self.r_end = None                      # pairs: key -> r_cut, or None while it is not known
+        self._set_as = {}                      # the order of the type names each pair's table was set with
+
+    def _validate(self, value):
+        if not isinstance(value, dict):
+            raise TypeError("%s values must be dicts" % self.name)
+        if set(value) != set(self.schema):
+            raise ValueError("%s: expected the keys %s, got %s" % (self.name, sorted(self.schema), sorted(value)))
+        out = {k: float(value[k]) for k in self.schema if k not in ("U", "F")}
+        for k in ("U", "F"):
+            out[k] = np.array(value[k], dtype=np.float64)
+            if out[k].ndim != 1:
+                raise ValueError("%s: %s must be a one-dimensional array" % (self.name, k))
+        if out["U"].shape != out["F"].shape:
+            raise ValueError("%s: U and F differ in length (%d, %d)" % (self.name, len(out["U"]), len(out["F"])))
+        least = 2 if self.closed else 1
+        if len(out["U"]) < least:
+            raise ValueError("%s: a table needs at least %d samples, got %d" % (self.name, least, len(out["U"])))
+        if not (np.isfinite(out["U"]).all() and np.isfinite(out["F"]).all()):
+            raise ValueError("%s: U and F must be finite" % self.name)
+        if not (np.isfinite(out["r_min"]) and out["r_min"] >= 0.0):
+            raise ValueError("%s: r_min must be finite and >= 0, got %r" % (self.name, out["r_min"]))
+        if self.closed and not (np.isfinite(out["r_max"]) and out["r_max"] > out["r_min"]):
+            raise ValueError("%s: r_max must be finite and > r_min, got %r" % (self.name, out["r_max"]))
+        return out
+
+    @staticmethod
+    def _same(a, b):
+        return all(np.array_equal(a[k], b[k]) for k in a)
+
+    def __setitem__(self, key, value):
+        k = self._key(key)
+        v = self._validate(value)
+        r_end = self.r_end(k) if self.r_end is not None else None
+        if r_end is not None and r_end > 0.0 and not v["r_min"] < r_end:
+            raise ValueError("%s[%r]: r_min = %g is not below r_cut = %g" % (self.name, key, v["r_min"], r_end))
+        as_set = tuple(key) if self.len_keys == 2 else key
+        if k in self._data and self._set_as[k] != as_set and not self._same(v, self._data[k]):
+            raise ValueError("%s[%r] differs from the table set for %r: both name the same rows" % (self.name, key, self._set_as[k]))
+        self._data[k] = v
+        self._set_as[k] = as_set
+        if self._on_change:
+            self._on_change()
+
+    def __getitem__(self, key):
+        """What was set, the arrays as copies: a table is replaced as a whole, not edited in place."""
+        k = self._key(key)
+        if k not in self._data:
+            raise KeyError("%s[%r] is not set" % (self.name, key))
+        return {name: (v.copy() if isinstance(v, np.ndarray) else v) for name, v in self._data[k].items()}
+
+
 class ScalarTypeParameter(TypeParameter):
     """Per-type-pair scalar (``r_cut`` / ``r_on``) with a default."""
 

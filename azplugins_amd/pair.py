@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .force import Force, ScalarTypeParameter, TypeParameter
+from .force import Force, ScalarTypeParameter, TableTypeParameter, TypeParameter
 
 _SHIFT = {"none": 0, "shift": 1, "xplor": 2}
 
@@ -545,5 +545,79 @@ class TwoPatchMorse(Pair):
         return g
 
 
+class Table(Pair):
+    """Tabulated pair potential (``hoomd.md.pair.Table``'s name; the reference has none, the semantics are defined in
+    ``include/azp.h`` and DESIGN 4.21). ``params[(a, b)] = dict(r_min=float, U=array, F=array)``: ``width = len(U)``
+    samples of the energy and of ``F = -dU/dr`` at ``r_min + k (r_cut - r_min) / width``; between them both are
+    interpolated linearly, toward zero at ``r_cut`` in the last interval. Pairs closer than ``r_min`` or beyond
+    ``r_cut`` contribute nothing. ``mode`` is always ``"none"``.
+
+    There is no ``_azplugins`` class behind it: the tables of all type pairs live in one device tensor this object owns,
+    ``(a, b)`` and ``(b, a)`` share their rows, and the parameter struct of a pair points at them."""
+
+    _entry = "azp_pair_forces_table"
+    _planned_entry = "azp_pair_forces_planned_table"
+    _schema = dict(r_min=float, U=np.ndarray, F=np.ndarray)
+    _accepted_modes = ("none",)
+
+    def __init__(self, nlist, default_r_cut=None, default_r_on=0.0, mode="none"):
+        super().__init__(nlist, default_r_cut=default_r_cut, default_r_on=default_r_on, mode=mode)
+        self.params = TableTypeParameter("params", self._schema, 2, self._mark_dirty, self._readback)
+        self.params.r_end = self._r_cut_if_known
+
+    def _r_cut_if_known(self, key):
+        try:
+            return self.r_cut[key]
+        except KeyError:
+            return None
+
+    def _readback(self, key):
+        return None  # (params[...] hands back what was set: there is no C++ object that could hold anything else)
+
+    def _build_tables(self):
+        """Pack every type pair's samples for its current ``r_cut`` (``dr = (r_cut - r_min) / width``, so a changed
+        ``r_cut`` repacks) into one device tensor and point the parameter structs at it."""
+        import torch
+
+        types = self._state.types
+        T = len(types)
+        dev = self._state.device
+        name = type(self).__name__
+        packed, first = {}, 0
+        for i, a in enumerate(types):
+            for b in types[i:]:
+                d = self.params.get_raw((a, b))
+                if d is None:
+                    raise _lib.AzpError("%s.params[(%r, %r)] is not set" % (name, a, b))
+                rc = self.r_cut[(a, b)]
+                if rc == 0.0:
+                    continue  # never evaluated: no rows
+                rows = _lib.table_pack(d["r_min"], rc, d["U"], d["F"], closed=False)
+                if rows is None:
+                    raise _lib.AzpError("%s.params[(%r, %r)]: needs 0 <= r_min < r_cut and finite U, F of equal length "
+                                        "(r_min = %g, r_cut = %g)" % (name, a, b, d["r_min"], rc))
+                packed[(a, b)] = (first, rows)
+                first += len(rows)
+        all_rows = np.concatenate([rows for _, rows in packed.values()] + [np.zeros((1, 4))])
+        d_rows = torch.from_numpy(all_rows).to(dev)
+        assert d_rows.data_ptr() % 32 == 0
+        entries, rc2, ro2 = [], np.zeros(T * T), np.zeros(T * T)
+        for i, a in enumerate(types):
+            for j, b in enumerate(types):
+                key = (a, b) if i <= j else (b, a)
+                rc2[i * T + j] = self.r_cut[key] ** 2
+                ro2[i * T + j] = self.r_on[key] ** 2
+                if key in packed:
+                    at, rows = packed[key]
+                    entries.append((self.params.get_raw(key)["r_min"], self.r_cut[key], d_rows.data_ptr() + 32 * at, len(rows)))
+                else:
+                    entries.append((0.0, 0.0, 0, 0))
+        # argument structs kept by _compute_speculative and the plan's row classes refer to the old tensors and cutoffs
+        self._spec_cache = None
+        self._plan_builds = None
+        self._tables = dict(params=torch.from_numpy(_lib.table_params_rows(entries)).to(dev), rcutsq=torch.from_numpy(rc2).to(dev),
+                            ronsq=torch.from_numpy(ro2).to(dev), rows=d_rows)
+
+
 __all__ = ["Colloid", "DPDGeneralWeight", "DPDConservativeGeneralWeight", "ExpandedYukawa", "Hertz",
-           "PerturbedLennardJones", "TwoPatchMorse"]
+           "PerturbedLennardJones", "Table", "TwoPatchMorse"]

@@ -17,6 +17,8 @@
  *                                   (src/PotentialBondGPUKernel.cu.inc:25-29)
  *   azp_angle_forces_*           (no counterpart in the reference: HOOMD's md.angle conventions, defined here)
  *   azp_dihedral_forces_*        (no counterpart in the reference: md.dihedral's names, semantics defined here)
+ *   azp_pair_forces_table, azp_bond_forces_table
+ *                                (no counterpart in the reference: md.pair.Table / md.bond.Table, semantics defined here)
  *
  * Conventions (all restated from HOOMD-blue's ForceCompute data model):
  *   - Scalar = double. Scalar4 arrays are 4 consecutive doubles.
@@ -98,6 +100,35 @@ typedef struct azp_tpm_params { double M_d, M_rinv, r_eq, omega, alpha; uint8_t 
 typedef struct azp_dw_params { double r_1, r_diff, U_1, U_tilt; } azp_dw_params;
 /* src/BondEvaluatorQuartic.h:68-82 */
 typedef struct azp_quartic_params { double k, r_0, b_1, b_2, U_0, sigma_6, epsilon_x_4, delta; } azp_quartic_params;
+
+/* Tabulated potentials (no counterpart in the reference: HOOMD's md.pair.Table / md.bond.Table names, semantics
+ * DEFINED HERE). A table has n intervals of equal length dr from r_min: knots r_k = r_min + k dr,
+ * k = 0..n, with values U_k and F_k = -dU/dr at r_k (F is supplied by the user, not derived). For
+ * r_min <= r < r_min + n dr:
+ *     s = (r - r_min) / dr,  k = min(floor(s), n - 1),  f = s - k,
+ *     U(r) = U_k + f (U_{k+1} - U_k),  F(r) = F_k + f (F_{k+1} - F_k),  force_divr = F(r) / r.
+ * d_rows: n rows of four doubles {U_k, U_{k+1} - U_k, F_k, F_{k+1} - F_k} in device memory, 32-byte aligned
+ * (azp_table_pack writes them): one 32-byte read per evaluation, no read of row k + 1.
+ *   pair (azp_pair_forces_table): n = width, dr = (r_cut - r_min) / width with r_cut from d_rcutsq (r_max is ignored);
+ *     the value at r_cut is not stored, U_n = F_n = 0 is folded into row n - 1. r < r_min or r >= r_cut: nothing.
+ *     r_cut = 0, n = 0 or d_rows = NULL: the type pair is never evaluated.
+ *   bond (azp_bond_forces_table): n = width - 1, dr = (r_max - r_min) / n, both end points stored. r < r_min or
+ *     r >= r_max (or n = 0, d_rows = NULL, r_max <= r_min): the evaluator rejects the bond BEFORE any table read and
+ *     the kernel raises *d_flags ("bond out of bounds"). */
+typedef struct azp_table_params
+    {
+    double r_min;
+    double r_max;         /* bonds; ignored for pairs */
+    const double* d_rows; /* n x 4, device memory */
+    uint32_t n;           /* intervals */
+    uint32_t _pad;
+    } azp_table_params;
+/* Host function: `width` samples U, F -> rows. closed = 0 (pair form): the samples are the knots 0 .. width - 1 of
+ * width intervals on [r_min, r_end), the knot at r_end is the implicit zero; width rows are written. closed = 1 (bond
+ * form): the samples are all knots of width - 1 intervals on [r_min, r_end]; width - 1 rows are written.
+ * AZP_ERROR_INVALID_ARGUMENT (nothing written): a NULL pointer, width < 1 (closed: < 2), r_min < 0 or not finite,
+ * r_end <= r_min or not finite, a non-finite U or F. */
+int azp_table_pack(double r_min, double r_end, const double* U, const double* F, uint32_t width, int closed, double* out_rows);
 
 /* Host-side construction / inspection of the parameter structs: what the
  * reference does in each struct's pybind11::dict constructor and asDict() /
@@ -217,6 +248,9 @@ int azp_pair_forces_expanded_yukawa(const azp_pair_args* args, const azp_yukawa_
 int azp_pair_forces_colloid(const azp_pair_args* args, const azp_colloid_params* d_params, void* stream);
 /* PotentialPairConservativeGeneralWeight (src/export_PotentialPairDPDThermo.cc.inc:33-35) */
 int azp_pair_forces_dpd_conservative(const azp_pair_args* args, const azp_dpd_params* d_params, void* stream);
+/* Tabulated pair potential (azp_table_params above). shift_mode must be AZP_SHIFT_NONE: AZP_ERROR_INVALID_ARGUMENT
+ * otherwise. The rows every d_params entry points at are borrowed for the call like d_params itself. */
+int azp_pair_forces_table(const azp_pair_args* args, const azp_table_params* d_params, void* stream);
 
 /* ---- tile plan: compiled neighbor list for the LDS-staged pair kernel ----
  * The generic azp_pair_forces_* kernels gather every neighbor position through
@@ -320,6 +354,8 @@ int azp_pair_forces_planned_colloid(azp_pair_plan* plan, const azp_pair_args* ar
                                     void* stream);
 int azp_pair_forces_planned_dpd_conservative(azp_pair_plan* plan, const azp_pair_args* args,
                                              const azp_dpd_params* d_params, void* stream);
+int azp_pair_forces_planned_table(azp_pair_plan* plan, const azp_pair_args* args, const azp_table_params* d_params,
+                                  void* stream);
 
 /* Mirrors hoomd::md::kernel::dpd_pair_args_t. */
 typedef struct azp_dpd_args
@@ -392,6 +428,9 @@ int azp_bond_forces_double_well(const azp_bond_args* args, const azp_dw_params* 
                                 void* stream);
 int azp_bond_forces_quartic(const azp_bond_args* args, const azp_quartic_params* d_params, unsigned int* d_flags,
                             void* stream);
+/* Tabulated bond potential (azp_table_params above): a bond outside [r_min, r_max) raises *d_flags. */
+int azp_bond_forces_table(const azp_bond_args* args, const azp_table_params* d_params, unsigned int* d_flags,
+                          void* stream);
 
 /* ---- angle forces ----
  * Three-body bending potentials over a per-particle angle table. The reference holds no angle code; the semantics
