@@ -252,7 +252,7 @@ class NlistArgs(C.Structure):
         ("d_head_list", C.c_void_p),
         ("d_nlist", C.c_void_p),
         ("row_capacity", C.c_uint32),
-        ("_pad2", C.c_uint32),
+        ("fractional_cells", C.c_uint32),
         ("d_max_neigh", C.c_void_p),
     ]
 

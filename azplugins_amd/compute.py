@@ -559,8 +559,7 @@ def rdf_from_counts(counts, n_a, n_b, n_ab, volume, r_max):
 
 def perpendicular_widths(box):
     """Distances between opposite faces of ``box`` (a ``state.Box``; HOOMD ``BoxDim.getNearestPlaneDistance``)."""
-    t = box.xy * box.yz - box.xz
-    return (box.Lx / np.sqrt(1.0 + box.xy * box.xy + t * t), box.Ly / np.sqrt(1.0 + box.yz * box.yz), box.Lz)
+    return box.nearest_plane_distance
 
 
 def _check_rdf_filter(name, f):

@@ -38,15 +38,51 @@ __device__ __forceinline__ int cell_coord(const GridDev& g, int k, double x)
     return c;
     }
 
+// Fractional cells (azp_nlist_args.fractional_cells): the grid lives in the coordinates f along the lattice vectors,
+// f in [-0.5, 0.5) for a wrapped particle (wrap_into_box's own frame); the cells are parallelepipeds.
+struct FracDev
+    {
+    double xy, xzp, yz; // xzp = xz - xy yz
+    double Lxinv, Lyinv, Lzinv;
+    };
+
+static FracDev make_frac_dev(const azp_box& b)
+    {
+    FracDev f;
+    f.xy = b.tilt[0]; f.xzp = b.tilt[1] - b.tilt[0] * b.tilt[2]; f.yz = b.tilt[2];
+    f.Lxinv = 1.0 / b.L[0]; f.Lyinv = 1.0 / b.L[1]; f.Lzinv = 1.0 / b.L[2];
+    return f;
+    }
+
+__device__ __forceinline__ double3 fractional(const FracDev& f, double x, double y, double z)
+    {
+    return make_double3(__builtin_fma(-f.xzp, z, __builtin_fma(-f.xy, y, x)) * f.Lxinv, __builtin_fma(-f.yz, z, y) * f.Lyinv,
+                        z * f.Lzinv);
+    }
+
+__device__ __forceinline__ uint32_t cell_index(const GridDev& g, const double3& p)
+    {
+    const int cx = cell_coord(g, 0, p.x), cy = cell_coord(g, 1, p.y), cz = cell_coord(g, 2, p.z);
+    return (uint32_t)((cz * g.dim[1] + cy) * g.dim[0] + cx);
+    }
+
 __global__ void __launch_bounds__(256) cell_assign_kernel(uint32_t n_total, const double* __restrict__ pos, GridDev g,
                                                           uint32_t* __restrict__ cell_of)
     {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_total)
         return;
+    cell_of[i] = cell_index(g, load_scalar3_of4(pos, i));
+    }
+
+__global__ void __launch_bounds__(256) cell_assign_frac_kernel(uint32_t n_total, const double* __restrict__ pos, GridDev g, FracDev fr,
+                                                               uint32_t* __restrict__ cell_of)
+    {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_total)
+        return;
     const double3 p = load_scalar3_of4(pos, i);
-    const int cx = cell_coord(g, 0, p.x), cy = cell_coord(g, 1, p.y), cz = cell_coord(g, 2, p.z);
-    cell_of[i] = (uint32_t)((cz * g.dim[1] + cy) * g.dim[0] + cx);
+    cell_of[i] = cell_index(g, fractional(fr, p.x, p.y, p.z));
     }
 
 // cell_start[c] = first position in the sorted order whose cell id is >= c
@@ -99,9 +135,22 @@ __global__ void __launch_bounds__(256) bin_assign_count_kernel(uint32_t n_total,
     uint32_t c = 0;
     if (active)
         {
+        c = cell_index(g, load_scalar3_of4(pos, i));
+        cell_of[i] = c;
+        }
+    (void)wave_aggregated_add(count, c, active);
+    }
+
+__global__ void __launch_bounds__(256) bin_assign_count_frac_kernel(uint32_t n_total, const double* __restrict__ pos, GridDev g, FracDev fr,
+                                                                    uint32_t* __restrict__ cell_of, uint32_t* __restrict__ count)
+    {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = i < n_total;
+    uint32_t c = 0;
+    if (active)
+        {
         const double3 p = load_scalar3_of4(pos, i);
-        const int cx = cell_coord(g, 0, p.x), cy = cell_coord(g, 1, p.y), cz = cell_coord(g, 2, p.z);
-        c = (uint32_t)((cz * g.dim[1] + cy) * g.dim[0] + cx);
+        c = cell_index(g, fractional(fr, p.x, p.y, p.z));
         cell_of[i] = c;
         }
     (void)wave_aggregated_add(count, c, active);
@@ -296,6 +345,7 @@ struct NlistKArgs
     uint32_t row_capacity;
     BoxDev box;
     GridDev grid;
+    FracDev frac;
     uint32_t N;
     uint32_t ntypes;
     };
@@ -312,8 +362,13 @@ struct NlistKArgs
 // streamed out once instead of with scattered 4-byte stores.
 // FILL = false: count; FILL = true: write rows at head_list[i].
 // MI = true: per-pair minimum image (boxes with < 4 cells along a periodic axis);
-// MI = false: images resolved once per staged candidate. Orthorhombic boxes only
-// (nlist_scan refuses tilted ones).
+// MI = false: images resolved once per staged candidate.
+// FRAC = true (MI = false only): fractional cells, possibly of a tilted box -- the image of a staged particle is the
+// one whose fractional coordinates lie nearest to the home cell's centre, n_k = rint(f_k - fc_k) lattice vectors
+// taken off per periodic axis. Unique: with >= 4 cells per periodic axis everything in the stencil lies within
+// 1.5 / dim <= 0.375 of the centre; and two such images within r_list of each other are each other's minimum image
+// (a slab of cells is >= r_list thick, so their f differ by <= 1 / dim, any other image by >= 1 - 3 / dim more).
+// With MI = true the per-pair min_image takes its triclinic branch by itself: one instance for both kinds of cells.
 // Dense cells are handled in batches of NL_CAP candidates x NL_HOME home particles.
 // ---------------------------------------------------------------------------
 constexpr uint32_t NL_CAP = 1280;
@@ -328,9 +383,29 @@ struct NlStencil
     uint32_t off[28];
     };
 
-template<bool FILL, bool MI> __global__ void __launch_bounds__(NL_THREADS) nlist_cell_kernel(const NlistKArgs a, uint32_t ncell,
-                                                                                      uint32_t nblocks_pad8)
+// the image of (x, y, z) nearest to the point fc of fractional space
+__device__ __forceinline__ void image_near_frac(const BoxDev& b, const FracDev& fr, double fcx, double fcy, double fcz, double& x, double& y,
+                                                double& z)
     {
+    const double3 f = fractional(fr, x, y, z);
+    if (b.pz)
+        {
+        const double n = rint(f.z - fcz);
+        z = __builtin_fma(-b.Lz, n, z); y = __builtin_fma(-b.Lz * b.yz, n, y); x = __builtin_fma(-b.Lz * b.xz, n, x);
+        }
+    if (b.py)
+        {
+        const double n = rint(f.y - fcy);
+        y = __builtin_fma(-b.Ly, n, y); x = __builtin_fma(-b.Ly * b.xy, n, x);
+        }
+    if (b.px)
+        x = __builtin_fma(-b.Lx, rint(f.x - fcx), x);
+    }
+
+template<bool FILL, bool MI, bool FRAC = false> __global__ void __launch_bounds__(NL_THREADS) nlist_cell_kernel(const NlistKArgs a, uint32_t ncell,
+                                                                                                    uint32_t nblocks_pad8)
+    {
+    static_assert(!(MI && FRAC), "per-pair minimum image needs no fractional form");
     __shared__ double sx[NL_CAP + 128], sy[NL_CAP + 128], sz[NL_CAP + 128];
     __shared__ uint32_t sidx[NL_CAP + 128], styp[NL_CAP + 128];
     __shared__ uint32_t run[NL_HOME];
@@ -396,7 +471,7 @@ template<bool FILL, bool MI> __global__ void __launch_bounds__(NL_THREADS) nlist
     __syncthreads();
     const uint32_t total = st.off[27];
 
-    // cell centre: reference point of the staged images
+    // cell centre: reference point of the staged images (FRAC: in fractional coordinates, as the grid is)
     const double ccx = a.grid.lo[0] + (cx + 0.5) / a.grid.winv[0];
     const double ccy = a.grid.lo[1] + (cy + 0.5) / a.grid.winv[1];
     const double ccz = a.grid.lo[2] + (cz + 0.5) / a.grid.winv[2];
@@ -429,7 +504,9 @@ template<bool FILL, bool MI> __global__ void __launch_bounds__(NL_THREADS) nlist
                 const uint32_t j = a.order[st.first[s] + (g - st.off[s])];
                 const double4 pj = load_scalar4(a.pos, j);
                 double x = pj.x, y = pj.y, z = pj.z;
-                if (!MI)
+                if (FRAC)
+                    image_near_frac(a.box, a.frac, ccx, ccy, ccz, x, y, z);
+                else if (!MI)
                     {
                     if (a.box.px) x = __builtin_fma(-a.box.Lx, rint((x - ccx) * a.box.Lxinv), x);
                     if (a.box.py) y = __builtin_fma(-a.box.Ly, rint((y - ccy) * a.box.Lyinv), y);
@@ -448,7 +525,9 @@ template<bool FILL, bool MI> __global__ void __launch_bounds__(NL_THREADS) nlist
                     continue; // ghost: no row
                 const double4 pi = load_scalar4(a.pos, i);
                 double xi = pi.x, yi = pi.y, zi = pi.z;
-                if (!MI)
+                if (FRAC)
+                    image_near_frac(a.box, a.frac, ccx, ccy, ccz, xi, yi, zi);
+                else if (!MI)
                     {
                     if (a.box.px) xi = __builtin_fma(-a.box.Lx, rint((xi - ccx) * a.box.Lxinv), xi);
                     if (a.box.py) yi = __builtin_fma(-a.box.Ly, rint((yi - ccy) * a.box.Lyinv), yi);
@@ -567,6 +646,8 @@ static int check_nlist_args(const azp_nlist_args* a)
     for (int k = 0; k < 3; ++k)
         if (a->grid.dim[k] == 0 || !(a->grid.width[k] > 0.0))
             return AZP_ERROR_INVALID_ARGUMENT;
+    if (a->fractional_cells > 1)
+        return AZP_ERROR_INVALID_ARGUMENT;
     return 0;
     }
 
@@ -588,6 +669,7 @@ static NlistKArgs make_nlist_kargs(const azp_nlist_args& a)
     k.row_capacity = a.row_capacity;
     k.box = make_box_dev(a.box);
     k.grid = make_grid_dev(a.grid);
+    k.frac = make_frac_dev(a.box);
     k.N = a.N;
     k.ntypes = a.ntypes;
     return k;
@@ -602,8 +684,12 @@ extern "C" int azp_nlist_cell_assign(const azp_nlist_args* args, void* stream)
     if (args->n_total == 0)
         return AZP_SUCCESS;
     const uint32_t grid = (args->n_total + 255u) / 256u;
-    hipLaunchKernelGGL(cell_assign_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args->n_total,
-                       args->d_pos, make_grid_dev(args->grid), args->d_cell_of);
+    if (args->fractional_cells)
+        hipLaunchKernelGGL(cell_assign_frac_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args->n_total,
+                           args->d_pos, make_grid_dev(args->grid), make_frac_dev(args->box), args->d_cell_of);
+    else
+        hipLaunchKernelGGL(cell_assign_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args->n_total,
+                           args->d_pos, make_grid_dev(args->grid), args->d_cell_of);
     return (int)hipGetLastError();
     }
 
@@ -618,7 +704,10 @@ extern "C" int azp_nlist_bin(const azp_nlist_args* args, uint32_t* d_cursor, uin
     if (e != hipSuccess)
         return (int)e;
     const uint32_t n = args->n_total;
-    if (n)
+    if (n && args->fractional_cells)
+        hipLaunchKernelGGL(bin_assign_count_frac_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n, args->d_pos, make_grid_dev(args->grid),
+                           make_frac_dev(args->box), args->d_cell_of, d_cursor);
+    else if (n)
         hipLaunchKernelGGL(bin_assign_count_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n, args->d_pos, make_grid_dev(args->grid),
                            args->d_cell_of, d_cursor);
     const uint32_t nblk = (ncell + 4095u) / 4096u;
@@ -668,9 +757,11 @@ static int nlist_scan(const azp_nlist_args* args, void* stream, bool fill)
         return AZP_ERROR_INVALID_ARGUMENT; // the 27-cell search needs cells as wide as the list radius
     if (fill && args->row_capacity && (!args->d_n_neigh || !args->d_max_neigh))
         return AZP_ERROR_INVALID_ARGUMENT;
-    // The cells are Cartesian and the search reaches +-1 cell: across a periodic y or z face of a tilted box the image of
-    // a neighbor is shifted by xy Ly (xz Lz, yz Lz), not a whole number of cells, and pairs would be dropped silently
-    if (args->box.tilt[0] != 0.0 || args->box.tilt[1] != 0.0 || args->box.tilt[2] != 0.0)
+    // Cartesian cells and a search that reaches +-1 cell: across a periodic y or z face of a tilted box the image of a
+    // neighbor is shifted by xy Ly (xz Lz, yz Lz), not a whole number of cells, and pairs would be dropped silently.
+    // Fractional cells follow the lattice vectors: there the +-1 stencil is complete in any box.
+    const bool frac = args->fractional_cells != 0;
+    if (!frac && (args->box.tilt[0] != 0.0 || args->box.tilt[1] != 0.0 || args->box.tilt[2] != 0.0))
         return AZP_ERROR_INVALID_ARGUMENT;
     if (args->N == 0)
         return AZP_SUCCESS;
@@ -687,11 +778,13 @@ static int nlist_scan(const azp_nlist_args* args, void* stream, bool fill)
     if (fill)
         {
         if (mi) hipLaunchKernelGGL((nlist_cell_kernel<true, true>), dim3(grid), dim3(NL_THREADS), 0, s, k, ncell, grid);
+        else if (frac) hipLaunchKernelGGL((nlist_cell_kernel<true, false, true>), dim3(grid), dim3(NL_THREADS), 0, s, k, ncell, grid);
         else hipLaunchKernelGGL((nlist_cell_kernel<true, false>), dim3(grid), dim3(NL_THREADS), 0, s, k, ncell, grid);
         }
     else
         {
         if (mi) hipLaunchKernelGGL((nlist_cell_kernel<false, true>), dim3(grid), dim3(NL_THREADS), 0, s, k, ncell, grid);
+        else if (frac) hipLaunchKernelGGL((nlist_cell_kernel<false, false, true>), dim3(grid), dim3(NL_THREADS), 0, s, k, ncell, grid);
         else hipLaunchKernelGGL((nlist_cell_kernel<false, false>), dim3(grid), dim3(NL_THREADS), 0, s, k, ncell, grid);
         }
     return (int)hipGetLastError();

@@ -1202,9 +1202,9 @@ int plan_build_from_cells(PairPlan& p, const azp_nlist_args& c, const azp_pair_a
     ++p.builds;
     if (c.N == 0)
         return AZP_SUCCESS;
-    if (c.box.tilt[0] != 0.0 || c.box.tilt[1] != 0.0 || c.box.tilt[2] != 0.0 || c.ntypes > 255)
+    if (c.box.tilt[0] != 0.0 || c.box.tilt[1] != 0.0 || c.box.tilt[2] != 0.0 || c.fractional_cells || c.ntypes > 255)
         {
-        p.invalid_reason = 6; // cells of a tilted box are not binned by azp_nlist_cell_assign either; types are staged as bytes
+        p.invalid_reason = 6; // this compiler reads Cartesian cells of an orthorhombic box alone; types are staged as bytes
         return AZP_SUCCESS;
         }
     uint32_t row_cap = c.row_capacity ? c.row_capacity : 160u;

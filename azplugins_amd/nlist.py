@@ -7,6 +7,7 @@ buffers; the binning, counting and filling are libazp kernels.
 """
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -17,6 +18,31 @@ from . import _lib
 def _padded_rows(max_row):
     """Row capacity for rows of up to ``max_row`` entries: ~6 % head room, a multiple of 8 entries (32-B aligned rows)."""
     return (int(max_row * 1.06) + 4 + 7) // 8 * 8
+
+
+def cell_grid(box, r_list_max, sub=1):
+    """The cell grid of ``box`` (a ``state.Box``) for a list radius ``r_list_max``: ``(dims, lo, width, fractional)``.
+
+    ``dims[k] = max(floor(w_k / (r_list_max / sub)), 1)`` with ``w`` the box's perpendicular widths
+    (``Box.nearest_plane_distance``): a slab of cells is at least ``r_list_max / sub`` thick, so two particles within
+    ``r_list_max`` differ by at most ``sub`` cells along every axis. An untilted box gets Cartesian cells
+    (``fractional`` False: ``lo = -L / 2``, ``width = L / dims``, where w = L). A tilted box gets cells in the fractional
+    coordinates f along its lattice vectors, f_z = z / Lz, f_y = (y - yz z) / Ly, f_x = (x - xy y - (xz - xy yz) z) / Lx,
+    each on [-0.5, 0.5) (``fractional`` True: ``lo = -0.5``, ``width = 1 / dims``): parallelepipeds, for which the +-1
+    stencil is complete across the tilted periodic faces. Every periodic axis needs ``w_k >= 2 r_list_max`` (else the
+    minimum image of a listed pair is not unique): ``AzpError`` otherwise. Host arithmetic only."""
+    r = float(r_list_max)
+    fractional = bool(box.is_triclinic)
+    L = [box.Lx, box.Ly, box.Lz]
+    w = box.nearest_plane_distance if fractional else L
+    for k in range(3):
+        if box.periodic[k] and w[k] < 2.0 * r:
+            raise _lib.AzpError("box dimension %d (%g%s) is smaller than 2 (r_cut + buffer) = %g"
+                                % (k, w[k], " between its tilted faces" if fractional else "", 2 * r))
+    dims = tuple(max(int(math.floor(w[k] / (r / sub))), 1) for k in range(3))
+    if fractional:
+        return dims, (-0.5, -0.5, -0.5), tuple(1.0 / d for d in dims), True
+    return dims, tuple(-0.5 * L[k] for k in range(3)), tuple(L[k] / dims[k] for k in range(3)), False
 
 
 class NeighborList:
@@ -158,7 +184,9 @@ class NeighborList:
 
 
 class Cell(NeighborList):
-    """Cell-list neighbor list (full storage, as HOOMD's GPU pair kernels use)."""
+    """Cell-list neighbor list (full storage, as HOOMD's GPU pair kernels use). Any box of ``state.Box``: an untilted
+    one is binned in Cartesian cells, a tilted one in cells along its lattice vectors (``cell_grid``); in a tilted box
+    the list always has its HOOMD-format rows (no fused mode) and its consumers compile their tile plans from them."""
 
     # azp_nlist_bin (counting sort in libazp) instead of the framework's sort pipeline: by default (None) where the cells
     # number more than 2^16 (16-bit keys do not hold them and the framework sort needs four radix passes), AZP_NATIVE_BINNING=1 / 0
@@ -315,10 +343,7 @@ class Cell(NeighborList):
         if rl_max <= 0.0:
             raise _lib.AzpError("neighbor list has no consumer with r_cut > 0")
         box = state.box
-        L = box.L
-        for k in range(3):
-            if box.periodic[k] and L[k] < 2.0 * rl_max:
-                raise _lib.AzpError("box dimension %d (%g) is smaller than 2 (r_cut + buffer) = %g" % (k, L[k], 2 * rl_max))
+        grid = cell_grid(box, rl_max)  # (refuses a box too narrow for the list radius)
         n_total = state.n_max
         N = state.N
         a = _lib.NlistArgs()
@@ -326,10 +351,6 @@ class Cell(NeighborList):
         a.n_total = n_total
         a.d_pos = state.pos.data_ptr()
         a.box = box.to_c()
-        # grid over the periodic box; a triclinic box is binned in its bounding
-        # orthorhombic frame only when untilted, so require orthorhombic here
-        if box.is_triclinic:
-            raise _lib.AzpError("Cell neighbor list: triclinic boxes are not supported yet")
         a.ntypes = ntypes
         # (kept across rebuilds while the cutoffs stand: a host-to-device copy from pageable memory waits for the stream)
         key = (self._consumer_version, self.buffer, str(dev), ntypes)
@@ -340,9 +361,9 @@ class Cell(NeighborList):
         a.d_rlistsq = rlistsq.data_ptr()
         stream = torch.cuda.current_stream(dev).cuda_stream
         self._rl_max, self._box_at_build = rl_max, box
-        self._fused_active = self._fused_eligible()
+        self._fused_active = self._fused_eligible(box)
         sub = 2 if (self._fused_active and self._half_cells_wanted(box, rl_max, n_total)) else 1
-        bins = self._bin(a, box, rl_max, n_total, sub, dev, stream)
+        bins = self._bin(a, box, rl_max, n_total, sub, dev, stream, grid if sub == 1 else None)
 
         keep = []
         if "bond" in self.exclusions and state.n_bonds:
@@ -382,7 +403,7 @@ class Cell(NeighborList):
 
     def _half_cells_wanted(self, box, rl_max, n_total):
         mode = self.half_cells
-        if mode <= 0 or self._half_failures >= 2:
+        if mode <= 0 or self._half_failures >= 2 or box.is_triclinic:
             return False
         L = box.L
         dims = [max(int(np.floor(L[k] / (0.5 * rl_max))), 1) for k in range(3)]
@@ -391,20 +412,21 @@ class Cell(NeighborList):
             return False
         return mode >= 2 or n_total >= 0.75 * dims[0] * dims[1] * dims[2]
 
-    def _bin(self, a, box, rl_max, n_total, sub, dev, stream):
-        """Bin the particles of ``a.d_pos`` into cells at least ``rl_max / sub`` wide: fills the grid, d_cell_of,
-        d_order, d_cell_start of ``a``; returns the tensors to keep alive."""
+    def _bin(self, a, box, rl_max, n_total, sub, dev, stream, grid=None):
+        """Bin the particles of ``a.d_pos`` into cells at least ``rl_max / sub`` wide (``grid``: cell_grid's answer for
+        these arguments, if the caller has it): fills the grid, d_cell_of, d_order, d_cell_start of ``a``; returns the
+        tensors to keep alive."""
         import torch
 
         l = _lib.lib()
-        L = box.L
+        dims, lo, width, fractional = grid or cell_grid(box, rl_max, sub)
         for k in range(3):
-            dim = max(int(np.floor(L[k] / (rl_max / sub))), 1)
-            a.grid.dim[k] = dim
-            a.grid.width[k] = L[k] / dim
-            a.grid.lo[k] = -0.5 * L[k]
+            a.grid.dim[k] = dims[k]
+            a.grid.width[k] = width[k]
+            a.grid.lo[k] = lo[k]
             a.grid.periodic[k] = 1 if box.periodic[k] else 0
         a.cell_subdivision = sub
+        a.fractional_cells = 1 if fractional else 0  # (a tilted box: cells along its lattice vectors)
         ncell = int(a.grid.dim[0]) * int(a.grid.dim[1]) * int(a.grid.dim[2])
         cell_of = torch.empty(n_total, dtype=torch.int32, device=dev)
         a.d_cell_of = cell_of.data_ptr()
@@ -450,8 +472,10 @@ class Cell(NeighborList):
         bins = self._bin(a, self._box_at_build, self._rl_max, a.n_total, 1, dev, torch.cuda.current_stream(dev).cuda_stream)
         self._keep = (self._keep[0], bins, self._keep[2])
 
-    def _fused_eligible(self):
-        return bool(self.fused and not self._compact and len(self._consumers) == 1 and self._consumers[0].takes_plan_from_cells())
+    def _fused_eligible(self, box):
+        # (the plan compiler reads Cartesian cells: in a tilted box the consumer compiles its plan from the list's rows)
+        return bool(self.fused and not self._compact and not box.is_triclinic and len(self._consumers) == 1
+                    and self._consumers[0].takes_plan_from_cells())
 
     def compile_plan(self, plan, pair_args, stream):
         """Fused mode: compile the consumer's tile plan (``_lib.PairPlan``, for its azp_pair_args) straight from the

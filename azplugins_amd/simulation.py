@@ -316,7 +316,10 @@ class Simulation:
         arrays. Every step the ghost rows of the arrays the forces read are exchanged; when
         any rank's distance check asks for a neighbor-list rebuild, all ranks migrate their
         particles and re-select their ghosts first (HOOMD: Communicator::migrateParticles /
-        exchangeGhosts ahead of NeighborList::compute)."""
+        exchangeGhosts ahead of NeighborList::compute). A tilted box is refused: the domain's slabs are Cartesian."""
+        if self.state.box.is_triclinic:
+            raise _lib.AzpError("attach_domain: %r is tilted -- a domain cuts the box into Cartesian slabs, whose ghost layers "
+                                "do not follow a tilted periodic face; run a tilted box on one device" % (self.state.box,))
         for kind, g in self.state.groups.items():
             if g.n and g.tags is None:
                 raise _lib.AzpError("attach_domain: a %s needs its topology by tag (State.set_global_%ss) -- the index-based "

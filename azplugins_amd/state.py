@@ -11,6 +11,8 @@ objects the reference's force classes are attached to (``hoomd.Snapshot``,
 * ``accel`` (n_max, 4) float64 ax, ay, az, 0: ``None`` until a ``flow.Langevin`` run creates it
 """
 
+import math
+
 import numpy as np
 
 from . import _lib
@@ -47,6 +49,13 @@ class Box:
     @property
     def is_triclinic(self):
         return self.xy != 0.0 or self.xz != 0.0 or self.yz != 0.0
+
+    @property
+    def nearest_plane_distance(self):
+        """Distances between opposite faces of the box (HOOMD ``BoxDim.getNearestPlaneDistance``): the widths of the
+        box perpendicular to its yz, xz and xy faces."""
+        t = self.xy * self.yz - self.xz
+        return (self.Lx / math.sqrt(1.0 + self.xy * self.xy + t * t), self.Ly / math.sqrt(1.0 + self.yz * self.yz), self.Lz)
 
     def to_c(self):
         key = (self.Lx, self.Ly, self.Lz, self.xy, self.xz, self.yz, self.periodic)

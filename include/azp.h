@@ -573,8 +573,9 @@ int azp_dihedral_forces_opls(const azp_dihedral_args* args, const azp_dihedral_o
  * d_cell_sorted) -> cell_bounds -> count -> (caller: exclusive scan) -> fill. */
 typedef struct azp_cell_grid
     {
-    double lo[3];        /* lower corner of the grid                     */
-    double width[3];     /* cell width, >= largest r_list (>= half of it with azp_nlist_args.cell_subdivision = 2) */
+    double lo[3];        /* lower corner of the grid (fractional cells: in units of f, -0.5) */
+    double width[3];     /* cell width, >= largest r_list (>= half of it with azp_nlist_args.cell_subdivision = 2);
+                          * fractional cells: in units of f, 1 / dim, the slab of cells then >= r_list thick */
     uint32_t dim[3];
     int32_t periodic[3]; /* 1: cell index wraps; 0: clamped (ghost slab) */
     } azp_cell_grid;
@@ -611,7 +612,12 @@ typedef struct azp_nlist_args
      * larger rows if it exceeds row_capacity). row_capacity = 0: rows are exact
      * (head_list from a scan of the count pass). */
     uint32_t row_capacity;
-    uint32_t _pad2;
+    /* 0: Cartesian cells, grid.lo / grid.width in length units (orthorhombic boxes only for count / fill).
+     * 1: fractional cells, parallelepipeds along the lattice vectors of `box`: particles are binned by
+     *    f_z = z / Lz, f_y = (y - yz z) / Ly, f_x = (x - xy y - (xz - xy yz) z) / Lx, each in [-0.5, 0.5) for a wrapped
+     *    particle; grid.lo = -0.5 and grid.width = 1 / dim in those units. Any box, tilted or not. Other values:
+     *    AZP_ERROR_INVALID_ARGUMENT. */
+    uint32_t fractional_cells;
     uint32_t* d_max_neigh;
     } azp_nlist_args;
 
@@ -624,11 +630,19 @@ int azp_nlist_cell_bounds(const azp_nlist_args* args, void* stream);
  * grid has more than 32,768 cells). Grids of many small cells (cell_subdivision = 2) get a multi-workgroup scan
  * and a thread-per-cell sort. */
 int azp_nlist_bin(const azp_nlist_args* args, uint32_t* d_cursor, uint32_t* d_order_tmp, void* stream);
-/* Orthorhombic boxes only: the cells are Cartesian and the search reaches +-1 cell, while across a periodic y or z
- * face of a tilted box the image of a neighbor is shifted by xy Ly (xz Lz, yz Lz), which is no whole number of
- * cells. A box with a non-zero tilt is refused with AZP_ERROR_INVALID_ARGUMENT before anything is launched or
- * written (as azp_pair_plan_build_from_cells refuses it with invalid_reason 6): build the u32 list for such a box
- * elsewhere (HOOMD's own list, as the adapter does) and hand it to the force kernels / azp_pair_plan_build. */
+/* The search reaches +-1 cell around a particle's own.
+ * fractional_cells = 0 (Cartesian cells): orthorhombic boxes only -- across a periodic y or z face of a tilted box
+ * the image of a neighbor is shifted by xy Ly (xz Lz, yz Lz), which is no whole number of cells. A box with a non-zero
+ * tilt is refused with AZP_ERROR_INVALID_ARGUMENT before anything is launched or written.
+ * fractional_cells = 1: any box. The caller chooses dim[k] <= w_k / r_list with the perpendicular widths
+ * w_x = Lx / sqrt(1 + xy^2 + (xy yz - xz)^2), w_y = Ly / sqrt(1 + yz^2), w_z = Lz, so that a slab of cells is at least
+ * r_list thick and two particles within r_list differ by at most one cell along every axis; a periodic axis needs
+ * w_k >= 2 r_list (the minimum image is then unique). With fewer than 4 cells on some periodic axis the minimum image
+ * is taken per pair; otherwise once per staged particle, relative to the home cell's centre in fractional
+ * coordinates. An untilted box gives the same rows as Cartesian cells of the same dims.
+ * cell_subdivision > 1 is refused by both kinds. azp_pair_plan_build_from_cells takes Cartesian cells of an
+ * orthorhombic box only (invalid_reason 6 otherwise): for a tilted box fill the u32 list here and hand it to the force
+ * kernels / azp_pair_plan_build. */
 int azp_nlist_count(const azp_nlist_args* args, void* stream);
 int azp_nlist_fill(const azp_nlist_args* args, void* stream);
 
@@ -641,8 +655,8 @@ int azp_nlist_fill(const azp_nlist_args* args, void* stream);
  * ntypes. Invalid plans (azp_pair_plan_query): invalid_reason 3 = a row exceeded row_capacity
  * (retry with max_row; hard limit 504), 2 = a tile stages more than 2559 particles, 4 / 5 =
  * particles not spatially sorted (the members of a tile of 256 sit in more than 128 cells, or
- * the cells around them number more than 512 / hold more than 8192 particles), 6 = tilted box
- * or more than 255 types -- build the u32 list and azp_pair_plan_build instead. The rows hold
+ * the cells around them number more than 512 / hold more than 8192 particles), 6 = tilted box,
+ * fractional cells or more than 255 types -- build the u32 list and azp_pair_plan_build instead. The rows hold
  * the exact list plus, rarely, pairs a few 1e-6 r_list beyond it (single-precision acceptance
  * test with a margin that covers its own rounding); the force kernels' FP64 cutoff test ignores them. Synchronises the
  * stream once; owns device workspace (2 x row_capacity x 2 B per particle + the stage lists).
