@@ -4,7 +4,8 @@
 ``.bond`` / ``.external`` / ``.compute`` / ``.flow`` / ``.update`` / ``.evaporate`` / ``.variant`` (class names, parameters, modes); ``wall``
 holds the reference's legacy wall potentials (LJ 9-3, colloid) with geometries defined by this project; ``angle`` holds harmonic and
 cosine-squared bending with HOOMD's ``md.angle`` conventions and ``dihedral`` periodic and OPLS torsions under ``md.dihedral``'s
-names (the reference has no angle or dihedral code); ``thermostats`` holds the Berendsen, Bussi and MTTK thermostats of ``ConstantVolume``
+names (the reference has no angle or dihedral code); ``update.BoxResize`` with the box variants of ``variant.box`` and the scalar
+variants of ``variant`` follows ``hoomd.update.BoxResize`` / ``hoomd.variant`` (the reference has no box-resize code either); ``thermostats`` holds the Berendsen, Bussi and MTTK thermostats of ``ConstantVolume``
 under ``hoomd.md.methods.thermostats``' names and ``minimize`` the FIRE energy minimizer under ``hoomd.md.minimize``'s. The compute path is libazp.so (hand-written
 HIP for gfx950, C ABI in ``include/azp.h``); there is no CPU fallback.
 """

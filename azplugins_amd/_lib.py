@@ -429,6 +429,20 @@ class TypeUpdateArgs(C.Structure):
     ]
 
 
+class BoxResizeArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_type_mask", C.c_void_p),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("M", C.c_double * 6),
+        ("box", Box),
+    ]
+
+
 EVAPORATE_NO_LIMIT = 0xFFFFFFFF
 
 
@@ -579,6 +593,7 @@ SYMBOLS = {
     "azp_fire_advance": (C.c_int, [C.POINTER(FireArgs), _VP]),
     "azp_fire_step_one": (C.c_int, [C.POINTER(FireArgs), _VP]),
     "azp_type_update_region": (C.c_int, [C.POINTER(TypeUpdateArgs), _VP]),
+    "azp_box_resize": (C.c_int, [C.POINTER(BoxResizeArgs), _VP]),
     "azp_evaporate_scratch_size": (C.c_uint64, [C.c_uint32]),
     "azp_evaporate": (C.c_int, [C.POINTER(EvaporateArgs), _VP]),
     "azp_evaporate_local_keys": (C.c_int, [C.POINTER(EvaporateArgs), _VP]),

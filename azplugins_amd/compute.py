@@ -465,6 +465,7 @@ class _Recorder:
         self.trigger = trigger if isinstance(trigger, Periodic) else Periodic(trigger)
         self._rows = None  # (capacity, row width) device tensor
         self._steps = []
+        self._volumes = []  # the volume of the box each row was recorded in (host data: no synchronisation)
 
     def timesteps_in_run(self, t0, n):
         """The timesteps at which ``run(n)`` starting at timestep ``t0`` records: those of t0 + 1 ... t0 + n at which the
@@ -489,6 +490,7 @@ class _Recorder:
             self._rows = rows = grown
         self._compute._launch(rows.data_ptr() + k * width * 8)
         self._steps.append(int(timestep))
+        self._volumes.append(st.box.volume)  # (an update.BoxResize may change the box before the row is read)
 
     @property
     def timesteps(self):
@@ -530,7 +532,8 @@ class ThermodynamicRecorder(_Recorder):
         if not self.thermo._attached:
             raise DataAccessError("table")
         host, ctx = self.thermo._context(self._rows[:k])
-        rows = [thermo_quantities(host[i], *ctx) for i in range(k)]
+        # (each row with the volume of the box it was recorded in, not the box of this moment)
+        rows = [thermo_quantities(host[i], ctx[0], self._volumes[i], *ctx[2:]) for i in range(k)]
         return {name: np.array([r[name] for r in rows]) for name in THERMO_PROPERTIES}
 
 
@@ -784,6 +787,7 @@ class RDFRecorder(_Recorder):
     def reset(self):
         self._rows = None
         self._steps = []
+        self._volumes = []
 
     def _table(self, name):
         k = len(self._steps)
@@ -817,8 +821,7 @@ class RDFRecorder(_Recorder):
         c = self.rdf_compute
         if t.shape[0] == 0:
             return np.zeros((0, nb))
-        vol = c._volume()
-        return np.stack([rdf_from_counts(r[:nb], r[nb], r[nb + 1], r[nb + 2], vol, c.r_max) for r in t])
+        return np.stack([rdf_from_counts(r[:nb], r[nb], r[nb + 1], r[nb + 2], vol, c.r_max) for r, vol in zip(t, self._volumes)])
 
     @property
     def mean_rdf(self):
@@ -828,7 +831,12 @@ class RDFRecorder(_Recorder):
         if t.shape[0] == 0:
             return np.zeros(nb)
         c = self.rdf_compute
-        return _rdf_normalize(t[:, :nb].sum(axis=0), sum(self._pairs(t)), c._volume(), c.r_max)
+        vols = self._volumes
+        if all(v == vols[0] for v in vols):  # one box throughout: the counts are added as integers
+            return _rdf_normalize(t[:, :nb].sum(axis=0), sum(self._pairs(t)), vols[0], c.r_max)
+        # frames recorded in different boxes: each frame's counts weighted with its own volume
+        weighted = (t[:, :nb].astype(np.float64) * np.array(vols)[:, None]).sum(axis=0)
+        return _rdf_normalize(weighted, sum(self._pairs(t)), 1.0, c.r_max)
 
 
 __all__ = ["CartesianVelocityFieldCompute", "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder",

@@ -75,6 +75,7 @@ class NeighborList:
         self._built_consumer_version = None
         self._order_generation = 0        # State.order_generation the list was built for
         self._type_generation = 0         # State.type_generation the list was built for
+        self._box_generation = 0          # State.box_generation the list was built for
         # domain-decomposed runs (azplugins_amd.domain): the rebuild decision is collective
         # (reduce_flag: bool -> bool, an all-reduce over the ranks) and particles migrate /
         # ghosts are re-selected before the list is rebuilt (before_rebuild(state))
@@ -228,6 +229,13 @@ class Cell(NeighborList):
             if not force and self.built and self.before_rebuild is not None:
                 self.before_rebuild(state)
             force = True
+        if state.box_generation != self._box_generation:
+            # the box changed (State.set_box, update.BoxResize): the cell grid, the image shifts of the rows and the
+            # displacements since the last build no longer hold (HOOMD rebuilds on a box change too). Fused mode is
+            # decided again by this build (_fused_eligible)
+            if not force and self.built and self.before_rebuild is not None:
+                self.before_rebuild(state)
+            force = True
         if state.order_generation != self._order_generation or self._built_consumer_version != self._consumer_version:
             force = True  # re-indexed particles (ParticleSorter: every stored index is stale) or a changed r_cut matrix
         if not force and self.built:
@@ -252,7 +260,8 @@ class Cell(NeighborList):
         for the current consumers and particle order, a check is due, and no collective decides the rebuild."""
         return (self.n_neigh is not None and self.reduce_flag is None and self.before_rebuild is None
                 and self._built_consumer_version == self._consumer_version and self._built_generation != state.position_generation
-                and state.order_generation == self._order_generation and state.type_generation == self._type_generation)
+                and state.order_generation == self._order_generation and state.type_generation == self._type_generation
+                and state.box_generation == self._box_generation)
 
     def begin_check(self, state):
         """Queue the distance check on the current stream and its 16-byte readback on a side stream (ordered after
@@ -388,6 +397,7 @@ class Cell(NeighborList):
             self._fill(stream)
         self._order_generation = state.order_generation
         self._type_generation = state.type_generation
+        self._box_generation = state.box_generation
         self._built_consumer_version = self._consumer_version
         self._disp, self._disp_generation = 0.0, state.position_generation
         self.num_builds += 1

@@ -78,7 +78,12 @@ class Periodic:
 
 def _launch(a, st, stream, *names):
     """Queue the libazp integration entries ``names`` with their argument struct ``a`` pointed at the state's arrays of
-    this moment (they are replaced when particles migrate between ranks or are re-sorted)."""
+    this moment (they are replaced when particles migrate between ranks or are re-sorted), and at the state's box when
+    ``box_generation`` has moved since the struct's box was written (``State.set_box``, ``update.BoxResize``)."""
+    generation = getattr(st, "box_generation", 0)  # (a stand-in state without the counter keeps its box)
+    if getattr(a, "_box_generation", None) != generation:
+        a.box = st.box.to_c()
+        a._box_generation = generation
     a.d_pos = st.pos.data_ptr()
     a.d_vel = st.vel.data_ptr()
     a.d_net_force = st.net_force.data_ptr()
@@ -491,8 +496,10 @@ class Simulation:
         # Inside a run nothing reads the velocities between step two of one step and step one of the next: where the
         # stepper can (_fusable) they are one kernel (same arithmetic, one pass over the arrays). Where a writer is due,
         # the full-step velocities of the previous step have to exist: its step two runs on its own (the same arithmetic,
-        # bit for bit), the writer records, and this step starts with a plain step one. An updater changes types alone:
-        # it splits the fusion only for kernels that read them (_updaters_split: a flow method filtered by type)
+        # bit for bit), the writer records, and this step starts with a plain step one. An updater that changes types
+        # splits the fusion only for kernels that read them (_updaters_split: a flow method filtered by type); one that
+        # changes the box (update.BoxResize) splits nothing: its kernel is queued ahead of the fused one, which reads the
+        # box in its wrap alone, after step two's half kick
         fusable, updaters_split = steppers[0]._fusable, steppers[0]._updaters_split
         # (a bond force examines the "evaluator rejected its parameters" flag of step k when step k + 1 is queued, and
         # once more after the loop: no host round trip behind every launch)
@@ -503,7 +510,7 @@ class Simulation:
             for k in range(steps):
                 writers = self._writers_due() if k else []
                 updaters = self._updaters_due()
-                split = k > 0 and bool(not fusable or writers or (updaters and updaters_split))
+                split = k > 0 and bool(not fusable or writers or (updaters_split and any(u._changes_types for u in updaters)))
                 if split:
                     for s in steppers:
                         s._step_two(self, self.timestep - 1)
@@ -555,12 +562,13 @@ class Simulation:
 
     def _run_updaters(self, due):
         """The updaters whose trigger fires at this timestep (HOOMD runs its updaters ahead of the integrator's
-        step). They change particle types: every neighbor list and tile plan is rebuilt before the next force
-        evaluation (the reference: notifyParticleSort(), src/TypeUpdater.cc:86-87) -- whether or not a type really
-        changed, so that nothing is read back from the device."""
+        step). Where one of them changes particle types (``_Updater._changes_types``), every neighbor list and tile plan
+        is rebuilt before the next force evaluation (the reference: notifyParticleSort(), src/TypeUpdater.cc:86-87) --
+        whether or not a type really changed, so that nothing is read back from the device."""
         for u in due:
             u._update(self, self.timestep)
-        if due:
+        # (an updater that leaves the types alone -- update.BoxResize -- answers for its own generation counters)
+        if any(u._changes_types for u in due):
             self.state.type_generation += 1
 
     def _run_tuners(self, integ):

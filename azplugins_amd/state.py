@@ -57,8 +57,24 @@ class Box:
         t = self.xy * self.yz - self.xz
         return (self.Lx / math.sqrt(1.0 + self.xy * self.xy + t * t), self.Ly / math.sqrt(1.0 + self.yz * self.yz), self.Lz)
 
+    @property
+    def volume(self):
+        return self.Lx * self.Ly * self.Lz
+
+    def _key(self):
+        return (self.Lx, self.Ly, self.Lz, self.xy, self.xz, self.yz, self.periodic)
+
+    def __eq__(self, other):
+        """Equal in all six numbers and the periodic flags."""
+        return isinstance(other, Box) and other._key() == self._key()
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = object.__hash__  # (a box is mutable: hashed by identity, as before it had an __eq__)
+
     def to_c(self):
-        key = (self.Lx, self.Ly, self.Lz, self.xy, self.xz, self.yz, self.periodic)
+        key = self._key()
         if getattr(self, "_c_key", None) != key:  # (called for every launch: build the struct once per box)
             self._c = _lib.make_box(key[:3], key[3:6], [int(p) for p in self.periodic])
             self._c_key = key
@@ -412,7 +428,7 @@ class State:
         self.N = p.N if n_local is None else int(n_local)
         self.n_ghost = p.N - self.N
         self.types = list(p.types)
-        self.box = Box.from_box(snapshot.configuration.box)
+        self._box = Box.from_box(snapshot.configuration.box)
         f64 = torch.float64
         self.pos = torch.from_numpy(_pos4(p.position, p.typeid)).to(self.device)
         vel = np.zeros((p.N, 4))
@@ -435,10 +451,32 @@ class State:
         self.position_generation = 0  # bumped whenever positions change
         self.order_generation = 0     # bumped whenever the particles are re-indexed (sort, migration)
         self.type_generation = 0      # bumped whenever an updater may have changed the types in pos.w
+        self.box_generation = 0       # bumped whenever the box changes (set_box): cell grids and image shifts are stale
 
     @property
     def n_max(self):
         return self.N + self.n_ghost
+
+    @property
+    def box(self):
+        """The simulation box. Assigning one (or ``set_box``) that differs from the current box in an edge, a tilt factor
+        or a periodic flag bumps ``box_generation`` and ``position_generation``: neighbor lists are rebuilt and the
+        steppers wrap with the new box from the next step on. The particles are NOT moved (``update.BoxResize`` scales
+        them); the box object itself is treated as immutable -- change the box by assigning a new one."""
+        return self._box
+
+    @box.setter
+    def box(self, box):
+        self.set_box(box)
+
+    def set_box(self, box):
+        """HOOMD ``State.set_box``: see ``box``. A box equal to the current one changes nothing."""
+        box = Box.from_box(box)
+        if box == self._box:
+            return
+        self._box = box
+        self.box_generation += 1
+        self.position_generation += 1
 
     @property
     def typeid_host(self):

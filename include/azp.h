@@ -1088,6 +1088,46 @@ int azp_evaporate(const azp_evaporate_args* args, void* stream);
 int azp_evaporate_local_keys(const azp_evaporate_args* args, void* stream);
 int azp_evaporate_apply_below(const azp_evaporate_args* args, uint64_t threshold_key, void* stream);
 
+/* ---- box resize: the particles of a box that changes (HOOMD hoomd.update.BoxResize) ----
+ * The reference holds no box-resize code; these are HOOMD's documented semantics. One asynchronous launch over rows
+ * [0, N), one row per lane, no LDS and no atomics: the result does not depend on the launch shape.
+ *
+ * A row is SELECTED if d_type_mask is NULL, or if its type t (low 32 bits of pos.w) has t < ntypes and
+ * d_type_mask[t] != 0. A selected row is mapped affinely from the old box to the new one, r' = M r, with
+ * M = H_new H_old^-1 (H: the lattice vectors as columns, upper triangular) computed by the CALLER in float64 and
+ * passed as M = {M00, M01, M02, M11, M12, M22}; the kernel divides nothing and evaluates, in this order,
+ *     x' = fma(M02, z, fma(M01, y, M00 * x))
+ *     y' = fma(M12, z, M11 * y)
+ *     z' = M22 * z
+ * (three, two and one roundings). pos.w keeps its bits; velocities are not an argument (HOOMD does not scale them).
+ *
+ * Then EVERY row, selected or not, is wrapped into `box` (the NEW box) and its image counters (d_image, N x 3, may
+ * be NULL) are updated. A selected row keeps its fractional coordinates up to rounding: one shift per axis, the wrap
+ * of the integration kernels. An unselected row keeps its position and may lie several images outside a box that has
+ * shrunk: it is first taken back by k = rint(f) lattice vectors per periodic axis, f its fractional coordinate in the
+ * new box along that axis -- z first (z -= k Lz, y -= k (Lz yz), x -= k (Lz xz), each one FMA with the product in
+ * parentheses rounded once), then y from the shifted y and z (y -= k Ly, x -= k (Ly xy)), then x -- and then wrapped
+ * with one shift per axis like the others, which settles a row left on a face ([-L/2, L/2)).
+ * A non-periodic axis is scaled but not wrapped. The caller keeps the periodic flags of the old box.
+ *
+ * NULL args, a NULL d_pos, a mask with ntypes == 0, an edge that is not positive and finite, a tilt or an entry of M
+ * that is not finite, block_size not a multiple of 64 or above 256: AZP_ERROR_INVALID_ARGUMENT, nothing launched.
+ * N == 0: success without a launch. */
+typedef struct azp_box_resize_args
+    {
+    double* d_pos;              /* N x 4 */
+    int32_t* d_image;           /* N x 3, may be NULL */
+    const uint8_t* d_type_mask; /* ntypes bytes, may be NULL (every row is selected) */
+    uint32_t N;
+    uint32_t ntypes;            /* entries of d_type_mask */
+    uint32_t block_size;        /* 0: 256 */
+    uint32_t _pad;
+    double M[6];                /* M00, M01, M02, M11, M12, M22 */
+    azp_box box;                /* the new box */
+    } azp_box_resize_args;
+
+int azp_box_resize(const azp_box_resize_args* args, void* stream);
+
 /* ---- velocity / velocity-field computes ----
  * Replaces the reference's GPU drivers of hoomd.azplugins.compute: the per-particle loop of
  * src/VelocityFieldComputeGPU.cuh:35-71 (CartesianVelocityFieldCompute, CylindricalVelocityFieldCompute) and
