@@ -35,6 +35,16 @@ inline BoxDev make_box_dev(const azp_box& b)
     return d;
     }
 
+// perpendicular widths of the box (HOOMD BoxDim::getNearestPlaneDistance), on the host
+inline void box_plane_distances(const azp_box& b, double w[3])
+    {
+    const double xy = b.tilt[0], xz = b.tilt[1], yz = b.tilt[2];
+    const double t = xy * yz - xz;
+    w[0] = b.L[0] / sqrt(1.0 + xy * xy + t * t);
+    w[1] = b.L[1] / sqrt(1.0 + yz * yz);
+    w[2] = b.L[2];
+    }
+
 // Minimum image, rint form (mul + v_rndne_f64 + fma per axis: 3 FP64 ops, fewer
 // than compare/select on 64-bit values). Agrees with the compare form of the
 // CPU oracle away from exact ties at +-L/2.

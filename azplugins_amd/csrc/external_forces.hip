@@ -248,14 +248,10 @@ extern "C" int azp_spherical_barrier_valid(double R, const azp_box* box)
     {
     if (!box)
         return 0;
-    // nearest plane distances of a triclinic box (HOOMD BoxDim::getNearestPlaneDistance)
-    const double xy = box->tilt[0], xz = box->tilt[1], yz = box->tilt[2];
-    const double term = xy * yz - xz;
-    const double dx = box->L[0] / sqrt(1.0 + xy * xy + term * term);
-    const double dy = box->L[1] / sqrt(1.0 + yz * yz);
-    const double dz = box->L[2];
+    double w[3];
+    azp::box_plane_distances(*box, w);
     const double two_R = 2.0 * R;
-    return (R >= 0.0 && dx >= two_R && dy >= two_R && dz >= two_R) ? 1 : 0;
+    return (R >= 0.0 && w[0] >= two_R && w[1] >= two_R && w[2] >= two_R) ? 1 : 0;
     }
 
 // ---- halo pack: gather rows into the send buffer ----

@@ -1,90 +1,12 @@
 // nlist.hip -- cell-list neighbor-list build on the GPU.
 // Produces HOOMD-format full neighbor lists (n_neigh / head_list / nlist) that
 // the force kernels consume; see include/azp.h for the call sequence.
-#include "azp_device.hpp"
+// The grid, the cell rule and the counting sort by cell are cell_bin.hpp's; what is here: the cell bounds of the
+// framework-sort path, the per-cell sorts that make azp_nlist_bin's order stable, the row kernel, the distance check.
+#include "cell_bin.hpp"
 
 namespace azp
 {
-struct GridDev
-    {
-    double lo[3], winv[3];
-    int dim[3];
-    int periodic[3];
-    };
-
-static GridDev make_grid_dev(const azp_cell_grid& g)
-    {
-    GridDev d;
-    for (int k = 0; k < 3; ++k)
-        {
-        d.lo[k] = g.lo[k];
-        d.winv[k] = 1.0 / g.width[k];
-        d.dim[k] = (int)g.dim[k];
-        d.periodic[k] = g.periodic[k];
-        }
-    return d;
-    }
-
-__device__ __forceinline__ int cell_coord(const GridDev& g, int k, double x)
-    {
-    int c = (int)floor((x - g.lo[k]) * g.winv[k]);
-    if (g.periodic[k])
-        {
-        c %= g.dim[k];
-        if (c < 0) c += g.dim[k];
-        }
-    else
-        c = min(max(c, 0), g.dim[k] - 1);
-    return c;
-    }
-
-// Fractional cells (azp_nlist_args.fractional_cells): the grid lives in the coordinates f along the lattice vectors,
-// f in [-0.5, 0.5) for a wrapped particle (wrap_into_box's own frame); the cells are parallelepipeds.
-struct FracDev
-    {
-    double xy, xzp, yz; // xzp = xz - xy yz
-    double Lxinv, Lyinv, Lzinv;
-    };
-
-static FracDev make_frac_dev(const azp_box& b)
-    {
-    FracDev f;
-    f.xy = b.tilt[0]; f.xzp = b.tilt[1] - b.tilt[0] * b.tilt[2]; f.yz = b.tilt[2];
-    f.Lxinv = 1.0 / b.L[0]; f.Lyinv = 1.0 / b.L[1]; f.Lzinv = 1.0 / b.L[2];
-    return f;
-    }
-
-__device__ __forceinline__ double3 fractional(const FracDev& f, double x, double y, double z)
-    {
-    return make_double3(__builtin_fma(-f.xzp, z, __builtin_fma(-f.xy, y, x)) * f.Lxinv, __builtin_fma(-f.yz, z, y) * f.Lyinv,
-                        z * f.Lzinv);
-    }
-
-__device__ __forceinline__ uint32_t cell_index(const GridDev& g, const double3& p)
-    {
-    const int cx = cell_coord(g, 0, p.x), cy = cell_coord(g, 1, p.y), cz = cell_coord(g, 2, p.z);
-    return (uint32_t)((cz * g.dim[1] + cy) * g.dim[0] + cx);
-    }
-
-__global__ void __launch_bounds__(256) cell_assign_kernel(uint32_t n_total, const double* __restrict__ pos, GridDev g,
-                                                          uint32_t* __restrict__ cell_of)
-    {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_total)
-        return;
-    cell_of[i] = cell_index(g, load_scalar3_of4(pos, i));
-    }
-
-__global__ void __launch_bounds__(256) cell_assign_frac_kernel(uint32_t n_total, const double* __restrict__ pos, GridDev g, FracDev fr,
-                                                               uint32_t* __restrict__ cell_of)
-    {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_total)
-        return;
-    const double3 p = load_scalar3_of4(pos, i);
-    cell_of[i] = cell_index(g, fractional(fr, p.x, p.y, p.z));
-    }
-
 // cell_start[c] = first position in the sorted order whose cell id is >= c
 __global__ void __launch_bounds__(256) cell_bounds_kernel(uint32_t n_total, uint32_t ncell,
                                                           const uint32_t* __restrict__ cell_sorted,
@@ -102,170 +24,15 @@ __global__ void __launch_bounds__(256) cell_bounds_kernel(uint32_t n_total, uint
     cell_start[c] = lo;
     }
 
-// ---- binning in one call (azp_nlist_bin): counting sort of the particles by cell, stable in the particle index ----
-// Lanes of a wave that hold the same key add to its counter with ONE atomic (consecutive particles of a spatially sorted
-// system sit in the same cell: a plain atomic per lane serialises 32-deep on one address). Returns this lane's slot
-// base + rank among the wave's lanes with that key.
-__device__ __forceinline__ uint32_t wave_aggregated_add(uint32_t* counters, uint32_t key, bool active)
+// ---- azp_nlist_bin: bin_particles (cell_bin.hpp) into order_tmp, then the order inside every cell ----
+struct OrderSink
     {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t result = 0;
-    unsigned long long todo = __ballot(active);
-    while (todo)
-        {
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t k0 = (uint32_t)__shfl((int)key, leader, 64);
-        const unsigned long long same = __ballot(active && key == k0) & todo;
-        uint32_t base = 0;
-        if ((int)lane == leader)
-            base = atomicAdd(&counters[k0], (uint32_t)__popcll(same));
-        base = (uint32_t)__shfl((int)base, leader, 64);
-        if (active && key == k0)
-            result = base + (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-        todo &= ~same;
-        }
-    return result;
-    }
-
-__global__ void __launch_bounds__(256) bin_assign_count_kernel(uint32_t n_total, const double* __restrict__ pos, GridDev g,
-                                                               uint32_t* __restrict__ cell_of, uint32_t* __restrict__ count)
-    {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = i < n_total;
-    uint32_t c = 0;
-    if (active)
-        {
-        c = cell_index(g, load_scalar3_of4(pos, i));
-        cell_of[i] = c;
-        }
-    (void)wave_aggregated_add(count, c, active);
-    }
-
-__global__ void __launch_bounds__(256) bin_assign_count_frac_kernel(uint32_t n_total, const double* __restrict__ pos, GridDev g, FracDev fr,
-                                                                    uint32_t* __restrict__ cell_of, uint32_t* __restrict__ count)
-    {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = i < n_total;
-    uint32_t c = 0;
-    if (active)
-        {
-        const double3 p = load_scalar3_of4(pos, i);
-        c = cell_index(g, fractional(fr, p.x, p.y, p.z));
-        cell_of[i] = c;
-        }
-    (void)wave_aggregated_add(count, c, active);
-    }
-
-// exclusive scan of ncell counts into cell_start[0 .. ncell] by ONE workgroup of 1,024 threads, 4,096 counters per
-// trip (four per thread, wave scans by shuffles, one LDS hop for the 16 wave totals; the carry in a register);
-// count[] is left holding the cell starts too (the scatter's cursors)
-__global__ void __launch_bounds__(1024) bin_scan_kernel(uint32_t ncell, uint32_t* __restrict__ count, uint32_t* __restrict__ cell_start)
-    {
-    __shared__ uint32_t s_wave[16];
-    const uint32_t t = threadIdx.x;
-    uint32_t carry = 0;
-    for (uint32_t c0 = 0; c0 < ncell; c0 += 4096u)
-        {
-        const uint32_t c = c0 + 4u * t;
-        uint32_t v[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k)
-            v[k] = (c + k < ncell) ? count[c + k] : 0u;
-        uint32_t total;
-        uint32_t acc = carry + block_exclusive_scan<16>(v[0] + v[1] + v[2] + v[3], s_wave, total);
-        __syncthreads(); // (the next trip writes s_wave again)
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k)
-            {
-            if (c + k < ncell)
-                {
-                cell_start[c + k] = acc;
-                count[c + k] = acc;
-                }
-            acc += v[k];
-            }
-        carry += total;
-        }
-    if (t == 0)
-        cell_start[ncell] = carry;
-    }
-
-// The same scan for grids of many cells (half-width cells: 2^18 at N = 2^20), where one workgroup's 64 dependent trips
-// would take longer than the rest of the binning: every workgroup scans 4,096 cells on its own and leaves its total,
-// one workgroup scans the totals, a third pass adds them in.
-__global__ void __launch_bounds__(1024) bin_scan_local_kernel(uint32_t ncell, const uint32_t* __restrict__ count, uint32_t* __restrict__ cell_start,
-                                                              uint32_t* __restrict__ block_total)
-    {
-    __shared__ uint32_t s_wave[16];
-    const uint32_t t = threadIdx.x;
-    const uint32_t c = blockIdx.x * 4096u + 4u * t;
-    uint32_t v[4];
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k)
-        v[k] = (c + k < ncell) ? count[c + k] : 0u;
-    uint32_t total;
-    uint32_t acc = block_exclusive_scan<16>(v[0] + v[1] + v[2] + v[3], s_wave, total);
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k)
-        {
-        if (c + k < ncell)
-            cell_start[c + k] = acc;
-        acc += v[k];
-        }
-    if (t == 0)
-        block_total[blockIdx.x] = total;
-    }
-
-// The scan of the block totals, in place: x[0 .. n) become their exclusive prefix sums and x[n] the grand total. ONE
-// pointer (bin_scan_kernel's two are __restrict__ and may not name the same array); one value per thread and trip,
-// a trip's reads all precede its writes (the barriers), the carry in a register.
-__global__ void __launch_bounds__(1024) bin_scan_totals_kernel(uint32_t n, uint32_t* x)
-    {
-    __shared__ uint32_t s_wave[16];
-    const uint32_t t = threadIdx.x;
-    uint32_t carry = 0;
-    for (uint32_t c0 = 0; c0 < n; c0 += 1024u)
-        {
-        const uint32_t c = c0 + t;
-        const uint32_t mine = (c < n) ? x[c] : 0u;
-        uint32_t total;
-        const uint32_t before = block_exclusive_scan<16>(mine, s_wave, total);
-        __syncthreads(); // (every read of x[] and s_wave of this trip is done)
-        if (c < n)
-            x[c] = carry + before;
-        carry += total;
-        }
-    if (t == 0)
-        x[n] = carry;
-    }
-
-__global__ void __launch_bounds__(256) bin_scan_add_kernel(uint32_t ncell, const uint32_t* __restrict__ block_start, uint32_t* __restrict__ count,
-                                                           uint32_t* __restrict__ cell_start)
-    {
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c < ncell)
-        {
-        const uint32_t v = cell_start[c] + block_start[c >> 12];
-        cell_start[c] = v;
-        count[c] = v;
-        }
-    else if (c == ncell)
-        cell_start[ncell] = block_start[(ncell + 4095u) >> 12]; // (the scan of the totals leaves the grand total behind the last)
-    }
-
-__global__ void __launch_bounds__(256) bin_scatter_kernel(uint32_t n_total, const uint32_t* __restrict__ cell_of,
-                                                          uint32_t* __restrict__ cursor, uint32_t* __restrict__ order_tmp)
-    {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = i < n_total;
-    const uint32_t c = active ? cell_of[i] : 0u;
-    const uint32_t slot = wave_aggregated_add(cursor, c, active); // (any order of the WAVES inside a cell: the next kernel sorts it)
-    if (active)
-        order_tmp[slot] = i;
-    }
+    uint32_t* order_tmp;
+    __device__ void operator()(uint32_t slot, uint32_t i) const { order_tmp[slot] = i; }
+    };
 
 // One wave per cell: the cell's particle indices in ascending order (a rank sort: an index's position is the number
-// of smaller ones). Makes the permutation independent of the order in which the atomics above landed: neighbor rows,
+// of smaller ones). Makes the permutation independent of the order in which the scatter's atomics landed: neighbor rows,
 // and with them the summation order of the forces, are reproducible from run to run.
 __global__ void __launch_bounds__(256) bin_sort_cells_kernel(uint32_t ncell, const uint32_t* __restrict__ cell_start,
                                                              const uint32_t* __restrict__ order_tmp, uint32_t* __restrict__ order)
@@ -685,11 +452,11 @@ extern "C" int azp_nlist_cell_assign(const azp_nlist_args* args, void* stream)
         return AZP_SUCCESS;
     const uint32_t grid = (args->n_total + 255u) / 256u;
     if (args->fractional_cells)
-        hipLaunchKernelGGL(cell_assign_frac_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args->n_total,
-                           args->d_pos, make_grid_dev(args->grid), make_frac_dev(args->box), args->d_cell_of);
+        hipLaunchKernelGGL((cell_assign_kernel<true, false>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args->n_total,
+                           args->d_pos, make_grid_dev(args->grid), make_frac_dev(args->box), args->d_cell_of, (uint32_t*)nullptr);
     else
-        hipLaunchKernelGGL(cell_assign_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args->n_total,
-                           args->d_pos, make_grid_dev(args->grid), args->d_cell_of);
+        hipLaunchKernelGGL((cell_assign_kernel<false, false>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args->n_total,
+                           args->d_pos, make_grid_dev(args->grid), FracDev{}, args->d_cell_of, (uint32_t*)nullptr);
     return (int)hipGetLastError();
     }
 
@@ -700,30 +467,15 @@ extern "C" int azp_nlist_bin(const azp_nlist_args* args, uint32_t* d_cursor, uin
         return AZP_ERROR_INVALID_ARGUMENT;
     const uint32_t ncell = args->grid.dim[0] * args->grid.dim[1] * args->grid.dim[2];
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(d_cursor, 0, sizeof(uint32_t) * (size_t)ncell, s);
+    const uint32_t n = args->n_total;
+    const FracDev frac = make_frac_dev(args->box);
+    // (the block totals of the three-kernel scan live in d_order_tmp, which the scatter fills only afterwards)
+    const hipError_t e = bin_particles(n, args->d_pos, make_grid_dev(args->grid), args->fractional_cells ? &frac : nullptr, args->d_cell_of,
+                                       d_cursor, args->d_cell_start, d_order_tmp, OrderSink{d_order_tmp}, s);
     if (e != hipSuccess)
         return (int)e;
-    const uint32_t n = args->n_total;
-    if (n && args->fractional_cells)
-        hipLaunchKernelGGL(bin_assign_count_frac_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n, args->d_pos, make_grid_dev(args->grid),
-                           make_frac_dev(args->box), args->d_cell_of, d_cursor);
-    else if (n)
-        hipLaunchKernelGGL(bin_assign_count_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n, args->d_pos, make_grid_dev(args->grid),
-                           args->d_cell_of, d_cursor);
-    const uint32_t nblk = (ncell + 4095u) / 4096u;
-    if (nblk > 8u && nblk + 1u <= n)
-        {
-        // (the totals live in d_order_tmp, which the scatter fills only afterwards; bin_scan_totals_kernel turns nblk
-        // totals into their nblk starts + the grand total at [nblk]: nblk + 1 <= n words)
-        hipLaunchKernelGGL(bin_scan_local_kernel, dim3(nblk), dim3(1024), 0, s, ncell, d_cursor, args->d_cell_start, d_order_tmp);
-        hipLaunchKernelGGL(bin_scan_totals_kernel, dim3(1), dim3(1024), 0, s, nblk, d_order_tmp);
-        hipLaunchKernelGGL(bin_scan_add_kernel, dim3((ncell + 1u + 255u) / 256u), dim3(256), 0, s, ncell, d_order_tmp, d_cursor, args->d_cell_start);
-        }
-    else
-        hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, s, ncell, d_cursor, args->d_cell_start);
     if (n)
         {
-        hipLaunchKernelGGL(bin_scatter_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, n, args->d_cell_of, d_cursor, d_order_tmp);
         if ((uint64_t)n <= 6ull * ncell)
             hipLaunchKernelGGL(bin_sort_small_cells_kernel, dim3((ncell + 255u) / 256u), dim3(256), 0, s, ncell, args->d_cell_start, d_order_tmp,
                                const_cast<uint32_t*>(args->d_order));

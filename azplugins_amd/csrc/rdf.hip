@@ -11,9 +11,9 @@
 //              in chunks of 256 (x, y, z as three double arrays; a candidate outside B is staged as NaN, which fails
 //              rsq < r_max^2), every lane tests every staged candidate (one LDS address per wave: a broadcast read).
 //   cells      (orthorhombic box, >= 3 cells of width >= r_max on every periodic axis; a non-periodic axis has
-//              clamped cells, as azp_cell_grid.periodic = 0). All n_total particles are binned by a counting sort that
-//              lives in this file's scratch: histogram of the cells (integer atomics), one-workgroup exclusive scan,
-//              scatter of (x, y, z, flags) rows into cell order. No order is imposed inside a cell: pair counts do not
+//              clamped cells, as azp_cell_grid.periodic = 0). All n_total particles are binned by the counting sort of
+//              cell_bin.hpp (bin_particles, the one azp_nlist_bin runs) in this call's scratch; its scatter writes
+//              (x, y, z, flags) rows into cell order. No order is imposed inside a cell: pair counts do not
 //              depend on it. rdf_cells then gives every workgroup a contiguous range of cells (xcd_remap: one eighth of
 //              the cells per XCD); per cell, its rows are taken 256 at a time, a tile of T rows is served by
 //              256 / pow2ceil(T) lanes per row, and the members of the 27 stencil cells are staged through LDS in
@@ -35,7 +35,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "azp_device.hpp"
+#include "cell_bin.hpp"
 
 namespace azp
 {
@@ -44,18 +44,8 @@ constexpr uint32_t RDF_CHUNK = 256;
 constexpr uint32_t RDF_CHUNK_TESTS = RDF_BLOCK * RDF_CHUNK;       // most increments a bin gets from one staged chunk
 constexpr uint32_t RDF_FLUSH_AT = 0xFFFFFFFFu - RDF_CHUNK_TESTS;  // flush once `pending` has passed this
 constexpr uint32_t RDF_TARGET_BLOCKS = 2048;                      // 256 CUs x 8
-constexpr uint32_t RDF_SCAN_BLOCK = 1024;
 constexpr uint32_t RDF_MAX_CELLS = 1u << 21;
 constexpr uint32_t RDF_AUTO_CELLS_MIN_N = 0;  // path 0 takes the cells wherever they are valid
-
-struct RdfGrid
-    {
-    double lo[3];
-    double inv_w[3];
-    uint32_t dim[3];
-    int periodic[3];
-    uint32_t ncell;
-    };
 
 struct RdfKArgs
     {
@@ -71,10 +61,9 @@ struct RdfKArgs
     uint32_t ntypes;
     uint32_t num_bins;
     // cells path
-    RdfGrid grid;
+    GridDev grid;
+    uint32_t ncell;
     double* sorted;        // n_total x 4: x, y, z, flags (1: row of A below N, 2: member of B)
-    uint32_t* cell_id;     // n_total
-    uint32_t* count;       // ncell: histogram, then the scatter's cursors
     uint32_t* start;       // ncell + 1
     uint32_t cells_per_block;
     uint32_t seg_len;      // all-pairs: candidates per segment of B (a multiple of RDF_CHUNK)
@@ -173,81 +162,24 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_all_pairs(const RdfKArgs a)
     }
 
 // ---------------------------------------------------------------------------------------------------------------
-// binning: histogram, scan, scatter
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rdf_cell_axis(const RdfGrid& g, int d, double x)
-    {
-    // (fmin / fmax drop a NaN: such a particle lands in cell 0 of the axis and pairs with nothing)
-    const double f = fmin(fmax((x - g.lo[d]) * g.inv_w[d], -1.0e9), 1.0e9);
-    int c = (int)floor(f);
-    const int dim = (int)g.dim[d];
-    if (g.periodic[d])
-        {
-        c %= dim;
-        if (c < 0)
-            c += dim;
-        }
-    else
-        c = min(max(c, 0), dim - 1);
-    return (uint32_t)c;
-    }
-
-__global__ void __launch_bounds__(RDF_BLOCK) rdf_bin_count(const RdfKArgs a)
-    {
-    const uint64_t p = (uint64_t)blockIdx.x * RDF_BLOCK + threadIdx.x;
-    if (p >= a.n_total)
-        return;
-    const double3 r = load_scalar3_of4(a.pos, (uint32_t)p);
-    const uint32_t c = (rdf_cell_axis(a.grid, 2, r.z) * a.grid.dim[1] + rdf_cell_axis(a.grid, 1, r.y)) * a.grid.dim[0]
-                       + rdf_cell_axis(a.grid, 0, r.x);
-    a.cell_id[p] = c;
-    atomicAdd(&a.count[c], 1u);
-    }
-
-// exclusive scan of count[0, ncell) into start[0, ncell], one workgroup; count is cleared (the scatter's cursors).
-// Tiles of 1024 cells, lane t on cell base + t (coalesced: a lane-contiguous span per thread costs one cache line per
-// lane and load, 97 us for 46,656 cells at the rate of one CU's address unit); a shuffle scan inside each wave, the 16
-// wave totals through LDS, the running total carried from tile to tile.
-__global__ void __launch_bounds__(RDF_SCAN_BLOCK) rdf_bin_scan(uint32_t* count, uint32_t* start, uint32_t ncell)
-    {
-    constexpr uint32_t NW = RDF_SCAN_BLOCK / WAVE;
-    __shared__ uint32_t s_wave[NW];
-    const uint32_t tid = threadIdx.x;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < ncell; base += RDF_SCAN_BLOCK)
-        {
-        const uint32_t k = base + tid;  // (ncell <= RDF_MAX_CELLS: no overflow)
-        const uint32_t c = k < ncell ? count[k] : 0u;
-        uint32_t total;
-        const uint32_t before = block_exclusive_scan<NW>(c, s_wave, total);
-        if (k < ncell)
-            {
-            start[k] = carry + before;
-            count[k] = 0;
-            }
-        carry += total;
-        __syncthreads(); // (the next tile writes s_wave again)
-        }
-    if (tid == 0)
-        start[ncell] = carry;
-    }
-
-__global__ void __launch_bounds__(RDF_BLOCK) rdf_bin_scatter(const RdfKArgs a)
-    {
-    const uint64_t p = (uint64_t)blockIdx.x * RDF_BLOCK + threadIdx.x;
-    if (p >= a.n_total)
-        return;
-    const double4 r = load_scalar4(a.pos, (uint32_t)p);
-    const uint32_t c = a.cell_id[p];
-    const uint32_t slot = a.start[c] + atomicAdd(&a.count[c], 1u);
-    const uint32_t flags = ((p < a.N && rdf_in_mask(a.mask_a, a.ntypes, r.w)) ? 1u : 0u)
-                           | (rdf_in_mask(a.mask_b, a.ntypes, r.w) ? 2u : 0u);
-    store_scalar4(a.sorted, slot, r.x, r.y, r.z, (double)flags);
-    }
-
-// ---------------------------------------------------------------------------------------------------------------
 // pair counts from the binned particles
 // ---------------------------------------------------------------------------------------------------------------
+// what bin_particles' scatter leaves at a particle's slot of the cell order: its row of `sorted`
+struct RdfRowSink
+    {
+    const double* pos;
+    const uint8_t* mask_a;
+    const uint8_t* mask_b;
+    double* sorted;
+    uint32_t N, ntypes;
+    __device__ void operator()(uint32_t slot, uint32_t p) const
+        {
+        const double4 r = load_scalar4(pos, p);
+        const uint32_t flags = ((p < N && rdf_in_mask(mask_a, ntypes, r.w)) ? 1u : 0u) | (rdf_in_mask(mask_b, ntypes, r.w) ? 2u : 0u);
+        store_scalar4(sorted, slot, r.x, r.y, r.z, (double)flags);
+        }
+    };
+
 __global__ void __launch_bounds__(RDF_BLOCK) rdf_cells(const RdfKArgs a)
     {
     extern __shared__ uint32_t s_hist[];
@@ -258,7 +190,7 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_cells(const RdfKArgs a)
         s_hist[k] = 0;
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const uint64_t c0 = (uint64_t)b * a.cells_per_block;
-    const uint32_t c1 = (uint32_t)std::min<uint64_t>(c0 + a.cells_per_block, a.grid.ncell);
+    const uint32_t c1 = (uint32_t)std::min<uint64_t>(c0 + a.cells_per_block, a.ncell);
     const uint32_t last_bin = a.num_bins - 1;
     const double nan = __builtin_nan("");
     const uint32_t dx = a.grid.dim[0], dy = a.grid.dim[1], dz = a.grid.dim[2];
@@ -392,18 +324,9 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_group_counts(const RdfKArgs a)
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
-// perpendicular widths of the box (HOOMD BoxDim::getNearestPlaneDistance)
-static void rdf_widths(const azp_box& b, double w[3])
-    {
-    const double xy = b.tilt[0], xz = b.tilt[1], yz = b.tilt[2];
-    const double t = xy * yz - xz;
-    w[0] = b.L[0] / std::sqrt(1.0 + xy * xy + t * t);
-    w[1] = b.L[1] / std::sqrt(1.0 + yz * yz);
-    w[2] = b.L[2];
-    }
-
-// the cell grid of the cells path; false if the box does not allow it
-static bool rdf_make_grid(const azp_box& b, double r_max, uint32_t n_total, RdfGrid& g)
+// the cell grid of the cells path; false if the box does not allow it (winv = dim / L, filled here: make_grid_dev's
+// 1 / (L / dim) may differ in the last bit)
+static bool rdf_make_grid(const azp_box& b, double r_max, uint32_t n_total, GridDev& g)
     {
     if (b.tilt[0] != 0.0 || b.tilt[1] != 0.0 || b.tilt[2] != 0.0)
         return false;
@@ -427,19 +350,19 @@ static bool rdf_make_grid(const azp_box& b, double r_max, uint32_t n_total, RdfG
         return false;
     for (int d = 0; d < 3; ++d)
         {
-        g.dim[d] = (uint32_t)dim[d];
+        g.dim[d] = (int)dim[d];
         g.lo[d] = -0.5 * b.L[d];
-        g.inv_w[d] = dim[d] / b.L[d];
+        g.winv[d] = dim[d] / b.L[d];
         g.periodic[d] = b.periodic[d] != 0;
         }
-    g.ncell = g.dim[0] * g.dim[1] * g.dim[2];
     return true;
     }
 
 struct RdfPlan
     {
     int path;  // 1 all-pairs, 2 cells
-    RdfGrid grid;
+    GridDev grid;
+    uint32_t ncell;
     uint64_t off_cell_id, off_count, off_start, bytes;
     };
 
@@ -456,7 +379,7 @@ static int rdf_plan(const azp_rdf_args* a, RdfPlan& p)
         if (!(a->box.L[d] > 0.0))
             return AZP_ERROR_INVALID_ARGUMENT;
     double w[3];
-    rdf_widths(a->box, w);
+    box_plane_distances(a->box, w);
     for (int d = 0; d < 3; ++d)
         if (a->box.periodic[d] && a->r_max > 0.5 * w[d])
             return AZP_ERROR_INVALID_ARGUMENT;  // the minimum image would not be unique
@@ -467,10 +390,11 @@ static int rdf_plan(const azp_rdf_args* a, RdfPlan& p)
     p.bytes = 0;
     if (p.path == 2)
         {
+        p.ncell = (uint32_t)p.grid.dim[0] * (uint32_t)p.grid.dim[1] * (uint32_t)p.grid.dim[2];
         p.off_cell_id = rdf_align((uint64_t)a->n_total * 32);
         p.off_count = p.off_cell_id + rdf_align((uint64_t)a->n_total * 4);
-        p.off_start = p.off_count + rdf_align((uint64_t)p.grid.ncell * 4);
-        p.bytes = p.off_start + rdf_align(((uint64_t)p.grid.ncell + 1) * 4);
+        p.off_start = p.off_count + rdf_align((uint64_t)p.ncell * 4);
+        p.bytes = p.off_start + rdf_align(((uint64_t)p.ncell + 1) * 4);
         }
     return AZP_SUCCESS;
     }
@@ -534,25 +458,19 @@ extern "C" int azp_rdf_counts(const azp_rdf_args* args, void* stream)
         }
     char* base = static_cast<char*>(args->d_scratch);
     k.grid = p.grid;
+    k.ncell = p.ncell;
     k.sorted = reinterpret_cast<double*>(base);
-    k.cell_id = reinterpret_cast<uint32_t*>(base + p.off_cell_id);
-    k.count = reinterpret_cast<uint32_t*>(base + p.off_count);
     k.start = reinterpret_cast<uint32_t*>(base + p.off_start);
-    if ((e = hipMemsetAsync(k.count, 0, (uint64_t)p.grid.ncell * 4, st)) != hipSuccess)
-        return (int)e;
-    const uint32_t n_blocks = (uint32_t)(((uint64_t)args->n_total + RDF_BLOCK - 1) / RDF_BLOCK);
-    hipLaunchKernelGGL(rdf_bin_count, dim3(n_blocks), dim3(RDF_BLOCK), 0, st, k);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(rdf_bin_scan, dim3(1), dim3(RDF_SCAN_BLOCK), 0, st, k.count, k.start, p.grid.ncell);
-    if ((e = hipGetLastError()) != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(rdf_bin_scatter, dim3(n_blocks), dim3(RDF_BLOCK), 0, st, k);
-    if ((e = hipGetLastError()) != hipSuccess)
+    // (the block totals of the three-kernel scan live in the head of `sorted`, which the scatter fills only afterwards:
+    // nblk + 1 <= n_total words fit into n_total rows)
+    const RdfRowSink sink = {k.pos, k.mask_a, k.mask_b, k.sorted, k.N, k.ntypes};
+    e = bin_particles(args->n_total, k.pos, k.grid, nullptr, reinterpret_cast<uint32_t*>(base + p.off_cell_id),
+                      reinterpret_cast<uint32_t*>(base + p.off_count), k.start, reinterpret_cast<uint32_t*>(base), sink, st);
+    if (e != hipSuccess)
         return (int)e;
     // (a multiple of 8 workgroups, each a contiguous range of cells: xcd_remap gives every XCD one eighth of the grid)
-    const uint32_t grid = (std::min(p.grid.ncell, RDF_TARGET_BLOCKS) + 7u) & ~7u;
-    k.cells_per_block = (p.grid.ncell + grid - 1) / grid;
+    const uint32_t grid = (std::min(p.ncell, RDF_TARGET_BLOCKS) + 7u) & ~7u;
+    k.cells_per_block = (p.ncell + grid - 1) / grid;
     hipLaunchKernelGGL(rdf_cells, dim3(grid), dim3(RDF_BLOCK), lds, st, k);
     return (int)hipGetLastError();
     }

@@ -1,4 +1,4 @@
-"""azp_nlist_bin (csrc/nlist.hip: counting sort of the particles by cell + per-cell sort) on every one of its paths,
+"""azp_nlist_bin (counting sort of the particles by cell, csrc/cell_bin.hpp, + per-cell sort, csrc/nlist.hip) on every one of its paths,
 through the C ABI against numpy's stable sort; the row builder on grids of many cells against the all-pairs reference
 with both binnings; nlist.Cell._bin on its three branches through the API.
 
@@ -173,6 +173,39 @@ def test_bin_wraps_and_clamps():
         e[p // 4] = 1e-6 * w[p // 4]
         either = {int(B.cell_rule(xyz[p: p + 1] + s * e, -0.5 * L, w, dims, periodic)[0]) for s in (-1.0, 1.0)}
         assert int(cell_of[p]) in either, p
+
+
+def test_bin_keeps_nan_and_huge_coordinates_out_of_the_conversion():
+    """(1, 0, 1)-periodic grid, a dozen ordinary particles (0.3 of a width off their cell's centre at most) and six
+    that no cell rule covers: NaN, +1e300 and -1e300, each once on a periodic axis (x) and once on the clamped one (y).
+    cell_coord bounds the coordinate before it converts it to int, so every particle gets SOME cell of the grid, the
+    same one from azp_nlist_bin and azp_nlist_cell_assign, and the binning of all 18 is consistent; the ordinary ones
+    have the reference's cells."""
+    dims, periodic = (5, 4, 6), (1, 0, 1)
+    ncell = int(np.prod(dims))
+    n_ok = 12
+    cell = (np.arange(n_ok, dtype=np.int64) * 23 + 5) % ncell
+    ijk = np.stack([cell % dims[0], (cell // dims[0]) % dims[1], cell // (dims[0] * dims[1])], axis=1)
+    jitter = np.stack([0.6 * (syn.u01(31, np.arange(n_ok, dtype=np.uint64), c) - 0.5) for c in range(3)], axis=1)
+    L = np.asarray(dims) * B.CELL_WIDTH
+    ok = -0.5 * L + (ijk + 0.5 + jitter) * B.CELL_WIDTH
+    assert np.array_equal(B.cell_rule(ok, -0.5 * L, B.CELL_WIDTH, dims, periodic), cell)
+    bad = np.tile(ok[:1], (6, 1))
+    for k, v in enumerate((np.nan, 1e300, -1e300)):
+        bad[2 * k, 0] = v      # periodic axis
+        bad[2 * k + 1, 1] = v  # clamped axis
+    xyz = np.concatenate([ok[:6], bad, ok[6:]])
+    is_ok = np.r_[np.ones(6, bool), np.zeros(6, bool), np.ones(6, bool)]
+    n = xyz.shape[0]
+    a, t = bin_args(xyz, dims, L, periodic)
+    assert call_bin(a, t) == 0
+    cell_of, order, start = host(t["cell_of"])[:n], host(t["order"])[:n], host(t["cell_start"])[: ncell + 1]
+    assert np.all(cell_of < ncell)
+    assert np.array_equal(assigned_cells(a, t)[:n], cell_of)
+    assert np.array_equal(np.sort(order), np.arange(n))
+    assert np.array_equal(start, np.r_[0, np.cumsum(np.bincount(cell_of, minlength=ncell))])
+    assert np.array_equal(cell_of[is_ok], cell)
+    assert_binned(a, t, n, ncell)
 
 
 def test_bin_edges():

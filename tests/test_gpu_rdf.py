@@ -190,6 +190,49 @@ def test_two_cells_on_an_axis():
     assert _lib.lib().azp_rdf_scratch_size(C.byref(a), C.byref(need)) == 0 and need.value == 0
 
 
+def _grid_rule(L, periodic, r_max, n_total):
+    """rdf_make_grid (csrc/rdf.hip) restated: floor(L / r_max) cells per axis, at least 1 and at most 1024 (fewer than
+    3 on a periodic axis: no grid); while there are more cells than max(64, 2 n_total) (at most 2^21), every axis is
+    scaled by min(cbrt(cap / cells), 0.95), rounded down, not below 3 (periodic) or 1."""
+    dim = [np.floor(L[d] / r_max) for d in range(3)]
+    if any(periodic[d] and dim[d] < 3 for d in range(3)):
+        return None
+    dim = [min(max(x, 1.0), 1024.0) for x in dim]
+    cap = min(float(1 << 21), max(64.0, 2.0 * n_total))
+    for _ in range(64):
+        if np.prod(dim) <= cap:
+            break
+        f = min(np.cbrt(cap / np.prod(dim)), 0.95)
+        dim = [max(3.0 if periodic[d] else 1.0, np.floor(dim[d] * f)) for d in range(3)]
+    return tuple(int(x) for x in dim) if np.prod(dim) <= (1 << 21) else None
+
+
+@pytest.mark.parametrize("dims,n", [((17, 17, 15), 2400), ((33, 33, 34), 19000)], ids=["scan1", "scan3x10"])
+def test_cells_path_on_every_scan_path(dims, n):
+    """The counting sort behind the cells path (cell_bin.hpp) on the scan paths the small fixtures do not reach:
+    4,335 cells take more than one trip of the single workgroup, 37,026 cells the three-kernel scan with 10 blocks of
+    4,096, the last one partial (the rule of binning_cases.paths_of). Orthorhombic periodic box of
+    L_k = (dims_k + 0.5) r_max, uniform random fill, r_max = 1, 32 bins: _grid_rule gives exactly dims (n is large enough
+    for the cap max(64, 2 n) to leave the grid alone). The whole row of the cells path equals the all-pairs row, which
+    shares no binning code with it; about two ordered pairs per particle are counted."""
+    import binning_cases as B
+
+    r_max = 1.0
+    L = tuple((d + 0.5) * r_max for d in dims)
+    assert _grid_rule(L, fx.PBC, r_max, n) == dims
+    assert B.paths_of(dims, n)[0] == ("scan1x2" if n == 2400 else "scan3x10") and int(np.prod(dims)) % B.SCAN_BLOCK != 0
+    xyz, types = fx._uniform(n, L, 41)
+    f = fx._fixture(xyz, types, L, r_max, 32, (fx.ALL_ALL, fx.AB_BC))
+    sim = _sim(f)
+    for group in f["groups"]:
+        rows = {path: _row(_compute(sim, f, group, path)) for path in (CELLS, ALL_PAIRS)}
+        assert rows[CELLS].shape == (f["num_bins"] + 4,)
+        assert np.array_equal(rows[CELLS], rows[ALL_PAIRS]), (group, np.nonzero(rows[CELLS] != rows[ALL_PAIRS])[0][:8])
+        assert int(rows[CELLS][:-4].sum()) > 0
+        if group == fx.ALL_ALL:
+            assert n < int(rows[CELLS][:-4].sum()) < 3 * n
+
+
 # ---------------------------------------------------------------------------
 # mid size
 # ---------------------------------------------------------------------------

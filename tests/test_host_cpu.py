@@ -193,6 +193,14 @@ def test_external_barrier_host_logic(oracle):
     tri = _lib.make_box((20.0, 20.0, 10.0), tilt=(0.0, 0.0, -0.4))
     assert l.azp_planar_barrier_valid(7.9, C.byref(tri)) == 1
     assert l.azp_planar_barrier_valid(8.0, C.byref(tri)) == 0
+    # spherical, triclinic, the x width binding: 2R <= Lx / sqrt(1 + xy^2 + (xy yz - xz)^2), well below Lx and the others
+    L, tilt = (10.0, 20.0, 20.0), (0.5, 0.3, 0.2)
+    w = azp.Box(*L, xy=tilt[0], xz=tilt[1], yz=tilt[2]).nearest_plane_distance
+    assert w[0] < 0.9 * L[0] and w[0] < 0.5 * min(w[1], w[2])
+    tri = _lib.make_box(L, tilt=tilt)
+    assert l.azp_spherical_barrier_valid(0.5 * w[0] * (1.0 - 1e-12), C.byref(tri)) == 1
+    assert l.azp_spherical_barrier_valid(0.5 * w[0] * (1.0 + 1e-12), C.byref(tri)) == 0
+    assert l.azp_spherical_barrier_valid(0.5 * L[0], C.byref(tri)) == 0
 
 
 def test_cpp_class_names_match_reference_module():
