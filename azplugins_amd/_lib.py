@@ -387,6 +387,40 @@ class ThermostatArgs(C.Structure):
     ]
 
 
+BAROSTAT_NSTATE = 24
+(BAROSTAT_NU, BAROSTAT_ALPHA, BAROSTAT_LAMBDA, BAROSTAT_B) = (0, 3, 6, 9)  # three slots each: x, y, z
+(BAROSTAT_ALPHA_T, BAROSTAT_ENERGY, BAROSTAT_V, BAROSTAT_P, BAROSTAT_NONFINITE, BAROSTAT_REF_KT, BAROSTAT_K, BAROSTAT_W) = (
+    12, 13, 14, 15, 18, 19, 20, 21)
+BAROSTAT_CLOSE, BAROSTAT_OPEN = 1, 2
+BAROSTAT_COUPLE = {"none": 0, "xy": 1, "xz": 2, "yz": 3, "xyz": 4}
+
+
+class BarostatArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_vel", C.c_void_p),
+        ("d_net_force", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_state", C.c_void_p),
+        ("d_sums", C.c_void_p),
+        ("d_thermostat_state", C.c_void_p),
+        ("box", Box),
+        ("dt", C.c_double),
+        ("S", C.c_double * 3),
+        ("tauS", C.c_double),
+        ("ndof", C.c_double),
+        ("thermostat_kT", C.c_double),
+        ("thermostat_tau", C.c_double),
+        ("timestep", C.c_uint64),
+        ("thermostat_kind", C.c_uint32),
+        ("thermostat_seed", C.c_uint32),
+        ("couple", C.c_uint32),
+        ("box_dof", C.c_uint32),
+        ("phase", C.c_uint32),
+        ("N", C.c_uint32),
+    ]
+
+
 FIRE_NSTATE = 16
 (FIRE_DT, FIRE_ALPHA, FIRE_KEEP, FIRE_MIX, FIRE_N_POS, FIRE_N_STEPS, FIRE_U, FIRE_U_PREV, FIRE_P, FIRE_VV, FIRE_FF, FIRE_CONVERGED,
  FIRE_NONFINITE) = range(13)
@@ -587,6 +621,9 @@ SYMBOLS = {
     "azp_thermostat_step_two": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
     "azp_thermostat_advance": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
     "azp_thermostat_step_one": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
+    "azp_barostat_advance": (C.c_int, [C.POINTER(BarostatArgs), _VP]),
+    "azp_barostat_step_one": (C.c_int, [C.POINTER(BarostatArgs), _VP]),
+    "azp_barostat_step_two": (C.c_int, [C.POINTER(BarostatArgs), _VP]),
     "azp_fire_partials_size": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
     "azp_fire_measure": (C.c_int, [C.POINTER(FireArgs), _VP]),
     "azp_fire_step_two": (C.c_int, [C.POINTER(FireArgs), _VP]),

@@ -23,7 +23,7 @@ import itertools
 import numpy as np
 
 from . import _lib
-from .simulation import All, ConstantVolume, Periodic, Type
+from .simulation import All, ConstantPressure, ConstantVolume, Periodic, Type
 
 
 class DataAccessError(_lib.AzpError):
@@ -304,11 +304,12 @@ def thermo_quantities(sums, n_global, volume, conserves_momentum, rotational):
 
 
 def _integrator_flags(integ):
-    """(conserves_momentum, rotational) of ``thermo_quantities`` for an integrator: ``ConstantVolume`` conserves the
-    linear momentum, ``flow.Langevin`` / ``flow.Brownian`` and an integrator without a method do not."""
+    """(conserves_momentum, rotational) of ``thermo_quantities`` for an integrator: ``ConstantVolume`` and
+    ``ConstantPressure`` conserve the linear momentum, ``flow.Langevin`` / ``flow.Brownian`` and an integrator without a
+    method do not."""
     if integ is None:
         return False, False
-    return any(isinstance(m, ConstantVolume) for m in integ.methods), bool(integ.integrate_rotational_dof)
+    return any(isinstance(m, (ConstantVolume, ConstantPressure)) for m in integ.methods), bool(integ.integrate_rotational_dof)
 
 
 class ThermodynamicQuantities(_Compute):

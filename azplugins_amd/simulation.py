@@ -6,6 +6,7 @@ validated as in src/pytest/test_pair_dpd.py.
 """
 
 import ctypes as C
+import math
 import warnings
 
 import numpy as np
@@ -95,7 +96,8 @@ def _launch(a, st, stream, *names):
 
 
 class _DeviceControlled:
-    """A stepper whose step is controlled on the device (the thermostats, ``minimize.FIRE``) and the buffers it owns: the
+    """A stepper whose step is controlled on the device (the thermostats, ``minimize.FIRE``, ``ConstantPressure``, which
+    sizes no partials: its sums are ``azp_thermo_sums``') and the buffers it owns: the
     control state, float64 doubles made at the first run, which persist across runs and follow the particles to their
     device, and the partials that its sums pass through."""
 
@@ -131,7 +133,8 @@ class ConstantVolume:
     ``thermostat``: None (NVE, the fused kernels) or one of ``azplugins_amd.thermostats`` (``Berendsen``, ``Bussi``,
     ``MTTK``), which rescales the velocities of all particles once per step on the device. A
     thermostatted method integrates translational degrees of freedom of a single-domain run only; out of scope:
-    rotational degrees of freedom, ``Type`` filters, decomposed runs, Nose-Hoover chains, ``ConstantPressure``."""
+    rotational degrees of freedom, ``Type`` filters, decomposed runs, Nose-Hoover chains. Constant pressure:
+    ``ConstantPressure``."""
 
     def __init__(self, filter=None, thermostat=None):
         if filter is not None and not isinstance(filter, All):
@@ -204,12 +207,285 @@ class ConstantVolume:
             self._rotational_step(sim, False)
 
 
+_AXES = ("x", "y", "z")
+
+
+class ConstantPressure(_DeviceControlled):
+    """``hoomd.md.methods.ConstantPressure`` on the three lengths of an orthorhombic box: a Martyna-Tobias-Klein barostat
+    (NPH), with one of ``azplugins_amd.thermostats`` NPT. HOOMD-blue's source is not available to this project: the
+    scheme is defined in ``include/azp.h`` and ``DESIGN.md`` 4.23 and runs in libazp (``csrc/barostat.hip``).
+
+    ``S``: the target stress: a float (the pressure), a callable of the timestep (the ``variant`` classes included), or
+    six values xx, yy, zz, yz, xz, xy whose last three are 0. ``tauS`` > 0: the barostat's time constant.
+    ``couple``: ``"none"``, ``"xy"``, ``"xz"``, ``"yz"`` or ``"xyz"``: the coupled axes change at one rate.
+    ``thermostat``: None or a ``Berendsen``, ``Bussi`` or ``MTTK``; it acts on the particles only, the box rates are not
+    thermostatted. ``box_dof``: which of Lx, Ly, Lz (and, always False here, the tilts xz, yz, xy) are free.
+    ``rescale_all`` has no effect (all particles are integrated), ``gamma`` must be 0.
+
+    One rate nu_a per axis lives in a device-resident state that persists across runs: ``run(10); run(10)`` equals
+    ``run(20)`` bit for bit. ``barostat_dof`` (the three nu), ``barostat_energy`` (W / 2 sum nu_a^2) and ``reference_kT``
+    can be read between runs (reading synchronises); ``barostat_dof`` and ``reference_kT`` can be set. For hydrostatic S,
+    K + U + S V + ``barostat_energy`` (+ the thermostat's ``energy``) is conserved up to the integrator's error. Without a
+    thermostat the barostat's mass W = (Nf + 3) kT_ref tauS^2 takes kT_ref = 2 K / Nf from the first step of the first run.
+
+    The box lives on the host: every step the host reads the three scale factors from the device (ONE HOST WAIT PER
+    STEP) and sets the box through ``State.set_box``, so every neighbor list is rebuilt every step, as under an
+    ``update.BoxResize`` that fires every step. While such a method is present the virial pass of every force runs
+    every step (at most 8 forces).
+
+    Refused: a filter other than ``All()``, rotational degrees of freedom, decomposed runs, tilted boxes, a free axis
+    that is not periodic, tilt degrees of freedom, ``gamma`` != 0, fewer than 2 particles, a second method next to it."""
+
+    _name = "ConstantPressure"
+    _fusable = False
+    _updaters_split = False
+
+    def __init__(self, filter, S, tauS, couple, thermostat=None, box_dof=(True, True, True, False, False, False),
+                 rescale_all=False, gamma=0.0):
+        if filter is not None and not isinstance(filter, All):
+            raise _lib.AzpError("ConstantPressure: only filter=All() is supported (the barostat scales every particle), got %r" % (filter,))
+        self.filter = All() if filter is None else filter
+        self.S = S
+        tauS = float(tauS)
+        if not (math.isfinite(tauS) and tauS > 0.0):
+            raise _lib.AzpError("ConstantPressure: tauS must be > 0, got %r" % (tauS,))
+        self.tauS = tauS
+        if couple not in _lib.BAROSTAT_COUPLE:
+            raise _lib.AzpError("ConstantPressure: couple must be one of %s, got %r" % (sorted(_lib.BAROSTAT_COUPLE), couple))
+        self.couple = couple
+        box_dof = tuple(bool(b) for b in box_dof)
+        if len(box_dof) != 6:
+            raise _lib.AzpError("ConstantPressure: box_dof takes six flags (Lx, Ly, Lz, xz, yz, xy), got %r" % (box_dof,))
+        if any(box_dof[3:]):
+            raise _lib.AzpError("ConstantPressure: tilt degrees of freedom are not supported (box_dof = %r): the box stays "
+                                "orthorhombic" % (box_dof,))
+        self.box_dof = box_dof
+        if float(gamma) != 0.0:
+            raise _lib.AzpError("ConstantPressure: gamma = %r: the Langevin piston is not supported, gamma must be 0" % (gamma,))
+        self.gamma = 0.0
+        self.rescale_all = bool(rescale_all)
+        self._thermostat = None
+        self.thermostat = thermostat
+        self._pending = [0.0] * _lib.BAROSTAT_NSTATE
+        self._row = None
+        self._thermo = None
+        self._first = True
+
+    @property
+    def S(self):
+        return self._S
+
+    @S.setter
+    def S(self, S):
+        if not callable(S):
+            try:
+                S = (float(S),) * 3 + (0.0,) * 3
+            except TypeError:
+                S = tuple(float(x) for x in S)
+                if len(S) != 6:
+                    raise _lib.AzpError("ConstantPressure: S is a float, a callable of the timestep or six values xx, yy, zz, "
+                                        "yz, xz, xy; got %r" % (S,))
+            if not all(math.isfinite(x) for x in S):
+                raise _lib.AzpError("ConstantPressure: S must be finite, got %r" % (S,))
+            if any(x != 0.0 for x in S[3:]):
+                raise _lib.AzpError("ConstantPressure: shear stresses are not supported (S = %r): yz, xz and xy must be 0" % (S,))
+        self._S = S
+
+    def _S_at(self, timestep):
+        """(S_xx, S_yy, S_zz) at ``timestep``."""
+        if not callable(self._S):
+            return self._S[:3]
+        s = float(self._S(timestep))
+        if not math.isfinite(s):
+            raise _lib.AzpError("ConstantPressure: S must be finite, got %r at timestep %d" % (s, timestep))
+        return (s, s, s)
+
+    @property
+    def thermostat(self):
+        return self._thermostat
+
+    @thermostat.setter
+    def thermostat(self, thermostat):
+        from .thermostats import _Thermostat
+
+        if thermostat is not None and not isinstance(thermostat, _Thermostat):
+            raise _lib.AzpError("ConstantPressure: thermostat must be None or one of azplugins_amd.thermostats, got %r" % (thermostat,))
+        if self._thermostat is not None:
+            self._thermostat._holders.discard(self)
+        if thermostat is not None:
+            thermostat._holders.add(self)
+        self._thermostat = thermostat
+
+    # -- device-resident state ---------------------------------------------------
+    def _slots(self, k, n=1):
+        """Slots k .. k + n - 1 of the state; reading synchronises."""
+        if self._state is None:
+            return tuple(self._pending[k:k + n])
+        return tuple(self._state[k:k + n].tolist())
+
+    def _set_slots(self, k, values, what):
+        values = [float(v) for v in values]
+        if not all(math.isfinite(v) for v in values):
+            raise _lib.AzpError("ConstantPressure: %s must be finite, got %r" % (what, values))
+        if self._state is None:
+            self._pending[k:k + len(values)] = values
+        else:
+            import torch
+
+            self._state[k:k + len(values)] = torch.tensor(values, dtype=torch.float64)
+
+    @property
+    def barostat_dof(self):
+        """(nu_x, nu_y, nu_z): the rates of the three box lengths, d ln L_a / dt."""
+        return self._slots(_lib.BAROSTAT_NU, 3)
+
+    @barostat_dof.setter
+    def barostat_dof(self, value):
+        value = tuple(value)
+        if len(value) != 3:
+            raise _lib.AzpError("ConstantPressure: barostat_dof takes (nu_x, nu_y, nu_z), got %r" % (value,))
+        self._set_slots(_lib.BAROSTAT_NU, value, "barostat_dof")
+
+    @property
+    def barostat_energy(self):
+        """(W / 2)(nu_x^2 + nu_y^2 + nu_z^2) as of the last step run (0 before the first)."""
+        return self._slots(_lib.BAROSTAT_ENERGY)[0]
+
+    @property
+    def reference_kT(self):
+        """kT_ref of the barostat's mass W = (Nf + 3) kT_ref tauS^2 in a run without a thermostat: 2 K / Nf at the first
+        step of the first run (0 before it), or what was set. With a thermostat its kT is used instead."""
+        return self._slots(_lib.BAROSTAT_REF_KT)[0]
+
+    @reference_kT.setter
+    def reference_kT(self, value):
+        if not float(value) >= 0.0:
+            raise _lib.AzpError("ConstantPressure: reference_kT must be >= 0 (0: measure it at the next step), got %r" % (value,))
+        self._set_slots(_lib.BAROSTAT_REF_KT, [value], "reference_kT")
+
+    # -- the stepper (DESIGN 4.20, 4.23) -------------------------------------------
+    def _check(self, sim, integ):
+        """What ``ConstantPressure`` cannot do, each refused with its reason."""
+        st = sim.state
+        if len(integ.methods) != 1:
+            raise _lib.AzpError("ConstantPressure must be the only method of the integrator (it scales every particle and the "
+                                "box), got %r" % (integ.methods,))
+        if not isinstance(self.filter, All):
+            raise _lib.AzpError("ConstantPressure: only filter=All() is supported (the barostat scales every particle), got %r"
+                                % (self.filter,))
+        if integ.integrate_rotational_dof:
+            raise _lib.AzpError("ConstantPressure: rotational degrees of freedom are not integrated (integrate_rotational_dof=True)")
+        if sim.domain is not None:
+            raise _lib.AzpError("ConstantPressure does not run decomposed (the domain's slabs are cut once, and the pressure "
+                                "would need a collective every step)")
+        if st.N < 2:
+            raise _lib.AzpError("ConstantPressure: fewer than 2 particles leave no degree of freedom (Nf = 3 N - 3), N = %d" % st.N)
+        box = st.box
+        if box.is_triclinic:
+            raise _lib.AzpError("ConstantPressure: %r is tilted: only orthorhombic boxes are supported" % (box,))
+        for k in range(3):
+            if self.box_dof[k] and not box.periodic[k]:
+                raise _lib.AzpError("ConstantPressure: the box is not periodic along %s, which box_dof leaves free: a free axis "
+                                    "must be periodic" % _AXES[k])
+        if len(integ.forces) > _lib.THERMO_MAX_FORCES:
+            raise _lib.AzpError("ConstantPressure sums the virials of at most %d forces, the integrator has %d"
+                                % (_lib.THERMO_MAX_FORCES, len(integ.forces)))
+        th = self._thermostat
+        if th is not None:
+            if th._kind == _lib.THERMOSTAT_BERENDSEN and th.tau < integ.dt:
+                raise _lib.AzpError("%s: tau = %r is below dt = %r (the rescaling factor's radicand can turn negative)"
+                                    % (th._name, th.tau, integ.dt))
+            if any(m is not self for m in th._holders):
+                raise _lib.AzpError("%s: one thermostat object is held by two methods (its state belongs to one run)" % th._name)
+
+    def _begin(self, sim):
+        import torch
+
+        from .compute import ThermodynamicQuantities
+
+        integ, st = sim.operations.integrator, sim.state
+        self._check(sim, integ)
+        dev = st.vel.device
+        if self._state is None or self._state.device != dev:
+            start = self._pending if self._state is None else self._state.cpu().tolist()
+            self._state = torch.tensor(start, dtype=torch.float64, device=dev)
+        if self._row is None or self._row.device != dev:
+            self._row = torch.zeros(_lib.THERMO_NSUMS, dtype=torch.float64, device=dev)
+        if self._thermo is None:
+            self._thermo = ThermodynamicQuantities(All())  # (never in sim.operations.computes: its launch machinery alone)
+        self._thermo._sim = sim
+        a = self._args = _lib.BarostatArgs()
+        a.d_state = self._state.data_ptr()
+        a.d_sums = self._row.data_ptr()
+        a.box = st.box.to_c()
+        a.dt = integ.dt
+        a.tauS = self.tauS
+        a.ndof = float(3 * st.N - 3)
+        a.couple = _lib.BAROSTAT_COUPLE[self.couple]
+        a.box_dof = sum(1 << k for k in range(3) if self.box_dof[k])
+        th = self._thermostat
+        if th is not None:
+            if th._kind == _lib.THERMOSTAT_BUSSI:
+                sim._warn_if_seed_unset()
+            if th._state is None or th._state.device != dev:
+                start = th._pending if th._state is None else th._state.cpu().tolist()
+                th._state = torch.tensor(start, dtype=torch.float64, device=dev)
+            a.d_thermostat_state = th._state.data_ptr()
+            a.thermostat_tau = th.tau
+            a.thermostat_kind = th._kind
+            a.thermostat_seed = int(sim.seed or 0) & 0xFFFF
+            th._ndof = a.ndof
+        self._stream = _lib.raw_stream(st.device)
+        self._first = True  # (the first step opens from a sums pass of the state as it stands)
+
+    def _advance(self, sim, timestep, phase):
+        a = self._args
+        a.S[:] = self._S_at(timestep)
+        a.timestep = timestep
+        a.phase = phase
+        th = self._thermostat
+        if th is not None:
+            a.thermostat_kT = th._kT_at(timestep)
+            if phase & _lib.BAROSTAT_OPEN:
+                th._last_kT = a.thermostat_kT
+        _launch(a, sim.state, self._stream, "azp_barostat_advance")
+
+    def _step_one(self, sim, timestep, fused):
+        from .state import Box
+
+        st = sim.state
+        if self._first:
+            self._thermo._launch(self._row.data_ptr())
+            self._first = False
+        self._advance(sim, timestep, _lib.BAROSTAT_OPEN)
+        # the one host read of the step: the box lives on the host (DESIGN 4.23)
+        host = self._state.tolist()
+        if host[_lib.BAROSTAT_NONFINITE] != 0.0:
+            raise _lib.AzpError("ConstantPressure: the barostat's state is not finite at timestep %d (nu = %r, K = %r, W = %r): "
+                                "no kinetic energy to take reference_kT from, or the run has diverged"
+                                % (timestep, host[_lib.BAROSTAT_NU:_lib.BAROSTAT_NU + 3], host[_lib.BAROSTAT_K], host[_lib.BAROSTAT_W]))
+        lam = host[_lib.BAROSTAT_LAMBDA:_lib.BAROSTAT_LAMBDA + 3]
+        box = st.box
+        st.set_box(Box(lam[0] * box.Lx, lam[1] * box.Ly, lam[2] * box.Lz, periodic=box.periodic))
+        _launch(self._args, st, self._stream, "azp_barostat_step_one")
+
+    def _step_two(self, sim, timestep):
+        _launch(self._args, sim.state, self._stream, "azp_barostat_step_two")
+        self._thermo._launch(self._row.data_ptr())
+        # (the close half belongs to the end of the step: S and kT of the timestep the next step opens at. Always a
+        # launch of its own, at the end of a run too: run(a); run(b) is run(a + b) bit for bit)
+        self._advance(sim, timestep + 1, _lib.BAROSTAT_CLOSE)
+
+    def __repr__(self):
+        return "ConstantPressure(S=%r, tauS=%r, couple=%r, thermostat=%r)" % (self._S, self.tauS, self.couple, self._thermostat)
+
+
 class Integrator:
     """``hoomd.md.Integrator`` reduced: ``dt``, ``forces``, ``methods``,
     ``integrate_rotational_dof`` (orientations and angular momenta of particles with a
     non-zero moment of inertia are integrated with the net torque, HOOMD's default False).
-    ``methods`` holds one ``ConstantVolume``, or one or more ``flow.Langevin`` / ``flow.Brownian`` with
-    pairwise-disjoint filters (an ``All()`` filter stands alone)."""
+    ``methods`` holds one ``ConstantVolume``, one ``ConstantPressure``, or one or more ``flow.Langevin`` /
+    ``flow.Brownian`` with pairwise-disjoint filters (an ``All()`` filter stands alone)."""
 
     def __init__(self, dt, forces=None, methods=None, integrate_rotational_dof=False):
         self.dt = float(dt)
@@ -394,8 +670,9 @@ class Simulation:
                 f._attach(self)
                 if f not in self._attached:
                     self._attached.append(f)
-        if self._has_thermo():
-            # (a ThermodynamicQuantities reads the per-particle virials: the virial pass of every force runs every step)
+        if self._has_thermo() or self._barostat(integ) is not None:
+            # (a ThermodynamicQuantities and a ConstantPressure read the per-particle virials: the virial pass of every
+            # force runs every step)
             for f in integ.forces:
                 f.compute_virial = True
             for c in self._thermo_computes():
@@ -405,6 +682,11 @@ class Simulation:
         from .compute import ThermodynamicQuantities
 
         return [c for c in self.operations.computes if isinstance(c, ThermodynamicQuantities)]
+
+    @staticmethod
+    def _barostat(integ):
+        """The first ``ConstantPressure`` among the integrator's methods, or None."""
+        return next((m for m in integ.methods if isinstance(m, ConstantPressure)), None)
 
     def _has_thermo(self):
         return bool(self.operations.computes) and bool(self._thermo_computes())
@@ -475,6 +757,9 @@ class Simulation:
         fire = isinstance(integ, FIRE)
         if fire:
             integ._check(self)
+        barostat = None if fire else self._barostat(integ)
+        if barostat is not None:
+            barostat._check(self, integ)
         flow_methods = [] if fire else self._check_flow_methods(integ)
         if self.domain is not None:
             self._wire_domain()
@@ -482,11 +767,13 @@ class Simulation:
         if steps == 0 or not integ.methods:
             return
         # what moves the particles, each with the stepper interface: the minimizer, the flow methods, or
-        # the one ConstantVolume (its thermostat where it has one)
+        # a ConstantPressure, or the one ConstantVolume (its thermostat where it has one)
         if fire:
             steppers = [integ]
         elif flow_methods:
             steppers = flow_methods
+        elif barostat is not None:
+            steppers = [barostat]
         elif len(integ.methods) != 1 or not isinstance(integ.methods[0], ConstantVolume):
             raise _lib.AzpError("Integrator.methods must hold exactly one ConstantVolume (all particles); got %r" % (integ.methods,))
         else:

@@ -14,8 +14,11 @@ on the device, and step one does v <- alpha v ahead of the half kick. Nothing is
 set between runs; reading synchronises. The state lives in a small device tensor owned by the thermostat and persists
 across ``run`` calls: ``run(10); run(10)`` equals ``run(20)`` bit for bit.
 
-Out of scope: rotational degrees of freedom, ``Type`` filters, decomposed runs, Nose-Hoover chains longer than one,
-``ConstantPressure``, an ``_azplugins`` pybind class."""
+``ConstantPressure(..., thermostat=...)`` takes the same objects: there the barostat's advance runs the thermostat's on this
+state (``DESIGN.md`` 4.23). One thermostat object belongs to one method.
+
+Out of scope: rotational degrees of freedom, ``Type`` filters, decomposed runs, Nose-Hoover chains longer than one, an
+``_azplugins`` pybind class."""
 
 import math
 import weakref

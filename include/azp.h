@@ -928,6 +928,105 @@ int azp_thermostat_step_two(const azp_thermostat_args* args, void* stream);
 int azp_thermostat_advance(const azp_thermostat_args* args, void* stream);
 int azp_thermostat_step_one(const azp_thermostat_args* args, void* stream);
 
+/* ---- barostat (azplugins_amd.ConstantPressure: NPH, and NPT with one of the thermostats above) ----
+ * Name and parameter keys are hoomd.md.methods.ConstantPressure's; HOOMD-blue's source is not available to this
+ * project, so the scheme is DEFINED HERE and pinned by tests/barostat_ref.py. A Martyna-Tobias-Klein
+ * barostat on the three lengths of an orthorhombic box: one rate nu_a per axis a in {x, y, z}, all N particles,
+ * translational degrees of freedom. The box itself belongs to the caller (the host), who reads lambda from d_state.
+ *
+ * Inputs of the advance: d_sums, the 20 doubles of azp_thermo_sums over all particles (K_aa = slots 4, 7, 9; W_aa = slots
+ * 10, 13, 15); box.L; S; dt; tauS; Nf = `ndof` (the driver passes 3 N - 3). In this order, plain IEEE, no contraction:
+ *   K      = 0.5 ((K_xx + K_yy) + K_zz)
+ *   V      = (Lx Ly) Lz
+ *   kT_ref = thermostat_kT with a thermostat (d_thermostat_state != NULL). Without one: d_state[REF_KT] if that is > 0,
+ *            else (2 K) / Nf, which is then stored in REF_KT (the first advance of a fresh state measures it)
+ *   W      = ((Nf + 3) kT_ref) (tauS tauS)
+ *   G_a    = (((K_aa + W_aa) - V S_a) + (2 K) / Nf) / W        for an axis whose box_dof bit is set, else 0
+ *   couple: the free axes of the coupled set C ({x,y}, {x,z}, {y,z} or {x,y,z}) all take (sum of G_c over C in the order
+ *            x, y, z, a frozen axis adding its 0) / (number of free axes in C); AZP_BAROSTAT_COUPLE_NONE: nothing
+ *   half update ("close" and "open" alike):  nu_a = nu_a + (0.5 dt) G_a for a free axis; nu_a = 0 for a frozen one
+ * phase & AZP_BAROSTAT_CLOSE: one half update. phase & AZP_BAROSTAT_OPEN: one half update, then
+ *   trace    = (nu_x + nu_y) + nu_z
+ *   alpha_a  = exp(-((nu_a + trace / Nf) (0.5 dt)))
+ *   lambda_a = exp(nu_a dt)
+ *   b_a      = (dt exp(x)) s(x), x = nu_a (0.5 dt), s(x) = 1 + x2 (1/6 + x2 (1/120 + x2 (1/5040 + x2 (1/362880)))), x2 = x x:
+ *              sinh(x) / x, whose truncation is below 2^-53 for |x| <= 0.1
+ *   alpha_T  = 1, or with a thermostat the alpha of its advance (the thermostat's scheme above, on d_thermostat_state, with
+ *              this K, thermostat_kT / _tau / _kind / _seed, `timestep`, dt and Nf); nu is not thermostatted
+ * Close and open in one call are the two half updates one after the other, from the same G: bit for bit what two calls give.
+ * Every call then writes ENERGY = (0.5 W) ((nu_x nu_x + nu_y nu_y) + nu_z nu_z), K, V, P_aa = (K_aa + W_aa) / V, W and
+ * NONFINITE = 1 if any nu, alpha, lambda or b is not finite (else 0).
+ *
+ * One step t -> t + dt:
+ *   azp_barostat_advance(OPEN)   from the sums of the state at t
+ *   the caller reads lambda and multiplies its box lengths by it: args.box of the calls below is the NEW box
+ *   azp_barostat_step_one        c_a = alpha_T alpha_a; v_a = c_a v_a; v += ((dt / 2) f) (1 / m);
+ *                                r_a = lambda_a r_a + b_a v_a; wrap into the new box (image counters updated) as
+ *                                azp_integrate_nve_step_one does; pos.w and vel.w are preserved
+ *   the forces at t + dt, with virials (the caller's)
+ *   azp_barostat_step_two        v += ((dt / 2) f) (1 / m); v_a = alpha_a v_a
+ *   azp_thermo_sums into d_sums, then azp_barostat_advance(CLOSE), in the new box
+ * Conserved for S_x = S_y = S_z = S: K + U + S V + ENERGY (+ the thermostat's energy).
+ * The step kernels read alpha, lambda, b and alpha_T from d_state. Plain IEEE arithmetic in the order written, no
+ * contraction, no atomics. Asynchronous on `stream`.
+ * AZP_ERROR_INVALID_ARGUMENT: NULL args, N == 0, a NULL array the call uses (d_image may be NULL), dt <= 0, a tilted box, an
+ * edge <= 0, a free axis that is not periodic, box_dof bits above 7; for the advance also tauS <= 0, ndof < 3, an unknown
+ * couple code, a phase of 0 or above 3, S not finite, and with a thermostat what azp_thermostat_advance refuses. */
+#define AZP_BAROSTAT_NSTATE 24
+#define AZP_BAROSTAT_NU 0        /* 0, 1, 2: nu_x, nu_y, nu_z */
+#define AZP_BAROSTAT_ALPHA 3     /* 3, 4, 5 */
+#define AZP_BAROSTAT_LAMBDA 6    /* 6, 7, 8 */
+#define AZP_BAROSTAT_B 9         /* 9, 10, 11 */
+#define AZP_BAROSTAT_ALPHA_T 12
+#define AZP_BAROSTAT_ENERGY 13
+#define AZP_BAROSTAT_V 14        /* the volume the last advance saw */
+#define AZP_BAROSTAT_P 15        /* 15, 16, 17: P_xx, P_yy, P_zz it saw */
+#define AZP_BAROSTAT_NONFINITE 18
+#define AZP_BAROSTAT_REF_KT 19   /* kT_ref of a run without thermostat; 0: not measured yet */
+#define AZP_BAROSTAT_K 20        /* the kinetic energy it saw */
+#define AZP_BAROSTAT_W 21        /* the barostat's mass W */
+
+#define AZP_BAROSTAT_CLOSE 1u
+#define AZP_BAROSTAT_OPEN 2u
+
+typedef enum azp_barostat_couple
+    {
+    AZP_BAROSTAT_COUPLE_NONE = 0,
+    AZP_BAROSTAT_COUPLE_XY = 1,
+    AZP_BAROSTAT_COUPLE_XZ = 2,
+    AZP_BAROSTAT_COUPLE_YZ = 3,
+    AZP_BAROSTAT_COUPLE_XYZ = 4
+    } azp_barostat_couple;
+
+typedef struct azp_barostat_args
+    {
+    double* d_pos;               /* N x 4 (type in w is preserved); step one */
+    double* d_vel;               /* N x 4 (vx, vy, vz, mass); step one and step two */
+    const double* d_net_force;   /* N x 4; step one and step two */
+    int32_t* d_image;            /* N x 3 periodic image counters, may be NULL; step one */
+    double* d_state;             /* AZP_BAROSTAT_NSTATE doubles */
+    const double* d_sums;        /* AZP_THERMO_NSUMS doubles; the advance */
+    double* d_thermostat_state;  /* AZP_THERMOSTAT_NSTATE doubles, or NULL: no thermostat; the advance */
+    azp_box box;
+    double dt;
+    double S[3];                 /* S_xx, S_yy, S_zz */
+    double tauS;
+    double ndof;                 /* Nf */
+    double thermostat_kT;        /* kT at `timestep` */
+    double thermostat_tau;
+    uint64_t timestep;
+    uint32_t thermostat_kind;    /* azp_thermostat_kind */
+    uint32_t thermostat_seed;    /* low 16 bits used */
+    uint32_t couple;             /* azp_barostat_couple */
+    uint32_t box_dof;            /* bit a set: axis a is free */
+    uint32_t phase;              /* AZP_BAROSTAT_CLOSE | AZP_BAROSTAT_OPEN */
+    uint32_t N;
+    } azp_barostat_args;
+
+int azp_barostat_advance(const azp_barostat_args* args, void* stream);
+int azp_barostat_step_one(const azp_barostat_args* args, void* stream);
+int azp_barostat_step_two(const azp_barostat_args* args, void* stream);
+
 /* ---- energy minimization (azplugins_amd.minimize.FIRE) ----
  * Name and parameter keys are hoomd.md.minimize.FIRE's; HOOMD-blue's source is not available to this project, so the
  * scheme is DEFINED HERE and pinned by tests/fire_ref.py. FIRE (Bitzek et al. 2006) is velocity Verlet
