@@ -23,7 +23,9 @@ import itertools
 import numpy as np
 
 from . import _lib
-from .simulation import All, ConstantPressure, ConstantVolume, Periodic, Type
+from .filter import All, Type
+from .methods import ConstantPressure, ConstantVolume
+from .trigger import Periodic
 
 
 class DataAccessError(_lib.AzpError):

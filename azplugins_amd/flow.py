@@ -5,13 +5,13 @@ integration methods that consume them, ``Langevin`` (``TwoStepLangevinFlow``) an
 The fields are plain parameter holders (they pickle); ``_cpp()`` gives the ``_azplugins`` object with the
 reference's constructor and properties, which also evaluates the field on the host."""
 
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib
-from .simulation import All, Type
+from .filter import All, Type
+from .methods import _launch
 
 
 def _finite(x, what):
@@ -190,21 +190,12 @@ class _FlowMethod:
         self._args = a
         self._stream = _lib.raw_stream(st.device)
 
-    def _launch(self, name, st, timestep):
-        """Queue the libazp entry ``name`` with the struct pointed at the state's arrays and at ``timestep`` (random
-        numbers and kT)."""
+    def _at(self, timestep):
+        """The argument struct at ``timestep`` (random numbers and kT)."""
         a = self._args
-        a.d_pos = st.pos.data_ptr()
-        a.d_vel = st.vel.data_ptr()
-        a.d_accel = st.accel.data_ptr() if st.accel is not None else None
-        a.d_net_force = st.net_force.data_ptr()
-        a.d_image = st.image.data_ptr()
-        a.d_tag = st.tag.data_ptr()
-        a.box = st.box.to_c()
-        a.N = st.N
         a.timestep = int(timestep)
         a.kT = self._kT(timestep)
-        _lib.check(getattr(_lib.lib(), name)(C.byref(a), self._stream), name)
+        return a
 
 
 class Langevin(_FlowMethod):
@@ -225,12 +216,12 @@ class Langevin(_FlowMethod):
         """Step one of the step starting at ``timestep`` (fused: preceded by step two of the previous step, whose
         random numbers and kT belong to ``timestep - 1``; step one itself draws nothing)."""
         if fused:
-            self._launch("azp_integrate_langevin_flow_step_two_one", sim.state, timestep - 1)
+            _launch(self._at(timestep - 1), sim.state, self._stream, "azp_integrate_langevin_flow_step_two_one")
         else:
-            self._launch("azp_integrate_langevin_flow_step_one", sim.state, timestep)
+            _launch(self._at(timestep), sim.state, self._stream, "azp_integrate_langevin_flow_step_one")
 
     def _step_two(self, sim, timestep):
-        self._launch("azp_integrate_langevin_flow_step_two", sim.state, timestep)
+        _launch(self._at(timestep), sim.state, self._stream, "azp_integrate_langevin_flow_step_two")
 
 
 class Brownian(_FlowMethod):
@@ -249,7 +240,7 @@ class Brownian(_FlowMethod):
 
     def _step_one(self, sim, timestep, fused):
         """The whole step starting at ``timestep``."""
-        self._launch("azp_integrate_brownian_flow_step", sim.state, timestep)
+        _launch(self._at(timestep), sim.state, self._stream, "azp_integrate_brownian_flow_step")
 
     def _step_two(self, sim, timestep):
         pass  # Brownian dynamics has no second half

@@ -30,7 +30,9 @@ import math
 import weakref
 
 from . import _lib
-from .simulation import All, ConstantVolume, Integrator, _DeviceControlled, _launch
+from .filter import All
+from .methods import ConstantVolume, _ControlState, _DeviceControlled, _bind_partials, _launch
+from .simulation import Integrator
 
 
 def _positive(name, value):
@@ -76,6 +78,8 @@ class FIRE(Integrator, _DeviceControlled):
         self.fdec_alpha = _in_unit_interval("fdec_alpha", fdec_alpha)
         self.min_steps_adapt = _count("min_steps_adapt", min_steps_adapt)
         self.min_steps_conv = _count("min_steps_conv", min_steps_conv)
+        self._control = _ControlState("minimize.FIRE", self._initial())
+        self._partials = None
         self._n = 0            # N of the last run
         self._sim = None       # (weak) the simulation of the last run
 
@@ -114,7 +118,10 @@ class FIRE(Integrator, _DeviceControlled):
         ended with step two it leaves the partials that step two left, bit for bit)."""
         st = sim.state
         a = self._args = _lib.FireArgs()
-        self._bind_control(a, st, self._initial(), "azp_fire_partials_size")
+        if self._state is None:
+            self._control.reset(self._initial())  # (dt and alpha_start as they are at the first run)
+        a.d_state = self._control.bind(st.vel.device)
+        self._partials = _bind_partials(a, st, "azp_fire_partials_size", self._partials)
         a.dt_max, a.force_tol, a.energy_tol = self.dt, self.force_tol, self.energy_tol
         a.finc_dt, a.fdec_dt, a.alpha_start, a.fdec_alpha = self.finc_dt, self.fdec_dt, self.alpha_start, self.fdec_alpha
         a.min_steps_adapt, a.min_steps_conv = self.min_steps_adapt, self.min_steps_conv
@@ -132,7 +139,7 @@ class FIRE(Integrator, _DeviceControlled):
     # -- results ----------------------------------------------------------------
     def _read(self):
         """The state on the host (synchronises), refusing a minimization whose sums became non-finite."""
-        s = self._state.cpu().tolist()
+        s = self._control.host()
         if s[_lib.FIRE_NONFINITE] != 0.0:
             raise _lib.AzpError("minimize.FIRE: forces or velocities became non-finite (overlapping particles, or a time step "
                                 "too large for the stiffest force); nothing was moved from that step on")
@@ -162,10 +169,7 @@ class FIRE(Integrator, _DeviceControlled):
     def reset(self):
         """Back to the initial control state (time step ``dt``, alpha ``alpha_start``, not converged); the velocities of
         the attached state are zeroed, the masses in ``vel.w`` stay."""
-        if self._state is not None:
-            import torch
-
-            self._state.copy_(torch.tensor(self._initial(), dtype=torch.float64))
+        self._control.reset(self._initial())
         sim = self._sim() if self._sim is not None else None
         if sim is not None and sim.state is not None:
             sim.state.vel[:, :3] = 0.0

@@ -1,483 +1,23 @@
-"""Minimal simulation driver: the slice of ``hoomd.Simulation`` /
-``hoomd.md.Integrator`` the reference's tests exercise -- attach forces to a
-state, ``run(0)`` to evaluate them, and a velocity-Verlet NVE step
-(``hoomd.md.methods.ConstantVolume``) so thermostatting pair forces can be
-validated as in src/pytest/test_pair_dpd.py.
+"""The simulation driver: ``hoomd.Simulation``, its operations lists (integrator, computes, updaters, writers, tuners)
+and ``hoomd.md.Integrator``, reduced to what this project runs. ``Simulation.run`` attaches the forces to the state,
+evaluates them (``run(0)``) and steps: one loop for every integration path (``DESIGN.md`` 4.20), around whatever moves
+the particles -- ``methods.ConstantVolume`` (NVE, the dummy integrator of the reference's tests,
+src/pytest/test_pair.py:325-327) or its thermostat (``thermostats``), ``methods.ConstantPressure``, ``minimize.FIRE``,
+the flow methods (``flow``) -- with the updaters ahead of each step, the writers after it, the particle sorter and a
+domain's halo exchange between the position update and the forces. The methods, the filters and the trigger live in
+``methods``, ``filter`` and ``trigger``; their names are re-exported here.
 """
 
 import ctypes as C
-import math
 import warnings
 
 import numpy as np
 
 from . import _lib
+from .filter import All, Type  # noqa: F401 (re-exported, as the names below)
+from .methods import ConstantPressure, ConstantVolume, _check_moves_all, _launch  # noqa: F401
 from .state import State
-
-
-class All:
-    """``hoomd.filter.All``: every particle. The only filter the NVE kernels implement."""
-
-    def __eq__(self, other):
-        return isinstance(other, All)
-
-    def __hash__(self):
-        return hash("All")
-
-
-class Type:
-    """``hoomd.filter.Type``: the particles of the named types. ``types`` is one type name or an iterable of type
-    names. Computes and the flow methods (``flow.Langevin``, ``flow.Brownian``) accept it; ``ConstantVolume``
-    integrates all particles (``All`` only)."""
-
-    def __init__(self, types):
-        if isinstance(types, str):
-            types = [types]
-        self.types = tuple(types)
-        if not all(isinstance(t, str) for t in self.types):
-            raise _lib.AzpError("Type: type names must be strings, got %r" % (types,))
-
-    def mask(self, type_names):
-        """One byte per type of ``type_names`` (the state's types): 1 if the type is selected."""
-        missing = [t for t in self.types if t not in type_names]
-        if missing:
-            raise _lib.AzpError("Type filter names %s, which the state does not have (types %s)" % (missing, list(type_names)))
-        return np.array([1 if t in self.types else 0 for t in type_names], dtype=np.uint8)
-
-    def __eq__(self, other):
-        return isinstance(other, Type) and set(self.types) == set(other.types)
-
-    def __hash__(self):
-        return hash(("Type", frozenset(self.types)))
-
-    def __repr__(self):
-        return "Type(%r)" % (list(self.types),)
-
-
-class Periodic:
-    """``hoomd.trigger.Periodic``: fires at the timesteps t with ``(t - phase) % period == 0``."""
-
-    def __init__(self, period, phase=0):
-        if isinstance(period, bool) or int(period) != period or int(period) < 1:
-            raise _lib.AzpError("Periodic: period must be a positive integer, got %r" % (period,))
-        if isinstance(phase, bool) or int(phase) != phase:
-            raise _lib.AzpError("Periodic: phase must be an integer, got %r" % (phase,))
-        self.period, self.phase = int(period), int(phase)
-
-    def __call__(self, timestep):
-        return (int(timestep) - self.phase) % self.period == 0
-
-    def __eq__(self, other):
-        return isinstance(other, Periodic) and (other.period, other.phase) == (self.period, self.phase)
-
-    def __hash__(self):
-        return hash(("Periodic", self.period, self.phase))
-
-    def __repr__(self):
-        return "Periodic(period=%d, phase=%d)" % (self.period, self.phase)
-
-
-def _launch(a, st, stream, *names):
-    """Queue the libazp integration entries ``names`` with their argument struct ``a`` pointed at the state's arrays of
-    this moment (they are replaced when particles migrate between ranks or are re-sorted), and at the state's box when
-    ``box_generation`` has moved since the struct's box was written (``State.set_box``, ``update.BoxResize``)."""
-    generation = getattr(st, "box_generation", 0)  # (a stand-in state without the counter keeps its box)
-    if getattr(a, "_box_generation", None) != generation:
-        a.box = st.box.to_c()
-        a._box_generation = generation
-    a.d_pos = st.pos.data_ptr()
-    a.d_vel = st.vel.data_ptr()
-    a.d_net_force = st.net_force.data_ptr()
-    a.d_image = st.image.data_ptr()
-    a.N = st.N
-    lib = _lib.lib()
-    for name in names:
-        _lib.check(getattr(lib, name)(C.byref(a), stream), name)
-
-
-class _DeviceControlled:
-    """A stepper whose step is controlled on the device (the thermostats, ``minimize.FIRE``, ``ConstantPressure``, which
-    sizes no partials: its sums are ``azp_thermo_sums``') and the buffers it owns: the
-    control state, float64 doubles made at the first run, which persist across runs and follow the particles to their
-    device, and the partials that its sums pass through."""
-
-    _state = None
-    _partials = None
-
-    def _bind_control(self, a, st, start, size_entry):
-        """Make the state from the list ``start`` (first run) or move it to the device of ``st``, size the partials with
-        libazp's ``size_entry``, and point the argument struct ``a`` at both and at the box."""
-        import torch
-
-        dev = st.vel.device
-        if self._state is None or self._state.device != dev:
-            start = start if self._state is None else self._state.cpu().tolist()
-            self._state = torch.tensor(start, dtype=torch.float64, device=dev)
-        need = C.c_uint64(0)
-        _lib.check(getattr(_lib.lib(), size_entry)(st.N, C.byref(need)), size_entry)
-        if self._partials is None or self._partials.numel() * 8 < need.value or self._partials.device != dev:
-            self._partials = torch.zeros(int(need.value) // 8, dtype=torch.float64, device=dev)
-        a.d_partials = self._partials.data_ptr()
-        a.partials_bytes = self._partials.numel() * 8
-        a.d_state = self._state.data_ptr()
-        a.box = st.box.to_c()
-
-
-class ConstantVolume:
-    """NVE integration method (velocity Verlet) on all particles
-    (``hoomd.md.methods.ConstantVolume(filter=hoomd.filter.All())``; without a
-    thermostat it is the dummy integrator of the reference's tests,
-    src/pytest/test_pair.py:325-327). Any other filter is rejected: the kernels
-    integrate all N particles.
-
-    ``thermostat``: None (NVE, the fused kernels) or one of ``azplugins_amd.thermostats`` (``Berendsen``, ``Bussi``,
-    ``MTTK``), which rescales the velocities of all particles once per step on the device. A
-    thermostatted method integrates translational degrees of freedom of a single-domain run only; out of scope:
-    rotational degrees of freedom, ``Type`` filters, decomposed runs, Nose-Hoover chains. Constant pressure:
-    ``ConstantPressure``."""
-
-    def __init__(self, filter=None, thermostat=None):
-        if filter is not None and not isinstance(filter, All):
-            raise _lib.AzpError("ConstantVolume: only filter=All() (or None) is supported, got %r" % (filter,))
-        self.filter = All() if filter is None else filter
-        self._thermostat = None
-        self.thermostat = thermostat
-
-    @property
-    def thermostat(self):
-        return self._thermostat
-
-    @thermostat.setter
-    def thermostat(self, thermostat):
-        from .thermostats import _Thermostat
-
-        if thermostat is not None and not isinstance(thermostat, _Thermostat):
-            raise _lib.AzpError("ConstantVolume: thermostat must be None or one of azplugins_amd.thermostats, got %r" % (thermostat,))
-        if self._thermostat is not None:
-            self._thermostat._holders.discard(self)
-        if thermostat is not None:
-            thermostat._holders.add(self)
-        self._thermostat = thermostat
-
-    # -- the stepper of the NVE path; with a thermostat the thermostat steps --------
-    _fusable = True
-    _updaters_split = False  # (an updater changes types alone, which these kernels do not read)
-
-    def _begin(self, sim):
-        integ = sim.operations.integrator
-        a = self._args = _lib.NVEArgs()
-        a.box = sim.state.box.to_c()
-        a.dt = integ.dt
-        self._stream = _lib.raw_stream(sim.state.device)
-        self._rot = None
-        if integ.integrate_rotational_dof:
-            if sim.domain is not None and not all(n in sim.domain.names for n in ("orientation", "angmom", "inertia")):
-                raise _lib.AzpError("integrate_rotational_dof in a decomposed run: the domain must carry orientation, angmom "
-                                    "and inertia (they migrate with the particles)")
-            self._rot = _lib.NVERotArgs()
-            self._rot.dt = integ.dt
-
-    def _rotational_step(self, sim, one):
-        st, rot, forces = sim.state, self._rot, sim.operations.integrator.forces
-        torque = forces[0].torque_tensor  # the net torque, kept alive until the kernel is queued
-        if len(forces) > 1:
-            torque = torque.clone()
-            for f in forces[1:]:
-                torque += f.torque_tensor
-        rot.d_orientation = st.orientation.data_ptr()
-        rot.d_angmom = st.angmom.data_ptr()
-        rot.d_inertia = st.inertia.data_ptr()
-        rot.d_net_torque = torque.data_ptr()
-        rot.N = st.N
-        fn = _lib.lib().azp_integrate_nve_rot_step_one if one else _lib.lib().azp_integrate_nve_rot_step_two
-        _lib.check(fn(C.byref(rot), self._stream), "azp_integrate_nve_rot_step")
-
-    def _step_one(self, sim, timestep, fused):
-        """Velocity Verlet (libazp kernels): v += a dt/2, x += v dt, wrap | forces | v += a dt/2; ``fused``: behind step
-        two of the previous step, in one kernel."""
-        _launch(self._args, sim.state, self._stream, "azp_integrate_nve_step_two_one" if fused else "azp_integrate_nve_step_one")
-        if self._rot is not None:
-            if fused:
-                self._rotational_step(sim, False)  # (step two of the previous step: the torques are still its own)
-            self._rotational_step(sim, True)
-
-    def _step_two(self, sim, timestep):
-        _launch(self._args, sim.state, self._stream, "azp_integrate_nve_step_two")
-        if self._rot is not None:
-            self._rotational_step(sim, False)
-
-
-_AXES = ("x", "y", "z")
-
-
-class ConstantPressure(_DeviceControlled):
-    """``hoomd.md.methods.ConstantPressure`` on the three lengths of an orthorhombic box: a Martyna-Tobias-Klein barostat
-    (NPH), with one of ``azplugins_amd.thermostats`` NPT. HOOMD-blue's source is not available to this project: the
-    scheme is defined in ``include/azp.h`` and ``DESIGN.md`` 4.23 and runs in libazp (``csrc/barostat.hip``).
-
-    ``S``: the target stress: a float (the pressure), a callable of the timestep (the ``variant`` classes included), or
-    six values xx, yy, zz, yz, xz, xy whose last three are 0. ``tauS`` > 0: the barostat's time constant.
-    ``couple``: ``"none"``, ``"xy"``, ``"xz"``, ``"yz"`` or ``"xyz"``: the coupled axes change at one rate.
-    ``thermostat``: None or a ``Berendsen``, ``Bussi`` or ``MTTK``; it acts on the particles only, the box rates are not
-    thermostatted. ``box_dof``: which of Lx, Ly, Lz (and, always False here, the tilts xz, yz, xy) are free.
-    ``rescale_all`` has no effect (all particles are integrated), ``gamma`` must be 0.
-
-    One rate nu_a per axis lives in a device-resident state that persists across runs: ``run(10); run(10)`` equals
-    ``run(20)`` bit for bit. ``barostat_dof`` (the three nu), ``barostat_energy`` (W / 2 sum nu_a^2) and ``reference_kT``
-    can be read between runs (reading synchronises); ``barostat_dof`` and ``reference_kT`` can be set. For hydrostatic S,
-    K + U + S V + ``barostat_energy`` (+ the thermostat's ``energy``) is conserved up to the integrator's error. Without a
-    thermostat the barostat's mass W = (Nf + 3) kT_ref tauS^2 takes kT_ref = 2 K / Nf from the first step of the first run.
-
-    The box lives on the host: every step the host reads the three scale factors from the device (ONE HOST WAIT PER
-    STEP) and sets the box through ``State.set_box``, so every neighbor list is rebuilt every step, as under an
-    ``update.BoxResize`` that fires every step. While such a method is present the virial pass of every force runs
-    every step (at most 8 forces).
-
-    Refused: a filter other than ``All()``, rotational degrees of freedom, decomposed runs, tilted boxes, a free axis
-    that is not periodic, tilt degrees of freedom, ``gamma`` != 0, fewer than 2 particles, a second method next to it."""
-
-    _name = "ConstantPressure"
-    _fusable = False
-    _updaters_split = False
-
-    def __init__(self, filter, S, tauS, couple, thermostat=None, box_dof=(True, True, True, False, False, False),
-                 rescale_all=False, gamma=0.0):
-        if filter is not None and not isinstance(filter, All):
-            raise _lib.AzpError("ConstantPressure: only filter=All() is supported (the barostat scales every particle), got %r" % (filter,))
-        self.filter = All() if filter is None else filter
-        self.S = S
-        tauS = float(tauS)
-        if not (math.isfinite(tauS) and tauS > 0.0):
-            raise _lib.AzpError("ConstantPressure: tauS must be > 0, got %r" % (tauS,))
-        self.tauS = tauS
-        if couple not in _lib.BAROSTAT_COUPLE:
-            raise _lib.AzpError("ConstantPressure: couple must be one of %s, got %r" % (sorted(_lib.BAROSTAT_COUPLE), couple))
-        self.couple = couple
-        box_dof = tuple(bool(b) for b in box_dof)
-        if len(box_dof) != 6:
-            raise _lib.AzpError("ConstantPressure: box_dof takes six flags (Lx, Ly, Lz, xz, yz, xy), got %r" % (box_dof,))
-        if any(box_dof[3:]):
-            raise _lib.AzpError("ConstantPressure: tilt degrees of freedom are not supported (box_dof = %r): the box stays "
-                                "orthorhombic" % (box_dof,))
-        self.box_dof = box_dof
-        if float(gamma) != 0.0:
-            raise _lib.AzpError("ConstantPressure: gamma = %r: the Langevin piston is not supported, gamma must be 0" % (gamma,))
-        self.gamma = 0.0
-        self.rescale_all = bool(rescale_all)
-        self._thermostat = None
-        self.thermostat = thermostat
-        self._pending = [0.0] * _lib.BAROSTAT_NSTATE
-        self._row = None
-        self._thermo = None
-        self._first = True
-
-    @property
-    def S(self):
-        return self._S
-
-    @S.setter
-    def S(self, S):
-        if not callable(S):
-            try:
-                S = (float(S),) * 3 + (0.0,) * 3
-            except TypeError:
-                S = tuple(float(x) for x in S)
-                if len(S) != 6:
-                    raise _lib.AzpError("ConstantPressure: S is a float, a callable of the timestep or six values xx, yy, zz, "
-                                        "yz, xz, xy; got %r" % (S,))
-            if not all(math.isfinite(x) for x in S):
-                raise _lib.AzpError("ConstantPressure: S must be finite, got %r" % (S,))
-            if any(x != 0.0 for x in S[3:]):
-                raise _lib.AzpError("ConstantPressure: shear stresses are not supported (S = %r): yz, xz and xy must be 0" % (S,))
-        self._S = S
-
-    def _S_at(self, timestep):
-        """(S_xx, S_yy, S_zz) at ``timestep``."""
-        if not callable(self._S):
-            return self._S[:3]
-        s = float(self._S(timestep))
-        if not math.isfinite(s):
-            raise _lib.AzpError("ConstantPressure: S must be finite, got %r at timestep %d" % (s, timestep))
-        return (s, s, s)
-
-    @property
-    def thermostat(self):
-        return self._thermostat
-
-    @thermostat.setter
-    def thermostat(self, thermostat):
-        from .thermostats import _Thermostat
-
-        if thermostat is not None and not isinstance(thermostat, _Thermostat):
-            raise _lib.AzpError("ConstantPressure: thermostat must be None or one of azplugins_amd.thermostats, got %r" % (thermostat,))
-        if self._thermostat is not None:
-            self._thermostat._holders.discard(self)
-        if thermostat is not None:
-            thermostat._holders.add(self)
-        self._thermostat = thermostat
-
-    # -- device-resident state ---------------------------------------------------
-    def _slots(self, k, n=1):
-        """Slots k .. k + n - 1 of the state; reading synchronises."""
-        if self._state is None:
-            return tuple(self._pending[k:k + n])
-        return tuple(self._state[k:k + n].tolist())
-
-    def _set_slots(self, k, values, what):
-        values = [float(v) for v in values]
-        if not all(math.isfinite(v) for v in values):
-            raise _lib.AzpError("ConstantPressure: %s must be finite, got %r" % (what, values))
-        if self._state is None:
-            self._pending[k:k + len(values)] = values
-        else:
-            import torch
-
-            self._state[k:k + len(values)] = torch.tensor(values, dtype=torch.float64)
-
-    @property
-    def barostat_dof(self):
-        """(nu_x, nu_y, nu_z): the rates of the three box lengths, d ln L_a / dt."""
-        return self._slots(_lib.BAROSTAT_NU, 3)
-
-    @barostat_dof.setter
-    def barostat_dof(self, value):
-        value = tuple(value)
-        if len(value) != 3:
-            raise _lib.AzpError("ConstantPressure: barostat_dof takes (nu_x, nu_y, nu_z), got %r" % (value,))
-        self._set_slots(_lib.BAROSTAT_NU, value, "barostat_dof")
-
-    @property
-    def barostat_energy(self):
-        """(W / 2)(nu_x^2 + nu_y^2 + nu_z^2) as of the last step run (0 before the first)."""
-        return self._slots(_lib.BAROSTAT_ENERGY)[0]
-
-    @property
-    def reference_kT(self):
-        """kT_ref of the barostat's mass W = (Nf + 3) kT_ref tauS^2 in a run without a thermostat: 2 K / Nf at the first
-        step of the first run (0 before it), or what was set. With a thermostat its kT is used instead."""
-        return self._slots(_lib.BAROSTAT_REF_KT)[0]
-
-    @reference_kT.setter
-    def reference_kT(self, value):
-        if not float(value) >= 0.0:
-            raise _lib.AzpError("ConstantPressure: reference_kT must be >= 0 (0: measure it at the next step), got %r" % (value,))
-        self._set_slots(_lib.BAROSTAT_REF_KT, [value], "reference_kT")
-
-    # -- the stepper -------------------------------------------
-    def _check(self, sim, integ):
-        """What ``ConstantPressure`` cannot do, each refused with its reason."""
-        st = sim.state
-        if len(integ.methods) != 1:
-            raise _lib.AzpError("ConstantPressure must be the only method of the integrator (it scales every particle and the "
-                                "box), got %r" % (integ.methods,))
-        if not isinstance(self.filter, All):
-            raise _lib.AzpError("ConstantPressure: only filter=All() is supported (the barostat scales every particle), got %r"
-                                % (self.filter,))
-        if integ.integrate_rotational_dof:
-            raise _lib.AzpError("ConstantPressure: rotational degrees of freedom are not integrated (integrate_rotational_dof=True)")
-        if sim.domain is not None:
-            raise _lib.AzpError("ConstantPressure does not run decomposed (the domain's slabs are cut once, and the pressure "
-                                "would need a collective every step)")
-        if st.N < 2:
-            raise _lib.AzpError("ConstantPressure: fewer than 2 particles leave no degree of freedom (Nf = 3 N - 3), N = %d" % st.N)
-        box = st.box
-        if box.is_triclinic:
-            raise _lib.AzpError("ConstantPressure: %r is tilted: only orthorhombic boxes are supported" % (box,))
-        for k in range(3):
-            if self.box_dof[k] and not box.periodic[k]:
-                raise _lib.AzpError("ConstantPressure: the box is not periodic along %s, which box_dof leaves free: a free axis "
-                                    "must be periodic" % _AXES[k])
-        if len(integ.forces) > _lib.THERMO_MAX_FORCES:
-            raise _lib.AzpError("ConstantPressure sums the virials of at most %d forces, the integrator has %d"
-                                % (_lib.THERMO_MAX_FORCES, len(integ.forces)))
-        th = self._thermostat
-        if th is not None:
-            if th._kind == _lib.THERMOSTAT_BERENDSEN and th.tau < integ.dt:
-                raise _lib.AzpError("%s: tau = %r is below dt = %r (the rescaling factor's radicand can turn negative)"
-                                    % (th._name, th.tau, integ.dt))
-            if any(m is not self for m in th._holders):
-                raise _lib.AzpError("%s: one thermostat object is held by two methods (its state belongs to one run)" % th._name)
-
-    def _begin(self, sim):
-        import torch
-
-        from .compute import ThermodynamicQuantities
-
-        integ, st = sim.operations.integrator, sim.state
-        self._check(sim, integ)
-        dev = st.vel.device
-        if self._state is None or self._state.device != dev:
-            start = self._pending if self._state is None else self._state.cpu().tolist()
-            self._state = torch.tensor(start, dtype=torch.float64, device=dev)
-        if self._row is None or self._row.device != dev:
-            self._row = torch.zeros(_lib.THERMO_NSUMS, dtype=torch.float64, device=dev)
-        if self._thermo is None:
-            self._thermo = ThermodynamicQuantities(All())  # (never in sim.operations.computes: its launch machinery alone)
-        self._thermo._sim = sim
-        a = self._args = _lib.BarostatArgs()
-        a.d_state = self._state.data_ptr()
-        a.d_sums = self._row.data_ptr()
-        a.box = st.box.to_c()
-        a.dt = integ.dt
-        a.tauS = self.tauS
-        a.ndof = float(3 * st.N - 3)
-        a.couple = _lib.BAROSTAT_COUPLE[self.couple]
-        a.box_dof = sum(1 << k for k in range(3) if self.box_dof[k])
-        th = self._thermostat
-        if th is not None:
-            if th._kind == _lib.THERMOSTAT_BUSSI:
-                sim._warn_if_seed_unset()
-            if th._state is None or th._state.device != dev:
-                start = th._pending if th._state is None else th._state.cpu().tolist()
-                th._state = torch.tensor(start, dtype=torch.float64, device=dev)
-            a.d_thermostat_state = th._state.data_ptr()
-            a.thermostat_tau = th.tau
-            a.thermostat_kind = th._kind
-            a.thermostat_seed = int(sim.seed or 0) & 0xFFFF
-            th._ndof = a.ndof
-        self._stream = _lib.raw_stream(st.device)
-        self._first = True  # (the first step opens from a sums pass of the state as it stands)
-
-    def _advance(self, sim, timestep, phase):
-        a = self._args
-        a.S[:] = self._S_at(timestep)
-        a.timestep = timestep
-        a.phase = phase
-        th = self._thermostat
-        if th is not None:
-            a.thermostat_kT = th._kT_at(timestep)
-            if phase & _lib.BAROSTAT_OPEN:
-                th._last_kT = a.thermostat_kT
-        _launch(a, sim.state, self._stream, "azp_barostat_advance")
-
-    def _step_one(self, sim, timestep, fused):
-        from .state import Box
-
-        st = sim.state
-        if self._first:
-            self._thermo._launch(self._row.data_ptr())
-            self._first = False
-        self._advance(sim, timestep, _lib.BAROSTAT_OPEN)
-        # the one host read of the step: the box lives on the host
-        host = self._state.tolist()
-        if host[_lib.BAROSTAT_NONFINITE] != 0.0:
-            raise _lib.AzpError("ConstantPressure: the barostat's state is not finite at timestep %d (nu = %r, K = %r, W = %r): "
-                                "no kinetic energy to take reference_kT from, or the run has diverged"
-                                % (timestep, host[_lib.BAROSTAT_NU:_lib.BAROSTAT_NU + 3], host[_lib.BAROSTAT_K], host[_lib.BAROSTAT_W]))
-        lam = host[_lib.BAROSTAT_LAMBDA:_lib.BAROSTAT_LAMBDA + 3]
-        box = st.box
-        st.set_box(Box(lam[0] * box.Lx, lam[1] * box.Ly, lam[2] * box.Lz, periodic=box.periodic))
-        _launch(self._args, st, self._stream, "azp_barostat_step_one")
-
-    def _step_two(self, sim, timestep):
-        _launch(self._args, sim.state, self._stream, "azp_barostat_step_two")
-        self._thermo._launch(self._row.data_ptr())
-        # (the close half belongs to the end of the step: S and kT of the timestep the next step opens at. Always a
-        # launch of its own, at the end of a run too: run(a); run(b) is run(a + b) bit for bit)
-        self._advance(sim, timestep + 1, _lib.BAROSTAT_CLOSE)
-
-    def __repr__(self):
-        return "ConstantPressure(S=%r, tauS=%r, couple=%r, thermostat=%r)" % (self._S, self.tauS, self.couple, self._thermostat)
+from .trigger import Periodic  # noqa: F401
 
 
 class Integrator:
@@ -828,21 +368,7 @@ class Simulation:
 
     def _check_thermostat(self, integ, method):
         """What a thermostatted ``ConstantVolume`` cannot do, each refused with its reason."""
-        th = method.thermostat
-        if not isinstance(method.filter, All):
-            raise _lib.AzpError("%s: a thermostat needs filter=All() (it rescales with the kinetic energy of all particles), "
-                                "got %r" % (th._name, method.filter))
-        if integ.integrate_rotational_dof:
-            raise _lib.AzpError("%s: rotational degrees of freedom are not thermostatted (integrate_rotational_dof=True)" % th._name)
-        if self.domain is not None:
-            raise _lib.AzpError("%s does not run decomposed (the kinetic energy would need a collective every step)" % th._name)
-        if self.state.N < 2:
-            raise _lib.AzpError("%s: fewer than 2 particles leave no degree of freedom (Nf = 3 N - 3), N = %d" % (th._name, self.state.N))
-        if th._kind == _lib.THERMOSTAT_BERENDSEN and th.tau < integ.dt:
-            raise _lib.AzpError("%s: tau = %r is below dt = %r (the rescaling factor's radicand can turn negative)"
-                                % (th._name, th.tau, integ.dt))
-        if any(m is not method for m in th._holders):
-            raise _lib.AzpError("%s: one thermostat object is held by two methods (its state belongs to one run)" % th._name)
+        _check_moves_all(method.thermostat._name, "the kinetic energy", method, self, integ)
 
     def _updaters_due(self):
         return [u for u in self.operations.updaters if u.trigger(self.timestep)]

@@ -24,7 +24,7 @@ import math
 import weakref
 
 from . import _lib
-from .simulation import _DeviceControlled, _launch
+from .methods import _ControlState, _DeviceControlled, _bind_partials, _launch
 
 
 class _Thermostat(_DeviceControlled):
@@ -35,8 +35,9 @@ class _Thermostat(_DeviceControlled):
     def __init__(self, kT, tau):
         self.kT = kT
         self.tau = tau
-        self._holders = weakref.WeakSet()  # the ConstantVolume methods that hold this thermostat
-        self._pending = [0.0] * _lib.THERMOSTAT_NSTATE  # what the state (AZP_THERMOSTAT_NSTATE doubles) starts from
+        self._holders = weakref.WeakSet()  # the methods (ConstantVolume, ConstantPressure) that hold this thermostat
+        self._control = _ControlState(self._name, [0.0] * _lib.THERMOSTAT_NSTATE)  # (AZP_THERMOSTAT_NSTATE doubles)
+        self._partials = None
         self._ndof = 0.0     # Nf of the last run
         self._last_kT = 0.0  # kT of the last step run
 
@@ -70,21 +71,18 @@ class _Thermostat(_DeviceControlled):
             raise _lib.AzpError("%s: kT must be > 0, got %r at timestep %d" % (self._name, kT, timestep))
         return kT
 
-    # -- device-resident state -------------------------------------------------
-    def _slot(self, k):
-        """Slot k of the state; reading synchronises."""
-        if self._state is None:
-            return self._pending[k]
-        return float(self._state[k].item())
+    # -- what a holder asks of its thermostat (ConstantVolume: the stepper below; ConstantPressure: in its advance) -------
+    def _bind(self, sim):
+        """Bind for this run: the seed warning (Bussi), Nf, and the state on the particles' device; returns its pointer."""
+        if self._kind == _lib.THERMOSTAT_BUSSI:
+            sim._warn_if_seed_unset()
+        self._ndof = float(3 * sim.state.N - 3)
+        return self._control.bind(sim.state.vel.device)
 
-    def _set_slot(self, k, value):
-        value = float(value)
-        if not math.isfinite(value):
-            raise _lib.AzpError("%s: state values must be finite, got %r" % (self._name, value))
-        if self._state is None:
-            self._pending[k] = value
-        else:
-            self._state[k] = value
+    def _open_step(self, timestep):
+        """kT for the step that opens at ``timestep``, which becomes the kT of the last step run."""
+        self._last_kT = self._kT_at(timestep)
+        return self._last_kT
 
     # -- the stepper of a thermostatted ConstantVolume (DESIGN 4.20) ---------------
     # The thermostat needs the kinetic energy of all particles between step two of one step and step one of the next,
@@ -98,23 +96,21 @@ class _Thermostat(_DeviceControlled):
         and K of the first step from a pass of its own (the velocities may have been changed between runs)."""
         integ, st = sim.operations.integrator, sim.state
         sim._check_thermostat(integ, integ.methods[0])
-        if self._kind == _lib.THERMOSTAT_BUSSI:
-            sim._warn_if_seed_unset()
         a = self._args = _lib.ThermostatArgs()
-        self._bind_control(a, st, self._pending, "azp_thermostat_partials_size")
+        a.d_state = self._bind(sim)
+        self._partials = _bind_partials(a, st, "azp_thermostat_partials_size", self._partials)
         a.dt = integ.dt
         a.tau = self._tau
-        a.ndof = float(3 * st.N - 3)
+        a.ndof = self._ndof
         a.seed = int(sim.seed or 0) & 0xFFFF
         a.kind = self._kind
-        self._ndof = a.ndof
         self._stream = _lib.raw_stream(st.device)
         _launch(a, st, self._stream, "azp_thermostat_kinetic")
 
     def _step_one(self, sim, timestep, fused):
         a = self._args
         a.timestep = timestep
-        a.kT = self._last_kT = self._kT_at(timestep)
+        a.kT = self._open_step(timestep)
         _launch(a, sim.state, self._stream, "azp_thermostat_advance", "azp_thermostat_step_one")
 
     def _step_two(self, sim, timestep):
@@ -124,11 +120,11 @@ class _Thermostat(_DeviceControlled):
     def energy(self):
         """The energy the thermostat has taken out of the particles: the running sum of K - alpha^2 K, so that
         K + U + ``energy`` is conserved up to the integrator's error."""
-        return self._slot(_lib.THERMOSTAT_ENERGY)
+        return self._control.get(_lib.THERMOSTAT_ENERGY)[0]
 
     @energy.setter
     def energy(self, value):
-        self._set_slot(_lib.THERMOSTAT_ENERGY, value)
+        self._control.set(_lib.THERMOSTAT_ENERGY, [value], "energy")
 
     def __repr__(self):
         return "%s(kT=%r, tau=%r)" % (type(self).__name__, self._kT, self._tau)
@@ -141,9 +137,6 @@ class Berendsen(_Thermostat):
 
     _name = "thermostats.Berendsen"
     _kind = _lib.THERMOSTAT_BERENDSEN
-
-    def __init__(self, kT, tau):
-        super().__init__(kT, tau)
 
 
 class Bussi(_Thermostat):
@@ -168,19 +161,15 @@ class MTTK(_Thermostat):
     _name = "thermostats.MTTK"
     _kind = _lib.THERMOSTAT_MTTK
 
-    def __init__(self, kT, tau):
-        super().__init__(kT, tau)
-
     @property
     def translational_dof(self):
         """(xi, eta): the thermostat's momentum and position."""
-        return self._slot(_lib.THERMOSTAT_XI), self._slot(_lib.THERMOSTAT_ETA)
+        return self._control.get(_lib.THERMOSTAT_XI, 2)
 
     @translational_dof.setter
     def translational_dof(self, value):
         xi, eta = value
-        self._set_slot(_lib.THERMOSTAT_XI, xi)
-        self._set_slot(_lib.THERMOSTAT_ETA, eta)
+        self._control.set(_lib.THERMOSTAT_XI, [xi, eta], "translational_dof")
 
     @property
     def energy(self):

@@ -11,7 +11,8 @@ import ctypes as C
 import math
 
 from . import _lib
-from .simulation import Periodic
+from .filter import All, Type
+from .trigger import Periodic
 
 
 class _Updater:
@@ -156,8 +157,6 @@ class BoxResize(_Updater):
 
 
 def _check_filter(filter):
-    from .simulation import All, Type
-
     if filter is None:
         return All()
     if not isinstance(filter, (All, Type)):
@@ -168,8 +167,6 @@ def _check_filter(filter):
 def _device_mask(st, filter):
     """The filter's byte per type on the state's device; None for ``All()``. (``Type.mask`` refuses a type the state lacks.)"""
     import torch
-
-    from .simulation import All
 
     if isinstance(filter, All):
         return None

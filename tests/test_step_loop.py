@@ -4,6 +4,7 @@ record what is asked of them, and libazp is wrapped so that every entry point th
 called. The event logs in ``EXPECTED`` were recorded with this harness from the separate loops that NVE, thermostatted,
 FIRE and flow runs had before they shared one; the one loop has to reproduce them exactly."""
 
+import ctypes as C
 import warnings
 
 import pytest
@@ -13,7 +14,8 @@ from azplugins_amd import _lib
 
 N = 6
 DT = 0.005
-PATHS = ["nve", "nve_rot", "nve_domain", "bussi", "fire", "langevin", "langevin_brownian"]
+PATHS = ["nve", "nve_rot", "nve_domain", "bussi", "fire", "langevin", "langevin_brownian", "nph", "npt_bussi"]
+LAMBDA = (1.25, 1.0, 0.8)  # the scale factors every opening barostat advance "computes": the box changes every step
 
 
 def _kT(log):
@@ -22,6 +24,14 @@ def _kT(log):
         return 1.0 + 0.125 * t
 
     return kT
+
+
+def _S(log):
+    def S(t):
+        log.append("S(%d)" % t)
+        return 0.5 + 0.25 * t
+
+    return S
 
 
 class _State:
@@ -46,11 +56,19 @@ class _State:
         self.inertia = torch.ones((N, 3), dtype=f64)
         self.accel = None
         self.groups = {}
-        self.position_generation = self.order_generation = self.type_generation = 0
+        self.position_generation = self.order_generation = self.type_generation = self.box_generation = 0
 
     @property
     def n_max(self):
         return self.N + self.n_ghost
+
+    def set_box(self, box):
+        """As ``State.set_box``: a box that differs bumps ``box_generation`` and ``position_generation``."""
+        if box == self.box:
+            return
+        self.box = box
+        self.box_generation += 1
+        self.position_generation += 1
 
 
 class _Nlist:
@@ -72,11 +90,13 @@ class _Nlist:
 class _Force:
     defer_flag_check = False
     compute_virial = False
+    _virial_evaluated = False
     _state = None
 
     def __init__(self, log, name, with_nlist=False):
         self._log, self._name = log, name
-        self.force_tensor = torch.zeros((N, 4), dtype=torch.float64)
+        self.force_tensor = self._force = torch.zeros((N, 4), dtype=torch.float64)
+        self._virial = torch.zeros((6, N), dtype=torch.float64)
         self.torque_tensor = torch.zeros((N, 4), dtype=torch.float64)
         if with_nlist:
             self.nlist = _Nlist(log)
@@ -120,7 +140,9 @@ class _Domain:
 class _Lib:
     """libazp with every launch recorded instead of made: host-only calls pass through, an entry point that takes a
     stream returns 0 after its name and the scalars of its argument struct went into the log, marked STALE if the
-    struct does not point at the state's arrays of that moment."""
+    struct does not point at the state's arrays of that moment. The barostat's entries also log their phase and the box
+    lengths of their struct (a launch with a stale box shows), and an opening advance writes ``LAMBDA`` into the state
+    tensor, as the kernel would; the sums pass logs how many forces and virials it was pointed at."""
 
     state = None
 
@@ -140,10 +162,18 @@ class _Lib:
                     log.append("%s N=%d" % (name, args[0]))
                 else:
                     st = self.state
-                    stale = any(getattr(a, "d_" + f) != getattr(st, f).data_ptr() for f in ("pos", "vel", "image", "net_force")
-                                if hasattr(a, "d_" + f))
+                    # (the sums pass of an All() filter reads no positions: its d_pos stays null)
+                    arrays = ("vel",) if name == "azp_thermo_sums" else ("pos", "vel", "image", "net_force")
+                    stale = any(getattr(a, "d_" + f) != getattr(st, f).data_ptr() for f in arrays if hasattr(a, "d_" + f))
+                    extra = ""
+                    if name == "azp_thermo_sums":
+                        extra = " n_forces=%d virials=%d" % (a.n_forces, sum(1 for k in range(a.n_forces) if a.d_virial[k]))
+                    elif name.startswith("azp_barostat_"):
+                        extra = " phase=%d L=%r" % (a.phase, tuple(a.box.L))
+                        if name == "azp_barostat_advance" and a.phase & _lib.BAROSTAT_OPEN:
+                            (C.c_double * 3).from_address(a.d_state + 8 * _lib.BAROSTAT_LAMBDA)[:] = LAMBDA
                     log.append(name + "".join(" %s=%r" % (f, getattr(a, f)) for f in ("timestep", "kT", "dt", "N") if hasattr(a, f))
-                               + (" STALE" if stale else ""))
+                               + extra + (" STALE" if stale else ""))
                 return 0
 
         self.__dict__[name] = fn
@@ -184,6 +214,9 @@ def make_sim(path, monkeypatch, seed=1, writer=3, updater=4, tuner=5):
     elif path == "langevin_brownian":
         methods = [flow.Langevin(filter=azp.Type("A"), kT=_kT(log), flow_field=u),
                    flow.Brownian(filter=azp.Type("B"), kT=2.0, flow_field=u)]
+    elif path in ("nph", "npt_bussi"):
+        th = thermostats.Bussi(kT=_kT(log), tau=0.5) if path == "npt_bussi" else None
+        methods = [azp.ConstantPressure(azp.All(), S=_S(log), tauS=1.0, couple="xyz", thermostat=th)]
     if path == "fire":
         integ = minimize.FIRE(dt=DT, force_tol=1e-3, angmom_tol=1e-3, energy_tol=1e-7, forces=forces,
                               methods=[azp.ConstantVolume(azp.All())])
@@ -209,6 +242,8 @@ def _events(path, runs, monkeypatch):
         sim.run(steps)
     log.append("timestep=%d position_generation=%d type_generation=%d"
                % (sim.timestep, sim.state.position_generation, sim.state.type_generation))
+    if path in ("nph", "npt_bussi"):
+        log.append("box_generation=%d" % sim.state.box_generation)
     return log
 
 
@@ -249,8 +284,9 @@ def test_no_methods_and_malformed_methods(monkeypatch):
     assert not any(f.defer_flag_check for f in sim.operations.integrator.forces)
 
 
-@pytest.mark.parametrize("path", ["langevin", "fire"])
+@pytest.mark.parametrize("path", ["langevin", "fire", "nph", "npt_bussi"])
 def test_flow_and_fire_checks_come_first_even_at_zero_steps(path, monkeypatch):
+    """(the barostat's refusals too come ahead of the forces, even at ``run(0)``)"""
     sim, log = make_sim(path, monkeypatch)
     sim.operations.integrator.integrate_rotational_dof = True
     with pytest.raises(_lib.AzpError, match="rotational"):
@@ -275,6 +311,35 @@ def test_thermostat_refusals_and_seed_warning_follow_the_first_forces(monkeypatc
     k = [i for i, e in enumerate(log) if e.startswith("warning")]
     assert len(k) == 1 and "seed" in log[k[0]] and sim.seed == 0
     assert log[k[0] - 1].startswith("azp_sum_forces") and log[k[0] + 1].startswith("azp_thermostat_kinetic")
+
+
+def test_barostat_refusals_name_it_and_its_seed_warning_follows_the_first_forces(monkeypatch):
+    import azplugins_amd as azp
+
+    for path in ("nph", "npt_bussi"):
+        sim, log = make_sim(path, monkeypatch)
+        sim.operations.integrator.methods.append(azp.ConstantVolume())
+        with pytest.raises(_lib.AzpError, match="only method"):
+            sim.run(0)
+        assert log == []
+    # a thermostat's own refusal (held by two methods) comes from the barostat's check: ahead of the forces, at run(0)
+    sim, log = make_sim("npt_bussi", monkeypatch)
+    other = azp.ConstantVolume(thermostat=sim.operations.integrator.methods[0].thermostat)  # (held weakly: keep it)
+    with pytest.raises(_lib.AzpError, match="two methods"):
+        sim.run(0)
+    assert log == [] and other.thermostat is not None
+    # the seed warning: after the forces, ahead of the first sums pass
+    sim, log = make_sim("npt_bussi", monkeypatch, seed=None)
+    with warnings.catch_warnings():
+        warnings.simplefilter("always")
+        monkeypatch.setattr(warnings, "showwarning", lambda message, *a, **k: log.append("warning: %s" % message))
+        sim.run(0)
+        assert not any(e.startswith("warning") for e in log)
+        sim.run(1)
+    k = [i for i, e in enumerate(log) if e.startswith("warning")]
+    assert len(k) == 1 and "seed" in log[k[0]] and sim.seed == 0
+    assert log[k[0] - 1].startswith("azp_sum_forces") and not any(e.startswith(("azp_thermo", "azp_barostat")) for e in log[: k[0]])
+    assert any(e.startswith("azp_thermo_sums") for e in log[k[0]:])
 
 
 def test_flow_seed_warning_follows_the_first_forces(monkeypatch):
@@ -1212,5 +1277,389 @@ writer(12)
 f0.check_flags(wait=True) deferred=False
 f1.check_flags(wait=True) deferred=False
 timestep=12 position_generation=12 type_generation=3
+""",
+    ('nph', 'run0'): """
+run(0)
+f0.compute(0) deferred=False
+f1.compute(0) deferred=False
+azp_sum_forces N=6
+timestep=0 position_generation=0 type_generation=0
+box_generation=0
+""",
+    ('nph', 'run1'): """
+run(1)
+f0.compute(0) deferred=False
+f1.compute(0) deferred=False
+azp_sum_forces N=6
+updater(0)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(0)
+azp_barostat_advance timestep=0 dt=0.005 N=6 phase=2 L=(8.0, 8.0, 8.0)
+azp_barostat_step_one timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+f0.compute(1) deferred=True
+f1.compute(1) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(1)
+azp_barostat_advance timestep=1 dt=0.005 N=6 phase=1 L=(10.0, 8.0, 6.4)
+f0.check_flags(wait=True) deferred=False
+f1.check_flags(wait=True) deferred=False
+timestep=1 position_generation=2 type_generation=1
+box_generation=1
+""",
+    ('nph', 'run7_run5'): """
+run(7)
+f0.compute(0) deferred=False
+f1.compute(0) deferred=False
+azp_sum_forces N=6
+updater(0)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(0)
+azp_barostat_advance timestep=0 dt=0.005 N=6 phase=2 L=(8.0, 8.0, 8.0)
+azp_barostat_step_one timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+f0.compute(1) deferred=True
+f1.compute(1) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(1)
+azp_barostat_advance timestep=1 dt=0.005 N=6 phase=1 L=(10.0, 8.0, 6.4)
+S(1)
+azp_barostat_advance timestep=1 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+azp_barostat_step_one timestep=1 dt=0.005 N=6 phase=2 L=(12.5, 8.0, 5.120000000000001)
+f0.compute(2) deferred=True
+f1.compute(2) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=1 dt=0.005 N=6 phase=2 L=(12.5, 8.0, 5.120000000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(2)
+azp_barostat_advance timestep=2 dt=0.005 N=6 phase=1 L=(12.5, 8.0, 5.120000000000001)
+S(2)
+azp_barostat_advance timestep=2 dt=0.005 N=6 phase=2 L=(12.5, 8.0, 5.120000000000001)
+azp_barostat_step_one timestep=2 dt=0.005 N=6 phase=2 L=(15.625, 8.0, 4.096000000000001)
+f0.compute(3) deferred=True
+f1.compute(3) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=2 dt=0.005 N=6 phase=2 L=(15.625, 8.0, 4.096000000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(3)
+azp_barostat_advance timestep=3 dt=0.005 N=6 phase=1 L=(15.625, 8.0, 4.096000000000001)
+writer(3)
+S(3)
+azp_barostat_advance timestep=3 dt=0.005 N=6 phase=2 L=(15.625, 8.0, 4.096000000000001)
+azp_barostat_step_one timestep=3 dt=0.005 N=6 phase=2 L=(19.53125, 8.0, 3.276800000000001)
+f0.compute(4) deferred=True
+f1.compute(4) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=3 dt=0.005 N=6 phase=2 L=(19.53125, 8.0, 3.276800000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(4)
+azp_barostat_advance timestep=4 dt=0.005 N=6 phase=1 L=(19.53125, 8.0, 3.276800000000001)
+updater(4)
+S(4)
+azp_barostat_advance timestep=4 dt=0.005 N=6 phase=2 L=(19.53125, 8.0, 3.276800000000001)
+azp_barostat_step_one timestep=4 dt=0.005 N=6 phase=2 L=(24.4140625, 8.0, 2.621440000000001)
+sort(5)
+nlist.particles_sorted
+f0.compute(5) deferred=True
+f1.compute(5) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=4 dt=0.005 N=6 phase=2 L=(24.4140625, 8.0, 2.621440000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(5)
+azp_barostat_advance timestep=5 dt=0.005 N=6 phase=1 L=(24.4140625, 8.0, 2.621440000000001)
+S(5)
+azp_barostat_advance timestep=5 dt=0.005 N=6 phase=2 L=(24.4140625, 8.0, 2.621440000000001)
+azp_barostat_step_one timestep=5 dt=0.005 N=6 phase=2 L=(30.517578125, 8.0, 2.097152000000001)
+f0.compute(6) deferred=True
+f1.compute(6) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=5 dt=0.005 N=6 phase=2 L=(30.517578125, 8.0, 2.097152000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(6)
+azp_barostat_advance timestep=6 dt=0.005 N=6 phase=1 L=(30.517578125, 8.0, 2.097152000000001)
+writer(6)
+S(6)
+azp_barostat_advance timestep=6 dt=0.005 N=6 phase=2 L=(30.517578125, 8.0, 2.097152000000001)
+azp_barostat_step_one timestep=6 dt=0.005 N=6 phase=2 L=(38.14697265625, 8.0, 1.6777216000000008)
+f0.compute(7) deferred=True
+f1.compute(7) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=6 dt=0.005 N=6 phase=2 L=(38.14697265625, 8.0, 1.6777216000000008)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(7)
+azp_barostat_advance timestep=7 dt=0.005 N=6 phase=1 L=(38.14697265625, 8.0, 1.6777216000000008)
+f0.check_flags(wait=True) deferred=False
+f1.check_flags(wait=True) deferred=False
+run(5)
+f0.compute(7) deferred=False
+f1.compute(7) deferred=False
+azp_sum_forces N=6
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(7)
+azp_barostat_advance timestep=7 dt=0.005 N=6 phase=2 L=(38.14697265625, 8.0, 1.6777216000000008)
+azp_barostat_step_one timestep=7 dt=0.005 N=6 phase=2 L=(47.6837158203125, 8.0, 1.3421772800000007)
+f0.compute(8) deferred=True
+f1.compute(8) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=7 dt=0.005 N=6 phase=2 L=(47.6837158203125, 8.0, 1.3421772800000007)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(8)
+azp_barostat_advance timestep=8 dt=0.005 N=6 phase=1 L=(47.6837158203125, 8.0, 1.3421772800000007)
+updater(8)
+S(8)
+azp_barostat_advance timestep=8 dt=0.005 N=6 phase=2 L=(47.6837158203125, 8.0, 1.3421772800000007)
+azp_barostat_step_one timestep=8 dt=0.005 N=6 phase=2 L=(59.604644775390625, 8.0, 1.0737418240000005)
+f0.compute(9) deferred=True
+f1.compute(9) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=8 dt=0.005 N=6 phase=2 L=(59.604644775390625, 8.0, 1.0737418240000005)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(9)
+azp_barostat_advance timestep=9 dt=0.005 N=6 phase=1 L=(59.604644775390625, 8.0, 1.0737418240000005)
+writer(9)
+S(9)
+azp_barostat_advance timestep=9 dt=0.005 N=6 phase=2 L=(59.604644775390625, 8.0, 1.0737418240000005)
+azp_barostat_step_one timestep=9 dt=0.005 N=6 phase=2 L=(74.50580596923828, 8.0, 0.8589934592000005)
+sort(10)
+nlist.particles_sorted
+f0.compute(10) deferred=True
+f1.compute(10) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=9 dt=0.005 N=6 phase=2 L=(74.50580596923828, 8.0, 0.8589934592000005)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(10)
+azp_barostat_advance timestep=10 dt=0.005 N=6 phase=1 L=(74.50580596923828, 8.0, 0.8589934592000005)
+S(10)
+azp_barostat_advance timestep=10 dt=0.005 N=6 phase=2 L=(74.50580596923828, 8.0, 0.8589934592000005)
+azp_barostat_step_one timestep=10 dt=0.005 N=6 phase=2 L=(93.13225746154785, 8.0, 0.6871947673600004)
+f0.compute(11) deferred=True
+f1.compute(11) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=10 dt=0.005 N=6 phase=2 L=(93.13225746154785, 8.0, 0.6871947673600004)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(11)
+azp_barostat_advance timestep=11 dt=0.005 N=6 phase=1 L=(93.13225746154785, 8.0, 0.6871947673600004)
+S(11)
+azp_barostat_advance timestep=11 dt=0.005 N=6 phase=2 L=(93.13225746154785, 8.0, 0.6871947673600004)
+azp_barostat_step_one timestep=11 dt=0.005 N=6 phase=2 L=(116.41532182693481, 8.0, 0.5497558138880003)
+f0.compute(12) deferred=True
+f1.compute(12) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=11 dt=0.005 N=6 phase=2 L=(116.41532182693481, 8.0, 0.5497558138880003)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(12)
+azp_barostat_advance timestep=12 dt=0.005 N=6 phase=1 L=(116.41532182693481, 8.0, 0.5497558138880003)
+writer(12)
+f0.check_flags(wait=True) deferred=False
+f1.check_flags(wait=True) deferred=False
+timestep=12 position_generation=24 type_generation=3
+box_generation=12
+""",
+    ('npt_bussi', 'run0'): """
+run(0)
+f0.compute(0) deferred=False
+f1.compute(0) deferred=False
+azp_sum_forces N=6
+timestep=0 position_generation=0 type_generation=0
+box_generation=0
+""",
+    ('npt_bussi', 'run1'): """
+run(1)
+f0.compute(0) deferred=False
+f1.compute(0) deferred=False
+azp_sum_forces N=6
+updater(0)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(0)
+kT(0)
+azp_barostat_advance timestep=0 dt=0.005 N=6 phase=2 L=(8.0, 8.0, 8.0)
+azp_barostat_step_one timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+f0.compute(1) deferred=True
+f1.compute(1) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(1)
+kT(1)
+azp_barostat_advance timestep=1 dt=0.005 N=6 phase=1 L=(10.0, 8.0, 6.4)
+f0.check_flags(wait=True) deferred=False
+f1.check_flags(wait=True) deferred=False
+timestep=1 position_generation=2 type_generation=1
+box_generation=1
+""",
+    ('npt_bussi', 'run7_run5'): """
+run(7)
+f0.compute(0) deferred=False
+f1.compute(0) deferred=False
+azp_sum_forces N=6
+updater(0)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(0)
+kT(0)
+azp_barostat_advance timestep=0 dt=0.005 N=6 phase=2 L=(8.0, 8.0, 8.0)
+azp_barostat_step_one timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+f0.compute(1) deferred=True
+f1.compute(1) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=0 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(1)
+kT(1)
+azp_barostat_advance timestep=1 dt=0.005 N=6 phase=1 L=(10.0, 8.0, 6.4)
+S(1)
+kT(1)
+azp_barostat_advance timestep=1 dt=0.005 N=6 phase=2 L=(10.0, 8.0, 6.4)
+azp_barostat_step_one timestep=1 dt=0.005 N=6 phase=2 L=(12.5, 8.0, 5.120000000000001)
+f0.compute(2) deferred=True
+f1.compute(2) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=1 dt=0.005 N=6 phase=2 L=(12.5, 8.0, 5.120000000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(2)
+kT(2)
+azp_barostat_advance timestep=2 dt=0.005 N=6 phase=1 L=(12.5, 8.0, 5.120000000000001)
+S(2)
+kT(2)
+azp_barostat_advance timestep=2 dt=0.005 N=6 phase=2 L=(12.5, 8.0, 5.120000000000001)
+azp_barostat_step_one timestep=2 dt=0.005 N=6 phase=2 L=(15.625, 8.0, 4.096000000000001)
+f0.compute(3) deferred=True
+f1.compute(3) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=2 dt=0.005 N=6 phase=2 L=(15.625, 8.0, 4.096000000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(3)
+kT(3)
+azp_barostat_advance timestep=3 dt=0.005 N=6 phase=1 L=(15.625, 8.0, 4.096000000000001)
+writer(3)
+S(3)
+kT(3)
+azp_barostat_advance timestep=3 dt=0.005 N=6 phase=2 L=(15.625, 8.0, 4.096000000000001)
+azp_barostat_step_one timestep=3 dt=0.005 N=6 phase=2 L=(19.53125, 8.0, 3.276800000000001)
+f0.compute(4) deferred=True
+f1.compute(4) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=3 dt=0.005 N=6 phase=2 L=(19.53125, 8.0, 3.276800000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(4)
+kT(4)
+azp_barostat_advance timestep=4 dt=0.005 N=6 phase=1 L=(19.53125, 8.0, 3.276800000000001)
+updater(4)
+S(4)
+kT(4)
+azp_barostat_advance timestep=4 dt=0.005 N=6 phase=2 L=(19.53125, 8.0, 3.276800000000001)
+azp_barostat_step_one timestep=4 dt=0.005 N=6 phase=2 L=(24.4140625, 8.0, 2.621440000000001)
+sort(5)
+nlist.particles_sorted
+f0.compute(5) deferred=True
+f1.compute(5) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=4 dt=0.005 N=6 phase=2 L=(24.4140625, 8.0, 2.621440000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(5)
+kT(5)
+azp_barostat_advance timestep=5 dt=0.005 N=6 phase=1 L=(24.4140625, 8.0, 2.621440000000001)
+S(5)
+kT(5)
+azp_barostat_advance timestep=5 dt=0.005 N=6 phase=2 L=(24.4140625, 8.0, 2.621440000000001)
+azp_barostat_step_one timestep=5 dt=0.005 N=6 phase=2 L=(30.517578125, 8.0, 2.097152000000001)
+f0.compute(6) deferred=True
+f1.compute(6) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=5 dt=0.005 N=6 phase=2 L=(30.517578125, 8.0, 2.097152000000001)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(6)
+kT(6)
+azp_barostat_advance timestep=6 dt=0.005 N=6 phase=1 L=(30.517578125, 8.0, 2.097152000000001)
+writer(6)
+S(6)
+kT(6)
+azp_barostat_advance timestep=6 dt=0.005 N=6 phase=2 L=(30.517578125, 8.0, 2.097152000000001)
+azp_barostat_step_one timestep=6 dt=0.005 N=6 phase=2 L=(38.14697265625, 8.0, 1.6777216000000008)
+f0.compute(7) deferred=True
+f1.compute(7) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=6 dt=0.005 N=6 phase=2 L=(38.14697265625, 8.0, 1.6777216000000008)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(7)
+kT(7)
+azp_barostat_advance timestep=7 dt=0.005 N=6 phase=1 L=(38.14697265625, 8.0, 1.6777216000000008)
+f0.check_flags(wait=True) deferred=False
+f1.check_flags(wait=True) deferred=False
+run(5)
+f0.compute(7) deferred=False
+f1.compute(7) deferred=False
+azp_sum_forces N=6
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(7)
+kT(7)
+azp_barostat_advance timestep=7 dt=0.005 N=6 phase=2 L=(38.14697265625, 8.0, 1.6777216000000008)
+azp_barostat_step_one timestep=7 dt=0.005 N=6 phase=2 L=(47.6837158203125, 8.0, 1.3421772800000007)
+f0.compute(8) deferred=True
+f1.compute(8) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=7 dt=0.005 N=6 phase=2 L=(47.6837158203125, 8.0, 1.3421772800000007)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(8)
+kT(8)
+azp_barostat_advance timestep=8 dt=0.005 N=6 phase=1 L=(47.6837158203125, 8.0, 1.3421772800000007)
+updater(8)
+S(8)
+kT(8)
+azp_barostat_advance timestep=8 dt=0.005 N=6 phase=2 L=(47.6837158203125, 8.0, 1.3421772800000007)
+azp_barostat_step_one timestep=8 dt=0.005 N=6 phase=2 L=(59.604644775390625, 8.0, 1.0737418240000005)
+f0.compute(9) deferred=True
+f1.compute(9) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=8 dt=0.005 N=6 phase=2 L=(59.604644775390625, 8.0, 1.0737418240000005)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(9)
+kT(9)
+azp_barostat_advance timestep=9 dt=0.005 N=6 phase=1 L=(59.604644775390625, 8.0, 1.0737418240000005)
+writer(9)
+S(9)
+kT(9)
+azp_barostat_advance timestep=9 dt=0.005 N=6 phase=2 L=(59.604644775390625, 8.0, 1.0737418240000005)
+azp_barostat_step_one timestep=9 dt=0.005 N=6 phase=2 L=(74.50580596923828, 8.0, 0.8589934592000005)
+sort(10)
+nlist.particles_sorted
+f0.compute(10) deferred=True
+f1.compute(10) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=9 dt=0.005 N=6 phase=2 L=(74.50580596923828, 8.0, 0.8589934592000005)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(10)
+kT(10)
+azp_barostat_advance timestep=10 dt=0.005 N=6 phase=1 L=(74.50580596923828, 8.0, 0.8589934592000005)
+S(10)
+kT(10)
+azp_barostat_advance timestep=10 dt=0.005 N=6 phase=2 L=(74.50580596923828, 8.0, 0.8589934592000005)
+azp_barostat_step_one timestep=10 dt=0.005 N=6 phase=2 L=(93.13225746154785, 8.0, 0.6871947673600004)
+f0.compute(11) deferred=True
+f1.compute(11) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=10 dt=0.005 N=6 phase=2 L=(93.13225746154785, 8.0, 0.6871947673600004)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(11)
+kT(11)
+azp_barostat_advance timestep=11 dt=0.005 N=6 phase=1 L=(93.13225746154785, 8.0, 0.6871947673600004)
+S(11)
+kT(11)
+azp_barostat_advance timestep=11 dt=0.005 N=6 phase=2 L=(93.13225746154785, 8.0, 0.6871947673600004)
+azp_barostat_step_one timestep=11 dt=0.005 N=6 phase=2 L=(116.41532182693481, 8.0, 0.5497558138880003)
+f0.compute(12) deferred=True
+f1.compute(12) deferred=True
+azp_sum_forces N=6
+azp_barostat_step_two timestep=11 dt=0.005 N=6 phase=2 L=(116.41532182693481, 8.0, 0.5497558138880003)
+azp_thermo_sums N=6 n_forces=2 virials=2
+S(12)
+kT(12)
+azp_barostat_advance timestep=12 dt=0.005 N=6 phase=1 L=(116.41532182693481, 8.0, 0.5497558138880003)
+writer(12)
+f0.check_flags(wait=True) deferred=False
+f1.check_flags(wait=True) deferred=False
+timestep=12 position_generation=24 type_generation=3
+box_generation=12
 """,
 }
