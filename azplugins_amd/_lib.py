@@ -100,6 +100,29 @@ class BondArgs(C.Structure):
     ]
 
 
+class PairGroupArgs(C.Structure):
+    """azp_special_pair_args (``BondedForce`` finds a kind's struct as ``<Kind>Args``: the special pairs are the kind
+    "pair"; ``PairArgs`` is the non-bonded pair kernels')."""
+
+    _fields_ = [
+        ("d_force", C.c_void_p),
+        ("d_virial", C.c_void_p),
+        ("virial_pitch", C.c_uint64),
+        ("N", C.c_uint32),
+        ("n_max", C.c_uint32),
+        ("d_pos", C.c_void_p),
+        ("box", Box),
+        ("d_gpu_pairlist", C.c_void_p),
+        ("d_gpu_pair_pos", C.c_void_p),
+        ("d_gpu_n_pairs", C.c_void_p),
+        ("pitch", C.c_uint64),
+        ("n_pair_types", C.c_uint32),
+        ("compute_virial", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 class AngleEntry(C.Structure):
     _fields_ = [("idx", C.c_uint32 * 2), ("type", C.c_uint32), ("pos", C.c_uint32)]
 
@@ -326,6 +349,10 @@ class RdfArgs(C.Structure):
         ("d_scratch", C.c_void_p),
         ("scratch_bytes", C.c_uint64),
     ]
+
+
+class RdfExclusionArgs(C.Structure):
+    _fields_ = [("rdf", RdfArgs), ("d_n_excl", C.c_void_p), ("d_excl", C.c_void_p), ("excl_pitch", C.c_uint64)]
 
 
 FLOW_CONSTANT = 0
@@ -580,6 +607,9 @@ SYMBOLS = {
     "azp_aniso_forces_planned_two_patch_morse": (C.c_int, [_VP, C.POINTER(AnisoArgs), _VP, _VP]),
     "azp_bond_forces_double_well": (C.c_int, [C.POINTER(BondArgs), _VP, _VP, _VP]),
     "azp_bond_forces_quartic": (C.c_int, [C.POINTER(BondArgs), _VP, _VP, _VP]),
+    "azp_special_pair_lj_params_make": (None, [_D] * 3 + [_VP]),
+    "azp_special_pair_lj_params_unpack": (None, [_VP] + [_PD] * 3),
+    "azp_special_pair_forces_lj": (C.c_int, [C.POINTER(PairGroupArgs), _VP, _VP]),
     "azp_angle_harmonic_params_make": (None, [_D] * 2 + [_VP]),
     "azp_angle_harmonic_params_unpack": (None, [_VP] + [_PD] * 2),
     "azp_angle_cossq_params_make": (None, [_D] * 2 + [_VP]),
@@ -642,6 +672,7 @@ SYMBOLS = {
     "azp_thermo_sums": (C.c_int, [C.POINTER(ThermoArgs), _VP]),
     "azp_rdf_scratch_size": (C.c_int, [C.POINTER(RdfArgs), C.POINTER(C.c_uint64)]),
     "azp_rdf_counts": (C.c_int, [C.POINTER(RdfArgs), _VP]),
+    "azp_rdf_subtract_excluded": (C.c_int, [C.POINTER(RdfExclusionArgs), _VP]),
     "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
     "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
     "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),

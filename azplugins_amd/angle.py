@@ -13,9 +13,10 @@ An angle has members ``a, b, c`` with ``b`` the vertex (``Snapshot.angles.group`
 
 ``F_a = -dU/dc (dcb / (|dab||dcb|) - c dab / |dab|^2)``, ``F_c`` likewise with a and c exchanged, ``F_b = -F_a - F_c``.
 Every member gets a third of ``U`` and, with ``compute_virial``, a third of ``dab (x) F_a + dcb (x) F_c``. Coincident
-members (``|dab|`` or ``|dcb|`` equal to 0) are undefined. Angles add no neighbor-list exclusions.
+members (``|dab|`` or ``|dcb|`` equal to 0) are undefined. Angles add no neighbor-list exclusions by themselves:
+``nlist.Cell(exclusions=("bond", "angle"))`` or ``"1-3"`` does.
 
-Out of scope: impropers, tabulated angles, 1-3 exclusions, an ``_azplugins`` class."""
+Out of scope: impropers, tabulated angles, an ``_azplugins`` class."""
 
 import ctypes as C
 import math

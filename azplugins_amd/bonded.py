@@ -12,11 +12,12 @@ from .force import Force, TypeParameter
 class BondedForce(Force):
     """``params[type] = dict(...)`` per group type; ``block_size``: 0 (256) or 64, 128, 256.
 
-    A kind declares ``_kind`` ("bond", "angle" or "dihedral": the ``State`` group it reads, its ``_lib`` argument struct
+    A kind declares ``_kind`` ("bond", "angle", "dihedral" or "pair": the ``State`` group it reads, its ``_lib`` argument struct
     and that struct's table, count and type-number fields all carry the name) and ``_param_doubles``; a potential
     declares ``_entry``, ``_schema``, ``_pack`` and ``_unpack`` and, to range-check what is set, ``_parameter``."""
 
     _kind = None
+    _args_struct = None    # the ``_lib`` struct where it is not ``<Kind>Args`` (special pairs: ``PairArgs`` is taken)
     _entry = None
     _schema = None
     _parameter = TypeParameter
@@ -75,7 +76,7 @@ class BondedForce(Force):
         if self._tables is None or self._tables.shape[0] != n_types:
             self._build_tables()
         tab = getattr(st, kind + "_table")()
-        a = getattr(_lib, kind.capitalize() + "Args")()
+        a = getattr(_lib, self._args_struct or kind.capitalize() + "Args")()
         a.d_force = self._force.data_ptr()
         a.d_virial = self._virial.data_ptr()
         a.virial_pitch = st.N
@@ -85,7 +86,7 @@ class BondedForce(Force):
         a.box = st.box.to_c()
         setattr(a, "d_gpu_%slist" % kind, tab["table"].data_ptr())
         if "bond_pos" in tab:
-            a.d_gpu_bond_pos = tab["bond_pos"].data_ptr()
+            setattr(a, "d_gpu_%s_pos" % kind, tab["bond_pos"].data_ptr())
         setattr(a, "d_gpu_n_%ss" % kind, tab["n_%ss" % kind].data_ptr())
         a.pitch = tab["pitch"]
         setattr(a, "n_%s_types" % kind, n_types)

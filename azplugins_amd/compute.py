@@ -593,11 +593,23 @@ class RadialDistributionFunction(_Compute):
     the counts are added over the ranks (every rank gets the same result); ghosts are complete out to the
     decomposition's ``r_ghost`` minus the neighbor-list buffer, a larger ``r_max`` is refused.
 
+    ``exclusions``: the names a neighbor list takes (``nlist.NeighborList``; ``state.EXCLUSIONS``), default none. The
+    pairs they name are taken out of the counts again by a second kernel behind the pair pass
+    (``azp_rdf_subtract_excluded``): with ``("bond", "1-3", "1-4")`` on chains, what is left is the INTERMOLECULAR g(r)
+    plus the intramolecular pairs four or more bonds apart. ``num_pairs`` and with it the normalisation stay as they
+    are, so g(r) still tends to 1. ``excluded_pairs`` is the number of ordered pairs taken out. Single-domain states
+    only: on a decomposed run a non-empty ``exclusions`` is an ``AzpError`` (a particle that is its own periodic ghost
+    sits on two rows, and the exclusion table names one of them).
+
     Every property is computed when it is read, from the current state."""
 
-    def __init__(self, filter_a, filter_b, r_max, num_bins):
+    def __init__(self, filter_a, filter_b, r_max, num_bins, exclusions=()):
+        from .state import check_exclusions
+
         super().__init__(_check_rdf_filter("filter_a", filter_a), False)
         self._filter_b = _check_rdf_filter("filter_b", filter_b)
+        self.exclusions = tuple(exclusions)
+        self._exclusion_kinds = check_exclusions(self.exclusions, "RadialDistributionFunction(exclusions=...)")
         self.r_max = r_max
         self.num_bins = num_bins
         self.path = _lib.RDF_PATH_AUTO
@@ -712,7 +724,18 @@ class RadialDistributionFunction(_Compute):
         a.d_scratch = self._scratch.data_ptr()
         a.scratch_bytes = self._scratch.numel()
         a.d_out = d_out
-        _lib.check(lib.azp_rdf_counts(C.byref(a), _lib.raw_stream(st.device)), "azp_rdf_counts")
+        kinds = self._exclusion_kinds
+        if kinds and sim.domain is not None:
+            raise _lib.AzpError("RadialDistributionFunction: exclusions are not supported on a decomposed run (a particle "
+                                "that is its own periodic ghost sits on two rows, the exclusion table names one)")
+        stream = _lib.raw_stream(st.device)
+        _lib.check(lib.azp_rdf_counts(C.byref(a), stream), "azp_rdf_counts")
+        if kinds and any(g.n for g in st.groups.values()):
+            x = _lib.RdfExclusionArgs()
+            x.rdf = a
+            n_excl, excl, pitch = st.merged_exclusion_table(kinds)
+            x.d_n_excl, x.d_excl, x.excl_pitch = n_excl.data_ptr(), excl.data_ptr(), pitch
+            _lib.check(lib.azp_rdf_subtract_excluded(C.byref(x), stream), "azp_rdf_subtract_excluded")
 
     def _reduce(self, rows):
         """Rows of per-rank words (a (k, num_bins + 4) int64 device tensor: the uint64 words of the kernel, all below
@@ -753,6 +776,11 @@ class RadialDistributionFunction(_Compute):
         """int: N_A N_B - N_AB over the owned particles of the whole system."""
         n_a, n_b, n_ab = (int(x) for x in self._read("num_pairs")[self._num_bins:self._num_bins + 3])
         return n_a * n_b - n_ab
+
+    @property
+    def excluded_pairs(self):
+        """int: the ordered pairs that ``exclusions`` took out of the counts (0 without exclusions)."""
+        return int(self._read("excluded_pairs")[self._num_bins + 3])
 
     @property
     def rdf(self):

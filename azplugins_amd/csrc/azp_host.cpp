@@ -106,6 +106,24 @@ void azp_quartic_params_unpack(const azp_quartic_params* p, double* k, double* r
     *delta = p->delta;
     }
 
+// ---- special pairs (include/azp.h, "special pair forces"): LJ folds 4 eps sigma^12, 4 eps sigma^6 and r_cut^2 ----
+void azp_special_pair_lj_params_make(double epsilon, double sigma, double r_cut, azp_special_pair_lj_params* out)
+    {
+    const double s2 = sigma * sigma;
+    const double s6 = s2 * s2 * s2;
+    out->lj1 = 4.0 * epsilon * s6 * s6;
+    out->lj2 = 4.0 * epsilon * s6;
+    out->r_cutsq = r_cut * r_cut;
+    out->_pad = 0.0;
+    }
+void azp_special_pair_lj_params_unpack(const azp_special_pair_lj_params* p, double* epsilon, double* sigma, double* r_cut)
+    {
+    const bool set = p->lj1 != 0.0 && p->lj2 != 0.0;
+    *sigma = set ? std::pow(p->lj1 / p->lj2, 1. / 6.) : 0.0;
+    *epsilon = set ? p->lj2 * p->lj2 / (4.0 * p->lj1) : 0.0;
+    *r_cut = std::sqrt(p->r_cutsq);
+    }
+
 // ---- angle potentials (include/azp.h, "angle forces"): harmonic keeps (k, t0), cosine squared folds cos t0 ----
 void azp_angle_harmonic_params_make(double k, double t0, azp_angle_harmonic_params* out)
     {

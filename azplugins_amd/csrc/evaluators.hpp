@@ -677,4 +677,28 @@ struct EvalQuartic // src/BondEvaluatorQuartic.h:113-200
         }
     };
 
+// ---------------------------------------------------------------------------
+// Special pair evaluators (include/azp.h, "special pair forces": defined there, no counterpart in the reference)
+// ---------------------------------------------------------------------------
+struct EvalSpecialPairLJ
+    {
+    typedef azp_special_pair_lj_params Params;
+    static constexpr bool kSplitEnergy = false;
+    // U = r^-6 (lj1 r^-6 - lj2), F / r = r^-2 r^-6 (12 lj1 r^-6 - 6 lj2) inside r_cut, both 0 from r_cut on; no shift.
+    // Always evaluated: a pair beyond its cutoff is no error.
+    static __device__ __forceinline__ bool eval(const Params& p, double rsq, double& force_divr, double& pair_eng)
+        {
+        force_divr = 0.0;
+        pair_eng = 0.0;
+        if (rsq < p.r_cutsq)
+            {
+            const double r2inv = 1.0 / rsq;
+            const double r6inv = r2inv * r2inv * r2inv;
+            force_divr = r2inv * r6inv * (12.0 * p.lj1 * r6inv - 6.0 * p.lj2);
+            pair_eng = r6inv * (p.lj1 * r6inv - p.lj2);
+            }
+        return true;
+        }
+    };
+
 } // namespace azp

@@ -4,6 +4,8 @@
 // [0, r_max): counted iff rsq < r_max^2, r = sqrt(rsq) correctly rounded, k = min((uint32_t)(r * scale), num_bins - 1)
 // with scale = num_bins / r_max from the host. The output row is num_bins + 4 uint64: the counts, then N_A, N_B and
 // N_(A and B) over rows [0, N), then one zero. The call zeroes the row itself (hipMemsetAsync on the stream).
+// azp_rdf_subtract_excluded, queued behind it, takes the pairs of an exclusion table out of the row again and counts
+// them in that last word (rdf_subtract_excluded below): the intermolecular g(r).
 //
 // Two paths, the same integers wherever both are valid:
 //   all-pairs  (any box, any N) grid (ceil(N / 256), segments of B). Thread t of a workgroup holds row
@@ -322,6 +324,64 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_group_counts(const RdfKArgs a)
     }
 
 // ---------------------------------------------------------------------------------------------------------------
+// excluded pairs out of a finished row (azp_rdf_subtract_excluded)
+// ---------------------------------------------------------------------------------------------------------------
+// One lane per row i < N (grid-stride), walking the row's entries j of an exclusion table (entry s of row i at
+// s * pitch + i: coalesced; the partner rows are gathers). Where i is in A and j in B the pair goes through rdf_test
+// into the workgroup's histogram, exactly as the main pass put it there; the flush then SUBTRACTS the histogram from
+// the row (adds 2^64 - v: integer arithmetic modulo 2^64, exact as long as the pair was counted) and adds its total
+// to out[num_bins + 3]. The table is symmetric and free of duplicates, so every ordered pair comes up once.
+// A workgroup's histogram takes one increment per table entry of its rows; 2^32 of them would need a table of
+// 2^32 x 4 B per workgroup, which no device holds: no flush inside the loop.
+__global__ void __launch_bounds__(RDF_BLOCK) rdf_subtract_excluded(const RdfKArgs a, const uint32_t* __restrict__ n_excl,
+                                                                   const uint32_t* __restrict__ excl, const uint64_t pitch)
+    {
+    extern __shared__ uint32_t s_hist[];
+    __shared__ unsigned long long s_total;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < a.num_bins; k += RDF_BLOCK)
+        s_hist[k] = 0;
+    if (tid == 0)
+        s_total = 0;
+    __syncthreads();
+    const uint32_t last_bin = a.num_bins - 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * RDF_BLOCK + tid; i < a.N; i += (uint64_t)gridDim.x * RDF_BLOCK)
+        {
+        const uint32_t n = n_excl[i];
+        if (n == 0)
+            continue;
+        const double4 p = load_scalar4(a.pos, (uint32_t)i);
+        if (!rdf_in_mask(a.mask_a, a.ntypes, p.w))
+            continue;
+        for (uint32_t s = 0; s < n; ++s)
+            {
+            const uint32_t j = excl[(uint64_t)s * pitch + i];
+            if (j >= a.n_total || j == i)
+                continue;
+            const double4 q = load_scalar4(a.pos, j);
+            if (rdf_in_mask(a.mask_b, a.ntypes, q.w))
+                rdf_test(a.box, p.x - q.x, p.y - q.y, p.z - q.z, a.rmaxsq, a.scale, last_bin, s_hist);
+            }
+        }
+    __syncthreads();
+    unsigned long long mine = 0;
+    for (uint32_t k = tid; k < a.num_bins; k += RDF_BLOCK)
+        {
+        const uint32_t v = s_hist[k];
+        if (v)
+            {
+            atomicAdd(&a.out[k], 0ull - (unsigned long long)v);
+            mine += v;
+            }
+        }
+    if (mine)
+        atomicAdd(&s_total, mine);
+    __syncthreads();
+    if (tid == 0 && s_total)
+        atomicAdd(&a.out[a.num_bins + 3], s_total);
+    }
+
+// ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
 // the cell grid of the cells path; false if the box does not allow it (winv = dim / L, filled here: make_grid_dev's
@@ -472,5 +532,42 @@ extern "C" int azp_rdf_counts(const azp_rdf_args* args, void* stream)
     const uint32_t grid = (std::min(p.ncell, RDF_TARGET_BLOCKS) + 7u) & ~7u;
     k.cells_per_block = (p.ncell + grid - 1) / grid;
     hipLaunchKernelGGL(rdf_cells, dim3(grid), dim3(RDF_BLOCK), lds, st, k);
+    return (int)hipGetLastError();
+    }
+
+extern "C" int azp_rdf_subtract_excluded(const azp_rdf_exclusion_args* xargs, void* stream)
+    {
+    using namespace azp;
+    if (!xargs)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    const azp_rdf_args* args = &xargs->rdf;
+    azp_rdf_args any_path = *args;
+    any_path.path = 1;  // (the pair pass has run: which path it took does not matter here)
+    RdfPlan p;
+    const int rc = rdf_plan(&any_path, p);
+    if (rc != AZP_SUCCESS)
+        return rc;
+    if (!args->d_out || (args->n_total && !args->d_pos))
+        return AZP_ERROR_INVALID_ARGUMENT;
+    if (args->N == 0)
+        return AZP_SUCCESS;
+    if (!xargs->d_n_excl || !xargs->d_excl || xargs->excl_pitch < args->N)
+        return AZP_ERROR_INVALID_ARGUMENT;
+    RdfKArgs k = {};
+    k.pos = args->d_pos;
+    k.mask_a = args->d_type_mask_a;
+    k.mask_b = args->d_type_mask_b;
+    k.out = reinterpret_cast<unsigned long long*>(args->d_out);
+    k.box = make_box_dev(args->box);
+    k.rmaxsq = args->r_max * args->r_max;
+    k.scale = args->scale;
+    k.N = args->N;
+    k.n_total = args->n_total;
+    k.ntypes = args->ntypes;
+    k.num_bins = args->num_bins;
+    const uint32_t n_tiles = (args->N + RDF_BLOCK - 1) / RDF_BLOCK;
+    hipLaunchKernelGGL(rdf_subtract_excluded, dim3(std::min(n_tiles, RDF_TARGET_BLOCKS)), dim3(RDF_BLOCK),
+                       args->num_bins * sizeof(uint32_t), static_cast<hipStream_t>(stream), k, xargs->d_n_excl, xargs->d_excl,
+                       xargs->excl_pitch);
     return (int)hipGetLastError();
     }

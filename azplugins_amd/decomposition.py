@@ -264,7 +264,8 @@ def _snapshot_topology(snap):
     """The bonded topology of a snapshot by particle TAG: ``bond_tags`` / ``bond_typeid`` / ``bond_types`` and, when the
     snapshot has angles, ``angle_tags`` / ``angle_typeid`` / ``angle_types`` (absent without angles; a snapshot with
     angles but no bonds carries an empty bond list), and ``dihedral_tags`` / ``dihedral_typeid`` / ``dihedral_types`` in
-    the same way, only when it has dihedrals. None when there are neither bonds nor angles nor dihedrals."""
+    the same way, only when it has dihedrals, and ``pair_tags`` / ``pair_typeid`` / ``pair_types`` only when it has
+    special pairs. None when there are none of the four."""
     if not any(getattr(snap, kind + "s").N for kind in KINDS):
         return None
     tag = snap.particles.tag.astype(np.int64)

@@ -16,9 +16,10 @@ A dihedral has members ``a, b, c, d`` (``Snapshot.dihedrals.group``). With ``b1 
 ``g_c = -(1 + t) g_d + s g_a`` with ``s = b1 . b2 / |b2|^2`` and ``t = b3 . b2 / |b2|^2``. Every member gets a quarter
 of ``U`` and, with ``compute_virial``, a quarter of ``(-b1) (x) F_a + b2 (x) F_c + (b2 + b3) (x) F_d`` (zero trace).
 ``a, b, c`` or ``b, c, d`` collinear (``|n1|`` or ``|n2|`` equal to 0) and coincident members are undefined. Dihedrals
-add no neighbor-list exclusions.
+add no neighbor-list exclusions by themselves: ``nlist.Cell(exclusions=("bond", "1-3", "1-4"))`` excludes the 1-4
+pairs and ``special_pair.LJ`` puts them back scaled.
 
-Out of scope: impropers, tabulated dihedrals, 1-4 exclusions / special pairs, an ``_azplugins`` class."""
+Out of scope: impropers, tabulated dihedrals, ``special_pair.Coulomb`` (no charges), an ``_azplugins`` class."""
 
 import ctypes as C
 import math

@@ -360,5 +360,7 @@ class DeviceDomain:
         for kind, g in getattr(state, "groups", {}).items():
             if g.tags is not None:
                 state.relocalize(kind)  # tables and exclusions by local index: every index changed
+        if hasattr(state, "drop_exclusion_table"):
+            state.drop_exclusion_table()  # (rebuilt from the topology by tag when the list is: State.exclusion_table)
         state.position_generation += 1
         state.order_generation += 1  # every index changed: the list must be rebuilt

@@ -46,11 +46,18 @@ def cell_grid(box, r_list_max, sub=1):
 
 
 class NeighborList:
-    """Base: holds the device arrays in HOOMD's layout."""
+    """Base: holds the device arrays in HOOMD's layout.
+
+    ``exclusions``: any subset of "bond", "angle", "dihedral", "special_pair", "1-3" and "1-4" (``state.EXCLUSIONS``:
+    what each excludes), HOOMD's default ``("bond",)``. "body", "constraint" and "meshbond" are accepted
+    and exclude nothing (the project has none of them); any other name is an ``AzpError`` here."""
 
     def __init__(self, buffer, exclusions=("bond",)):
+        from .state import check_exclusions
+
         self.buffer = float(buffer)
-        self.exclusions = tuple(exclusions)
+        self.exclusions = tuple(exclusions)  # (as given; what they amount to is checked once, here)
+        self._exclusion_kinds = check_exclusions(self.exclusions, "NeighborList(exclusions=...)")
         self._consumers = []
         self.n_neigh = None
         self._head_list = None
@@ -375,8 +382,10 @@ class Cell(NeighborList):
         bins = self._bin(a, box, rl_max, n_total, sub, dev, stream, grid if sub == 1 else None)
 
         keep = []
-        if "bond" in self.exclusions and state.n_bonds:
-            n_excl, excl, pitch = state.exclusion_table()
+        kinds = self._exclusion_kinds
+        # (bond-only, the default: the bond table's partner column as it stands; anything else: the merged table)
+        if (state.n_bonds if kinds == ("bond",) else (kinds and any(g.n for g in state.groups.values()))):
+            n_excl, excl, pitch = state.exclusion_table(kinds)
             a.d_n_excl = n_excl.data_ptr()
             a.d_excl = excl.data_ptr()
             a.excl_pitch = pitch

@@ -432,6 +432,45 @@ int azp_bond_forces_quartic(const azp_bond_args* args, const azp_quartic_params*
 int azp_bond_forces_table(const azp_bond_args* args, const azp_table_params* d_params, unsigned int* d_flags,
                           void* stream);
 
+/* ---- special pair forces (azplugins_amd.special_pair) ----
+ * Two-body potentials over a per-particle table of SPECIAL PAIRS: pairs of particles that carry an interaction of
+ * their own, such as the scaled 1-4 pairs of an OPLS chain that the neighbor list excludes. The
+ * reference holds no such code; the names are HOOMD's md.special_pair, the semantics are DEFINED HERE.
+ *
+ * The table has the layout of the bond table (azp_bond_entry: partner, type; the particle's position in the pair in
+ * a plane of its own), and the kernel is the bond kernel with another evaluator: one lane per particle, no atomics,
+ * each member gets F on itself, U / 2 and, when compute_virial is set, half of the pair's virial; two calls give the
+ * same bits at every block size. With d the minimum-image separation and r = |d|:
+ *   LJ   U = 4 epsilon [(sigma / r)^12 - (sigma / r)^6] for r^2 < r_cut^2, U = 0 and F = 0 otherwise. NO shift: U
+ *        jumps at r_cut (HOOMD's md.special_pair.LJ). r = 0 is undefined.
+ * azp_special_pair_lj_params holds lj1 = 4 epsilon sigma^12, lj2 = 4 epsilon sigma^6 and r_cut^2, folded on the host
+ * in double; unpack returns sigma = (lj1 / lj2)^(1/6) and epsilon = lj2^2 / (4 lj1) (to rounding; 0, 0 where lj1 or
+ * lj2 is 0). The evaluator cannot reject its parameters: there is no flag word. Error returns as for the angle kernel. */
+typedef struct azp_special_pair_lj_params { double lj1, lj2, r_cutsq, _pad; } azp_special_pair_lj_params;
+
+typedef struct azp_special_pair_args
+    {
+    double* d_force;         /* N x 4, overwritten */
+    double* d_virial;        /* 6 x virial_pitch, written when compute_virial is set */
+    uint64_t virial_pitch;
+    uint32_t N;
+    uint32_t n_max;
+    const double* d_pos;     /* n_max x 4 */
+    azp_box box;
+    const azp_bond_entry* d_gpu_pairlist; /* entry s of particle i at s * pitch + i, s < d_gpu_n_pairs[i] */
+    const uint32_t* d_gpu_pair_pos;       /* i's position (0 or 1) in that pair */
+    const uint32_t* d_gpu_n_pairs;
+    uint64_t pitch;
+    uint32_t n_pair_types;
+    uint32_t compute_virial;
+    uint32_t block_size;     /* 0: 256; otherwise a multiple of 64, at most 256 */
+    uint32_t _pad;
+    } azp_special_pair_args;
+
+void azp_special_pair_lj_params_make(double epsilon, double sigma, double r_cut, azp_special_pair_lj_params* out);
+void azp_special_pair_lj_params_unpack(const azp_special_pair_lj_params* p, double* epsilon, double* sigma, double* r_cut);
+int azp_special_pair_forces_lj(const azp_special_pair_args* args, const azp_special_pair_lj_params* d_params, void* stream);
+
 /* ---- angle forces ----
  * Three-body bending potentials over a per-particle angle table. The reference holds no angle code; the semantics
  * are HOOMD's documented md.angle.Harmonic and md.angle.CosineSquared conventions, DEFINED HERE.
@@ -1325,7 +1364,8 @@ int azp_thermo_sums(const azp_thermo_args* args, void* stream);
  *   scale = num_bins / r_max is computed once by the caller in double and passed in;
  *   the minimum image is the one the force kernels use (triclinic boxes included).
  * azp_rdf_counts OVERWRITES the num_bins + 4 uint64 at d_out (uninitialised memory is fine, the call zeroes the row
- * on the stream): the counts, then N_A, N_B and N_(A and B) over rows [0, N), then one reserved zero. From these,
+ * on the stream): the counts, then N_A, N_B and N_(A and B) over rows [0, N), then one zero (the word that
+ * azp_rdf_subtract_excluded below counts in). From these,
  * g[k] = counts[k] V / (n_pairs (4 pi / 3)(r_(k+1)^3 - r_k^3)) with n_pairs = N_A N_B - N_(A and B)
  * (compute.rdf_from_counts). Integer accumulation only (LDS integer atomics, then 64-bit integer atomic adds): two
  * calls on the same state give the same bits. Asynchronous on `stream`, no host synchronisation, no readback.
@@ -1360,6 +1400,27 @@ typedef struct azp_rdf_args
 
 int azp_rdf_scratch_size(const azp_rdf_args* args, uint64_t* bytes);
 int azp_rdf_counts(const azp_rdf_args* args, void* stream);
+
+/* Intermolecular g(r): take the excluded pairs (a table of neighbor-list exclusions: entry s of row i is
+ * d_excl[s * excl_pitch + i], s < d_n_excl[i], i < N; symmetric, free of duplicates and of self-entries) out of a row
+ * that azp_rdf_counts has filled for `rdf` (the same arguments, the same d_out), queued on the same stream after it.
+ * One lane per row i walks the row's entries j; where i is in A and j in B the pair goes through the arithmetic of the
+ * main pass (the bin of a pair is a function of its rsq alone, so it is the bin the pair was counted in; a pair at
+ * rsq >= r_max^2 was not counted and is not subtracted) into an integer histogram of the workgroup, which is then
+ * SUBTRACTED from the row: 2^64 - v added with the 64-bit integer atomic. d_out[num_bins + 3], which azp_rdf_counts
+ * leaves zero, receives the number of ORDERED pairs subtracted. Integers only: two calls give the same bits. N_A, N_B
+ * and N_(A and B), and with them the normalisation n_pairs, stay as they are. An entry j >= n_total is skipped.
+ * Rows that sit on the rank twice (a particle and its own periodic ghost) are not handled: single-domain states only.
+ * AZP_ERROR_INVALID_ARGUMENT: what azp_rdf_counts refuses, a NULL table, excl_pitch < N. N == 0: success. */
+typedef struct azp_rdf_exclusion_args
+    {
+    azp_rdf_args rdf;           /* as given to azp_rdf_counts; path, d_scratch and scratch_bytes are not looked at */
+    const uint32_t* d_n_excl;   /* N */
+    const uint32_t* d_excl;     /* width x excl_pitch */
+    uint64_t excl_pitch;
+    } azp_rdf_exclusion_args;
+
+int azp_rdf_subtract_excluded(const azp_rdf_exclusion_args* args, void* stream);
 
 /* ---- wall potentials (azplugins_amd.wall) ----
  * Replace the reference's legacy wall evaluators src/WallEvaluatorLJ93.h:50-150 and
