@@ -387,6 +387,35 @@ class FlowMethodArgs(C.Structure):
     ]
 
 
+class LangevinArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_vel", C.c_void_p),
+        ("d_accel", C.c_void_p),
+        ("d_net_force", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("d_gamma", C.c_void_p),
+        ("d_type_mask", C.c_void_p),
+        ("d_orientation", C.c_void_p),
+        ("d_angmom", C.c_void_p),
+        ("d_inertia", C.c_void_p),
+        ("d_net_torque", C.c_void_p),
+        ("d_langevin_torque", C.c_void_p),
+        ("d_gamma_r", C.c_void_p),
+        ("box", Box),
+        ("dt", C.c_double),
+        ("kT", C.c_double),
+        ("timestep", C.c_uint64),
+        ("seed", C.c_uint32),
+        ("rotational", C.c_uint32),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 THERMOSTAT_BERENDSEN, THERMOSTAT_BUSSI, THERMOSTAT_MTTK = 0, 1, 2
 THERMOSTAT_NSTATE = 8
 (THERMOSTAT_ALPHA, THERMOSTAT_K, THERMOSTAT_ENERGY, THERMOSTAT_XI, THERMOSTAT_ETA, THERMOSTAT_ATTEMPTS) = range(6)
@@ -646,6 +675,10 @@ SYMBOLS = {
     "azp_integrate_langevin_flow_step_two": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
     "azp_integrate_langevin_flow_step_two_one": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
     "azp_integrate_brownian_flow_step": (C.c_int, [C.POINTER(FlowMethodArgs), _VP]),
+    "azp_integrate_langevin_step_one": (C.c_int, [C.POINTER(LangevinArgs), _VP]),
+    "azp_integrate_langevin_step_two": (C.c_int, [C.POINTER(LangevinArgs), _VP]),
+    "azp_integrate_langevin_step_two_one": (C.c_int, [C.POINTER(LangevinArgs), _VP]),
+    "azp_integrate_brownian_step": (C.c_int, [C.POINTER(LangevinArgs), _VP]),
     "azp_thermostat_partials_size": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
     "azp_thermostat_kinetic": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),
     "azp_thermostat_step_two": (C.c_int, [C.POINTER(ThermostatArgs), _VP]),

@@ -8,6 +8,7 @@
 
 #include "azp_device.hpp"
 #include "pair_kernel_host.hpp"
+#include "rotation.hpp"
 
 namespace azp
 {
@@ -371,68 +372,22 @@ extern "C" int azp_halo_unpack_fields(uint32_t n, uint32_t n_fields, const azp_h
 // ---- rotational half of the NVE step (azp_nve_rot_args, include/azp.h) ----
 namespace azp
 {
-struct Quat
-    {
-    double s, x, y, z;
-    };
-__device__ __forceinline__ void free_rotation(int axis, Quat& p, Quat& q, double I, double dt)
-    {
-    Quat pk, qk;
-    if (axis == 3)
-        {
-        pk = Quat {-p.z, p.y, -p.x, p.s};
-        qk = Quat {-q.z, q.y, -q.x, q.s};
-        }
-    else if (axis == 2)
-        {
-        pk = Quat {-p.y, -p.z, p.s, p.x};
-        qk = Quat {-q.y, -q.z, q.s, q.x};
-        }
-    else
-        {
-        pk = Quat {-p.x, p.s, p.z, -p.y};
-        qk = Quat {-q.x, q.s, q.z, -q.y};
-        }
-    const double phi = 0.25 / I * (p.s * qk.s + p.x * qk.x + p.y * qk.y + p.z * qk.z);
-    const double c = cos(dt * phi), sn = sin(dt * phi);
-    p = Quat {c * p.s + sn * pk.s, c * p.x + sn * pk.x, c * p.y + sn * pk.y, c * p.z + sn * pk.z};
-    q = Quat {c * q.s + sn * qk.s, c * q.x + sn * qk.x, c * q.y + sn * qk.y, c * q.z + sn * qk.z};
-    }
-
 template<bool STEP_ONE> __global__ void __launch_bounds__(256) nve_rot_kernel(const azp_nve_rot_args a)
     {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.N)
         return;
-    const double4 q4 = load_scalar4(a.d_orientation, i), p4 = load_scalar4(a.d_angmom, i), t4 = load_scalar4(a.d_net_torque, i);
-    Quat q = {q4.x, q4.y, q4.z, q4.w}, p = {p4.x, p4.y, p4.z, p4.w};
-    const double Ix = a.d_inertia[3ull * i], Iy = a.d_inertia[3ull * i + 1], Iz = a.d_inertia[3ull * i + 2];
-    // torque into the body frame: rotate(conj(q), t)
-    const double ux = -q.x, uy = -q.y, uz = -q.z;
-    const double c = q.s * q.s - (ux * ux + uy * uy + uz * uz);
-    const double d = 2.0 * (ux * t4.x + uy * t4.y + uz * t4.z);
-    double tx = c * t4.x + 2.0 * q.s * (uy * t4.z - uz * t4.y) + d * ux;
-    double ty = c * t4.y + 2.0 * q.s * (uz * t4.x - ux * t4.z) + d * uy;
-    double tz = c * t4.z + 2.0 * q.s * (ux * t4.y - uy * t4.x) + d * uz;
-    if (Ix == 0.0) tx = 0.0;
-    if (Iy == 0.0) ty = 0.0;
-    if (Iz == 0.0) tz = 0.0;
-    // p += dt * q * (0, t)
-    p.s += a.dt * -(q.x * tx + q.y * ty + q.z * tz);
-    p.x += a.dt * (q.s * tx + (q.y * tz - q.z * ty));
-    p.y += a.dt * (q.s * ty + (q.z * tx - q.x * tz));
-    p.z += a.dt * (q.s * tz + (q.x * ty - q.y * tx));
+    const double4 t4 = load_scalar4(a.d_net_torque, i);
+    Quat q = load_quat(a.d_orientation, i), p = load_quat(a.d_angmom, i);
+    const double3 I = make_double3(a.d_inertia[3ull * i], a.d_inertia[3ull * i + 1], a.d_inertia[3ull * i + 2]);
+    // torque into the body frame, then p += dt * q * (0, t) (rotation.hpp)
+    kick(p, q, zero_free_axes(to_body(q, t4.x, t4.y, t4.z), I), a.dt);
     if (STEP_ONE)
         {
-        if (Iz != 0.0) free_rotation(3, p, q, Iz, 0.5 * a.dt);
-        if (Iy != 0.0) free_rotation(2, p, q, Iy, 0.5 * a.dt);
-        if (Ix != 0.0) free_rotation(1, p, q, Ix, a.dt);
-        if (Iy != 0.0) free_rotation(2, p, q, Iy, 0.5 * a.dt);
-        if (Iz != 0.0) free_rotation(3, p, q, Iz, 0.5 * a.dt);
-        const double n = 1.0 / sqrt(q.s * q.s + q.x * q.x + q.y * q.y + q.z * q.z);
-        store_scalar4(a.d_orientation, i, q.s * n, q.x * n, q.y * n, q.z * n);
+        free_rotations(p, q, I, a.dt);
+        store_quat(a.d_orientation, i, q);
         }
-    store_scalar4(a.d_angmom, i, p.s, p.x, p.y, p.z);
+    store_quat(a.d_angmom, i, p);
     }
 
 template<bool STEP_ONE> static int launch_nve_rot(const azp_nve_rot_args* args, void* stream)

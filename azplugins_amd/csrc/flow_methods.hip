@@ -5,18 +5,11 @@
 //
 // One thread per particle, Scalar4 rows as two 16-byte loads. The flow kind is a template parameter. No atomics.
 //
-// Random stream: HOOMD-5's RandomGenerator(Seed(id, timestep, seed), Counter(tag)) as the DPD thermostat restates
-// it (evaluators.hpp: philox_key0, philox_u01): key = {id << 24 | (t >> 32 & 0xff) << 16 | seed16, t & 0xffffffff},
-// counter {k, tag, 0, 0} for draw k. HOOMD-blue's own source is not available to this project, so this bit layout is
-// NOT checked against HOOMD; the Philox core is checked by the golden known answers (philox4x32_10_kat).
-#include "azp_device.hpp"
-#include "evaluators.hpp"
+// The random stream, the type selection and the half steps themselves are langevin_device.hpp's, shared with langevin.hip.
+#include "langevin_device.hpp"
 
 namespace azp
 {
-constexpr uint32_t RNG_BROWNIAN_FLOW = 201; // src/RNGIdentifiers.h
-constexpr uint32_t RNG_LANGEVIN_FLOW = 202;
-
 struct FlowKArgs
     {
     double* pos;
@@ -28,12 +21,8 @@ struct FlowKArgs
     const double* gamma;
     const uint8_t* type_mask;
     BoxDev box;
-    double dt;
-    double kT;
-    uint64_t timestep;
+    LangevinScalars s;
     double p0, p1, p2;
-    uint32_t seed;
-    uint32_t noiseless;
     uint32_t N;
     uint32_t ntypes;
     };
@@ -47,62 +36,6 @@ template<int KIND> __device__ __forceinline__ double3 flow_velocity(const FlowKA
     return make_double3(a.p0 * (1. - yr * yr), 0.0, 0.0);
     }
 
-// the three uniform(-c, c) draws of one particle (UniformDistribution: a + (b - a) u01)
-__device__ __forceinline__ double3 uniform3(uint32_t id, uint32_t seed, uint32_t tag, uint64_t t, double c)
-    {
-    const uint32_t k0 = philox_key0(id, t, seed), k1 = (uint32_t)t;
-    double r[3];
-#pragma unroll
-    for (uint32_t k = 0; k < 3; ++k)
-        r[k] = -c + 2.0 * c * philox_u01(k0, k1, k, tag, 0, 0);
-    return make_double3(r[0], r[1], r[2]);
-    }
-
-// the type of row idx if this method integrates it, else -1
-__device__ __forceinline__ int selected_type(const FlowKArgs& a, double w)
-    {
-    const int type = type_from_w(w);
-    if ((uint32_t)type >= a.ntypes)
-        return -1;
-    if (a.type_mask && !a.type_mask[type])
-        return -1;
-    return type;
-    }
-
-// Langevin step two at position p (src/TwoStepLangevinFlow.h:193-245): returns the new acceleration, updates v
-template<int KIND>
-__device__ __forceinline__ double3 langevin_step_two(const FlowKArgs& a, uint32_t idx, const double4& p, int type, double4& v)
-    {
-    const double gamma = a.gamma[type];                                // :199-207
-    const double3 u = flow_velocity<KIND>(a, p.x, p.y, p.z);         // :210
-    double coeff = sqrt(6.0 * gamma * a.kT / a.dt);                   // :213
-    if (a.noiseless)                                                   // :214-215
-        coeff = 0.0;
-    const double3 R = uniform3(RNG_LANGEVIN_FLOW, a.seed, a.tag[idx], a.timestep, coeff); // :216-221
-    const double bx = R.x - gamma * (v.x - u.x);                       // :228
-    const double by = R.y - gamma * (v.y - u.y);
-    const double bz = R.z - gamma * (v.z - u.z);
-    const double4 f = load_scalar4(a.net_force, idx);                  // :231-232
-    const double minv = 1.0 / v.w;                                     // :234
-    const double ax = (f.x + bx) * minv, ay = (f.y + by) * minv, az = (f.z + bz) * minv; // :233-237
-    const double hdt = 0.5 * a.dt;                                     // :240
-    v.x += hdt * ax; v.y += hdt * ay; v.z += hdt * az;
-    return make_double3(ax, ay, az);
-    }
-
-// Langevin step one (src/TwoStepLangevinFlow.h:143-150): x += (v + a dt/2) dt, wrap, v += a dt/2
-__device__ __forceinline__ void langevin_step_one(const FlowKArgs& a, uint32_t idx, const double4& p, double4& v,
-                                                  const double3& acc)
-    {
-    const double hdt = 0.5 * a.dt;
-    double x = p.x + (v.x + hdt * acc.x) * a.dt;                       // :145
-    double y = p.y + (v.y + hdt * acc.y) * a.dt;
-    double z = p.z + (v.z + hdt * acc.z) * a.dt;
-    wrap_with_image(a.box, x, y, z, a.image, idx);                     // :146
-    v.x += hdt * acc.x; v.y += hdt * acc.y; v.z += hdt * acc.z;        // :149
-    store_scalar4(a.pos, idx, x, y, z, p.w);
-    }
-
 // MODE 0: step two. 1: step one. 2: step two of one time step, then step one of the next, in one pass (the
 // acceleration of step two stays in registers; same functions, same operation order: bit-identical to 0 then 1).
 template<int MODE, int KIND> __global__ void __launch_bounds__(256) langevin_flow_kernel(const FlowKArgs a)
@@ -111,14 +44,15 @@ template<int MODE, int KIND> __global__ void __launch_bounds__(256) langevin_flo
     if (idx >= a.N)
         return;
     const double4 p = load_scalar4(a.pos, idx);
-    const int type = selected_type(a, p.w);
+    const int type = selected_type(p.w, a.ntypes, a.type_mask);
     if (type < 0)
         return;
     double4 v = load_scalar4(a.vel, idx);
     double3 acc;
     if (MODE != 1)
         {
-        acc = langevin_step_two<KIND>(a, idx, p, type, v);
+        acc = langevin_step_two(a.s, a.gamma[type], flow_velocity<KIND>(a, p.x, p.y, p.z), a.tag[idx],
+                                load_scalar4(a.net_force, idx), v);
         store_scalar4(a.accel, idx, acc.x, acc.y, acc.z, 0.0);         // :244
         }
     else
@@ -127,7 +61,7 @@ template<int MODE, int KIND> __global__ void __launch_bounds__(256) langevin_flo
         acc = make_double3(a4.x, a4.y, a4.z);
         }
     if (MODE != 0)
-        langevin_step_one(a, idx, p, v, acc);
+        langevin_step_one(a.box, a.s.dt, a.pos, a.image, idx, p, v, acc);
     store_scalar4(a.vel, idx, v.x, v.y, v.z, v.w);
     }
 
@@ -138,21 +72,11 @@ template<int KIND> __global__ void __launch_bounds__(256) brownian_flow_kernel(c
     if (idx >= a.N)
         return;
     const double4 p = load_scalar4(a.pos, idx);
-    const int type = selected_type(a, p.w);
+    const int type = selected_type(p.w, a.ntypes, a.type_mask);
     if (type < 0)
         return;
-    const double gamma = a.gamma[type];                                // :143-150
-    const double3 u = flow_velocity<KIND>(a, p.x, p.y, p.z);         // :153
-    double coeff = sqrt(6.0 * gamma * a.kT / a.dt);                   // :156
-    if (a.noiseless)                                                   // :157-158
-        coeff = 0.0;
-    const double3 R = uniform3(RNG_BROWNIAN_FLOW, a.seed, a.tag[idx], a.timestep, coeff); // :161-166
-    const double4 f = load_scalar4(a.net_force, idx);                  // :169-170
-    double x = p.x + (u.x + (f.x + R.x) / gamma) * a.dt;               // :173
-    double y = p.y + (u.y + (f.y + R.y) / gamma) * a.dt;
-    double z = p.z + (u.z + (f.z + R.z) / gamma) * a.dt;
-    wrap_with_image(a.box, x, y, z, a.image, idx);                     // :174
-    store_scalar4(a.pos, idx, x, y, z, p.w);
+    brownian_step(a.s, a.box, a.gamma[type], flow_velocity<KIND>(a, p.x, p.y, p.z), a.tag[idx], load_scalar4(a.net_force, idx),
+                  a.pos, a.image, idx, p);
     }
 
 enum { LANGEVIN_TWO = 0, LANGEVIN_ONE = 1, LANGEVIN_TWO_ONE = 2, BROWNIAN = 3 };
@@ -198,12 +122,12 @@ static int launch_flow(int which, const azp_flow_method_args* args, void* stream
     k.gamma = args->d_gamma;
     k.type_mask = args->d_type_mask;
     k.box = make_box_dev(args->box);
-    k.dt = args->dt;
-    k.kT = args->kT;
-    k.timestep = args->timestep;
+    k.s.dt = args->dt;
+    k.s.kT = args->kT;
+    k.s.timestep = args->timestep;
     k.p0 = args->flow.p[0]; k.p1 = args->flow.p[1]; k.p2 = args->flow.p[2];
-    k.seed = args->seed & 0xffffu;
-    k.noiseless = args->noiseless;
+    k.s.seed = args->seed & 0xffffu;
+    k.s.noiseless = args->noiseless;
     k.N = args->N;
     k.ntypes = args->ntypes;
     const uint32_t grid = (args->N + bs - 1) / bs;

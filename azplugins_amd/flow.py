@@ -5,20 +5,8 @@ integration methods that consume them, ``Langevin`` (``TwoStepLangevinFlow``) an
 The fields are plain parameter holders (they pickle); ``_cpp()`` gives the ``_azplugins`` object with the
 reference's constructor and properties, which also evaluates the field on the host."""
 
-import math
-
-import numpy as np
-
 from . import _lib
-from .filter import All, Type
-from .methods import _launch
-
-
-def _finite(x, what):
-    x = float(x)
-    if not math.isfinite(x):
-        raise _lib.AzpError("%s must be finite, got %r" % (what, x))
-    return x
+from .methods import _finite, _launch, _StochasticMethod
 
 
 class FlowField:
@@ -110,75 +98,20 @@ class ParabolicFlow(FlowField):
         return "ParabolicFlow(mean_velocity=%r, separation=%r)" % (self._mean_velocity, self._separation)
 
 
-class _Gamma:
-    """Per-type friction coefficients: ``method.gamma["A"] = 2.0``; types never set take the default."""
-
-    def __init__(self, default, check):
-        self._check = check
-        self._values = {}
-        self.default = check(default)
-
-    def __setitem__(self, types, value):
-        value = self._check(value)
-        for t in ([types] if isinstance(types, str) else list(types)):
-            self._values[t] = value
-
-    def __getitem__(self, t):
-        return self._values.get(t, self.default)
-
-    def table(self, type_names):
-        return np.array([self[t] for t in type_names], dtype=np.float64)
-
-
-class _FlowMethod:
-    _name = None
-
+class _FlowMethod(_StochasticMethod):
     def __init__(self, filter, kT, flow_field, default_gamma=1.0, noiseless=False):
-        if not isinstance(filter, (All, Type)):
-            raise _lib.AzpError("%s: filter must be All() or Type(...), got %r" % (self._name, filter))
         if not isinstance(flow_field, FlowField):
             raise _lib.AzpError("%s: flow_field must be a ConstantFlow or a ParabolicFlow, got %r" % (self._name, flow_field))
-        if not callable(kT):
-            kT = _finite(kT, "%s kT" % self._name)
-            if kT < 0.0:
-                raise _lib.AzpError("%s: kT must be >= 0, got %r" % (self._name, kT))
-        self.filter = filter
-        self.kT = kT
+        super().__init__(filter, kT, default_gamma)
         self.flow_field = flow_field
-        self.gamma = _Gamma(default_gamma, self._check_gamma)
         self.noiseless = bool(noiseless)
-        self._tables = None
-
-    def _check_gamma(self, g):
-        raise NotImplementedError
-
-    def _kT(self, timestep):
-        """kT at ``timestep``, evaluated on the host (passed to the kernel by value)."""
-        return float(self.kT(timestep)) if callable(self.kT) else float(self.kT)
 
     # -- the stepper (DESIGN 4.20) -----------------------------------------------
-    _fusable = True
-    # a method filtered by type reads the types when its kernel runs: where an updater is due, step two of the previous
-    # step runs on its own ahead of the updater, as in HOOMD (the fused kernel is bit-identical to the two halves)
-    _updaters_split = True
-
     def _begin(self, sim):
-        """The seed warning; the accelerations of a first run; the gamma table and the type mask on the device; the
-        argument struct of this run."""
-        import torch
-
+        """The seed warning, the accelerations of a first run and the device tables (``_begin_tables``); the argument
+        struct of this run."""
         st = sim.state
-        sim._warn_if_seed_unset()
-        if self._uses_accel and (st.accel is None or st.accel.shape[0] != st.n_max):
-            # HOOMD computeAccelerations (prepRun): a = F_net / m on the first run of an integrator that needs it
-            st.accel = torch.zeros((st.n_max, 4), dtype=torch.float64, device=st.device)
-            st.accel[: st.N, :3] = st.net_force[: st.N, :3] / st.vel[: st.N, 3:4]
-        key = (tuple(st.types), tuple(self.gamma.table(st.types)), self.filter)
-        if self._tables is None or self._tables[0] != key:
-            g = torch.from_numpy(self.gamma.table(st.types)).to(st.device)
-            m = None if isinstance(self.filter, All) else torch.from_numpy(self.filter.mask(st.types)).to(st.device)
-            self._tables = (key, g, m)
-        _, g, m = self._tables
+        (g,), m = self._begin_tables(sim)
         a = _lib.FlowMethodArgs()
         a.d_gamma = g.data_ptr()
         a.d_type_mask = m.data_ptr() if m is not None else None
@@ -189,13 +122,6 @@ class _FlowMethod:
         a.flow = self.flow_field._c()
         self._args = a
         self._stream = _lib.raw_stream(st.device)
-
-    def _at(self, timestep):
-        """The argument struct at ``timestep`` (random numbers and kT)."""
-        a = self._args
-        a.timestep = int(timestep)
-        a.kT = self._kT(timestep)
-        return a
 
 
 class Langevin(_FlowMethod):

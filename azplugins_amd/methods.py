@@ -1,14 +1,18 @@
 """Integration methods under the names of ``hoomd.md.methods``: ``ConstantVolume`` (velocity Verlet; with one of
-``azplugins_amd.thermostats`` NVT) and ``ConstantPressure`` (a Martyna-Tobias-Klein barostat), and what every stepper's
+``azplugins_amd.thermostats`` NVT), ``ConstantPressure`` (a Martyna-Tobias-Klein barostat), ``Langevin`` and ``Brownian``
+(translation and rotation, ``DESIGN.md`` 4.25), and what every stepper's
 host side shares (``DESIGN.md`` 4.20): the launch helper ``_launch``, the owner of a device-resident control state
-``_ControlState``, the partials buffer of the controlled-Verlet schemes, and the refusals of the methods that move every
-particle. ``Simulation.run`` (``simulation.py``) drives them; ``thermostats``, ``minimize`` and ``flow`` build on them."""
+``_ControlState``, the partials buffer of the controlled-Verlet schemes, the refusals of the methods that move every
+particle, and the base of the Langevin / Brownian family ``_StochasticMethod``. ``Simulation.run`` (``simulation.py``)
+drives them; ``thermostats``, ``minimize`` and ``flow`` build on them."""
 
 import ctypes as C
 import math
 
+import numpy as np
+
 from . import _lib
-from .filter import All
+from .filter import All, Type
 
 
 def _launch(a, st, stream, *names):
@@ -31,6 +35,25 @@ def _launch(a, st, stream, *names):
     lib = _lib.lib()
     for name in names:
         _lib.check(getattr(lib, name)(C.byref(a), stream), name)
+
+
+def _net_torque(sim):
+    """The net torque on the particles of ``sim``: the sum of the forces' ``torque_tensor`` (without forces a zero tensor,
+    made once per state size); the caller keeps it until its kernel is queued."""
+    st, forces = sim.state, sim.operations.integrator.forces
+    if not forces:
+        zero = getattr(st, "_zero_torque", None)
+        if zero is None or zero.shape[0] != st.N:
+            import torch
+
+            zero = st._zero_torque = torch.zeros((st.N, 4), dtype=torch.float64, device=st.device)
+        return zero
+    torque = forces[0].torque_tensor
+    if len(forces) > 1:
+        torque = torque.clone()
+        for f in forces[1:]:
+            torque += f.torque_tensor
+    return torque
 
 
 class _ControlState:
@@ -181,12 +204,8 @@ class ConstantVolume(_HoldsThermostat):
             self._rot.dt = integ.dt
 
     def _rotational_step(self, sim, one):
-        st, rot, forces = sim.state, self._rot, sim.operations.integrator.forces
-        torque = forces[0].torque_tensor  # the net torque, kept alive until the kernel is queued
-        if len(forces) > 1:
-            torque = torque.clone()
-            for f in forces[1:]:
-                torque += f.torque_tensor
+        st, rot = sim.state, self._rot
+        torque = _net_torque(sim)  # (kept alive until the kernel is queued)
         rot.d_orientation = st.orientation.data_ptr()
         rot.d_angmom = st.angmom.data_ptr()
         rot.d_inertia = st.inertia.data_ptr()
@@ -417,3 +436,215 @@ class ConstantPressure(_HoldsThermostat, _DeviceControlled):
 
     def __repr__(self):
         return "ConstantPressure(S=%r, tauS=%r, couple=%r, thermostat=%r)" % (self._S, self.tauS, self.couple, self._thermostat)
+
+
+# ---------------------------------------------------------------------------
+# the Langevin / Brownian family: flow.Langevin, flow.Brownian, Langevin, Brownian
+# ---------------------------------------------------------------------------
+def _finite(x, what):
+    x = float(x)
+    if not math.isfinite(x):
+        raise _lib.AzpError("%s must be finite, got %r" % (what, x))
+    return x
+
+
+class _Gamma:
+    """Per-type friction coefficients: ``method.gamma["A"] = 2.0``; types never set take the default. ``check`` validates
+    a value and gives what is stored: a float (``gamma``) or a tuple of three (``gamma_r``, one per body axis)."""
+
+    def __init__(self, default, check):
+        self._check = check
+        self._values = {}
+        self.default = check(default)
+
+    def __setitem__(self, types, value):
+        value = self._check(value)
+        for t in ([types] if isinstance(types, str) else list(types)):
+            self._values[t] = value
+
+    def __getitem__(self, t):
+        return self._values.get(t, self.default)
+
+    def table(self, type_names):
+        """One row per type of ``type_names``: shape (ntypes,) or (ntypes, 3)."""
+        return np.array([self[t] for t in type_names], dtype=np.float64)
+
+
+class _StochasticMethod:
+    """What the Langevin and Brownian methods share, with a flow field (``flow``) or with rotation (below): a filter
+    ``All()`` or ``Type(...)``, ``kT`` evaluated on the host per step, per-type ``gamma``, and the stepper interface of
+    DESIGN 4.20. Several of them may sit in ``Integrator.methods`` with pairwise-disjoint filters
+    (``Simulation._check_flow_methods``)."""
+
+    _name = None
+    _uses_accel = False  # a Langevin method: step two stores what the next step one reads (State.accel, langevin_torque)
+    _fusable = True
+    # a method filtered by type reads the types when its kernel runs: where an updater is due, step two of the previous
+    # step runs on its own ahead of the updater, as in HOOMD (the fused kernel is bit-identical to the two halves)
+    _updaters_split = True
+
+    def __init__(self, filter, kT, default_gamma):
+        if not isinstance(filter, (All, Type)):
+            raise _lib.AzpError("%s: filter must be All() or Type(...), got %r" % (self._name, filter))
+        if not callable(kT):
+            kT = _finite(kT, "%s kT" % self._name)
+            if kT < 0.0:
+                raise _lib.AzpError("%s: kT must be >= 0, got %r" % (self._name, kT))
+        self.filter = filter
+        self.kT = kT
+        self.gamma = _Gamma(default_gamma, self._check_gamma)
+        self._tables = None
+
+    def _check_gamma(self, g):
+        raise NotImplementedError
+
+    def _kT(self, timestep):
+        """kT at ``timestep``, evaluated on the host (passed to the kernel by value)."""
+        return float(self.kT(timestep)) if callable(self.kT) else float(self.kT)
+
+    def _gamma_tables(self, types):
+        """The per-type tables the kernel reads, as numpy arrays in the order of its pointers."""
+        return (self.gamma.table(types),)
+
+    def _begin_tables(self, sim):
+        """The seed warning; the accelerations of a first run; the gamma tables and the type mask on the device (made
+        again when the types, a gamma or the filter changed). Returns (tables, mask or None)."""
+        import torch
+
+        st = sim.state
+        sim._warn_if_seed_unset()
+        if self._uses_accel and (st.accel is None or st.accel.shape[0] != st.n_max):
+            # HOOMD computeAccelerations (prepRun): a = F_net / m on the first run of an integrator that needs it
+            st.accel = torch.zeros((st.n_max, 4), dtype=torch.float64, device=st.device)
+            st.accel[: st.N, :3] = st.net_force[: st.N, :3] / st.vel[: st.N, 3:4]
+        tables = self._gamma_tables(st.types)
+        key = (tuple(st.types), tuple(t.tobytes() for t in tables), self.filter)
+        if self._tables is None or self._tables[0] != key:
+            g = tuple(torch.from_numpy(t).to(st.device) for t in tables)
+            m = None if isinstance(self.filter, All) else torch.from_numpy(self.filter.mask(st.types)).to(st.device)
+            self._tables = (key, g, m)
+        return self._tables[1:]
+
+    def _at(self, timestep):
+        """The argument struct at ``timestep`` (random numbers and kT)."""
+        a = self._args
+        a.timestep = int(timestep)
+        a.kT = self._kT(timestep)
+        return a
+
+
+class _RotationalMethod(_StochasticMethod):
+    """``Langevin`` and ``Brownian`` under the names of ``hoomd.md.methods``: translation as the flow methods at zero flow
+    (bit for bit), and the rotation of particles with a moment of inertia where ``Integrator.integrate_rotational_dof`` is
+    set (else the rotational arrays are not read). HOOMD-blue's source is not available to this project: the scheme is
+    defined in ``include/azp.h`` and ``DESIGN.md`` 4.25 and runs in libazp (``csrc/langevin.hip``), one thread moving and
+    rotating its particle in one pass."""
+
+    def __init__(self, filter, kT, default_gamma=1.0, default_gamma_r=(1.0, 1.0, 1.0)):
+        super().__init__(filter, kT, default_gamma)
+        self.gamma_r = _Gamma(default_gamma_r, self._check_gamma_r)
+
+    def _check_gamma_r(self, g):
+        try:
+            g = tuple(g)
+        except TypeError:
+            g = ()
+        if len(g) != 3:
+            raise _lib.AzpError("%s: gamma_r takes three values, one per body axis, got %r" % (self._name, g))
+        return tuple(self._check_gamma(x) for x in g)
+
+    def _gamma_tables(self, types):
+        return (self.gamma.table(types), self.gamma_r.table(types).reshape(len(types), 3))
+
+    def _begin(self, sim):
+        """The argument struct of this run; with rotation, the Langevin torques of a first run (zeros)."""
+        import torch
+
+        st, integ = sim.state, sim.operations.integrator
+        (g, g_r), m = self._begin_tables(sim)
+        a = self._args = _lib.LangevinArgs()
+        a.d_gamma = g.data_ptr()
+        a.d_gamma_r = g_r.data_ptr()
+        a.d_type_mask = m.data_ptr() if m is not None else None
+        a.dt = integ.dt
+        a.seed = int(sim.seed) & 0xFFFF
+        a.ntypes = len(st.types)
+        a.rotational = int(bool(integ.integrate_rotational_dof))
+        if a.rotational and self._uses_accel and (st.langevin_torque is None or st.langevin_torque.shape[0] != st.n_max):
+            st.langevin_torque = torch.zeros((st.n_max, 4), dtype=torch.float64, device=st.device)
+        self._stream = _lib.raw_stream(st.device)
+
+    def _queue(self, sim, timestep, name):
+        """Queue entry ``name`` with the random numbers and kT of ``timestep``, pointed at the arrays of this moment."""
+        a, st = self._at(timestep), sim.state
+        torque = None
+        if a.rotational:
+            torque = _net_torque(sim)  # (kept alive until the kernel is queued)
+            a.d_orientation = st.orientation.data_ptr()
+            a.d_angmom = st.angmom.data_ptr()
+            a.d_inertia = st.inertia.data_ptr()
+            a.d_net_torque = torque.data_ptr()
+            a.d_langevin_torque = st.langevin_torque.data_ptr() if self._uses_accel else None
+        _launch(a, st, self._stream, name)
+
+
+class Langevin(_RotationalMethod):
+    """``hoomd.md.methods.Langevin``: velocity Verlet with the friction -gamma v and a uniform random force of variance
+    2 gamma kT / dt per component in the acceleration (``flow.Langevin`` at zero flow), and for the rotation the NO_SQUISH
+    step of ``ConstantVolume`` with the body-frame Langevin torque b_k = R_k - gamma_r,k S_k / I_k, var(R_k) =
+    2 gamma_r,k kT / dt, computed in step two and used again by the next step one (``State.langevin_torque``).
+
+    ``kT``: a float >= 0 or a callable of the timestep; 0 is the noiseless run. ``gamma[type]`` >= 0,
+    ``gamma_r[type]`` three values >= 0. ``tally_reservoir_energy=True`` is refused: it would need a reduction every
+    step. Does not run decomposed."""
+
+    _name = "methods.Langevin"
+    _uses_accel = True
+
+    def __init__(self, filter, kT, tally_reservoir_energy=False, default_gamma=1.0, default_gamma_r=(1.0, 1.0, 1.0)):
+        if tally_reservoir_energy:
+            raise _lib.AzpError("methods.Langevin: tally_reservoir_energy=True is not supported (the reservoir energy would "
+                                "need a reduction over all particles every step)")
+        self.tally_reservoir_energy = False
+        super().__init__(filter, kT, default_gamma, default_gamma_r)
+
+    def _check_gamma(self, g):
+        g = _finite(g, "methods.Langevin gamma")
+        if g < 0.0:
+            raise _lib.AzpError("methods.Langevin: gamma and gamma_r must be >= 0, got %r" % (g,))
+        return g
+
+    def _step_one(self, sim, timestep, fused):
+        """Step one of the step starting at ``timestep`` (fused: preceded by step two of the previous step, whose
+        random numbers and kT belong to ``timestep - 1``; step one itself draws nothing)."""
+        if fused:
+            self._queue(sim, timestep - 1, "azp_integrate_langevin_step_two_one")
+        else:
+            self._queue(sim, timestep, "azp_integrate_langevin_step_one")
+
+    def _step_two(self, sim, timestep):
+        self._queue(sim, timestep, "azp_integrate_langevin_step_two")
+
+
+class Brownian(_RotationalMethod):
+    """``hoomd.md.methods.Brownian``: x += (F + R) dt / gamma (``flow.Brownian`` at zero flow), and for the rotation the
+    body-frame rotation vector dtheta_k = (torque_k + R_k) dt / gamma_r,k applied through the exponential map; velocities
+    and angular momenta are not touched.
+
+    ``kT``: a float >= 0 or a callable of the timestep; 0 is the noiseless run. ``gamma[type]`` > 0, ``gamma_r[type]``
+    three values > 0 (the step divides by them). Does not run decomposed."""
+
+    _name = "methods.Brownian"
+
+    def _check_gamma(self, g):
+        g = _finite(g, "methods.Brownian gamma")
+        if not g > 0.0:
+            raise _lib.AzpError("methods.Brownian: gamma and gamma_r must be > 0 (the step divides by them), got %r" % (g,))
+        return g
+
+    def _step_one(self, sim, timestep, fused):
+        """The whole step starting at ``timestep``."""
+        self._queue(sim, timestep, "azp_integrate_brownian_step")
+
+    def _step_two(self, sim, timestep):
+        pass  # Brownian dynamics has no second half

@@ -3,7 +3,7 @@ and ``hoomd.md.Integrator``, reduced to what this project runs. ``Simulation.run
 evaluates them (``run(0)``) and steps: one loop for every integration path (``DESIGN.md`` 4.20), around whatever moves
 the particles -- ``methods.ConstantVolume`` (NVE, the dummy integrator of the reference's tests,
 src/pytest/test_pair.py:325-327) or its thermostat (``thermostats``), ``methods.ConstantPressure``, ``minimize.FIRE``,
-the flow methods (``flow``) -- with the updaters ahead of each step, the writers after it, the particle sorter and a
+the Langevin / Brownian methods (``methods``, ``flow``) -- with the updaters ahead of each step, the writers after it, the particle sorter and a
 domain's halo exchange between the position update and the forces. The methods, the filters and the trigger live in
 ``methods``, ``filter`` and ``trigger``; their names are re-exported here.
 """
@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .filter import All, Type  # noqa: F401 (re-exported, as the names below)
-from .methods import ConstantPressure, ConstantVolume, _check_moves_all, _launch  # noqa: F401
+from .methods import Brownian, ConstantPressure, ConstantVolume, Langevin, _check_moves_all, _launch  # noqa: F401
 from .state import State
 from .trigger import Periodic  # noqa: F401
 
@@ -24,8 +24,9 @@ class Integrator:
     """``hoomd.md.Integrator`` reduced: ``dt``, ``forces``, ``methods``,
     ``integrate_rotational_dof`` (orientations and angular momenta of particles with a
     non-zero moment of inertia are integrated with the net torque, HOOMD's default False).
-    ``methods`` holds one ``ConstantVolume``, one ``ConstantPressure``, or one or more ``flow.Langevin`` /
-    ``flow.Brownian`` with pairwise-disjoint filters (an ``All()`` filter stands alone)."""
+    ``methods`` holds one ``ConstantVolume``, one ``ConstantPressure``, or one or more of ``methods.Langevin``,
+    ``methods.Brownian``, ``flow.Langevin`` and ``flow.Brownian`` with pairwise-disjoint filters (an ``All()`` filter
+    stands alone)."""
 
     def __init__(self, dt, forces=None, methods=None, integrate_rotational_dof=False):
         self.dt = float(dt)
@@ -398,34 +399,38 @@ class Simulation:
                     nl.particles_sorted()
 
     def _check_flow_methods(self, integ):
-        """The flow methods of ``integ`` (empty if it has none), after checking that they can run together."""
+        """The Langevin / Brownian methods of ``integ`` (``flow.*`` and ``methods.Langevin`` / ``methods.Brownian``: one
+        family; empty if it has none), after checking that they can run together."""
         from .flow import _FlowMethod
+        from .methods import _StochasticMethod
 
-        flow_methods = [m for m in integ.methods if isinstance(m, _FlowMethod)]
-        if not flow_methods:
-            return flow_methods
-        if len(flow_methods) != len(integ.methods):
-            raise _lib.AzpError("Integrator.methods: flow.Langevin / flow.Brownian cannot be mixed with other methods, got %r"
-                                % (integ.methods,))
-        if integ.integrate_rotational_dof:
+        family = [m for m in integ.methods if isinstance(m, _StochasticMethod)]
+        if not family:
+            return family
+        if len(family) != len(integ.methods):
+            raise _lib.AzpError("Integrator.methods: Langevin / Brownian methods (flow.* and methods.*) cannot be mixed with "
+                                "other methods, got %r" % (integ.methods,))
+        if integ.integrate_rotational_dof and any(isinstance(m, _FlowMethod) for m in family):
             raise _lib.AzpError("flow.Langevin / flow.Brownian do not integrate rotational degrees of freedom "
-                                "(integrate_rotational_dof=True)")
+                                "(integrate_rotational_dof=True); methods.Langevin / methods.Brownian do")
         if self.domain is not None:
-            raise _lib.AzpError("flow.Langevin / flow.Brownian do not run decomposed (their accelerations do not migrate)")
-        if any(any(m is o for o in flow_methods[:k]) for k, m in enumerate(flow_methods)):
-            raise _lib.AzpError("Integrator.methods holds the same flow method twice")
-        if len(flow_methods) > 1 and any(isinstance(m.filter, All) for m in flow_methods):
-            raise _lib.AzpError("Integrator.methods: a flow method with filter All() must be the only method")
+            raise _lib.AzpError("Langevin / Brownian methods do not run decomposed (their stored accelerations and torques do "
+                                "not migrate)")
+        if any(any(m is o for o in family[:k]) for k, m in enumerate(family)):
+            raise _lib.AzpError("Integrator.methods holds the same Langevin / Brownian method twice")
+        if len(family) > 1 and any(isinstance(m.filter, All) for m in family):
+            raise _lib.AzpError("Integrator.methods: a Langevin / Brownian method with filter All() must be the only method")
         seen = set()
-        for m in flow_methods:
+        for m in family:
             if isinstance(m.filter, All):
                 continue
             m.filter.mask(self.state.types)  # (rejects type names the state does not have)
             overlap = seen & set(m.filter.types)
             if overlap:
-                raise _lib.AzpError("Integrator.methods: the filters of the flow methods overlap (types %s)" % sorted(overlap))
+                raise _lib.AzpError("Integrator.methods: the filters of the Langevin / Brownian methods overlap (types %s)"
+                                    % sorted(overlap))
             seen |= set(m.filter.types)
-        return flow_methods
+        return family
 
     def kinetic_temperature(self):
         """Instantaneous kT = 2 KE / (3 N - 3) (HOOMD ThermodynamicQuantities)."""

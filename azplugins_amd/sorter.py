@@ -60,8 +60,8 @@ class ParticleSorter:
         N = st.N
         order = torch.sort(self.keys(st), stable=True).indices
         names = ("pos", "vel", "orientation", "tag", "image", "angmom", "inertia")
-        if st.accel is not None:
-            names += ("accel",)  # (a Langevin step one reads the acceleration of the previous step two)
+        # (a Langevin step one reads the acceleration and the Langevin torque of the previous step two)
+        names += tuple(n for n in ("accel", "langevin_torque") if getattr(st, n) is not None)
         for name in names:
             a = getattr(st, name)
             a[:N] = a[:N].index_select(0, order)

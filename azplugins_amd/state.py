@@ -8,7 +8,8 @@ objects the reference's force classes are attached to (``hoomd.Snapshot``,
 * ``orientation`` (n_max, 4) float64 quaternion, scalar part first
 * ``tag``   (n_max,) uint32 (stored as int32 bit pattern)
 * ``angmom`` (n_max, 4) float64 angular-momentum quaternion, ``inertia`` (n_max, 3) principal moments
-* ``accel`` (n_max, 4) float64 ax, ay, az, 0: ``None`` until a ``flow.Langevin`` run creates it
+* ``accel`` (n_max, 4) float64 ax, ay, az, 0: ``None`` until a ``flow.Langevin`` or ``methods.Langevin`` run creates it
+* ``langevin_torque`` (n_max, 4) float64 body-frame bx, by, bz, 0: ``None`` until a ``methods.Langevin`` run with rotation creates it
 """
 
 import math
@@ -596,9 +597,12 @@ class State:
         self.inertia = torch.from_numpy(np.ascontiguousarray(p.moment_inertia, dtype=np.float64)).to(self.device)
         self.net_force = torch.zeros((self.N, 4), dtype=f64, device=self.device)
         self.image = torch.zeros((p.N, 3), dtype=torch.int32, device=self.device)
-        # (n_max, 4) accelerations of the flow.Langevin method (HOOMD ParticleData accelerations): created by its first
+        # (n_max, 4) accelerations of the Langevin methods (HOOMD ParticleData accelerations): created by their first
         # run as F_net / m, then carried from step two to the next step one
         self.accel = None
+        # (n_max, 4) body-frame Langevin torques b_x, b_y, b_z, 0 of methods.Langevin with rotation: created
+        # by its first run as zeros, then carried from step two to the next step one
+        self.langevin_torque = None
         # bonds, angles (members a, b, c with b the vertex) and dihedrals (members a, b, c, d): one GroupStore each,
         # also reachable as bond_group, n_bonds, bond_table(), set_global_bonds(), ... (the delegations below the class)
         # (special pairs under the kind "pair": pair_group, n_pairs, pair_table(), set_global_pairs(), ...)

@@ -887,6 +887,72 @@ int azp_integrate_langevin_flow_step_two(const azp_flow_method_args* args, void*
 int azp_integrate_langevin_flow_step_two_one(const azp_flow_method_args* args, void* stream);
 int azp_integrate_brownian_flow_step(const azp_flow_method_args* args, void* stream);
 
+/* ---- Langevin and Brownian dynamics with rotation (azplugins_amd.methods.Langevin / .Brownian) ----
+ * Names and parameters are hoomd.md.methods'; HOOMD-blue's source is not available to this project, so the scheme is
+ * DEFINED HERE and pinned by tests/langevin_ref.py. One thread per particle does its translation and,
+ * where `rotational` is set, its rotation in the same pass.
+ *
+ * Translation: exactly the flow methods above at u = 0 and noiseless = 0 (the same device functions, ids 202 / 201,
+ * draws k = 0, 1, 2), bit for bit.
+ *
+ * Rotation. q = d_orientation (scalar first), p = d_angmom, I = d_inertia (N x 3), tau = d_net_torque (N x 4, space
+ * frame); body(tau) = rotate(conj(q), tau); S = vec(1/2 conj(q) p) the body angular momentum; an axis k with I_k == 0
+ * is not integrated. g_k = d_gamma_r[3 type + k]; R_k = -c_k + 2 c_k u01 with c_k = sqrt(6 g_k kT / dt), draw k + 3 of
+ * the translation's key.
+ *   Langevin step two (q at t + dt, p at the half step, tau the new torque):
+ *     b_k = R_k - g_k S_k / I_k (0 where I_k == 0), stored in d_langevin_torque (N x 4: b_x, b_y, b_z, 0; body frame);
+ *     T = body(tau) + b with the components of axes without inertia zeroed; p += dt q (0, T) -- the half kick of
+ *     azp_integrate_nve_rot_step_two.
+ *   Langevin step one: T = body(tau) + b as stored by the previous step two (zeros before the first); p += dt q (0, T);
+ *     free rotations about axes 3, 2, 1, 2, 3; q renormalised -- as azp_integrate_nve_rot_step_one.
+ *   The Langevin torque of step two is used again by the next step one, as the Langevin force is in the acceleration:
+ *   for a planar rotor without torque the full-step variance of S_z is then exactly kT I_z. With every
+ *   g_k = 0 the rotational half is the NVE one bit for bit.
+ *   Brownian step (id 201, draws 3..5), on the axes with I_k != 0:
+ *     dtheta_k = (body(tau)_k + R_k) dt / g_k (0 where I_k == 0); with |dtheta| > 0
+ *     q <- normalize(q (cos(|dtheta| / 2), sin(|dtheta| / 2) dtheta / |dtheta|)), the exponential map in the body frame;
+ *     with |dtheta| == 0 q is left as it is. p is not read or written, as the velocities are not.
+ * Rows are selected as by the flow methods (type < ntypes, d_type_mask); a row that is not selected keeps every bit.
+ * `timestep`, `kT`: of the step that step two (the Brownian step) belongs to; step one draws nothing.
+ * N == 0 returns success. AZP_ERROR_INVALID_ARGUMENT: a null pointer that the call needs (d_pos always; d_net_force,
+ * d_tag, d_gamma where a step two or a Brownian step runs; d_vel, d_accel for Langevin; with `rotational` d_orientation,
+ * d_inertia, d_net_torque, for Langevin d_angmom and d_langevin_torque too, and d_gamma_r where draws are made),
+ * ntypes == 0, dt <= 0, a block size other than 0 (256), 64, 128, 192, 256. */
+typedef struct azp_langevin_args
+    {
+    double* d_pos;              /* N x 4 (type in w is preserved) */
+    double* d_vel;              /* N x 4 (vx, vy, vz, mass); Langevin only */
+    double* d_accel;            /* N x 4 (ax, ay, az, 0); Langevin only */
+    const double* d_net_force;  /* N x 4 */
+    int32_t* d_image;           /* N x 3 periodic image counters, may be NULL */
+    const uint32_t* d_tag;      /* N */
+    const double* d_gamma;      /* ntypes friction coefficients */
+    const uint8_t* d_type_mask; /* ntypes bytes, may be NULL (every type) */
+    double* d_orientation;      /* N x 4 */
+    double* d_angmom;           /* N x 4; Langevin only */
+    const double* d_inertia;    /* N x 3 */
+    const double* d_net_torque; /* N x 4 */
+    double* d_langevin_torque;  /* N x 4 (b_x, b_y, b_z, 0), body frame; Langevin only */
+    const double* d_gamma_r;    /* ntypes x 3 rotational friction coefficients */
+    azp_box box;
+    double dt;
+    double kT;                  /* kT at `timestep` */
+    uint64_t timestep;
+    uint32_t seed;              /* low 16 bits used */
+    uint32_t rotational;        /* 0: the rotational pointers are not read */
+    uint32_t N;
+    uint32_t ntypes;
+    uint32_t block_size;        /* 0: 256 */
+    uint32_t _pad;
+    } azp_langevin_args;
+
+int azp_integrate_langevin_step_one(const azp_langevin_args* args, void* stream);
+int azp_integrate_langevin_step_two(const azp_langevin_args* args, void* stream);
+/* Step two of one time step (at args->timestep) and step one of the next in one kernel, bit-identical to the two calls:
+ * q, p, I and the torque are read once. */
+int azp_integrate_langevin_step_two_one(const azp_langevin_args* args, void* stream);
+int azp_integrate_brownian_step(const azp_langevin_args* args, void* stream);
+
 /* ---- thermostats of the NVE step (azplugins_amd.thermostats: Berendsen, Bussi, MTTK) ----
  * Names and parameter keys are hoomd.md.methods.thermostats'; HOOMD-blue's source is not available to this project,
  * so the scheme is DEFINED HERE and pinned by tests/thermostat_ref.py.
