@@ -355,6 +355,30 @@ class RdfExclusionArgs(C.Structure):
     _fields_ = [("rdf", RdfArgs), ("d_n_excl", C.c_void_p), ("d_excl", C.c_void_p), ("excl_pitch", C.c_uint64)]
 
 
+BONDED_HISTOGRAM_LDS_WORDS = 16384
+BONDED_HISTOGRAM_PATH_AUTO, BONDED_HISTOGRAM_PATH_LDS, BONDED_HISTOGRAM_PATH_GLOBAL = 0, 1, 2
+
+
+class BondedHistogramArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("N", C.c_uint32),
+        ("n_max", C.c_uint32),
+        ("box", Box),
+        ("arity", C.c_uint32),
+        ("n_types", C.c_uint32),
+        ("d_table", C.c_void_p),
+        ("d_table_pos", C.c_void_p),
+        ("d_counts", C.c_void_p),
+        ("pitch", C.c_uint64),
+        ("num_bins", C.c_uint32),
+        ("path", C.c_uint32),
+        ("r_min", C.c_double),
+        ("r_max", C.c_double),
+        ("d_out", C.c_void_p),
+    ]
+
+
 FLOW_CONSTANT = 0
 FLOW_PARABOLIC = 1
 
@@ -651,6 +675,8 @@ SYMBOLS = {
     "azp_dihedral_opls_params_unpack": (None, [_VP] + [_PD] * 4),
     "azp_dihedral_forces_periodic": (C.c_int, [C.POINTER(DihedralArgs), _VP, _VP]),
     "azp_dihedral_forces_opls": (C.c_int, [C.POINTER(DihedralArgs), _VP, _VP]),
+    "azp_angle_forces_table": (C.c_int, [C.POINTER(AngleArgs), _VP, _VP]),
+    "azp_dihedral_forces_table": (C.c_int, [C.POINTER(DihedralArgs), _VP, _VP]),
     "azp_nlist_cell_assign": (C.c_int, [C.POINTER(NlistArgs), _VP]),
     "azp_nlist_cell_bounds": (C.c_int, [C.POINTER(NlistArgs), _VP]),
     "azp_nlist_bin": (C.c_int, [C.POINTER(NlistArgs), _VP, _VP, _VP]),
@@ -706,6 +732,7 @@ SYMBOLS = {
     "azp_rdf_scratch_size": (C.c_int, [C.POINTER(RdfArgs), C.POINTER(C.c_uint64)]),
     "azp_rdf_counts": (C.c_int, [C.POINTER(RdfArgs), _VP]),
     "azp_rdf_subtract_excluded": (C.c_int, [C.POINTER(RdfExclusionArgs), _VP]),
+    "azp_bonded_histogram": (C.c_int, [C.POINTER(BondedHistogramArgs), _VP]),
     "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
     "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
     "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),

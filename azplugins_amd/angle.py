@@ -1,4 +1,5 @@
-"""Angle potentials: harmonic and cosine-squared bending on libazp's gfx950 angle kernel (``csrc/angle_forces.hip``).
+"""Angle potentials: harmonic, cosine-squared and tabulated bending on libazp's gfx950 angle kernel
+(``csrc/angle_forces.hip``).
 
 The reference holds no angle code (with HOOMD-blue, bending stiffness comes from ``hoomd.md.angle`` next to the
 plugin), so the semantics are DEFINED HERE and in ``include/azp.h``: HOOMD's documented
@@ -9,14 +10,16 @@ An angle has members ``a, b, c`` with ``b`` the vertex (``Snapshot.angles.group`
 ``s = max(sqrt(1 - c^2), 1e-3)`` (HOOMD's floor):
 
 * ``Harmonic``: ``U = 1/2 k (theta - t0)^2`` with ``theta = acos(c)``, ``dU/dc = -k (theta - t0) / s``;
-* ``CosineSquared``: ``U = 1/2 k (c - cos t0)^2``, ``dU/dc = k (c - cos t0)``.
+* ``CosineSquared``: ``U = 1/2 k (c - cos t0)^2``, ``dU/dc = k (c - cos t0)``;
+* ``Table``: ``U`` and the torque ``tau = -dU/dtheta`` sampled at equal steps of ``theta = acos(c)`` over [0, pi] and
+  interpolated linearly, ``dU/dc = tau / s``.
 
 ``F_a = -dU/dc (dcb / (|dab||dcb|) - c dab / |dab|^2)``, ``F_c`` likewise with a and c exchanged, ``F_b = -F_a - F_c``.
 Every member gets a third of ``U`` and, with ``compute_virial``, a third of ``dab (x) F_a + dcb (x) F_c``. Coincident
 members (``|dab|`` or ``|dcb|`` equal to 0) are undefined. Angles add no neighbor-list exclusions by themselves:
 ``nlist.Cell(exclusions=("bond", "angle"))`` or ``"1-3"`` does.
 
-Out of scope: impropers, tabulated angles, an ``_azplugins`` class."""
+Out of scope: impropers, an ``_azplugins`` class."""
 
 import ctypes as C
 import math
@@ -24,8 +27,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .bonded import BondedForce
-from .force import TypeParameter
+from .bonded import BondedForce, BondedTable
+from .force import BondedTableTypeParameter, TypeParameter
 
 
 class _AngleParameter(TypeParameter):
@@ -82,4 +85,19 @@ class CosineSquared(Angle):
     _unpack_entry = "azp_angle_cossq_params_unpack"
 
 
-__all__ = ["Angle", "Harmonic", "CosineSquared"]
+class Table(BondedTable, Angle):
+    """Tabulated angle potential (``hoomd.md.angle.Table``'s name; the reference has none, the semantics are defined in
+    ``include/azp.h`` and DESIGN 4.26). ``params[type] = dict(U=array, tau=array)``: ``width = len(U) >= 2`` samples of
+    the energy and of the torque ``tau = -dU/dtheta`` at ``theta_k = k pi / (width - 1)``, both end points included,
+    interpolated linearly in between. ``width`` is per type. [0, pi] is the whole domain of ``theta``: no angle is out
+    of bounds. ``tau`` is what the user supplies, not a derivative of the interpolated ``U``: the energy is conserved
+    to the accuracy of the table, not to rounding."""
+
+    _entry = "azp_angle_forces_table"
+    _schema = dict(U=np.ndarray, tau=np.ndarray)
+    _parameter = BondedTableTypeParameter
+    _param_doubles = 4
+    _domain = (0.0, math.pi)
+
+
+__all__ = ["Angle", "Harmonic", "CosineSquared", "Table"]

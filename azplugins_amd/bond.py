@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .bonded import BondedForce
+from .bonded import BondedForce, table_param_rows
 from .force import TableTypeParameter
 
 
@@ -155,22 +155,10 @@ class Table(Bond):
         return None  # (params[...] hands back what was set: there is no C++ object that could hold anything else)
 
     def _rows(self, types, values):
-        import torch
-
-        packed = []
-        for t, d in zip(types, values):
-            rows = _lib.table_pack(d["r_min"], d["r_max"], d["U"], d["F"], closed=True)
-            if rows is None:
-                raise _lib.AzpError("%s.params[%r]: needs 0 <= r_min < r_max and at least 2 finite samples in U and F"
-                                    % (type(self).__name__, t))
-            packed.append(rows)
-        self._table_rows = torch.from_numpy(np.concatenate(packed + [np.zeros((1, 4))])).to(self._state.device)
-        assert self._table_rows.data_ptr() % 32 == 0
-        entries, first = [], 0
-        for d, rows in zip(values, packed):
-            entries.append((d["r_min"], d["r_max"], self._table_rows.data_ptr() + 32 * first, len(rows)))
-            first += len(rows)
-        return _lib.table_params_rows(entries)
+        self._table_rows, params = table_param_rows(type(self).__name__, self._state.device, types,
+                                                    [(d["r_min"], d["r_max"], d["U"], d["F"]) for d in values],
+                                                    "needs 0 <= r_min < r_max and at least 2 finite samples in U and F")
+        return params
 
 
 __all__ = ["DoubleWell", "Quartic", "Table"]

@@ -9,6 +9,45 @@ from . import _lib
 from .force import Force, TypeParameter
 
 
+def table_param_rows(who, device, types, tables, refused):
+    """The device side of a tabulated bonded potential (``bond.Table``, ``angle.Table``, ``dihedral.Table``), from one
+    ``(lo, hi, U, F)`` per type -- samples at both ends of ``[lo, hi]`` and at equal steps in between, ``lo >= 0``.
+    ``azp_table_pack(closed = 1)`` makes each type's rows; the rows of all types go into ONE device tensor (32-byte
+    aligned, one spare row at the end) and each type's ``azp_table_params`` points at its first row. Returns that
+    tensor, which the caller keeps alive, and the structs as float64 words (``len(types)`` x 4). ``refused``: what to
+    say of a table the library does not take."""
+    import torch
+
+    packed = []
+    for t, (lo, hi, U, F) in zip(types, tables):
+        rows = _lib.table_pack(lo, hi, U, F, closed=True)
+        if rows is None:
+            raise _lib.AzpError("%s.params[%r]: %s" % (who, t, refused))
+        packed.append(rows)
+    dev_rows = torch.from_numpy(np.concatenate(packed + [np.zeros((1, 4))])).to(device)
+    assert dev_rows.data_ptr() % 32 == 0
+    entries, first = [], 0
+    for (lo, hi, _, _), rows in zip(tables, packed):
+        entries.append((lo, hi, dev_rows.data_ptr() + 32 * first, len(rows)))
+        first += len(rows)
+    return dev_rows, _lib.table_params_rows(entries)
+
+
+class BondedTable:
+    """Mixin of ``angle.Table`` and ``dihedral.Table``: ``params[type] = dict(U=array, tau=array)`` over the whole
+    domain ``_domain`` of the angle (what the kernel's evaluator reads the table over, starting at 0), through
+    ``table_param_rows``. There is no ``_azplugins`` class behind it: ``params[...]`` hands back what was set."""
+
+    _domain = None  # (0, upper limit of the table coordinate)
+
+    def _rows(self, types, values):
+        lo, hi = self._domain
+        self._table_rows, params = table_param_rows(type(self).__name__, self._state.device, types,
+                                                    [(lo, hi, d["U"], d["tau"]) for d in values],
+                                                    "needs at least 2 finite samples in U and tau")
+        return params
+
+
 class BondedForce(Force):
     """``params[type] = dict(...)`` per group type; ``block_size``: 0 (256) or 64, 128, 256.
 

@@ -15,6 +15,10 @@ synchronisation.
 ``RadialDistributionFunction`` is g(r) between two groups from exact integer pair counts (``csrc/rdf.hip``; not part of
 the reference: azplugins had ``analyze.rdf`` in its HOOMD-2 line, the semantics are this project's, DESIGN 4.14);
 ``RDFRecorder`` appends the counts to a device table inside ``Simulation.run`` in the same way.
+
+``BondedDistribution`` is the distribution of the bond lengths, the bending angles or the dihedral angles per group
+type, from exact integer counts over the per-particle tables the bonded forces walk (``csrc/bonded_histogram.hip``;
+this project's); ``BondedDistributionRecorder`` is its in-run recorder.
 """
 
 import ctypes as C
@@ -870,6 +874,258 @@ class RDFRecorder(_Recorder):
         return _rdf_normalize(weighted, sum(self._pairs(t)), 1.0, c.r_max)
 
 
-__all__ = ["CartesianVelocityFieldCompute", "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder",
+# ---------------------------------------------------------------------------
+# distributions of the bonded coordinates
+# ---------------------------------------------------------------------------
+def distribution_from_counts(counts, num_groups, bin_width):
+    """``counts / (num_groups * bin_width)`` per type (rows of ``counts``), zeros where a type has no groups. The
+    compute, the recorder and the tests all go through here."""
+    counts = np.asarray(counts, dtype=np.float64)
+    n = np.asarray(num_groups, dtype=np.float64).reshape(-1, 1)
+    return np.divide(counts, n * float(bin_width), out=np.zeros(counts.shape), where=n > 0)
+
+
+class BondedDistribution(_Compute):
+    """Distributions of the bonded coordinates of a state, one histogram per group type: the bond lengths
+    (``kind="bond"``), the lengths of the special pairs (``"pair"``), the bending angles (``"angle"``) or the dihedral
+    angles (``"dihedral"``) -- what a tabulated bonded potential (``bond.Table``, ``angle.Table``, ``dihedral.Table``) is
+    inverted from. Not part of the reference; the semantics are this project's (``include/azp.h``).
+
+    The coordinate of a group, with the minimum image of the force kernels:
+
+    * bond, pair: ``r`` on ``[r_min, r_max)``, both required, ``0 <= r_min < r_max``; a group outside the range is
+      counted in ``outside`` of its type;
+    * angle: ``theta = atan2(|dab x dcb|, dab . dcb)`` on [0, pi];
+    * dihedral: ``phi = atan2(|b2| (b1 . n2), n1 . n2)`` on [-pi, pi] (IUPAC, as ``dihedral``); ``r_min`` and ``r_max``
+      are refused for these two.
+
+    Bin ``k = min(int((x - lo) * (num_bins / (hi - lo))), num_bins - 1)``: lower edges are inclusive, ``theta == pi`` and
+    ``phi == pi`` fall into the last bin. ``num_bins`` lies in [1, 8192]. The counts are exact integers (an integer
+    histogram in LDS, 64-bit integer atomics: ``csrc/bonded_histogram.hip``) and two reads of one state agree bit for
+    bit. The kernel walks the per-particle table the forces walk, on the device: nothing travels to the host but the
+    result. On a decomposed run every group is counted by the rank that owns its first member and the rows are added
+    over the ranks; every rank gets the same result.
+
+    ``distribution`` is ``counts / (num_groups * bin_width)``: a probability density in the coordinate ITSELF, without
+    a Jacobian. A Boltzmann inversion divides by ``r^2`` or ``sin theta`` itself before it takes the logarithm. Its
+    integral over the range is the fraction of the groups that lie inside (1 for angles and dihedrals).
+
+    Refused with ``AzpError`` at construction or assignment: an unknown ``kind``, ``num_bins`` outside [1, 8192], a
+    missing or empty ``[r_min, r_max)`` for bonds and pairs, ``r_min`` or ``r_max`` for angles and dihedrals. ``path``:
+    0 (default) counts in LDS wherever ``n_types * (num_bins + 2)`` words fit into the 64 KiB of a workgroup and with
+    global integer atomics elsewhere, 1 / 2 force one of them. Every property is computed when it is read, from the
+    current state, and raises ``DataAccessError`` while the compute is not attached."""
+
+    KINDS = {"bond": 2, "pair": 2, "angle": 3, "dihedral": 4}
+
+    def __init__(self, kind, num_bins, r_min=None, r_max=None):
+        super().__init__(All(), False)
+        if kind not in self.KINDS:
+            raise _lib.AzpError("BondedDistribution: kind must be one of %s, got %r" % (sorted(self.KINDS), kind))
+        self._kind = kind
+        self.num_bins = num_bins
+        if self.KINDS[kind] == 2:
+            if r_min is None or r_max is None:
+                raise _lib.AzpError("BondedDistribution(%r): r_min and r_max are required" % kind)
+            lo, hi = float(r_min), float(r_max)
+            if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo < hi):
+                raise _lib.AzpError("BondedDistribution(%r): needs finite 0 <= r_min < r_max, got %r, %r" % (kind, r_min, r_max))
+        else:
+            if r_min is not None or r_max is not None:
+                raise _lib.AzpError("BondedDistribution(%r): the range is the whole domain of the angle, r_min and r_max "
+                                    "are not accepted" % kind)
+            lo, hi = (0.0, np.pi) if kind == "angle" else (-np.pi, np.pi)
+        self._range = (lo, hi)
+        self.path = _lib.BONDED_HISTOGRAM_PATH_AUTO
+        self._row = None
+
+    @property
+    def kind(self):
+        return self._kind
+
+    @property
+    def r_min(self):
+        return self._range[0] if self.KINDS[self._kind] == 2 else None
+
+    @property
+    def r_max(self):
+        return self._range[1] if self.KINDS[self._kind] == 2 else None
+
+    @property
+    def num_bins(self):
+        return self._num_bins
+
+    @num_bins.setter
+    def num_bins(self, value):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= _lib.RDF_MAX_BINS:
+            raise _lib.AzpError("BondedDistribution: num_bins must be an integer in [1, %d], got %r" % (_lib.RDF_MAX_BINS, value))
+        self._num_bins = int(value)
+
+    @property
+    def path(self):
+        return self._path
+
+    @path.setter
+    def path(self, value):
+        if value not in (_lib.BONDED_HISTOGRAM_PATH_AUTO, _lib.BONDED_HISTOGRAM_PATH_LDS, _lib.BONDED_HISTOGRAM_PATH_GLOBAL):
+            raise _lib.AzpError("BondedDistribution: path must be 0 (auto), 1 (LDS) or 2 (global atomics), got %r" % (value,))
+        self._path = int(value)
+
+    @property
+    def bin_edges(self):
+        """numpy.ndarray: the ``num_bins + 1`` edges of the bins."""
+        return np.linspace(self._range[0], self._range[1], self._num_bins + 1)
+
+    @property
+    def bin_centers(self):
+        e = self.bin_edges
+        return 0.5 * (e[1:] + e[:-1])
+
+    @property
+    def bin_width(self):
+        return (self._range[1] - self._range[0]) / self._num_bins
+
+    # -- one launch ----------------------------------------------------------
+    def _types(self):
+        return list(getattr(self._sim.state, self._kind + "_types"))
+
+    def _row_width(self):
+        """The uint64 words of one output row: per type counts[num_bins], outside, total (at least one type)."""
+        return max(len(self._types()), 1) * (self._num_bins + 2)
+
+    def _launch(self, d_out):
+        """Queue ``azp_bonded_histogram`` for the simulation's current state with the ``_row_width()`` words going to
+        ``d_out``."""
+        st = self._sim.state
+        kind = self._kind
+        tab = st.group_table(kind)
+        a = _lib.BondedHistogramArgs()
+        a.d_pos = st.pos.data_ptr()
+        a.N = st.N
+        a.n_max = st.n_max
+        a.box = st.box.to_c()
+        a.arity = self.KINDS[kind]
+        a.n_types = max(len(self._types()), 1)
+        a.d_table = tab["table"].data_ptr()
+        a.d_table_pos = tab["bond_pos"].data_ptr() if "bond_pos" in tab else None
+        a.d_counts = tab["n_%ss" % kind].data_ptr()
+        a.pitch = tab["pitch"]
+        a.num_bins = self._num_bins
+        a.path = self._path
+        if a.arity == 2:
+            a.r_min, a.r_max = self._range
+        a.d_out = d_out
+        _lib.check(_lib.lib().azp_bonded_histogram(C.byref(a), _lib.raw_stream(st.device)), "azp_bonded_histogram")
+
+    def _reduce(self, rows):
+        """Rows of per-rank words (a (k, row width) int64 device tensor: the uint64 words of the kernel, all below 2^63)
+        added over the ranks of a decomposed run, as numpy int64 of shape (k, n_types, num_bins + 2)."""
+        dom = self._sim.domain
+        if dom is not None:
+            rows = _all_reduce_sum(dom, rows.clone())
+        return rows.cpu().numpy().reshape(rows.shape[0], -1, self._num_bins + 2)[:, :len(self._types())]
+
+    def _read(self, name):
+        import torch
+
+        if not self._attached:
+            raise DataAccessError(name)
+        st = self._sim.state
+        width = self._row_width()
+        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
+            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
+        self._launch(self._row.data_ptr())
+        return self._reduce(self._row)[0]
+
+    @property
+    def types(self):
+        """list of str: the names of the group types, in row order."""
+        if not self._attached:
+            raise DataAccessError("types")
+        return self._types()
+
+    @property
+    def counts(self):
+        """numpy int64 (n_types, num_bins): the groups of each type per bin."""
+        return self._read("counts")[:, :self._num_bins].copy()
+
+    @property
+    def outside(self):
+        """numpy int64 (n_types,): the groups of each type outside ``[r_min, r_max)`` (bonds and pairs; 0 otherwise)."""
+        return self._read("outside")[:, self._num_bins].copy()
+
+    @property
+    def num_groups(self):
+        """numpy int64 (n_types,): all groups of each type, inside the range or not."""
+        return self._read("num_groups")[:, self._num_bins + 1].copy()
+
+    @property
+    def distribution(self):
+        """numpy float64 (n_types, num_bins): ``counts / (num_groups * bin_width)`` on ``bin_centers``, zeros for a
+        type without groups. No Jacobian: the inversion divides by ``r^2`` or ``sin theta`` itself."""
+        t = self._read("distribution")
+        return distribution_from_counts(t[:, :self._num_bins], t[:, self._num_bins + 1], self.bin_width)
+
+
+class BondedDistributionRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) that appends the histograms of ``dist`` (a ``BondedDistribution`` in
+    ``computes`` of the same simulation) to a device table of ``n_types * (num_bins + 2)`` words per row at the
+    timesteps ``trigger`` (an ``int`` period or a ``Periodic``) fires, as ``RDFRecorder`` does with its counts: the
+    kernel writes row k itself, nothing is read back and the host does not wait; the trajectory is the same bit for
+    bit with and without the recorder. Read after the run: ``timesteps``, ``counts`` (frames, n_types, num_bins),
+    ``num_groups`` (frames, n_types) and ``mean_distribution`` (n_types, num_bins), the sum of the counts over the sum
+    of the group numbers times the bin width. On a decomposed run the whole table is reduced once, when it is read.
+    ``reset()`` forgets the recorded frames (needed before ``dist.num_bins`` or the number of group types changes)."""
+
+    _dtype = "int64"
+
+    def __init__(self, dist, trigger):
+        if not isinstance(dist, BondedDistribution):
+            raise _lib.AzpError("BondedDistributionRecorder: dist must be a BondedDistribution, got %r" % (dist,))
+        self.dist = dist
+        super().__init__(trigger)
+
+    @property
+    def _compute(self):
+        return self.dist
+
+    def _row_width(self):
+        return self.dist._row_width()
+
+    def reset(self):
+        self._rows = None
+        self._steps = []
+        self._volumes = []
+
+    def _table(self, name):
+        k = len(self._steps)
+        if not self.dist._attached:
+            if k == 0:
+                return np.zeros((0, 0, self.dist.num_bins + 2), dtype=np.int64)
+            raise DataAccessError(name)
+        if k == 0:
+            return np.zeros((0, len(self.dist._types()), self.dist.num_bins + 2), dtype=np.int64)
+        return self.dist._reduce(self._rows[:k])
+
+    @property
+    def counts(self):
+        """numpy int64 (frames, n_types, num_bins)."""
+        return self._table("counts")[:, :, :self.dist.num_bins].copy()
+
+    @property
+    def num_groups(self):
+        """numpy int64 (frames, n_types)."""
+        return self._table("num_groups")[:, :, self.dist.num_bins + 1].copy()
+
+    @property
+    def mean_distribution(self):
+        """numpy float64 (n_types, num_bins): the counts of all frames over their group numbers and the bin width."""
+        t = self._table("mean_distribution")
+        nb = self.dist.num_bins
+        return distribution_from_counts(t[:, :, :nb].sum(axis=0), t[:, :, nb + 1].sum(axis=0), self.dist.bin_width)
+
+
+__all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute",
+           "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder", "distribution_from_counts",
            "RadialDistributionFunction", "ThermodynamicQuantities", "ThermodynamicRecorder", "VelocityCompute",
            "VelocityFieldCompute", "perpendicular_widths", "rdf_from_counts", "thermo_quantities"]

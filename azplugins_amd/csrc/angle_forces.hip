@@ -6,6 +6,10 @@
 // The lane keeps, of each angle, the force on its own position, a third of the energy and a third of the virial. The
 // three lanes of one angle evaluate the same expression on the same operands, so their forces add to zero to rounding.
 // Every table read is one 16-byte load.
+//
+// EvalAngleTable is the tabulated form (angle.Table; include/azp.h "tabulated angle and dihedral potentials", DESIGN
+// 4.26): the rows of EvalTable (evaluators.hpp) over theta in [0, pi], read with its interpolate().
+#include "evaluators.hpp"
 #include "bonded_kernel.hpp"
 
 namespace azp
@@ -34,6 +38,23 @@ struct EvalAngleCosineSquared
         }
     };
 
+// Tabulated U and torque tau = -dU/dtheta on n intervals of [0, pi]: g = dU/dc = tau / s, because dtheta/dc = -1 / s.
+// theta == pi gives an index of n (or just below): interpolate() clamps it to row n - 1 with f = 1, the last knot.
+struct EvalAngleTable
+    {
+    typedef azp_table_params Params;
+    static __device__ __forceinline__ void eval(const Params& p, double c, double s, double& U, double& g)
+        {
+        U = 0.0;
+        g = 0.0;
+        if (p.n == 0 || p.d_rows == nullptr)
+            return;
+        double tau;
+        EvalTable::interpolate(p.d_rows, p.n - 1, acos(c) * ((double)p.n / M_PI), U, tau);
+        g = tau * fast_rcp(s);
+        }
+    };
+
 struct AngleGeometry
     {
     typedef azp_angle_args Args;
@@ -42,8 +63,9 @@ struct AngleGeometry
     static constexpr uint32_t PARTNERS = 2;
     // An interior bead of a linear chain has 3 entries: BATCH = 3 holds it in one batch. The harmonic kernel takes 110
     // VGPRs at 2, 3 and 4 alike (acos sets its peak), the cosine-squared one 75 / 89 / 103.
+    // The table instance keeps 3 as well (profiles/bonded_table.md).
     static constexpr uint32_t BATCH = 3;
-    static constexpr bool FLAGS = false; // neither evaluator can reject its parameters
+    static constexpr bool FLAGS = false; // no evaluator can reject its parameters
 
     static bool tables(const Args& args, BondedKArgs& k)
         {
@@ -123,4 +145,10 @@ extern "C" int azp_angle_forces_cosine_squared(const azp_angle_args* args, const
                                                void* stream)
     {
     return azp::launch_bonded<azp::AngleGeometry, azp::EvalAngleCosineSquared>(args, d_params, nullptr, stream);
+    }
+
+// Tabulated angle potential (include/azp.h): no flag word, [0, pi] is the whole domain.
+extern "C" int azp_angle_forces_table(const azp_angle_args* args, const azp_table_params* d_params, void* stream)
+    {
+    return azp::launch_bonded<azp::AngleGeometry, azp::EvalAngleTable>(args, d_params, nullptr, stream);
     }

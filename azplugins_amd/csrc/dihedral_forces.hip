@@ -10,6 +10,10 @@
 // cos phi and sin phi come straight from the geometry (no atan2, no sincos): with n1 = b1 x b2, n2 = b2 x b3 and
 // q = 1 / (|n1||n2|), cos phi = (n1 . n2) q and sin phi = |b2| (b1 . n2) q. The multiples of phi follow from the
 // angle-addition recurrence, cos phi0 and sin phi0 are folded on the host.
+//
+// EvalDihedralTable is the tabulated form (dihedral.Table; include/azp.h "tabulated angle and dihedral potentials",
+// DESIGN 4.26): it is the one evaluator that needs phi itself and takes it with atan2.
+#include "evaluators.hpp"
 #include "bonded_kernel.hpp"
 
 #ifndef AZP_DIHEDRAL_BATCH
@@ -51,6 +55,24 @@ struct EvalDihedralOPLS
         }
     };
 
+// Tabulated U and torque tau = -dU/dphi on n intervals of [-pi, pi], stored over x = phi + pi in [0, 2 pi].
+// sin phi = +0 at planar trans gives phi = +pi, x = 2 pi and the last knot (the clamp of interpolate()); sin phi = -0
+// gives phi = -pi, x = 0 and the first knot. The two may differ: periodicity is the user's to keep.
+struct EvalDihedralTable
+    {
+    typedef azp_table_params Params;
+    static __device__ __forceinline__ void eval(const Params& p, double c, double s, double& U, double& dU)
+        {
+        U = 0.0;
+        dU = 0.0;
+        if (p.n == 0 || p.d_rows == nullptr)
+            return;
+        double tau;
+        EvalTable::interpolate(p.d_rows, p.n - 1, (atan2(s, c) + M_PI) * ((double)p.n / (2.0 * M_PI)), U, tau);
+        dU = -tau;
+        }
+    };
+
 struct DihedralGeometry
     {
     typedef azp_dihedral_args Args;
@@ -59,9 +81,10 @@ struct DihedralGeometry
     static constexpr uint32_t PARTNERS = 3;
     // BATCH = 3 is the largest that keeps 4 waves per SIMD (124 VGPRs; 143 and 3 waves at 4). An interior bead of a
     // linear chain has 4 entries and takes one turn of the tail loop; measured on C3, that still beats BATCH = 4 with
-    // its lost wave.
+    // its lost wave. The table instance takes 142 VGPRs and 3 waves at 2, 3 and 4 alike (atan2 sets its
+    // peak) and its times at the three lie within 2 %: it keeps 3 too (profiles/bonded_table.md).
     static constexpr uint32_t BATCH = AZP_DIHEDRAL_BATCH;
-    static constexpr bool FLAGS = false; // neither evaluator can reject its parameters
+    static constexpr bool FLAGS = false; // no evaluator can reject its parameters
 
     static bool tables(const Args& args, BondedKArgs& k)
         {
@@ -154,4 +177,10 @@ extern "C" int azp_dihedral_forces_periodic(const azp_dihedral_args* args, const
 extern "C" int azp_dihedral_forces_opls(const azp_dihedral_args* args, const azp_dihedral_opls_params* d_params, void* stream)
     {
     return azp::launch_bonded<azp::DihedralGeometry, azp::EvalDihedralOPLS>(args, d_params, nullptr, stream);
+    }
+
+// Tabulated dihedral potential (include/azp.h): no flag word, [-pi, pi] is the whole domain.
+extern "C" int azp_dihedral_forces_table(const azp_dihedral_args* args, const azp_table_params* d_params, void* stream)
+    {
+    return azp::launch_bonded<azp::DihedralGeometry, azp::EvalDihedralTable>(args, d_params, nullptr, stream);
     }

@@ -1,4 +1,5 @@
-"""Dihedral potentials: periodic and OPLS torsions on libazp's gfx950 dihedral kernel (``csrc/dihedral_forces.hip``).
+"""Dihedral potentials: periodic, OPLS and tabulated torsions on libazp's gfx950 dihedral kernel
+(``csrc/dihedral_forces.hip``).
 
 The reference holds no dihedral code (with HOOMD-blue, torsions come from ``hoomd.md.dihedral`` next to the plugin), so
 the semantics are DEFINED HERE and in ``include/azp.h``, under ``md.dihedral``'s class names and
@@ -9,7 +10,9 @@ A dihedral has members ``a, b, c, d`` (``Snapshot.dihedrals.group``). With ``b1 
 ``phi = atan2(|b2| (b1 . n2), n1 . n2)`` in (-pi, pi]: IUPAC, cis (``a`` eclipsing ``d``) is 0 and trans is pi.
 
 * ``Periodic``: ``U = 1/2 k (1 + d cos(n phi - phi0))``;
-* ``OPLS``: ``U = 1/2 [k1 (1 + cos phi) + k2 (1 - cos 2 phi) + k3 (1 + cos 3 phi) + k4 (1 - cos 4 phi)]``.
+* ``OPLS``: ``U = 1/2 [k1 (1 + cos phi) + k2 (1 - cos 2 phi) + k3 (1 + cos 3 phi) + k4 (1 - cos 4 phi)]``;
+* ``Table``: ``U`` and the torque ``tau = -dU/dphi`` sampled at equal steps of ``phi`` over [-pi, pi] and interpolated
+  linearly.
 
 ``F_m = -U'(phi) g_m`` with the gradient of ``phi`` in the Blondel-Karplus form, which has no ``1 / sin phi``:
 ``g_a = -(|b2| / |n1|^2) n1``, ``g_d = (|b2| / |n2|^2) n2``, ``g_b = -(1 + s) g_a + t g_d``,
@@ -19,7 +22,7 @@ of ``U`` and, with ``compute_virial``, a quarter of ``(-b1) (x) F_a + b2 (x) F_c
 add no neighbor-list exclusions by themselves: ``nlist.Cell(exclusions=("bond", "1-3", "1-4"))`` excludes the 1-4
 pairs and ``special_pair.LJ`` puts them back scaled.
 
-Out of scope: impropers, tabulated dihedrals, ``special_pair.Coulomb`` (no charges), an ``_azplugins`` class."""
+Out of scope: impropers, ``special_pair.Coulomb`` (no charges), an ``_azplugins`` class."""
 
 import ctypes as C
 import math
@@ -27,8 +30,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .bonded import BondedForce
-from .force import TypeParameter
+from .bonded import BondedForce, BondedTable
+from .force import BondedTableTypeParameter, TypeParameter
 
 
 class Dihedral(BondedForce):
@@ -105,4 +108,21 @@ class OPLS(Dihedral):
         return dict(k1=k[0].value, k2=k[1].value, k3=k[2].value, k4=k[3].value)
 
 
-__all__ = ["Dihedral", "Periodic", "OPLS"]
+class Table(BondedTable, Dihedral):
+    """Tabulated torsion (``hoomd.md.dihedral.Table``'s name; the reference has none, the semantics are defined in
+    ``include/azp.h`` and DESIGN 4.26). ``params[type] = dict(U=array, tau=array)``: ``width = len(U) >= 2`` samples of
+    the energy and of the torque ``tau = -dU/dphi`` at ``phi_k = -pi + 2 pi k / (width - 1)``, both end points
+    included, interpolated linearly in between. ``width`` is per type.
+
+    Periodicity is not enforced: ``U[0]`` may differ from ``U[-1]``. A planar trans dihedral reads the end its
+    ``sin phi`` names: ``sin phi = +0`` is ``phi = +pi`` and reads ``U[-1]``, ``tau[-1]``; ``sin phi = -0`` is
+    ``phi = -pi`` and reads ``U[0]``, ``tau[0]``. A table that is meant to be periodic stores equal ends. The rows are
+    kept over ``phi + pi`` in [0, 2 pi]."""
+
+    _entry = "azp_dihedral_forces_table"
+    _schema = dict(U=np.ndarray, tau=np.ndarray)
+    _parameter = BondedTableTypeParameter
+    _domain = (0.0, 2.0 * math.pi)
+
+
+__all__ = ["Dihedral", "Periodic", "OPLS", "Table"]

@@ -159,6 +159,41 @@ class TableTypeParameter(TypeParameter):
         return {name: (v.copy() if isinstance(v, np.ndarray) else v) for name, v in self._data[k].items()}
 
 
+class BondedTableTypeParameter(TypeParameter):
+    """``params`` of the tabulated angle and dihedral potentials (``angle.Table``, ``dihedral.Table``):
+    ``dict(U=array, tau=array)``, the energy and the torque ``tau = -dU/d(angle)`` as equally long one-dimensional
+    arrays of at least 2 samples over the whole domain of the angle, both end points included. There is no range to
+    give. Raises ``ValueError`` where the value is set: other keys than ``U`` and ``tau``, arrays that are not
+    one-dimensional, unequal lengths, fewer than 2 samples, non-finite entries."""
+
+    def _validate(self, value):
+        if not isinstance(value, dict):
+            raise TypeError("%s values must be dicts" % self.name)
+        if set(value) != {"U", "tau"}:
+            raise ValueError("%s: expected the keys ['U', 'tau'], got %s" % (self.name, sorted(value)))
+        try:
+            out = {k: np.array(value[k], dtype=np.float64) for k in ("U", "tau")}
+        except (TypeError, ValueError):
+            raise ValueError("%s: U and tau must be arrays of numbers" % self.name)
+        for k, v in out.items():
+            if v.ndim != 1:
+                raise ValueError("%s: %s must be a one-dimensional array" % (self.name, k))
+        if out["U"].shape != out["tau"].shape:
+            raise ValueError("%s: U and tau differ in length (%d, %d)" % (self.name, len(out["U"]), len(out["tau"])))
+        if len(out["U"]) < 2:
+            raise ValueError("%s: a table needs at least 2 samples, got %d" % (self.name, len(out["U"])))
+        if not (np.isfinite(out["U"]).all() and np.isfinite(out["tau"]).all()):
+            raise ValueError("%s: U and tau must be finite" % self.name)
+        return out
+
+    def __getitem__(self, key):
+        """What was set, the arrays as copies: a table is replaced as a whole, not edited in place."""
+        k = self._key(key)
+        if k not in self._data:
+            raise KeyError("%s[%r] is not set" % (self.name, key))
+        return {name: v.copy() for name, v in self._data[k].items()}
+
+
 class ScalarTypeParameter(TypeParameter):
     """Per-type-pair scalar (``r_cut`` / ``r_on``) with a default."""
 

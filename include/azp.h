@@ -19,6 +19,9 @@
  *   azp_dihedral_forces_*        (no counterpart in the reference: md.dihedral's names, semantics defined here)
  *   azp_pair_forces_table, azp_bond_forces_table
  *                                (no counterpart in the reference: md.pair.Table / md.bond.Table, semantics defined here)
+ *   azp_angle_forces_table, azp_dihedral_forces_table, azp_bonded_histogram
+ *                                (no counterpart in the reference: md.angle.Table / md.dihedral.Table and the
+ *                                   distributions they are inverted from, semantics defined here)
  *
  * Conventions (all restated from HOOMD-blue's ForceCompute data model):
  *   - Scalar = double. Scalar4 arrays are 4 consecutive doubles.
@@ -601,6 +604,30 @@ void azp_dihedral_opls_params_unpack(const azp_dihedral_opls_params* p, double* 
  * AZP_ERROR_INVALID_ARGUMENT; parameters beyond 64 KiB of LDS: AZP_ERROR_TOO_MANY_TYPES. */
 int azp_dihedral_forces_periodic(const azp_dihedral_args* args, const azp_dihedral_periodic_params* d_params, void* stream);
 int azp_dihedral_forces_opls(const azp_dihedral_args* args, const azp_dihedral_opls_params* d_params, void* stream);
+
+/* ---- tabulated angle and dihedral potentials (angle.Table, dihedral.Table) ----
+ * The names are HOOMD's md.angle.Table and md.dihedral.Table; the reference holds no such code, the semantics are
+ * DEFINED HERE. Both take azp_table_params (above) per type, with rows from azp_table_pack(closed = 1):
+ * `width` >= 2 samples of the energy U and of the TORQUE tau = -dU/d(angle), both end points stored, n = width - 1
+ * intervals, linear interpolation between the knots exactly as for the bond form (s, k = min(floor(s), n - 1),
+ * f = s - k, U = U_k + f (U_{k+1} - U_k), tau likewise). The widths are per type. The whole domain of the angle is
+ * covered, so nothing can be out of bounds: there is no flag word.
+ *
+ *   angle     knots theta_k = k pi / n on [0, pi]; r_min = 0, r_max = pi. With c and s = max(sin theta, 1e-3) of the
+ *             angle geometry above: theta = acos(c), s_index = theta * (n / pi), g = dU/dc = tau / s. theta == pi
+ *             gives s_index == n (or its neighbor in the last bit): the clamp k <= n - 1 then yields the value of the
+ *             last knot, U = U_n.
+ *   dihedral  knots phi_k = -pi + 2 pi k / n on [-pi, pi]; the table is packed and read over x = phi + pi in
+ *             [0, 2 pi] (azp_table_pack refuses r_min < 0), r_min = 0, r_max = 2 pi. With cos phi and sin phi of the
+ *             dihedral geometry above: phi = atan2(sin phi, cos phi), s_index = (phi + pi) * (n / (2 pi)),
+ *             U' = dU/dphi = -tau. Periodicity is NOT enforced: U_0 may differ from U_n. Planar trans reads the end
+ *             its sin phi names: sin phi = +0 gives phi = +pi and the LAST knot (U_n, tau_n), sin phi = -0 gives
+ *             phi = -pi and the FIRST knot (U_0, tau_0). A table that is meant to be periodic stores equal ends.
+ *
+ * A type with n == 0 or d_rows == NULL contributes nothing (no energy, no force). Everything else -- the geometry, the
+ * shares of energy and virial, the error returns -- is that of the analytic angle and dihedral entries above. */
+int azp_angle_forces_table(const azp_angle_args* args, const azp_table_params* d_params, void* stream);
+int azp_dihedral_forces_table(const azp_dihedral_args* args, const azp_table_params* d_params, void* stream);
 
 /* ---- neighbor-list build (the step before the path) ----
  * Cell list -> full Verlet list in the layout the force kernels consume.
@@ -1487,6 +1514,60 @@ typedef struct azp_rdf_exclusion_args
     } azp_rdf_exclusion_args;
 
 int azp_rdf_subtract_excluded(const azp_rdf_exclusion_args* args, void* stream);
+
+/* ---- distributions of the bonded coordinates (compute.BondedDistribution) ----
+ * Not part of the reference; the semantics are DEFINED HERE. One histogram per group type of the bond
+ * lengths, the bending angles or the dihedral angles of a state: what a tabulated bonded potential is inverted from.
+ * The groups come from the per-particle table of their kind (the one the force kernels walk; arity 2 is the layout of
+ * the bond table, which the special pairs share): one lane per row i < N walks its entries and counts those in which
+ * i is member 0 of the group, so every group with its first member on a row below N is counted exactly once (on a
+ * decomposed run every particle is a local row of exactly one rank). An entry whose type is >= n_types or which
+ * names a row >= n_max is skipped. The coordinate x of a group, separations by the minimum image of the force kernels:
+ *   arity 2   r = sqrt(|r_a - r_b|^2), correctly rounded, on [lo, hi) = [r_min, r_max): a group with r < r_min or
+ *             r >= r_max (or a NaN) goes to the `outside` word of its type
+ *   arity 3   theta = atan2(|dab x dcb|, dab . dcb) with dab = r_a - r_b, dcb = r_c - r_b, on [0, pi]: well
+ *             conditioned at 0 and pi, where acos is not
+ *   arity 4   phi = atan2(|b2| (b1 . n2), n1 . n2) on [-pi, pi], b1, b2, b3, n1, n2 as for the dihedral forces (the
+ *             common positive factor 1 / (|n1||n2|) of the force kernel's sin phi and cos phi is left out: atan2
+ *             does not see it)
+ *   bin       k = min((uint32_t)((x - lo) * scale), num_bins - 1), scale = num_bins / (hi - lo) in double, pi = M_PI:
+ *             lower edges are inclusive, theta == pi and phi == pi fall into the last bin.
+ * d_out: n_types * (num_bins + 2) uint64, per type counts[num_bins], then `outside`, then `total` = every group of the
+ * type that was looked at (the sum of the counts and of `outside`). The call OVERWRITES the row (it zeroes it on the
+ * stream first; uninitialised memory is fine), so a recorder can point it at a row of its table. Integers only:
+ * a uint32 histogram of the workgroup in LDS (integer LDS atomics), flushed into the row with 64-bit integer atomic
+ * adds on its non-zero words, and `total` summed from the finished row by a second small launch on the same stream;
+ * two calls give the same bits. No forces and no force parameters are read or written.
+ * path: 0 = automatic, 1 = the LDS histogram, 2 = 64-bit integer atomics straight on the row. The histogram of a
+ * workgroup is n_types * (num_bins + 2) words and a workgroup can have 64 KiB of LDS here, so path 1 exists for at
+ * most AZP_BONDED_HISTOGRAM_LDS_WORDS = 16384 words; path 0 takes it wherever it exists and path 2 elsewhere. Both
+ * give the same integers.
+ * AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written: NULL args; arity not 2, 3 or 4; num_bins < 1
+ * or > AZP_RDF_MAX_BINS; n_types == 0; path > 2, or 1 where the histogram does not fit; arity 2 without finite
+ * 0 <= r_min < r_max. N == 0: success before any array is looked at (a d_out that is given is zeroed, NULL is
+ * accepted). Otherwise also: a NULL d_out, d_pos, table or count array (arity 2: a NULL d_table_pos), pitch < N,
+ * N > n_max. A NaN coordinate (coincident or collinear members) goes to `outside`. */
+#define AZP_BONDED_HISTOGRAM_LDS_WORDS 16384
+
+typedef struct azp_bonded_histogram_args
+    {
+    const double* d_pos;         /* n_max x 4 */
+    uint32_t N;                  /* rows whose entries are walked */
+    uint32_t n_max;              /* rows an entry may name (N + ghosts) */
+    azp_box box;
+    uint32_t arity;              /* 2: bonds and special pairs, 3: angles, 4: dihedrals */
+    uint32_t n_types;
+    const void* d_table;         /* azp_bond_entry / azp_angle_entry / azp_dihedral_entry at [s * pitch + i] */
+    const uint32_t* d_table_pos; /* arity 2: the row's position in the group, [s * pitch + i] */
+    const uint32_t* d_counts;    /* N */
+    uint64_t pitch;
+    uint32_t num_bins;
+    uint32_t path;               /* 0 auto, 1 LDS histogram, 2 global atomics */
+    double r_min, r_max;         /* arity 2; ignored otherwise */
+    uint64_t* d_out;             /* n_types * (num_bins + 2), overwritten */
+    } azp_bonded_histogram_args;
+
+int azp_bonded_histogram(const azp_bonded_histogram_args* args, void* stream);
 
 /* ---- wall potentials (azplugins_amd.wall) ----
  * Replace the reference's legacy wall evaluators src/WallEvaluatorLJ93.h:50-150 and
