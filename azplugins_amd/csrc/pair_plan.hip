@@ -33,7 +33,7 @@ struct PlanKArgs
     const double* rinnersq; // optional (may be null): "core" class radius^2 per type pair
     uint32_t* slice_Kend;   // PLAN_SHELLS + 1 per slice, in batches of 4 entries per lane; zeroed before the build kernel
     uint32_t* slice_Kphase; // [2][n_slices]: core chunks (zeroed before the build kernel), sure chunks (set to ~0 before it);
-                            // diagnostic, no kernel consumes the phase counts
+                            // the tile kernel reads the core chunks for its tail phase, nothing the sure chunks
     uint32_t n_slices;
     double r_list_max;      // caller's hint (r_cut_max + 2 r_buff), 0 = unknown
     double r_list_estimate; // used when r_list_max is unknown: an estimate of r_cut_max + r_buff (0: one shell holds
@@ -426,7 +426,7 @@ __global__ void __launch_bounds__(PLAN_BUILD_THREADS) plan_build_kernel(const Pl
 #pragma unroll
             for (uint32_t sh = 0; sh <= PLAN_SHELLS; ++sh)
                 atomicMax(&a.slice_Kend[(PLAN_SHELLS + 1) * slice + sh], plan_row_batches(seg[PLAN_CLS_SHELL0 + (sh < PLAN_SHELL_CLASSES ? sh : PLAN_SHELL_CLASSES)], TPP));
-            // ordering class and diagnostic (no kernel consumes the phase counts): chunks that cover the core entries,
+            // ordering class, diagnostic and the end of the tile kernel's core phase: chunks that cover the core entries,
             // chunks made of core / sure entries alone
             atomicMax(&a.slice_Kphase[slice], (seg[PLAN_CLS_SURE] + 8u * TPP - 1u) / (8u * TPP));
             atomicMin(&a.slice_Kphase[a.n_slices + slice], seg[PLAN_CLS_NEAR] / (8u * TPP));

@@ -93,8 +93,9 @@ struct PairPlan
                                            // the in-range entries [0] / of buffer shell s [1 + s]; [PLAN_SHELLS] = whole rows
     uint32_t* d_slice_Kphase = nullptr;    // [2][n_slices]: chunks covering every entry of class core [0][slice]; chunks up to which
                                            // every row of the slice holds only entries of the classes core and sure [1][slice].
-                                           // Ordering class and diagnostic (azp_pair_plan_phase_chunks); no kernel consumes the
-                                           // phase counts or the two radii below
+                                           // Ordering class and diagnostic (azp_pair_plan_phase_chunks). The tile kernel reads
+                                           // [0][slice] and core_r below for its tail phase (pair_tiled.hpp, plan_core_reach_sq);
+                                           // nothing consumes [1][slice] or sure_r
     size_t cap_kphase = 0;
     float core_r = 0.f;                    // entries outside class core were at least this far apart at build time (the inner
                                            // radius hint minus a margin for the single-precision test); 0: no core class

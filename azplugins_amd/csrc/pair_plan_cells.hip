@@ -99,7 +99,7 @@ struct PlanCellsKArgs
     uint32_t* slice_K;
     uint32_t* slice_Kend;
     uint32_t* slice_Kphase; // [2][n_slices]: chunks covering class core; chunks holding only core / sure entries in every row
-                            // (diagnostic, no kernel consumes the phase counts)
+                            // (the tile kernel reads the core chunks for its tail phase)
     uint64_t* slice_head;
     uint4* cnl;
     uint32_t* flags;        // [0] sure radius, [1] invalid, [2] max staged set, [3] shell width, [4] most member cells of a tile, [5] longest row, [6] reason, [7] core radius
