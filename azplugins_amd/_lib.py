@@ -379,6 +379,30 @@ class BondedHistogramArgs(C.Structure):
     ]
 
 
+SF_MAX_VECTORS = 65536
+SF_POWERS_LDS_BYTES = 49152
+SF_PATH_AUTO, SF_PATH_DIRECT, SF_PATH_POWERS = 0, 1, 2
+
+
+class StructureFactorArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("box", Box),
+        ("d_type_mask_a", C.c_void_p),
+        ("d_type_mask_b", C.c_void_p),
+        ("same_groups", C.c_uint32),
+        ("n_vectors", C.c_uint32),
+        ("d_vectors", C.c_void_p),
+        ("m_max", C.c_uint32 * 3),
+        ("path", C.c_uint32),
+        ("d_out", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 FLOW_CONSTANT = 0
 FLOW_PARABOLIC = 1
 
@@ -733,6 +757,8 @@ SYMBOLS = {
     "azp_rdf_counts": (C.c_int, [C.POINTER(RdfArgs), _VP]),
     "azp_rdf_subtract_excluded": (C.c_int, [C.POINTER(RdfExclusionArgs), _VP]),
     "azp_bonded_histogram": (C.c_int, [C.POINTER(BondedHistogramArgs), _VP]),
+    "azp_structure_factor_scratch_size": (C.c_int, [C.POINTER(StructureFactorArgs), C.POINTER(C.c_uint64)]),
+    "azp_structure_factor_amplitudes": (C.c_int, [C.POINTER(StructureFactorArgs), _VP]),
     "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
     "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
     "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),

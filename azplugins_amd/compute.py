@@ -19,6 +19,10 @@ the reference: azplugins had ``analyze.rdf`` in its HOOMD-2 line, the semantics 
 ``BondedDistribution`` is the distribution of the bond lengths, the bending angles or the dihedral angles per group
 type, from exact integer counts over the per-particle tables the bonded forces walk (``csrc/bonded_histogram.hip``;
 this project's); ``BondedDistributionRecorder`` is its in-run recorder.
+
+``StructureFactor`` is the partial static structure factor S_AB(q) on the reciprocal-lattice vectors of the box, by the
+direct sum over the particles in a fixed order (``csrc/structure_factor.hip``; this project's, DESIGN 4.27);
+``StructureFactorRecorder`` appends the density amplitudes to a device table inside ``Simulation.run``.
 """
 
 import ctypes as C
@@ -1125,7 +1129,427 @@ class BondedDistributionRecorder(_Recorder):
         return distribution_from_counts(t[:, :, :nb].sum(axis=0), t[:, :, nb + 1].sum(axis=0), self.dist.bin_width)
 
 
+# ---------------------------------------------------------------------------
+# static structure factor
+# ---------------------------------------------------------------------------
+_TWO_PI = 2.0 * np.pi
+_SF_MAX_BLOCK = 1 << 24
+
+
+def reciprocal_vectors(box, m):
+    """q(m) = 2 pi H^-T m for integer triples ``m`` (n, 3) in ``box`` (a ``state.Box``), as (n, 3) float64, by forward
+    substitution in H^T q' = m: q'_x = h / Lx, q'_y = k / Ly - xy q'_x, q'_z = (l / Lz - xz q'_x) - yz q'_y, q = 2 pi q'."""
+    m = np.asarray(m, dtype=np.float64).reshape(-1, 3)
+    qx = m[:, 0] / box.Lx
+    qy = m[:, 1] / box.Ly - box.xy * qx
+    qz = (m[:, 2] / box.Lz - box.xz * qx) - box.yz * qy
+    return np.stack([_TWO_PI * qx, _TWO_PI * qy, _TWO_PI * qz], axis=1)
+
+
+def _sf_code(m):
+    m = np.asarray(m, dtype=np.int64) + (1 << 20)
+    return ((m[:, 2] << 42) | (m[:, 1] << 21) | m[:, 0]).astype(np.uint64)
+
+
+def structure_factor_vectors(box, q_max, num_bins, max_vectors_per_bin=None, seed=0):
+    """The wavevector set of ``StructureFactor``: (m, bin) with ``m`` (n, 3) int64 and ``bin`` (n,) int64.
+
+    All m = (h, k, l) != 0 with |q(m)|^2 < q_max^2 (|q|^2 = (q_x^2 + q_y^2) + q_z^2 of ``reciprocal_vectors``), one of each
+    +-pair (l > 0, or l == 0 and k > 0, or l == k == 0 and h > 0), in lexicographic order of (l, k, h); enumerated over
+    |m_k| <= floor(q_max |a_k| / 2 pi). ``bin`` = min(int(|q| num_bins / q_max), num_bins - 1). With
+    ``max_vectors_per_bin`` = M every bin keeps the M vectors of smallest key ``synthetic.hash64(seed, code(m), 0)``,
+    code = (l + 2^20) 2^42 + (k + 2^20) 2^21 + (h + 2^20), ties to the smaller code. ``AzpError``: a bounding block of more
+    than 2^24 triples, more than ``SF_MAX_VECTORS`` vectors after thinning."""
+    from .synthetic import hash64
+
+    q_max, num_bins = float(q_max), int(num_bins)
+    norms = (box.Lx, box.Ly * np.sqrt(1.0 + box.xy ** 2), box.Lz * np.sqrt(1.0 + box.xz ** 2 + box.yz ** 2))
+    M = [int(np.floor(q_max * a / _TWO_PI)) for a in norms]
+    block = (2 * M[0] + 1) * (2 * M[1] + 1) * (2 * M[2] + 1)
+    if block > _SF_MAX_BLOCK:
+        raise _lib.AzpError("StructureFactor: q_max = %r bounds %d integer triples in this box, more than 2^24; lower q_max"
+                            % (q_max, block))
+    h = np.arange(-M[0], M[0] + 1, dtype=np.int64)
+    k = np.arange(-M[1], M[1] + 1, dtype=np.int64)
+    kk, hh = (x.ravel() for x in np.meshgrid(k, h, indexing="ij"))
+    found, bins = [], []
+    for l in range(0, M[2] + 1):  # (the half space has no l < 0)
+        m = np.stack([hh, kk, np.full_like(hh, l)], axis=1)
+        if l == 0:
+            m = m[(kk > 0) | ((kk == 0) & (hh > 0))]
+        q = reciprocal_vectors(box, m)
+        qsq = (q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]
+        keep = qsq < q_max * q_max
+        found.append(m[keep])
+        bins.append(np.minimum((np.sqrt(qsq[keep]) * num_bins / q_max).astype(np.int64), num_bins - 1))
+    m, b = np.concatenate(found), np.concatenate(bins)
+    if max_vectors_per_bin is not None and len(m):
+        code = _sf_code(m)
+        key = hash64(seed, code, 0)
+        order = np.lexsort((code, key, b))  # by bin, then key, then code
+        first = np.searchsorted(b[order], np.arange(num_bins))  # where each bin starts in that order
+        rank = np.arange(len(m)) - first[b[order]]
+        keep = np.zeros(len(m), dtype=bool)
+        keep[order[rank < int(max_vectors_per_bin)]] = True
+        m, b = m[keep], b[keep]
+    if len(m) > _lib.SF_MAX_VECTORS:
+        raise _lib.AzpError("StructureFactor: %d wavevectors, more than the %d of AZP_SF_MAX_VECTORS; lower q_max or thin the "
+                            "set with max_vectors_per_bin" % (len(m), _lib.SF_MAX_VECTORS))
+    return m, b
+
+
+def structure_factor_from_amplitudes(row, n_vectors):
+    """S_AB(m) of every vector from one row of ``azp_structure_factor_amplitudes`` (4 n + 4 doubles: Re rho_A, Im rho_A,
+    Re rho_B, Im rho_B, then N_A, N_B, N_AB, 0; added over the ranks of a decomposed run):
+    S_AB(m) = (Re rho_A Re rho_B + Im rho_A Im rho_B) / sqrt(N_A N_B), i.e. |rho_A|^2 / N_A when B is A; zeros when a
+    group is empty. The compute, the recorder and the tests all go through here."""
+    row = np.asarray(row, dtype=np.float64)
+    n = int(n_vectors)
+    n_a, n_b = row[4 * n], row[4 * n + 1]
+    if not (n_a > 0.0 and n_b > 0.0):
+        return np.zeros(n)
+    return (row[:n] * row[2 * n:3 * n] + row[n:2 * n] * row[3 * n:4 * n]) / np.sqrt(n_a * n_b)
+
+
+def spherical_average(values, bins, num_bins):
+    """(mean, count) per |q| bin: the arithmetic mean of ``values`` over the vectors whose ``bins`` entry is k, NaN where
+    a bin has no vector, and the number of vectors per bin (int64)."""
+    bins = np.asarray(bins, dtype=np.int64)
+    count = np.bincount(bins, minlength=int(num_bins)).astype(np.int64)
+    total = np.bincount(bins, weights=np.asarray(values, dtype=np.float64), minlength=int(num_bins))
+    return np.divide(total, count, out=np.full(int(num_bins), np.nan), where=count > 0), count
+
+
+def _check_sf_filter(name, f):
+    if not isinstance(f, (All, Type)):
+        raise _lib.AzpError("StructureFactor: %s must be All() or Type(...), got %r" % (name, f))
+    return f
+
+
+class StructureFactor(_Compute):
+    """Partial static structure factor S_AB(q) between the groups ``filter_a`` and ``filter_b`` (``All()`` or
+    ``Type(...)``; they may overlap) on the reciprocal-lattice vectors of the box, by the direct sum over the particles
+    (``csrc/structure_factor.hip``). Not part of the reference; the semantics are this project's (``include/azp.h``,
+    DESIGN 4.27).
+
+    For a 3-D box periodic on all three axes with lattice matrix H (tilts included) the wavevectors are
+    q(m) = 2 pi H^-T m, m = (h, k, l) integers, so q . r = 2 pi m . f with f the fractional coordinates. The amplitude of
+    a group is rho_G(m) = sum_{j in G} exp(-2 pi i m . f_j) over the owned particles and
+    S_AB(m) = Re[rho_A(m) conj(rho_B(m))] / sqrt(N_A N_B) (Ashcroft-Langreth; |rho_A|^2 / N_A for one group; 0 when a
+    group is empty). ``vectors`` holds every m != 0 with |q(m)| < ``q_max``, one of each +-pair, ordered by (l, k, h)
+    (``structure_factor_vectors``); ``max_vectors_per_bin`` = M thins it to the M vectors of smallest hash per |q| bin
+    (deterministic in ``seed``, independent of N and of the ranks). ``structure_factor[k]`` is the arithmetic mean of
+    S_AB(m) over the vectors of bin k of ``num_bins`` equal bins on [0, q_max) and NaN where ``vectors_per_bin[k]`` is 0.
+
+    Refused with ``AzpError``: ``q_max <= 0``, ``num_bins`` outside [1, 8192], ``max_vectors_per_bin < 1``, a seed outside
+    [0, 2^64), a filter that is not ``All()`` or ``Type(...)`` (at construction or assignment); when a property is
+    read: a 2-D or not fully periodic box, an empty vector set (``q_max`` below the smallest |q| of the box), more
+    than 2^24 triples to enumerate, more than ``SF_MAX_VECTORS`` = 65,536 vectors. ``path``: 0 (default) takes the
+    powers kernel wherever its tables fit and the direct kernel elsewhere, 1 / 2 force one; a forced powers path
+    whose tables do not fit is refused. The sums have a fixed order: two reads of one state agree bit for bit. On a
+    decomposed run each rank sums its owned particles in the global box and the rows are added over the ranks before
+    normalising. The vector list is built on the host, cached on the device, and rebuilt when the box, ``q_max``,
+    ``num_bins``, the thinning or the seed changes. Every property is computed when it is read, from the current state."""
+
+    def __init__(self, filter_a, filter_b, q_max, num_bins, max_vectors_per_bin=None, seed=0):
+        super().__init__(_check_sf_filter("filter_a", filter_a), False)
+        self._filter_b = _check_sf_filter("filter_b", filter_b)
+        self.q_max = q_max
+        self.num_bins = num_bins
+        self.max_vectors_per_bin = max_vectors_per_bin
+        self.seed = seed
+        self.path = _lib.SF_PATH_AUTO
+        self._masks = None    # (types, mask a, mask b, device)
+        self._set = None      # (key, m, bins, device triples, m_max)
+        self._row = None
+        self._scratch = None
+
+    filter_a = _Compute.filter
+
+    @property
+    def filter_b(self):
+        return self._filter_b
+
+    @property
+    def q_max(self):
+        return self._q_max
+
+    @q_max.setter
+    def q_max(self, value):
+        value = float(value)
+        if not (value > 0.0 and np.isfinite(value)):
+            raise _lib.AzpError("StructureFactor: q_max must be positive, got %r" % (value,))
+        self._q_max = value
+
+    @property
+    def num_bins(self):
+        return self._num_bins
+
+    @num_bins.setter
+    def num_bins(self, value):
+        if isinstance(value, bool) or int(value) != value or not 1 <= int(value) <= _lib.RDF_MAX_BINS:
+            raise _lib.AzpError("StructureFactor: num_bins must be an integer in [1, %d], got %r" % (_lib.RDF_MAX_BINS, value))
+        self._num_bins = int(value)
+
+    @property
+    def max_vectors_per_bin(self):
+        return self._max_per_bin
+
+    @max_vectors_per_bin.setter
+    def max_vectors_per_bin(self, value):
+        if value is not None and (isinstance(value, bool) or int(value) != value or int(value) < 1):
+            raise _lib.AzpError("StructureFactor: max_vectors_per_bin must be None or a positive integer, got %r" % (value,))
+        self._max_per_bin = None if value is None else int(value)
+
+    @property
+    def seed(self):
+        return self._seed
+
+    @seed.setter
+    def seed(self, value):
+        if isinstance(value, bool) or int(value) != value or not 0 <= int(value) < 1 << 64:
+            raise _lib.AzpError("StructureFactor: seed must be an integer in [0, 2^64), got %r" % (value,))
+        self._seed = int(value)
+
+    @property
+    def path(self):
+        return self._path
+
+    @path.setter
+    def path(self, value):
+        if value not in (_lib.SF_PATH_AUTO, _lib.SF_PATH_DIRECT, _lib.SF_PATH_POWERS):
+            raise _lib.AzpError("StructureFactor: path must be 0 (auto), 1 (direct) or 2 (powers), got %r" % (value,))
+        self._path = int(value)
+
+    @property
+    def bin_edges(self):
+        """numpy.ndarray: the ``num_bins + 1`` edges of the |q| bins."""
+        return np.linspace(0.0, self._q_max, self._num_bins + 1)
+
+    @property
+    def bin_centers(self):
+        e = self.bin_edges
+        return 0.5 * (e[1:] + e[:-1])
+
+    # -- the vector set --------------------------------------------------------
+    def _vector_set(self, name="vectors"):
+        """(m, bins, device triples, m_max) for the current box, rebuilt when anything it depends on changed."""
+        import torch
+
+        if not self._attached:
+            raise DataAccessError(name)
+        st = self._sim.state
+        box = st.box
+        if not (box.Lx > 0.0 and box.Ly > 0.0 and box.Lz > 0.0):
+            raise _lib.AzpError("StructureFactor: a 3-D box is needed (2-D systems are not supported), got %r" % (box,))
+        if not all(box.periodic):
+            raise _lib.AzpError("StructureFactor: the box has to be periodic on all three axes (the wavevectors are those "
+                                "of its lattice), got periodic = %r" % (box.periodic,))
+        key = (st.box_generation, box._key(), self._q_max, self._num_bins, self._max_per_bin, self._seed, st.device)
+        if self._set is None or self._set[0] != key:
+            m, bins = structure_factor_vectors(box, self._q_max, self._num_bins, self._max_per_bin, self._seed)
+            if len(m) == 0:
+                raise _lib.AzpError("StructureFactor: q_max = %r is below the smallest |q| of the box: no wavevector" % (self._q_max,))
+            triples = torch.from_numpy(np.ascontiguousarray(m, dtype=np.int32)).to(st.device)
+            self._set = (key, m, bins, triples, tuple(int(x) for x in np.abs(m).max(axis=0)))
+        return self._set[1:]
+
+    def _row_width(self):
+        return 4 * len(self._vector_set()[0]) + 4
+
+    def _type_masks(self, st):
+        import torch
+
+        if self._masks is None or self._masks[0] != st.types or self._masks[3] != st.device:
+            m = [None if isinstance(f, All) else torch.from_numpy(f.mask(st.types)).to(st.device) for f in (self._filter, self._filter_b)]
+            self._masks = (list(st.types), m[0], m[1], st.device)
+        return self._masks[1], self._masks[2]
+
+    # -- one launch ----------------------------------------------------------
+    def _launch(self, d_out):
+        """Queue ``azp_structure_factor_amplitudes`` for the simulation's current state with the ``4 n + 4`` doubles
+        going to ``d_out``."""
+        import torch
+
+        st = self._sim.state
+        m, _, triples, m_max = self._vector_set()
+        a = _lib.StructureFactorArgs()
+        a.d_pos = st.pos.data_ptr()
+        a.N = st.N
+        a.ntypes = len(st.types)
+        a.box = st.box.to_c()
+        mask_a, mask_b = self._type_masks(st)
+        a.d_type_mask_a = mask_a.data_ptr() if mask_a is not None else None
+        a.d_type_mask_b = mask_b.data_ptr() if mask_b is not None else None
+        a.same_groups = 1 if self._filter == self._filter_b else 0
+        a.n_vectors = len(m)
+        a.d_vectors = triples.data_ptr()
+        for d in range(3):
+            a.m_max[d] = m_max[d]
+        a.path = self._path
+        lib = _lib.lib()
+        need = C.c_uint64(0)
+        _lib.check(lib.azp_structure_factor_scratch_size(C.byref(a), C.byref(need)), "azp_structure_factor_scratch_size")
+        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
+            # (sized for this N, vector count and group pair: grown when any of them asks for more)
+            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
+        a.d_scratch = self._scratch.data_ptr()
+        a.scratch_bytes = self._scratch.numel()
+        a.d_out = d_out
+        _lib.check(lib.azp_structure_factor_amplitudes(C.byref(a), _lib.raw_stream(st.device)), "azp_structure_factor_amplitudes")
+
+    def _reduce(self, rows):
+        """Rows of per-rank sums (a (k, 4 n + 4) float64 device tensor) added over the ranks of a decomposed run, as
+        numpy."""
+        dom = self._sim.domain
+        if dom is not None:
+            rows = _all_reduce_sum(dom, rows.clone())
+        return rows.cpu().numpy()
+
+    def _read(self, name):
+        import torch
+
+        if not self._attached:
+            raise DataAccessError(name)
+        st = self._sim.state
+        width = self._row_width()
+        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
+            self._row = torch.empty((1, width), dtype=torch.float64, device=st.device)
+        self._launch(self._row.data_ptr())
+        return self._reduce(self._row)[0]
+
+    @property
+    def vectors(self):
+        """numpy int64 (n, 3): the integer triples m = (h, k, l), ordered by (l, k, h)."""
+        return self._vector_set("vectors")[0].copy()
+
+    @property
+    def q_vectors(self):
+        """numpy float64 (n, 3): q(m) = 2 pi H^-T m."""
+        m = self._vector_set("q_vectors")[0]
+        return reciprocal_vectors(self._sim.state.box, m)
+
+    @property
+    def q(self):
+        """numpy float64 (n,): the lengths |q(m)|."""
+        m = self._vector_set("q")[0]
+        v = reciprocal_vectors(self._sim.state.box, m)
+        return np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+
+    @property
+    def vectors_per_bin(self):
+        """numpy int64 (num_bins,): the vectors of each |q| bin."""
+        return np.bincount(self._vector_set("vectors_per_bin")[1], minlength=self._num_bins).astype(np.int64)
+
+    @property
+    def amplitudes(self):
+        """numpy complex128 (2, n): rho_A(m) and rho_B(m)."""
+        row = self._read("amplitudes")
+        n = (len(row) - 4) // 4
+        return np.stack([row[:n] + 1j * row[n:2 * n], row[2 * n:3 * n] + 1j * row[3 * n:4 * n]])
+
+    @property
+    def group_sizes(self):
+        """tuple[int]: (N_A, N_B, N_AB) over the owned particles of the whole system."""
+        row = self._read("group_sizes")
+        return tuple(int(x) for x in row[-4:-1])
+
+    @property
+    def vector_structure_factor(self):
+        """numpy float64 (n,): S_AB(m) of every vector."""
+        row = self._read("vector_structure_factor")
+        return structure_factor_from_amplitudes(row, (len(row) - 4) // 4)
+
+    @property
+    def structure_factor(self):
+        """numpy float64 (num_bins,): the mean of S_AB(m) over the vectors of each |q| bin, NaN in an empty bin."""
+        row = self._read("structure_factor")
+        s = structure_factor_from_amplitudes(row, (len(row) - 4) // 4)
+        return spherical_average(s, self._vector_set()[1], self._num_bins)[0]
+
+
+class StructureFactorRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) that appends the amplitudes of ``sf`` (a ``StructureFactor`` in ``computes`` of
+    the same simulation) to a device table of ``4 n + 4`` doubles per row at the timesteps ``trigger`` (an ``int``
+    period or a ``Periodic``) fires, as ``RDFRecorder`` does with its counts: the kernel writes row k itself, nothing
+    is read back and the host does not wait; the trajectory is the same bit for bit with and without the recorder.
+    Read after the run: ``timesteps``, ``amplitudes`` (frames, 2, n), ``structure_factor`` (frames, num_bins) and
+    ``mean_structure_factor`` (num_bins,): S_AB(m) averaged over the frames, then over each bin's vectors. On a
+    decomposed run the whole table is reduced once, when it is read. All rows belong to ONE box: the |q| of a fixed m
+    changes with the box, so a record in a box different from the first row's (``update.BoxResize``,
+    ``ConstantPressure``), like a row width that changes, raises ``AzpError``; ``reset()`` forgets the recorded frames."""
+
+    def __init__(self, sf, trigger):
+        if not isinstance(sf, StructureFactor):
+            raise _lib.AzpError("StructureFactorRecorder: sf must be a StructureFactor, got %r" % (sf,))
+        self.sf = sf
+        self._box_key = None
+        super().__init__(trigger)
+
+    @property
+    def _compute(self):
+        return self.sf
+
+    def _row_width(self):
+        return self.sf._row_width()
+
+    def _record(self, sim, timestep):
+        key = sim.state.box._key()
+        if self._steps and key != self._box_key:
+            raise _lib.AzpError("StructureFactorRecorder: the box changed with rows recorded (the wavevectors of the first "
+                                "row are not those of %r); call reset() first" % (sim.state.box,))
+        super()._record(sim, timestep)
+        self._box_key = key
+
+    def reset(self):
+        self._rows = None
+        self._steps = []
+        self._volumes = []
+        self._box_key = None
+
+    def _table(self, name):
+        k = len(self._steps)
+        if k == 0:
+            return np.zeros((0, 4), dtype=np.float64)
+        if not self.sf._attached:
+            raise DataAccessError(name)
+        return self.sf._reduce(self._rows[:k])
+
+    @property
+    def amplitudes(self):
+        """numpy complex128 (frames, 2, n)."""
+        t = self._table("amplitudes")
+        n = (t.shape[1] - 4) // 4
+        return np.stack([t[:, :n] + 1j * t[:, n:2 * n], t[:, 2 * n:3 * n] + 1j * t[:, 3 * n:4 * n]], axis=1)
+
+    def _per_vector(self, name):
+        t = self._table(name)
+        n = (t.shape[1] - 4) // 4
+        return np.array([structure_factor_from_amplitudes(r, n) for r in t]).reshape(t.shape[0], n)
+
+    @property
+    def structure_factor(self):
+        """numpy float64 (frames, num_bins): each frame with its own group sizes."""
+        s = self._per_vector("structure_factor")
+        nb = self.sf.num_bins
+        if s.shape[0] == 0:
+            return np.zeros((0, nb))
+        bins = self.sf._vector_set()[1]
+        return np.stack([spherical_average(r, bins, nb)[0] for r in s])
+
+    @property
+    def mean_structure_factor(self):
+        """numpy float64 (num_bins,): the mean of S_AB(m) over the frames, then over each bin's vectors."""
+        s = self._per_vector("mean_structure_factor")
+        nb = self.sf.num_bins
+        if s.shape[0] == 0:
+            return np.full(nb, np.nan)
+        return spherical_average(s.mean(axis=0), self.sf._vector_set()[1], nb)[0]
+
+
 __all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute",
            "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder", "distribution_from_counts",
-           "RadialDistributionFunction", "ThermodynamicQuantities", "ThermodynamicRecorder", "VelocityCompute",
-           "VelocityFieldCompute", "perpendicular_widths", "rdf_from_counts", "thermo_quantities"]
+           "RadialDistributionFunction", "StructureFactor", "StructureFactorRecorder", "ThermodynamicQuantities",
+           "ThermodynamicRecorder", "VelocityCompute", "VelocityFieldCompute", "perpendicular_widths", "rdf_from_counts",
+           "reciprocal_vectors", "spherical_average", "structure_factor_from_amplitudes", "structure_factor_vectors",
+           "thermo_quantities"]

@@ -1569,6 +1569,71 @@ typedef struct azp_bonded_histogram_args
 
 int azp_bonded_histogram(const azp_bonded_histogram_args* args, void* stream);
 
+/* ---- static structure factor (compute.StructureFactor) ----
+ * Not part of the reference; the semantics are DEFINED HERE. For a 3-D box periodic on all three axes with
+ * lattice matrix H (columns a_1 = (Lx, 0, 0), a_2 = (xy Ly, Ly, 0), a_3 = (xz Lz, yz Lz, Lz)) the wavevectors are
+ * q(m) = 2 pi H^-T m for integer triples m = (h, k, l), so that q . r = 2 pi m . f with f the coordinates along the
+ * lattice vectors (f in [-0.5, 0.5) for a wrapped particle; csrc/cell_bin.hpp fractional()). For two groups A and B
+ * (d_type_mask_a / d_type_mask_b: one byte per type, NULL = every particle; the groups may overlap) the amplitude of a
+ * group is
+ *   rho_G(m) = sum over rows j < N of G of exp(-2 pi i m . f_j)           (ghost rows, >= N, are never read)
+ * and the partial structure factor (Ashcroft-Langreth) S_AB(m) = Re[rho_A(m) conj(rho_B(m))] / sqrt(N_A N_B)
+ * (compute.structure_factor_from_amplitudes). Which vectors, and how S_AB(m) is averaged over |q|, is the caller's
+ * matter (compute.StructureFactor: one of each +-pair with |q| < q_max, order (l, k, h)).
+ * azp_structure_factor_amplitudes OVERWRITES the 4 n_vectors + 4 doubles at d_out (uninitialised memory is fine):
+ * Re rho_A[0 .. n), Im rho_A[0 .. n), Re rho_B[0 .. n), Im rho_B[0 .. n), then N_A, N_B, N_(A and B) over rows [0, N)
+ * and one zero. same_groups != 0: B is A (d_type_mask_b is not looked at), the B half is the copy of the A half and is
+ * computed once. Asynchronous on `stream`, no host synchronisation, no readback.
+ * path: 1 = direct, t = h f_x + k f_y + l f_z and sincospi(2 t) per (particle, vector); 2 = powers, the term is the
+ * product e_x^h e_y^k e_z^l of per-particle tables in LDS that are built by repeated complex multiplication from the
+ * three base phasors sincospi(2 f) -- it needs m_max, the caller's bound of |h|, |k|, |l| over the vectors, and exists
+ * where 32 (m_max[0] + m_max[1] + m_max[2] + 3, made odd) 16 <= AZP_SF_POWERS_LDS_BYTES, i.e. a sum of at most 92; 0 = automatic: THE POWERS
+ * PATH WHEREVER IT EXISTS, the direct path elsewhere (the powers path was the faster one at every probed shape at
+ * which it exists: profiles/structure_factor.md). Both paths add the same terms in the same order.
+ * Order of summation: no floating-point atomics, every order is fixed by N and n_vectors alone, two calls on one
+ * state give the same bits. One lane owns one vector; a workgroup takes a chunk of `stages` stages of 256 particles; a
+ * lane adds the terms of a stage in row order to a stage accumulator (from +0.0), the stage accumulators in turn to its
+ * chunk accumulator (from +0.0); the n_chunks chunk sums of a (vector, slot) are folded as csrc/azp_reduce.hpp does
+ * (lane l of one wave adds the partials l, l + 64, ... in turn, then the butterfly). With
+ * target = clamp(4096 / ceil(n_vectors / 256), 16, 512): stages = max(1, ceil(ceil(N / 256) / target)), n_chunks =
+ * max(1, ceil(ceil(N / 256) / stages)). ADDITION DEPTH D = 256 + stages + ceil(n_chunks / 64) + 6 (278 at N = 2^20
+ * with up to 2,048 vectors). Error of one amplitude component: at most N_G 2^-52 (c_arg |m|_1 + c_trig + D) with
+ * c_arg = pi (e_f + 1.5), e_f the rounding of fractional() in units of 2^-53 (1 in an orthorhombic box: c_arg = 7.9; it
+ * grows with the tilts and the aspect ratio), and c_trig = 4 (derived in tests/structure_factor_ref.py).
+ * d_scratch: azp_structure_factor_scratch_size bytes, (n_slots n_vectors + 3) n_chunks doubles with n_slots = 2 for
+ * same_groups and 4 otherwise.
+ * AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written: NULL args; n_vectors == 0 or >
+ * AZP_SF_MAX_VECTORS; a non-periodic axis; a box length that is not positive and finite; path > 2, or 2 where the
+ * tables do not fit (never silently replaced); a mask with ntypes == 0; a NULL d_out or d_vectors; with N > 0 a NULL
+ * d_pos or too small a scratch. N == 0: success, the row is zeroed. With path 2 a vector beyond m_max is evaluated at
+ * the clamped index (a wrong amplitude, no wild read). */
+#define AZP_SF_MAX_VECTORS 65536
+#define AZP_SF_POWERS_LDS_BYTES 49152
+#define AZP_SF_PATH_AUTO 0
+#define AZP_SF_PATH_DIRECT 1
+#define AZP_SF_PATH_POWERS 2
+
+typedef struct azp_structure_factor_args
+    {
+    const double* d_pos;          /* N x 4 at least (x, y, z, type bits) */
+    uint32_t N;                   /* owned rows */
+    uint32_t ntypes;              /* entries of the masks */
+    azp_box box;                  /* global box, periodic on all three axes */
+    const uint8_t* d_type_mask_a; /* ntypes bytes, may be NULL */
+    const uint8_t* d_type_mask_b; /* ntypes bytes, may be NULL */
+    uint32_t same_groups;         /* B is A: computed once, copied */
+    uint32_t n_vectors;           /* 1 .. AZP_SF_MAX_VECTORS */
+    const int32_t* d_vectors;     /* n_vectors x 3 (h, k, l), device memory */
+    uint32_t m_max[3];            /* bound of |h|, |k|, |l| over d_vectors (the powers path sizes its tables by it) */
+    uint32_t path;                /* 0 auto, 1 direct, 2 powers */
+    double* d_out;                /* 4 n_vectors + 4, overwritten */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_structure_factor_args;
+
+int azp_structure_factor_scratch_size(const azp_structure_factor_args* args, uint64_t* bytes);
+int azp_structure_factor_amplitudes(const azp_structure_factor_args* args, void* stream);
+
 /* ---- wall potentials (azplugins_amd.wall) ----
  * Replace the reference's legacy wall evaluators src/WallEvaluatorLJ93.h:50-150 and
  * src/WallEvaluatorColloid.h:52-195 with their instantiation src/WallPotentials.h / src/WallPotentials.cu. The two
