@@ -355,6 +355,43 @@ class RdfExclusionArgs(C.Structure):
     _fields_ = [("rdf", RdfArgs), ("d_n_excl", C.c_void_p), ("d_excl", C.c_void_p), ("excl_pitch", C.c_uint64)]
 
 
+STEINHARDT_MAX_TERMS = 4
+STEINHARDT_MAX_L = 12
+STEINHARDT_MAX_BINS = 1024
+STEINHARDT_MAX_N = 1 << 21
+STEINHARDT_AVERAGE, STEINHARDT_CONNECTIONS = 1, 2
+STEINHARDT_CONNECTION_BINS = 33
+STEINHARDT_PATH_AUTO, STEINHARDT_PATH_ALL_PAIRS, STEINHARDT_PATH_CELLS = 0, 1, 2
+
+
+class SteinhardtArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("box", Box),
+        ("d_type_mask", C.c_void_p),
+        ("r_max", C.c_double),
+        ("q_threshold", C.c_double),
+        ("solid_threshold", C.c_uint32),
+        ("n_terms", C.c_uint32),
+        ("l", C.c_uint32 * STEINHARDT_MAX_TERMS),
+        ("norm", (C.c_double * (STEINHARDT_MAX_L + 1)) * STEINHARDT_MAX_TERMS),
+        ("flags", C.c_uint32),
+        ("path", C.c_uint32),
+        ("num_bins", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("d_num_neighbors", C.c_void_p),
+        ("d_words", C.c_void_p),
+        ("d_order", C.c_void_p),
+        ("d_avg_words", C.c_void_p),
+        ("d_num_connections", C.c_void_p),
+        ("d_summary", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 BONDED_HISTOGRAM_LDS_WORDS = 16384
 BONDED_HISTOGRAM_PATH_AUTO, BONDED_HISTOGRAM_PATH_LDS, BONDED_HISTOGRAM_PATH_GLOBAL = 0, 1, 2
 
@@ -759,6 +796,8 @@ SYMBOLS = {
     "azp_bonded_histogram": (C.c_int, [C.POINTER(BondedHistogramArgs), _VP]),
     "azp_structure_factor_scratch_size": (C.c_int, [C.POINTER(StructureFactorArgs), C.POINTER(C.c_uint64)]),
     "azp_structure_factor_amplitudes": (C.c_int, [C.POINTER(StructureFactorArgs), _VP]),
+    "azp_steinhardt_scratch_size": (C.c_int, [C.POINTER(SteinhardtArgs), C.POINTER(C.c_uint64)]),
+    "azp_steinhardt_compute": (C.c_int, [C.POINTER(SteinhardtArgs), _VP]),
     "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
     "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
     "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),

@@ -23,6 +23,11 @@ this project's); ``BondedDistributionRecorder`` is its in-run recor
 ``StructureFactor`` is the partial static structure factor S_AB(q) on the reciprocal-lattice vectors of the box, by the
 direct sum over the particles in a fixed order (``csrc/structure_factor.hip``; this project's, DESIGN 4.27);
 ``StructureFactorRecorder`` appends the density amplitudes to a device table inside ``Simulation.run``.
+
+``Steinhardt`` is the bond-orientational order q_l of every particle of a group (optionally Lechner and Dellago's
+neighbour average) and ``SolidLiquid`` ten Wolde and Frenkel's solid-bond count, from sums of spherical harmonics kept
+as integers in units of 2^-40 (``csrc/steinhardt.hip``; this project's); ``SteinhardtRecorder`` and
+``SolidLiquidRecorder`` append their summary row to a device table inside ``Simulation.run``.
 """
 
 import ctypes as C
@@ -1547,9 +1552,433 @@ class StructureFactorRecorder(_Recorder):
         return spherical_average(s.mean(axis=0), self.sf._vector_set()[1], nb)[0]
 
 
+# ---------------------------------------------------------------------------
+# bond-orientational order
+# ---------------------------------------------------------------------------
+STEINHARDT_FIXED = float(1 << 40)  # the fixed-point unit of the q_lm words is 2^-40
+
+
+def steinhardt_norms(l):
+    """``[N_l0 .. N_ll]`` with N_lm = sqrt((2l + 1) / (4 pi) (l - m)! / (l + m)!), the normalisation of the orthonormal
+    Y_lm: the ratio of the factorials exactly, then one division and one square root in double. The kernel gets these
+    numbers in its arguments and the test reference uses the same ones."""
+    import math
+    from fractions import Fraction
+
+    l = int(l)
+    return [math.sqrt(float(Fraction((2 * l + 1) * math.factorial(l - m), math.factorial(l + m))) / (4.0 * math.pi))
+            for m in range(l + 1)]
+
+
+def steinhardt_words(l):
+    """``(words, offsets)``: the int64 a particle owns for the terms ``l`` and where each term starts; component m of a
+    term sits at ``offset + 2 m`` (Re) and ``offset + 2 m + 1`` (Im)."""
+    offsets, words = [], 0
+    for x in l:
+        offsets.append(words)
+        words += 2 * (int(x) + 1)
+    return words, offsets
+
+
+def steinhardt_summary_width(n_terms, num_bins):
+    return 4 + int(n_terms) * (1 + int(num_bins)) + _lib.STEINHARDT_CONNECTION_BINS
+
+
+def steinhardt_summary(row, n_terms, num_bins):
+    """The summary row of ``azp_steinhardt_compute`` (int64) as a dict: ``num_particles`` (N_G), ``num_with_neighbors``,
+    ``sum_neighbors``, ``num_solid``, ``order_sums`` (n_terms exact integers, units of 2^-40), ``order`` (the group mean
+    per l: order_sums 2^-40 / N_G, 0 for an empty group), ``histogram`` (n_terms, num_bins) and
+    ``connection_histogram`` (33,)."""
+    row = np.asarray(row)
+    n_terms, num_bins = int(n_terms), int(num_bins)
+    if row.ndim != 1 or row.shape[0] != steinhardt_summary_width(n_terms, num_bins):
+        raise _lib.AzpError("steinhardt_summary: a row of %d words is expected for %d terms and %d bins, got shape %r"
+                            % (steinhardt_summary_width(n_terms, num_bins), n_terms, num_bins, row.shape))
+    n_g = int(row[0])
+    sums = [int(x) for x in row[4:4 + n_terms]]
+    h0 = 4 + n_terms
+    h1 = h0 + n_terms * num_bins
+    return dict(num_particles=n_g, num_with_neighbors=int(row[1]), sum_neighbors=int(row[2]), num_solid=int(row[3]),
+                order_sums=sums, order=np.array([s / STEINHARDT_FIXED / n_g if n_g else 0.0 for s in sums]),
+                histogram=row[h0:h1].reshape(n_terms, num_bins).astype(np.int64),
+                connection_histogram=row[h1:].astype(np.int64))
+
+
+def _check_l(name, l, single):
+    if isinstance(l, (int, np.integer)) and not isinstance(l, bool):
+        l = (l,)
+    elif single:
+        raise _lib.AzpError("%s: l must be one integer, got %r" % (name, l))
+    try:
+        l = tuple(l)
+    except TypeError:
+        raise _lib.AzpError("%s: l must be an integer or a sequence of integers, got %r" % (name, l))
+    if not 1 <= len(l) <= _lib.STEINHARDT_MAX_TERMS:
+        raise _lib.AzpError("%s: l must hold 1 to %d values, got %r" % (name, _lib.STEINHARDT_MAX_TERMS, l))
+    for x in l:
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= int(x) <= _lib.STEINHARDT_MAX_L:
+            raise _lib.AzpError("%s: every l must be an integer in 1 .. %d, got %r" % (name, _lib.STEINHARDT_MAX_L, x))
+    l = tuple(int(x) for x in l)
+    if len(set(l)) != len(l):
+        raise _lib.AzpError("%s: l holds a value twice: %r" % (name, l))
+    return l
+
+
+class _BondOrder(_Compute):
+    """What ``Steinhardt`` and ``SolidLiquid`` share: one call of ``azp_steinhardt_compute`` per read, the per-particle
+    device buffers it fills and the summary row."""
+
+    _flags = 0
+    _q_threshold = 0.0
+    _solid_threshold = 0
+
+    def __init__(self, filter, l, r_max, num_bins, single):
+        name = type(self).__name__
+        if not isinstance(filter, (All, Type)):
+            raise _lib.AzpError("%s: filter must be All() or Type(...), got %r" % (name, filter))
+        super().__init__(filter, False)
+        self._l = _check_l(name, l, single)
+        try:
+            r_max = float(r_max)
+        except (TypeError, ValueError):
+            raise _lib.AzpError("%s: r_max must be a number, got %r" % (name, r_max))
+        if not (r_max > 0.0 and np.isfinite(r_max)):
+            raise _lib.AzpError("%s: r_max must be positive, got %r" % (name, r_max))
+        self._r_max = r_max
+        if isinstance(num_bins, bool) or int(num_bins) != num_bins or not 1 <= int(num_bins) <= _lib.STEINHARDT_MAX_BINS:
+            raise _lib.AzpError("%s: num_bins must be an integer in 1 .. %d, got %r" % (name, _lib.STEINHARDT_MAX_BINS, num_bins))
+        self._num_bins = int(num_bins)
+        self.path = _lib.STEINHARDT_PATH_AUTO
+        self._out = None      # (N, device, dict of per-particle tensors)
+        self._row = None
+        self._scratch = None
+
+    @property
+    def l(self):
+        return self._l
+
+    @property
+    def r_max(self):
+        return self._r_max
+
+    @property
+    def path(self):
+        """0 (default): the cell-list kernels wherever the box allows them (orthorhombic, at least three cells of width
+        ``r_max`` on every periodic axis), the all-pairs kernels elsewhere; 1 / 2 force one of them."""
+        return self._path
+
+    @path.setter
+    def path(self, value):
+        if value not in (_lib.STEINHARDT_PATH_AUTO, _lib.STEINHARDT_PATH_ALL_PAIRS, _lib.STEINHARDT_PATH_CELLS):
+            raise _lib.AzpError("%s: path must be 0 (auto), 1 (all-pairs) or 2 (cells), got %r" % (type(self).__name__, value))
+        self._path = int(value)
+
+    def _row_width(self):
+        return steinhardt_summary_width(len(self._l), self._num_bins)
+
+    def _check_box(self, sim):
+        name = type(self).__name__
+        if sim.domain is not None:
+            raise _lib.AzpError("%s: decomposed runs are not supported (the second pass would need the q_lm of the ghost "
+                                "particles)" % name)
+        box = sim.state.box
+        widths = perpendicular_widths(box)
+        for d in range(3):
+            if not widths[d] > 0.0:
+                raise _lib.AzpError("%s: a 3-D box is needed (2-D systems are not supported), got %r" % (name, box))
+            if box.periodic[d] and self._r_max > 0.5 * widths[d]:
+                raise _lib.AzpError("%s: r_max = %r is larger than half the perpendicular width %r of periodic axis %d: the "
+                                    "minimum image would not be unique" % (name, self._r_max, widths[d], d))
+
+    def _args(self, st):
+        a = _lib.SteinhardtArgs()
+        a.N = st.N
+        a.ntypes = len(st.types)
+        a.box = st.box.to_c()
+        a.r_max = self._r_max
+        a.q_threshold = self._q_threshold
+        a.solid_threshold = self._solid_threshold
+        a.n_terms = len(self._l)
+        for t, l in enumerate(self._l):
+            a.l[t] = l
+            for m, v in enumerate(steinhardt_norms(l)):
+                a.norm[t][m] = v
+        a.flags = self._flags
+        a.path = self._path
+        a.num_bins = self._num_bins
+        return a
+
+    def _launch(self, d_out):
+        """Queue ``azp_steinhardt_compute`` for the simulation's current state with the summary row going to ``d_out``;
+        the per-particle results go to this compute's own buffers."""
+        import torch
+
+        sim = self._sim
+        st = sim.state
+        self._check_box(sim)
+        a = self._args(st)
+        if st.N > _lib.STEINHARDT_MAX_N:
+            raise _lib.AzpError("%s: %d particles are more than the %d the fixed-point sums are sized for"
+                                % (type(self).__name__, st.N, _lib.STEINHARDT_MAX_N))
+        a.d_pos = st.pos.data_ptr()
+        mask = self._type_mask(st)
+        a.d_type_mask = mask.data_ptr() if mask is not None else None
+        words = steinhardt_words(self._l)[0]
+        if self._out is None or self._out[0] != st.N or self._out[1] != st.device:
+            def buf(shape, dtype):
+                return torch.empty(shape, dtype=dtype, device=st.device)
+
+            n = max(st.N, 1)
+            self._out = (st.N, st.device, dict(
+                num_neighbors=buf((n,), torch.int32), words=buf((n, words), torch.int64),
+                order=buf((n, len(self._l)), torch.float64),
+                avg_words=buf((n, words), torch.int64) if self._flags & _lib.STEINHARDT_AVERAGE else None,
+                num_connections=buf((n,), torch.int32) if self._flags & _lib.STEINHARDT_CONNECTIONS else None))
+        out = self._out[2]
+        a.d_num_neighbors = out["num_neighbors"].data_ptr()
+        a.d_words = out["words"].data_ptr()
+        a.d_order = out["order"].data_ptr()
+        a.d_avg_words = out["avg_words"].data_ptr() if out["avg_words"] is not None else None
+        a.d_num_connections = out["num_connections"].data_ptr() if out["num_connections"] is not None else None
+        lib = _lib.lib()
+        need = C.c_uint64(0)
+        _lib.check(lib.azp_steinhardt_scratch_size(C.byref(a), C.byref(need)), "azp_steinhardt_scratch_size")
+        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
+            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
+        a.d_scratch = self._scratch.data_ptr()
+        a.scratch_bytes = self._scratch.numel()
+        a.d_summary = d_out
+        _lib.check(lib.azp_steinhardt_compute(C.byref(a), _lib.raw_stream(st.device)), "azp_steinhardt_compute")
+
+    def _read(self, name):
+        """One call on the current state, then ``name`` as numpy: ``summary`` (the row), ``num_neighbors``, ``qlm`` (the
+        fixed-point words S, (N, words) int64), ``qlm_average`` (T), ``order`` (N, len(l)) or ``num_connections``."""
+        import torch
+
+        if not self._attached:
+            raise DataAccessError(name)
+        st = self._sim.state
+        width = self._row_width()
+        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
+            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
+        self._launch(self._row.data_ptr())
+        if name == "summary":
+            return self._row.cpu().numpy()[0]
+        key = {"qlm": "words", "qlm_average": "avg_words"}.get(name, name)
+        t = self._out[2].get(key)
+        if t is None:
+            raise _lib.AzpError("%s: %s is not computed by this compute" % (type(self).__name__, name))
+        return t[: st.N].cpu().numpy()
+
+    def _summary(self, name="summary"):
+        if not self._attached:
+            raise DataAccessError(name)
+        return steinhardt_summary(self._read("summary"), len(self._l), self._num_bins)
+
+    @property
+    def num_neighbors(self):
+        """numpy int32 (N,): N_b per row, 0 outside the group."""
+        return self._read("num_neighbors")
+
+    @property
+    def num_particles(self):
+        """int: the size of the group."""
+        return self._summary("num_particles")["num_particles"]
+
+
+class Steinhardt(_BondOrder):
+    """Steinhardt's bond-orientational order parameters q_l of the particles selected by ``filter`` (``All()`` or
+    ``Type(...)``) of a 3-D system, for ``l`` = one integer or up to 4 distinct ones in 1 .. 12 (freud's
+    ``order.Steinhardt``; semantics: DESIGN 4.28). The neighbours of a particle are the particles of the group closer
+    than ``r_max`` (minimum image, ``rsq < r_max^2`` as ``RadialDistributionFunction``); q_lm(i) is the mean of
+    Y_lm over its bonds and q_l(i) = sqrt(4 pi / (2l + 1) sum_m |q_lm|^2). ``average=True`` gives Lechner and Dellago's
+    form: q_lm averaged over the particle and its neighbours before the norm is taken.
+
+    The sums over the bonds are kept as integers in units of 2^-40 (``_read("qlm")``), so they do not depend on the
+    order of summation: two reads of one state agree bit for bit, on either path, before and after the particle sorter.
+
+    ``num_neighbors`` (N,), ``particle_order`` (N, len(l)), row order like ``Force.forces``, rows outside the group 0;
+    ``order`` the group mean per l; ``histogram`` (len(l), num_bins) of ``particle_order`` over the group on [0, 1] with
+    ``bin_edges``. Every property is computed when it is read, from the current state. Refused with ``AzpError``: a
+    bad ``l``, ``r_max <= 0``, ``num_bins`` outside 1 .. 1024, a filter that is not ``All()`` or ``Type(...)``; when
+    read: ``r_max`` above half a periodic perpendicular width, a forced ``path`` the box does not allow, a decomposed
+    run."""
+
+    def __init__(self, filter, l, r_max, average=False, num_bins=100):
+        super().__init__(filter, l, r_max, num_bins, single=False)
+        self._average = bool(average)
+        self._flags = _lib.STEINHARDT_AVERAGE if self._average else 0
+
+    @property
+    def average(self):
+        return self._average
+
+    @property
+    def num_bins(self):
+        return self._num_bins
+
+    @property
+    def bin_edges(self):
+        """numpy.ndarray: the ``num_bins + 1`` edges of the histogram's bins on [0, 1]."""
+        return np.linspace(0.0, 1.0, self._num_bins + 1)
+
+    @property
+    def particle_order(self):
+        """numpy float64 (N, len(l)): q_l per row (the neighbour-averaged one with ``average=True``)."""
+        return self._read("order")
+
+    @property
+    def order(self):
+        """numpy float64 (len(l),): the mean of ``particle_order`` over the group, from the summary row."""
+        return self._summary("order")["order"]
+
+    @property
+    def histogram(self):
+        """numpy int64 (len(l), num_bins)."""
+        return self._summary("histogram")["histogram"]
+
+
+class SolidLiquid(_BondOrder):
+    """ten Wolde and Frenkel's solid-bond count for one ``l`` (freud's ``order.SolidLiquid`` without the clusters;
+    DESIGN 4.28): the bond between neighbours i and j is solid iff the normalised product
+    d(i, j) = Re sum_m q_lm(i) conj(q_lm(j)) / (|q(i)| |q(j)|) exceeds ``q_threshold``; ``num_connections`` (N,) counts a
+    particle's solid bonds and the particle is ``solid`` iff that is at least ``solid_threshold``. ``num_solid`` and
+    ``connection_histogram`` (33 words, the last for 32 and more) come from the summary row. Refused with ``AzpError``:
+    what ``Steinhardt`` refuses, an ``l`` that is not one integer, a ``q_threshold`` outside [-1, 1], a
+    ``solid_threshold`` that is not a positive integer."""
+
+    _flags = _lib.STEINHARDT_CONNECTIONS
+
+    def __init__(self, filter, l, r_max, q_threshold, solid_threshold):
+        super().__init__(filter, l, r_max, 1, single=True)
+        try:
+            q = float(q_threshold)
+        except (TypeError, ValueError):
+            raise _lib.AzpError("SolidLiquid: q_threshold must be a number, got %r" % (q_threshold,))
+        if not -1.0 <= q <= 1.0:
+            raise _lib.AzpError("SolidLiquid: q_threshold must lie in [-1, 1], got %r" % (q_threshold,))
+        if (isinstance(solid_threshold, bool) or not isinstance(solid_threshold, (int, np.integer))
+                or not 1 <= int(solid_threshold) < (1 << 31)):
+            raise _lib.AzpError("SolidLiquid: solid_threshold must be a positive integer, got %r" % (solid_threshold,))
+        self._q_threshold = q
+        self._solid_threshold = int(solid_threshold)
+
+    @property
+    def q_threshold(self):
+        return self._q_threshold
+
+    @property
+    def solid_threshold(self):
+        return self._solid_threshold
+
+    @property
+    def num_connections(self):
+        """numpy int32 (N,): solid bonds per row, 0 outside the group."""
+        return self._read("num_connections")
+
+    @property
+    def solid(self):
+        """numpy bool (N,): in the group and ``num_connections >= solid_threshold``."""
+        return self._read("num_connections") >= self._solid_threshold  # (a row outside the group has none, the threshold is >= 1)
+
+    @property
+    def num_solid(self):
+        return self._summary("num_solid")["num_solid"]
+
+    @property
+    def connection_histogram(self):
+        """numpy int64 (33,): particles of the group by ``num_connections``, the last word for 32 and more."""
+        return self._summary("connection_histogram")["connection_histogram"]
+
+
+class _BondOrderRecorder(_Recorder):
+    """The summary row of a ``Steinhardt`` or a ``SolidLiquid`` appended to a device table at the timesteps the trigger
+    fires inside ``Simulation.run``, as ``RDFRecorder`` does with its counts: the last kernel of the call writes row k
+    itself, nothing is read back, the host does not wait, and the trajectory is the same bit for bit with and without
+    the recorder."""
+
+    _dtype = "int64"
+    _kind = _BondOrder
+
+    def __init__(self, compute, trigger):
+        if not isinstance(compute, self._kind):
+            raise _lib.AzpError("%s: a %s is expected, got %r" % (type(self).__name__, self._kind.__name__, compute))
+        self._target = compute
+        super().__init__(trigger)
+
+    @property
+    def _compute(self):
+        return self._target
+
+    def _row_width(self):
+        return self._target._row_width()
+
+    def reset(self):
+        """Forget the recorded rows."""
+        self._rows = None
+        self._steps = []
+        self._volumes = []
+
+    def _table(self):
+        c = self._target
+        k = len(self._steps)
+        rows = self._rows[:k].cpu().numpy() if k else np.zeros((0, self._row_width()), dtype=np.int64)
+        return [steinhardt_summary(r, len(c.l), c._num_bins) for r in rows]
+
+    @property
+    def num_particles(self):
+        """numpy int64 (frames,): the size of the group."""
+        return np.array([r["num_particles"] for r in self._table()], dtype=np.int64)
+
+
+class SteinhardtRecorder(_BondOrderRecorder):
+    """Writer (``sim.operations.writers``) for a ``Steinhardt`` in ``computes`` of the same simulation. Read after the
+    run: ``timesteps``, ``order`` (frames, len(l)), ``histogram`` (frames, len(l), num_bins), ``num_particles``;
+    ``reset()`` forgets the frames."""
+
+    _kind = Steinhardt
+
+    def __init__(self, steinhardt, trigger):
+        super().__init__(steinhardt, trigger)
+        self.steinhardt = steinhardt
+
+    @property
+    def order(self):
+        t = self._table()
+        return np.array([r["order"] for r in t]).reshape(len(t), len(self._target.l))
+
+    @property
+    def histogram(self):
+        t = self._table()
+        c = self._target
+        return np.array([r["histogram"] for r in t], dtype=np.int64).reshape(len(t), len(c.l), c.num_bins)
+
+
+class SolidLiquidRecorder(_BondOrderRecorder):
+    """Writer (``sim.operations.writers``) for a ``SolidLiquid`` in ``computes`` of the same simulation. Read after the
+    run: ``timesteps``, ``num_solid`` (frames,), ``connection_histogram`` (frames, 33), ``num_particles``; ``reset()``
+    forgets the frames."""
+
+    _kind = SolidLiquid
+
+    def __init__(self, solid_liquid, trigger):
+        super().__init__(solid_liquid, trigger)
+        self.solid_liquid = solid_liquid
+
+    @property
+    def num_solid(self):
+        return np.array([r["num_solid"] for r in self._table()], dtype=np.int64)
+
+    @property
+    def connection_histogram(self):
+        t = self._table()
+        return np.array([r["connection_histogram"] for r in t], dtype=np.int64).reshape(len(t), _lib.STEINHARDT_CONNECTION_BINS)
+
+
 __all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute",
            "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder", "distribution_from_counts",
-           "RadialDistributionFunction", "StructureFactor", "StructureFactorRecorder", "ThermodynamicQuantities",
+           "RadialDistributionFunction", "SolidLiquid", "SolidLiquidRecorder", "Steinhardt", "SteinhardtRecorder",
+           "StructureFactor", "StructureFactorRecorder", "ThermodynamicQuantities",
            "ThermodynamicRecorder", "VelocityCompute", "VelocityFieldCompute", "perpendicular_widths", "rdf_from_counts",
-           "reciprocal_vectors", "spherical_average", "structure_factor_from_amplitudes", "structure_factor_vectors",
-           "thermo_quantities"]
+           "reciprocal_vectors", "spherical_average", "steinhardt_norms", "steinhardt_summary", "steinhardt_words",
+           "structure_factor_from_amplitudes", "structure_factor_vectors", "thermo_quantities"]

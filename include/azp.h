@@ -1634,6 +1634,87 @@ typedef struct azp_structure_factor_args
 int azp_structure_factor_scratch_size(const azp_structure_factor_args* args, uint64_t* bytes);
 int azp_structure_factor_amplitudes(const azp_structure_factor_args* args, void* stream);
 
+/* ---- bond-orientational order (compute.Steinhardt, compute.SolidLiquid) ----
+ * Not part of the reference; the semantics are DEFINED HERE. Steinhardt's q_l, Lechner and Dellago's
+ * neighbour average and ten Wolde and Frenkel's solid-bond count, for the rows [0, N) of a 3-D box.
+ * Group and neighbours: G = the rows whose type has a non-zero byte in d_type_mask (NULL: every row). The neighbours of
+ * i in G are the j in G, j != i, with rsq < r_max * r_max, where (dx, dy, dz) = r_i - r_j goes through the minimum image
+ * of the force kernels and rsq = dx dx + dy dy + dz dz: the acceptance rule of azp_rdf_counts. N_b(i) is their number,
+ * 0 for a row outside G. The bond is r_ij = -(dx, dy, dz), from i to j.
+ * First pass: for term t (l = l[t]) and m = 0 .. l
+ *   S_lm(i) = sum over the neighbours j of ( llrint(Re Y_lm(r_ij) 2^40), llrint(Im Y_lm(r_ij) 2^40) )   two int64
+ * with the orthonormal Y_lm in the Condon-Shortley phase; Y_l,-m = (-1)^m conj(Y_lm) is never stored. A row owns
+ * `words` = sum_t 2 (l[t] + 1) int64: term t from offset sum_{s<t} 2 (l[s] + 1), component m at + 2 m (Re), + 2 m + 1
+ * (Im, 0 for m = 0). Y_lm = N_lm Q_l^m(z / r) ((x + i y) / r)^m with r = sqrt(rsq) and IEEE quotients, Q_l^m = P_l^m /
+ * (1 - z^2)^(m / 2) by the upward recurrence Q_m^m = (-1)^m (2m - 1)!!, (l + 1 - m) Q_(l+1)^m = (2l + 1) z Q_l^m -
+ * (l + m) Q_(l-1)^m (csrc/steinhardt_device.hpp: no trigonometry, no pole). norm[t][m] = N_lm = sqrt((2l + 1) / (4 pi)
+ * (l - m)! / (l + m)!) comes from the caller. A bond with rsq == 0 counts in N_b and adds no term. The sums are
+ * integers: they do not depend on the order of the additions, two calls give the same bits on either path, and a
+ * particle keeps its words when the rows are re-ordered. |Y| <= 1.41 and N <= 2^21 keep |S| below 2^62.
+ * Finish: q_lm(i) = double(S_lm) 2^-40 / N_b(i), 0 where N_b == 0; q_l(i) = sqrt(4 pi / (2l + 1) (|q_l0|^2 +
+ * 2 sum_{m>0} |q_lm|^2)), added in the order m = 0, 1, ...
+ * AZP_STEINHARDT_AVERAGE: T_lm(i) = sum over k in {i} and the neighbours of i of llrint(q_lm(k) 2^40) for i in G (0
+ * elsewhere), qbar_lm = double(T) 2^-40 / (N_b(i) + 1), qbar_l from qbar_lm as q_l from q_lm.
+ * AZP_STEINHARDT_CONNECTIONS (n_terms == 1): with |q(i)| = sqrt(sum_{m=-l..l} |q_lm(i)|^2),
+ *   d(i, j) = Re sum_{m=-l..l} q_lm(i) conj(q_lm(j)) / (|q(i)| |q(j)|)
+ * the bond to neighbour j is solid iff d > q_threshold, never where either norm is 0; num_connections(i) is their
+ * number and i is solid iff i is in G and num_connections(i) >= solid_threshold.
+ * Outputs, all OVERWRITTEN (uninitialised memory is fine), per row of [0, N): d_num_neighbors, d_words (S), d_order
+ * (n_terms doubles: q_l, or qbar_l with AVERAGE; 0 outside G), d_avg_words (T, AVERAGE only), d_num_connections
+ * (CONNECTIONS only). d_summary: 4 + n_terms (1 + num_bins) + 33 int64, written by the last kernel with 64-bit integer
+ * atomics: N_G; the number of rows of G with N_b > 0; sum of N_b; N_solid (0 without CONNECTIONS); per term
+ * sum_{i in G} llrint(d_order 2^40); per term a histogram of d_order over G in num_bins bins on [0, 1], k =
+ * min((uint32_t)(q num_bins), num_bins - 1); 33 words of histogram of num_connections over G, the last for >= 32
+ * (zeros without CONNECTIONS).
+ * path: 0 = automatic (the cells wherever they are valid), 1 = all-pairs (any box), 2 = cells (orthorhombic box with at
+ * least three cells of width >= r_max on every periodic axis, the grid rule of azp_rdf_counts). Both give the same
+ * integers. The particles are binned by the counting sort of the neighbor list in the call's own scratch; candidates
+ * are staged through LDS; every accumulation is integer (LDS 64-bit integer atomics); no floating-point atomics.
+ * Asynchronous on `stream`: nothing is read back, nothing synchronises. d_scratch: azp_steinhardt_scratch_size bytes.
+ * AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written: NULL args; r_max not positive and finite;
+ * n_terms outside 1 .. AZP_STEINHARDT_MAX_TERMS; an l outside 1 .. AZP_STEINHARDT_MAX_L or given twice; a norm outside
+ * (0, 2); unknown flags; CONNECTIONS with n_terms != 1 or a q_threshold that is not finite; num_bins outside 1 ..
+ * AZP_STEINHARDT_MAX_BINS; N > 2^21; a box length that is not positive; r_max larger than half the perpendicular width
+ * of a periodic axis; path > 2, or 2 where the cells are not valid (never silently replaced); a mask with ntypes == 0;
+ * a NULL output that the flags ask for; with N > 0 a NULL d_pos or too small a scratch. N == 0: the summary is zeroed. */
+#define AZP_STEINHARDT_MAX_TERMS 4
+#define AZP_STEINHARDT_MAX_L 12
+#define AZP_STEINHARDT_MAX_BINS 1024
+#define AZP_STEINHARDT_MAX_N (1u << 21)
+#define AZP_STEINHARDT_AVERAGE 1u
+#define AZP_STEINHARDT_CONNECTIONS 2u
+#define AZP_STEINHARDT_CONNECTION_BINS 33
+
+typedef struct azp_steinhardt_args
+    {
+    const double* d_pos;          /* N x 4 (x, y, z, type bits) */
+    uint32_t N;
+    uint32_t ntypes;              /* entries of the mask */
+    azp_box box;
+    const uint8_t* d_type_mask;   /* ntypes bytes, may be NULL */
+    double r_max;
+    double q_threshold;           /* CONNECTIONS */
+    uint32_t solid_threshold;     /* CONNECTIONS */
+    uint32_t n_terms;
+    uint32_t l[AZP_STEINHARDT_MAX_TERMS];
+    double norm[AZP_STEINHARDT_MAX_TERMS][AZP_STEINHARDT_MAX_L + 1];
+    uint32_t flags;
+    uint32_t path;                /* 0 auto, 1 all-pairs, 2 cells */
+    uint32_t num_bins;
+    uint32_t _pad;
+    uint32_t* d_num_neighbors;    /* N */
+    int64_t* d_words;             /* N x words */
+    double* d_order;              /* N x n_terms */
+    int64_t* d_avg_words;         /* N x words, AVERAGE */
+    uint32_t* d_num_connections;  /* N, CONNECTIONS */
+    int64_t* d_summary;           /* 4 + n_terms (1 + num_bins) + 33 */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_steinhardt_args;
+
+int azp_steinhardt_scratch_size(const azp_steinhardt_args* args, uint64_t* bytes);
+int azp_steinhardt_compute(const azp_steinhardt_args* args, void* stream);
+
 /* ---- wall potentials (azplugins_amd.wall) ----
  * Replace the reference's legacy wall evaluators src/WallEvaluatorLJ93.h:50-150 and
  * src/WallEvaluatorColloid.h:52-195 with their instantiation src/WallPotentials.h / src/WallPotentials.cu. The two
