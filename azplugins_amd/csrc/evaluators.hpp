@@ -528,7 +528,7 @@ struct EvalTable
 
 // ---------------------------------------------------------------------------
 // XPLOR smoothing applied around any isotropic evaluator (HOOMD PotentialPair
-// restated; not pinned by a reference test).
+// restated; pinned against HOOMD's documented S(r) in closed form, tests/test_gpu_evaluator_cases.py).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void apply_xplor(double rsq, double ronsq, double rcutsq, double& force_divr,
                                             double& pair_eng)

@@ -253,6 +253,20 @@ def lattice_config(n_side, a, jitter, seed, ntypes=1, L_scale=None):
     return syn.pos4(xyz, typeid), L, typeid
 
 
+def _isolated_pairs(r_values, gap=40.0):
+    """2 n particles: pair k sits at y = k * gap, separated by r_k along x."""
+    n = len(r_values)
+    xyz = np.zeros((2 * n, 3))
+    xyz[0::2, 0] = -0.5 * r_values
+    xyz[1::2, 0] = 0.5 * r_values
+    xyz[0::2, 1] = xyz[1::2, 1] = (np.arange(n) - 0.5 * n) * gap
+    n_neigh = np.ones(2 * n, dtype=np.uint32)
+    head = np.arange(2 * n, dtype=np.uint64)
+    nlist = np.arange(2 * n, dtype=np.uint32) ^ 1
+    L = np.array([200.0, (n + 2) * gap, 200.0])
+    return syn.pos4(xyz), L, (n_neigh, head, nlist)
+
+
 def sym_table(ntypes, fn):
     """Symmetric per-type-pair table built from fn(i, j) for i <= j."""
     rows = [[None] * ntypes for _ in range(ntypes)]
