@@ -392,6 +392,34 @@ class SteinhardtArgs(C.Structure):
     ]
 
 
+CLUSTER_NONE = 0xFFFFFFFF
+CLUSTER_MAX_BINS = 1024
+CLUSTER_MAX_N = 1 << 30
+CLUSTER_PATH_AUTO, CLUSTER_PATH_ALL_PAIRS, CLUSTER_PATH_CELLS = 0, 1, 2
+
+
+class ClusterArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("box", Box),
+        ("d_type_mask", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("d_member", C.c_void_p),
+        ("member_min", C.c_uint32),
+        ("path", C.c_uint32),
+        ("r_max", C.c_double),
+        ("size_bins", C.c_uint32),
+        ("stages", C.c_uint32),
+        ("d_cluster_key", C.c_void_p),
+        ("d_cluster_size", C.c_void_p),
+        ("d_summary", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 BONDED_HISTOGRAM_LDS_WORDS = 16384
 BONDED_HISTOGRAM_PATH_AUTO, BONDED_HISTOGRAM_PATH_LDS, BONDED_HISTOGRAM_PATH_GLOBAL = 0, 1, 2
 
@@ -798,6 +826,8 @@ SYMBOLS = {
     "azp_structure_factor_amplitudes": (C.c_int, [C.POINTER(StructureFactorArgs), _VP]),
     "azp_steinhardt_scratch_size": (C.c_int, [C.POINTER(SteinhardtArgs), C.POINTER(C.c_uint64)]),
     "azp_steinhardt_compute": (C.c_int, [C.POINTER(SteinhardtArgs), _VP]),
+    "azp_cluster_scratch_size": (C.c_int, [C.POINTER(ClusterArgs), C.POINTER(C.c_uint64)]),
+    "azp_cluster_compute": (C.c_int, [C.POINTER(ClusterArgs), _VP]),
     "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
     "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
     "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),

@@ -28,6 +28,10 @@ direct sum over the particles in a fixed order (``csrc/structure_factor.hip``; t
 neighbour average) and ``SolidLiquid`` ten Wolde and Frenkel's solid-bond count, from sums of spherical harmonics kept
 as integers in units of 2^-40 (``csrc/steinhardt.hip``; this project's); ``SteinhardtRecorder`` and
 ``SolidLiquidRecorder`` append their summary row to a device table inside ``Simulation.run``.
+
+``Cluster`` is the connected components of the particles of a group closer than ``r_max`` (optionally of those a
+``SolidLiquid`` marks solid), labelled by a concurrent union-find on the device (``csrc/cluster.hip``; this project's,
+DESIGN 4.29); ``ClusterRecorder`` appends its summary row to a device table inside ``Simulation.run``.
 """
 
 import ctypes as C
@@ -1975,8 +1979,321 @@ class SolidLiquidRecorder(_BondOrderRecorder):
         return np.array([r["connection_histogram"] for r in t], dtype=np.int64).reshape(len(t), _lib.STEINHARDT_CONNECTION_BINS)
 
 
-__all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute",
-           "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder", "distribution_from_counts",
+# ---------------------------------------------------------------------------
+# clusters
+# ---------------------------------------------------------------------------
+def cluster_summary_width(size_bins):
+    return 6 + int(size_bins)
+
+
+def cluster_summary(row, size_bins):
+    """The summary row of ``azp_cluster_compute`` (int64) as a dict: ``num_particles`` (N_G), ``num_clusters``,
+    ``largest_cluster_size``, ``largest_cluster_key`` (-1 for an empty group), ``sum_size_squared``, ``num_edges`` and
+    ``size_histogram`` (size_bins,): clusters of size s at s - 1, the last word for ``size_bins`` and more."""
+    row = np.asarray(row)
+    size_bins = int(size_bins)
+    if row.ndim != 1 or row.shape[0] != cluster_summary_width(size_bins):
+        raise _lib.AzpError("cluster_summary: a row of %d words is expected for %d bins, got shape %r"
+                            % (cluster_summary_width(size_bins), size_bins, row.shape))
+    return dict(num_particles=int(row[0]), num_clusters=int(row[1]), largest_cluster_size=int(row[2]),
+                largest_cluster_key=int(row[3]), sum_size_squared=int(row[4]), num_edges=int(row[5]),
+                size_histogram=row[6:].astype(np.int64))
+
+
+def cluster_indices(keys, sizes):
+    """freud's ``cluster_idx`` from the per-row ``cluster_keys`` and ``cluster_sizes``: int64 (N,), 0 for the rows of the
+    largest cluster, 1 for the next and so on, clusters of one size in ascending order of their key, -1 for a row
+    outside the group (key ``CLUSTER_NONE``)."""
+    keys = np.asarray(keys).astype(np.int64).reshape(-1)
+    sizes = np.asarray(sizes).astype(np.int64).reshape(-1)
+    if keys.shape != sizes.shape:
+        raise _lib.AzpError("cluster_indices: keys and sizes differ in shape: %r and %r" % (keys.shape, sizes.shape))
+    idx = np.full(keys.shape, -1, dtype=np.int64)
+    inside = keys != _lib.CLUSTER_NONE
+    if inside.any():
+        uniq, first, inverse = np.unique(keys[inside], return_index=True, return_inverse=True)
+        order = np.lexsort((uniq, -sizes[inside][first]))  # by size, largest first, then by key
+        rank = np.empty(order.shape[0], dtype=np.int64)
+        rank[order] = np.arange(order.shape[0])
+        idx[inside] = rank[inverse.reshape(-1)]
+    return idx
+
+
+class Cluster(_Compute):
+    """The connected components of the particles selected by ``filter`` (``All()`` or ``Type(...)``) of a 3-D system,
+    two particles being joined where they are closer than ``r_max`` (minimum image, ``rsq < r_max^2`` as
+    ``RadialDistributionFunction`` and ``Steinhardt``); freud's ``cluster.Cluster`` on the device (semantics:
+    ``include/azp.h`` "clusters"). A particle without a neighbour is a cluster of one.
+
+    ``solid`` (a ``SolidLiquid`` in ``computes`` of the same simulation) restricts the group to the particles it marks
+    solid: every read first queues the ``SolidLiquid``'s own call and hands its ``num_connections`` buffer and its
+    ``solid_threshold`` to the kernel, nothing goes through the host. The largest cluster is then ten Wolde and
+    Frenkel's nucleus. ``r_max`` is the cluster's own and may differ from the one that defines the solid bonds.
+
+    Per row, in row order like ``Force.forces``: ``cluster_keys`` (uint32: the smallest tag of the row's cluster,
+    ``CLUSTER_NONE`` outside the group -- a label that survives the particle sorter), ``cluster_sizes`` (uint32, 0
+    outside the group), ``cluster_idx`` (freud's numbering from the two, see ``cluster_indices``). From the summary
+    row: ``num_particles``, ``num_clusters``, ``largest_cluster_size``, ``largest_cluster_key``, ``num_edges``,
+    ``mean_cluster_size`` (number average), ``weight_average_cluster_size`` (sum of size^2 over the number of
+    particles) and ``size_histogram`` (``size_bins`` words, the last for ``size_bins`` and more). All are exact integers or
+    quotients of two: two reads, the two paths and a sorted state agree bit for bit. Every property is computed when
+    it is read, from the current state. Refused with ``AzpError``: a filter that is not ``All()`` or ``Type(...)``,
+    ``r_max <= 0``, ``size_bins`` outside 1 .. 1024, a ``solid`` that is not a ``SolidLiquid``; when read: ``r_max`` above
+    half a periodic perpendicular width, a forced ``path`` the box does not allow, a decomposed run, a ``solid`` of
+    another simulation."""
+
+    def __init__(self, filter, r_max, solid=None, size_bins=64):
+        if not isinstance(filter, (All, Type)):
+            raise _lib.AzpError("Cluster: filter must be All() or Type(...), got %r" % (filter,))
+        super().__init__(filter, False)
+        try:
+            r_max = float(r_max)
+        except (TypeError, ValueError):
+            raise _lib.AzpError("Cluster: r_max must be a number, got %r" % (r_max,))
+        if not (r_max > 0.0 and np.isfinite(r_max)):
+            raise _lib.AzpError("Cluster: r_max must be positive, got %r" % (r_max,))
+        self._r_max = r_max
+        if solid is not None and not isinstance(solid, SolidLiquid):
+            raise _lib.AzpError("Cluster: solid must be a SolidLiquid or None, got %r" % (solid,))
+        self._solid = solid
+        if (isinstance(size_bins, bool) or not isinstance(size_bins, (int, np.integer))
+                or not 1 <= int(size_bins) <= _lib.CLUSTER_MAX_BINS):
+            raise _lib.AzpError("Cluster: size_bins must be an integer in 1 .. %d, got %r" % (_lib.CLUSTER_MAX_BINS, size_bins))
+        self._size_bins = int(size_bins)
+        self.path = _lib.CLUSTER_PATH_AUTO
+        self._stages = 0      # (tools/cluster_probe.py: 1 and 2 stop the call early, for timing)
+        self._out = None      # (N, device, keys, sizes)
+        self._row = None
+        self._solid_row = None
+        self._scratch = None
+
+    @property
+    def r_max(self):
+        return self._r_max
+
+    @property
+    def solid(self):
+        return self._solid
+
+    @property
+    def size_bins(self):
+        return self._size_bins
+
+    @property
+    def path(self):
+        """0 (default): the cell-list kernels wherever the box allows them (orthorhombic, at least three cells of width
+        ``r_max`` on every periodic axis), the all-pairs kernels elsewhere; 1 / 2 force one of them."""
+        return self._path
+
+    @path.setter
+    def path(self, value):
+        if isinstance(value, bool) or value not in (_lib.CLUSTER_PATH_AUTO, _lib.CLUSTER_PATH_ALL_PAIRS, _lib.CLUSTER_PATH_CELLS):
+            raise _lib.AzpError("Cluster: path must be 0 (auto), 1 (all-pairs) or 2 (cells), got %r" % (value,))
+        self._path = int(value)
+
+    def _row_width(self):
+        return cluster_summary_width(self._size_bins)
+
+    def _check_box(self, sim):
+        if sim.domain is not None:
+            raise _lib.AzpError("Cluster: decomposed runs are not supported (a cluster may span ranks)")
+        box = sim.state.box
+        widths = perpendicular_widths(box)
+        for d in range(3):
+            if not widths[d] > 0.0:
+                raise _lib.AzpError("Cluster: a 3-D box is needed (2-D systems are not supported), got %r" % (box,))
+            if box.periodic[d] and self._r_max > 0.5 * widths[d]:
+                raise _lib.AzpError("Cluster: r_max = %r is larger than half the perpendicular width %r of periodic axis %d: the "
+                                    "minimum image would not be unique" % (self._r_max, widths[d], d))
+
+    def _launch(self, d_out):
+        """Queue ``azp_cluster_compute`` for the simulation's current state with the summary row going to ``d_out``
+        (after the ``SolidLiquid``'s own call where ``solid`` is set); keys and sizes go to this compute's buffers."""
+        import torch
+
+        sim = self._sim
+        st = sim.state
+        self._check_box(sim)
+        if st.N > _lib.CLUSTER_MAX_N:
+            raise _lib.AzpError("Cluster: %d particles are more than the %d the 32-bit slots are sized for" % (st.N, _lib.CLUSTER_MAX_N))
+        solid = self._solid
+        if solid is not None and (solid._sim is not sim or not solid._attached):
+            raise _lib.AzpError("Cluster: solid must be in sim.operations.computes of the same simulation")
+        a = _lib.ClusterArgs()
+        a.N = st.N
+        a.ntypes = len(st.types)
+        a.box = st.box.to_c()
+        a.r_max = self._r_max
+        a.path = self._path
+        a.stages = self._stages
+        a.size_bins = self._size_bins
+        a.d_pos = st.pos.data_ptr()
+        a.d_tag = st.tag.data_ptr()
+        mask = self._type_mask(st)
+        a.d_type_mask = mask.data_ptr() if mask is not None else None
+        lib = _lib.lib()
+        need = C.c_uint64(0)
+        # (every refusal of the cluster's own comes before the SolidLiquid's launch)
+        _lib.check(lib.azp_cluster_scratch_size(C.byref(a), C.byref(need)), "azp_cluster_scratch_size")
+        if solid is not None:
+            width = solid._row_width()
+            if self._solid_row is None or self._solid_row.device != st.device or self._solid_row.shape[1] != width:
+                self._solid_row = torch.empty((1, width), dtype=torch.int64, device=st.device)
+            solid._launch(self._solid_row.data_ptr())
+            a.d_member = solid._out[2]["num_connections"].data_ptr()
+            a.member_min = solid.solid_threshold
+        if self._out is None or self._out[0] != st.N or self._out[1] != st.device:
+            n = max(st.N, 1)
+            self._out = (st.N, st.device, torch.empty((n,), dtype=torch.int32, device=st.device),
+                         torch.empty((n,), dtype=torch.int32, device=st.device))
+        a.d_cluster_key = self._out[2].data_ptr()
+        a.d_cluster_size = self._out[3].data_ptr()
+        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
+            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
+        a.d_scratch = self._scratch.data_ptr()
+        a.scratch_bytes = self._scratch.numel()
+        a.d_summary = d_out
+        _lib.check(lib.azp_cluster_compute(C.byref(a), _lib.raw_stream(st.device)), "azp_cluster_compute")
+
+    def _read(self, name):
+        """One call on the current state, then ``name`` as numpy: ``summary`` (the row), ``cluster_keys`` or
+        ``cluster_sizes`` (uint32), or ``both`` (keys, sizes) of that one call."""
+        import torch
+
+        if not self._attached:
+            raise DataAccessError(name)
+        st = self._sim.state
+        width = self._row_width()
+        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
+            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
+        self._launch(self._row.data_ptr())
+        if name == "summary":
+            return self._row.cpu().numpy()[0]
+        keys, sizes = (t[: st.N].cpu().numpy().view(np.uint32) for t in self._out[2:])
+        return {"cluster_keys": keys, "cluster_sizes": sizes, "both": (keys, sizes)}[name]
+
+    def _summary(self, name="summary"):
+        if not self._attached:
+            raise DataAccessError(name)
+        return cluster_summary(self._read("summary"), self._size_bins)
+
+    @property
+    def cluster_keys(self):
+        """numpy uint32 (N,): the smallest tag of the row's cluster, ``CLUSTER_NONE`` outside the group."""
+        return self._read("cluster_keys")
+
+    @property
+    def cluster_sizes(self):
+        """numpy uint32 (N,): the size of the row's cluster, 0 outside the group."""
+        return self._read("cluster_sizes")
+
+    @property
+    def cluster_idx(self):
+        """numpy int64 (N,): ``cluster_indices`` of the keys and sizes of one call."""
+        return cluster_indices(*self._read("both"))
+
+    @property
+    def num_particles(self):
+        """int: the size of the group."""
+        return self._summary("num_particles")["num_particles"]
+
+    @property
+    def num_clusters(self):
+        return self._summary("num_clusters")["num_clusters"]
+
+    @property
+    def largest_cluster_size(self):
+        return self._summary("largest_cluster_size")["largest_cluster_size"]
+
+    @property
+    def largest_cluster_key(self):
+        """int: the key of the largest cluster (the smallest key among equals), -1 for an empty group."""
+        return self._summary("largest_cluster_key")["largest_cluster_key"]
+
+    @property
+    def num_edges(self):
+        """int: pairs of the group closer than ``r_max``, each counted once."""
+        return self._summary("num_edges")["num_edges"]
+
+    @property
+    def mean_cluster_size(self):
+        """float: particles per cluster (the number average), 0 for an empty group."""
+        s = self._summary("mean_cluster_size")
+        return s["num_particles"] / s["num_clusters"] if s["num_clusters"] else 0.0
+
+    @property
+    def weight_average_cluster_size(self):
+        """float: sum of size^2 over the number of particles, 0 for an empty group."""
+        s = self._summary("weight_average_cluster_size")
+        return s["sum_size_squared"] / s["num_particles"] if s["num_particles"] else 0.0
+
+    @property
+    def size_histogram(self):
+        """numpy int64 (size_bins,): clusters of size s at s - 1, the last word for ``size_bins`` and more."""
+        return self._summary("size_histogram")["size_histogram"]
+
+
+class ClusterRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) for a ``Cluster`` in ``computes`` of the same simulation: its summary row
+    appended to a device table at the timesteps the trigger fires inside ``Simulation.run``, as ``SolidLiquidRecorder``
+    does -- the call's last kernels write row k themselves, nothing is read back, the host does not wait, and the
+    trajectory is the same bit for bit with and without the recorder. Read after the run: ``timesteps``,
+    ``num_particles``, ``num_clusters``, ``largest_cluster_size``, ``num_edges``, ``weight_average_cluster_size``
+    (frames,) and ``size_histogram`` (frames, size_bins); ``reset()`` forgets the frames."""
+
+    _dtype = "int64"
+
+    def __init__(self, cluster, trigger):
+        if not isinstance(cluster, Cluster):
+            raise _lib.AzpError("ClusterRecorder: a Cluster is expected, got %r" % (cluster,))
+        self.cluster = cluster
+        super().__init__(trigger)
+
+    @property
+    def _compute(self):
+        return self.cluster
+
+    def _row_width(self):
+        return self.cluster._row_width()
+
+    def reset(self):
+        """Forget the recorded rows."""
+        self._rows = None
+        self._steps = []
+        self._volumes = []
+
+    def _table(self):
+        k = len(self._steps)
+        return self._rows[:k].cpu().numpy() if k else np.zeros((0, self._row_width()), dtype=np.int64)
+
+    @property
+    def num_particles(self):
+        return self._table()[:, 0].copy()
+
+    @property
+    def num_clusters(self):
+        return self._table()[:, 1].copy()
+
+    @property
+    def largest_cluster_size(self):
+        return self._table()[:, 2].copy()
+
+    @property
+    def num_edges(self):
+        return self._table()[:, 5].copy()
+
+    @property
+    def weight_average_cluster_size(self):
+        t = self._table()
+        return np.divide(t[:, 4], t[:, 0], out=np.zeros(t.shape[0]), where=t[:, 0] != 0)
+
+    @property
+    def size_histogram(self):
+        return self._table()[:, 6:].copy()
+
+
+__all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute", "Cluster", "ClusterRecorder",
+           "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder", "cluster_indices", "cluster_summary", "distribution_from_counts",
            "RadialDistributionFunction", "SolidLiquid", "SolidLiquidRecorder", "Steinhardt", "SteinhardtRecorder",
            "StructureFactor", "StructureFactorRecorder", "ThermodynamicQuantities",
            "ThermodynamicRecorder", "VelocityCompute", "VelocityFieldCompute", "perpendicular_widths", "rdf_from_counts",

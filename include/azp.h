@@ -1715,6 +1715,67 @@ typedef struct azp_steinhardt_args
 int azp_steinhardt_scratch_size(const azp_steinhardt_args* args, uint64_t* bytes);
 int azp_steinhardt_compute(const azp_steinhardt_args* args, void* stream);
 
+/* ---- clusters (compute.Cluster) ----
+ * Not part of the reference; the semantics are DEFINED HERE. The connected components of the graph whose
+ * vertices are a group of the rows [0, N) of a 3-D box and whose edges are the pairs closer than r_max.
+ * Group: G = the rows whose type has a non-zero byte in d_type_mask (NULL: every row) and, where d_member is not NULL,
+ * d_member[i] >= member_min (compute.Cluster(solid=...): d_member = the num_connections of a SolidLiquid, member_min
+ * its solid_threshold).
+ * Edges: i, j in G, i != j, rsq < r_max * r_max, where (dx, dy, dz) = r_i - r_j goes through the minimum image of the
+ * force kernels and rsq = dx dx + dy dy + dz dz: the acceptance rule of azp_rdf_counts and azp_steinhardt_compute.
+ * Tilted boxes and non-periodic axes included.
+ * Clusters: the connected components. A row of G without an edge is a cluster of size 1.
+ * Outputs, all OVERWRITTEN, per row: d_cluster_key[i] = the smallest d_tag among the rows of i's cluster,
+ * AZP_CLUSTER_NONE outside G (the key does not depend on the order of the rows: it survives the particle sorter);
+ * d_cluster_size[i] = the size of i's cluster, 0 outside G.
+ * d_summary: 6 + size_bins int64, exact integers:
+ *   [0] N_G   [1] the number of clusters   [2] the size of the largest cluster   [3] the key of the largest cluster,
+ *   among equal sizes the smallest key, -1 when N_G == 0   [4] the sum over the clusters of size^2   [5] the number of
+ *   edges (accepted pairs counted once)   [6 + s - 1] the number of clusters of size s for s < size_bins, the last
+ *   word the number of clusters of size >= size_bins.
+ * Reproducibility: a concurrent union-find labels the components in whatever order the hardware takes the pairs;
+ * everything the call OUTPUTS is a function of the graph and the tags alone. Two calls, the two paths and a re-ordered
+ * state give the same key and size per tag and the same summary. Integer atomics only.
+ * path: 0 = automatic (the cells wherever they are valid), 1 = all-pairs (any box), 2 = cells (orthorhombic box with at
+ * least three cells of width >= r_max on every periodic axis: the grid rule of azp_steinhardt_compute).
+ * stages: 0 = the whole call. 1 and 2 are for timing only and leave the outputs unwritten but for a zeroed summary and
+ * (2) its word [5]: 1 stops after the rows are ordered, 2 after the union pass.
+ * N <= AZP_CLUSTER_MAX_N = 2^30: slots and AZP_CLUSTER_NONE fit 32 bits with room for the index arithmetic of the
+ * walk, and the sum of size^2 stays below 2^60.
+ * Asynchronous on `stream`: nothing is read back, nothing synchronises. d_scratch: azp_cluster_scratch_size bytes.
+ * AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written: NULL args; r_max not positive and finite;
+ * size_bins outside 1 .. AZP_CLUSTER_MAX_BINS; N > AZP_CLUSTER_MAX_N; a box length that is not positive; r_max larger
+ * than half the perpendicular width of a periodic axis; path > 2, or 2 where the cells are not valid (never silently
+ * replaced); stages > 2; a mask with ntypes == 0; a NULL d_summary; with N > 0 a NULL d_pos, d_tag, d_cluster_key or
+ * d_cluster_size or too small a scratch. N == 0: the summary is 0 but for [3] = -1. */
+#define AZP_CLUSTER_NONE 0xffffffffu
+#define AZP_CLUSTER_MAX_BINS 1024
+#define AZP_CLUSTER_MAX_N (1u << 30)
+
+typedef struct azp_cluster_args
+    {
+    const double* d_pos;          /* N x 4 (x, y, z, type bits) */
+    uint32_t N;
+    uint32_t ntypes;              /* entries of the mask */
+    azp_box box;
+    const uint8_t* d_type_mask;   /* ntypes bytes, may be NULL */
+    const uint32_t* d_tag;        /* N */
+    const uint32_t* d_member;     /* N, may be NULL */
+    uint32_t member_min;
+    uint32_t path;                /* 0 auto, 1 all-pairs, 2 cells */
+    double r_max;
+    uint32_t size_bins;           /* 1 .. AZP_CLUSTER_MAX_BINS */
+    uint32_t stages;              /* 0: everything */
+    uint32_t* d_cluster_key;      /* N */
+    uint32_t* d_cluster_size;     /* N */
+    int64_t* d_summary;           /* 6 + size_bins */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_cluster_args;
+
+int azp_cluster_scratch_size(const azp_cluster_args* args, uint64_t* bytes);
+int azp_cluster_compute(const azp_cluster_args* args, void* stream);
+
 /* ---- wall potentials (azplugins_amd.wall) ----
  * Replace the reference's legacy wall evaluators src/WallEvaluatorLJ93.h:50-150 and
  * src/WallEvaluatorColloid.h:52-195 with their instantiation src/WallPotentials.h / src/WallPotentials.cu. The two
