@@ -158,6 +158,9 @@ struct EvalPLJ
         if (count_in)
             n_in += in ? 1u : 0u;
         }
+    // The tile kernel's tail-phase loop: the one constant of eval_split_tail's force that has to come from VGPRs
+    // (a VALU instruction reads at most one 64-bit scalar) is placed there once, ahead of the loop.
+    static __device__ __forceinline__ void tail_resident(Coeff& c) { asm("" : "+v"(c.c6_lam)); }
     static __device__ __forceinline__ double finish_split(const Coeff& c, double pe_raw, double s1, double s2, uint32_t n_wca,
                                                           uint32_t n_in)
         {

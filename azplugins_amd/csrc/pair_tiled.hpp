@@ -42,7 +42,7 @@
 //   3. DPP butterfly over the TPP lanes, lane 0 stores force (and virial).
 // Same evaluators, same outputs as pair_kernel.hpp; results agree with it to
 // rounding (the periodic shift is applied to r_j instead of to r_i - r_j).
-// Counts and measurements of this form: profiles/tile_setup.md.
+// Counts and measurements of this form: profiles/tile_setup.md; of the phased loop's bookkeeping: profiles/pair_loop.md.
 #pragma once
 
 #include <type_traits>
@@ -377,7 +377,8 @@ __device__ __forceinline__ void tiled_loop(const TiledKArgs& a, const char* bx, 
 // the launch states that no other entry can have come inside the evaluator's core (plan_core_reach_sq), the iterations
 // from Kcore on run the tail form alone, without the core test: the form that test would have picked for them, so
 // the bits are the same. Kcore >= Kb / 2: every batch tested, as in tiled_loop (any other launch). The pipeline is
-// tiled_loop's; one iteration body serves both phases.
+// tiled_loop's; one iteration body serves both phases. What differs from tiled_loop is bookkeeping only (no arithmetic
+// operation, no order of a sum): the chunk load's address, the names of the index words and where c6_lam lives.
 template<class E, int TPP, int CAP, bool VIRIAL>
 __device__ __forceinline__ void tiled_loop_phases(const TiledKArgs& a, const char* bx, const typename E::Coeff& c0, double rcutsq_max,
                                                   const char* __restrict__ slice_base, uint32_t lane_off, uint32_t Kb, uint32_t Kcore,
@@ -385,34 +386,77 @@ __device__ __forceinline__ void tiled_loop_phases(const TiledKArgs& a, const cha
                                                   uint32_t& n_core, uint32_t& n_in, double (&es)[2])
     {
     const uint4 zero4 = make_uint4(0, 0, 0, 0);
+    // chunk kk of this lane: the chunk's base (slice base + kk KiB) stays in SGPRs and the lane part (16 lane, below
+    // 1 KiB) in one VGPR -- global_load_dwordx4 v, v_off, s[base:base+1], no vector address arithmetic in the loop. The
+    // empty asm names the base as a scalar and the lane part as a 32-bit vector at the load: without it the compiler
+    // keeps slice base + lane as a 64-bit vector outside the loop and adds the chunk offset to it with one VALU
+    // instruction per chunk. (The lane part is carried through the asm from load to load, so no copy is made of it;
+    // the pointer is named global again, the asm hides where it came from.)
+    uint32_t lane_part = lane_off;
     auto chunk_at = [&](uint32_t kk) -> uint4
-        { return *reinterpret_cast<const uint4*>(slice_base + (uint64_t)kk * 1024u + lane_off); };
+        {
+        uint64_t chunk_base = reinterpret_cast<uint64_t>(slice_base) + (uint64_t)kk * 1024u;
+        asm("" : "+s"(chunk_base), "+v"(lane_part));
+        typedef uint32_t words4 __attribute__((ext_vector_type(4)));
+        typedef const __attribute__((address_space(1))) char* gptr;
+        const words4 w = *reinterpret_cast<const __attribute__((address_space(1))) words4*>(reinterpret_cast<gptr>(chunk_base) + lane_part);
+        return make_uint4(w.x, w.y, w.z, w.w);
+        };
     const uint32_t K = Kb >> 1;         // whole iterations
     const uint32_t Kc = (Kb + 1u) >> 1; // chunks this lane reads (the last one only its first half when Kb is odd)
+    // the index words of the chunk in work, of the next one and of the one after it: three names that rotate through
+    // the unrolled loops below (no register copies)
     uint4 u = (Kc > 0) ? chunk_at(0) : zero4;
     uint4 un = (Kc > 1) ? chunk_at(1) : u;
+    uint4 un2;
     TileBatch A, B;
     tile_gather<CAP, 0>(A, u, bx);
-    auto iteration = [&](auto tail_tag, const uint32_t kk)
+    // the tail phase's copy of the coefficients keeps c6_lam in a VGPR pair (the one the chunk address used to hold):
+    // v_fma_f64 cannot take c12_lam and c6_lam both from SGPRs, and the compiler otherwise copies one of them into
+    // VGPRs once per batch
+    typename E::Coeff ct = c0;
+    if constexpr (!VIRIAL) // (with the virial's six accumulators the pair costs up to three spill slots)
+        E::tail_resident(ct);
+    // one iteration: chunk kk in w0 (its first half gathered in A), chunk kk + 1 in w1; the words two chunks ahead are
+    // loaded into w2
+    auto iteration = [&](auto tail_tag, const uint32_t kk, const uint4& w0, const uint4& w1, uint4& w2)
         {
         constexpr bool TAIL = decltype(tail_tag)::value;
-        const uint4 un2 = chunk_at((kk + 2 < Kc) ? kk + 2 : Kc - 1);
-        tile_gather<CAP, 1>(B, u, bx);
+        w2 = chunk_at((kk + 2 < Kc) ? kk + 2 : Kc - 1);
+        tile_gather<CAP, 1>(B, w0, bx);
         __builtin_amdgcn_sched_barrier(0);
-        tile_compute<E, CAP, VIRIAL, true, false, false, TAIL>(A, a, nullptr, nullptr, nullptr, c0, 0.0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
+        tile_compute<E, CAP, VIRIAL, true, false, false, TAIL>(A, a, nullptr, nullptr, nullptr, TAIL ? ct : c0, 0.0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
         __builtin_amdgcn_sched_barrier(0);
-        tile_gather<CAP, 0>(A, un, bx); // when kk + 1 == Kc: gathered, never used
+        tile_gather<CAP, 0>(A, w1, bx); // when kk + 1 == Kc: gathered, never used
         __builtin_amdgcn_sched_barrier(0);
-        tile_compute<E, CAP, VIRIAL, true, false, false, TAIL>(B, a, nullptr, nullptr, nullptr, c0, 0.0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
+        tile_compute<E, CAP, VIRIAL, true, false, false, TAIL>(B, a, nullptr, nullptr, nullptr, TAIL ? ct : c0, 0.0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);
         __builtin_amdgcn_sched_barrier(0);
-        u = un;
-        un = un2;
+        };
+    // iterations [kk, kend) of one phase. Tail phase: three at a time with the names rotating, the left-over one or two
+    // through a single-iteration body that moves them. The core phase is two iterations long in the mean (the plan's
+    // core count), so a three-iteration body would hardly ever be entered; it keeps the single-iteration body alone
+    // (unrolled as well, the hot instance grows by another 8 KB of code).
+    auto phase = [&](auto tail_tag, uint32_t kk, const uint32_t kend)
+        {
+        if constexpr (decltype(tail_tag)::value)
+            {
+            for (; kk + 3 <= kend; kk += 3)
+                {
+                iteration(tail_tag, kk, u, un, un2);
+                iteration(tail_tag, kk + 1, un, un2, u);
+                iteration(tail_tag, kk + 2, un2, u, un);
+                }
+            }
+        for (; kk < kend; ++kk)
+            {
+            iteration(tail_tag, kk, u, un, un2);
+            u = un;
+            un = un2;
+            }
         };
     const uint32_t K1 = (Kcore < K) ? Kcore : K; // iterations of the core phase
-    for (uint32_t kk = 0; kk < K1; ++kk)
-        iteration(std::false_type(), kk);
-    for (uint32_t kk = K1; kk < K; ++kk)
-        iteration(std::true_type(), kk);
+    phase(std::false_type(), 0, K1);
+    phase(std::true_type(), K1, K);
     // A holds the first half of chunk K (the tested form serves either phase)
     if (Kb & 1u)
         tile_compute<E, CAP, VIRIAL, true, false, false>(A, a, nullptr, nullptr, nullptr, c0, 0.0, rcutsq_max, pi, typei, fx, fy, fz, pe, v, n_core, n_in, es);

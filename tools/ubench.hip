@@ -1,6 +1,7 @@
 // ubench.hip -- per-instruction VALU issue cost on gfx950 for the ops the pair
 // kernels use (fp64 fma/mul/add, v_rcp_f64, v_cmp_f64, v_cndmask_b32, cvt),
-// at 1..4 waves per SIMD, plus the accuracy of v_rcp_f64 / v_rsq_f64.
+// and the bookkeeping ops of the tile loop (v_mov_b64, v_lshl_add_u64, v_cmp_gt_f64 and
+// v_cmp_gt_u32 alone), at 1..4 waves per SIMD, plus the accuracy of v_rcp_f64 / v_rsq_f64.
 // Build: hipcc -O3 --offload-arch=gfx950 tools/ubench.hip -o tools/ubench
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -27,6 +28,10 @@ template<int OP> __global__ void k(double* out, int iters, double seed)
         if (OP == 7) { REP8(asm volatile("v_rsq_f64 %0, %0\n v_rsq_f64 %1, %1\n v_rsq_f64 %2, %2\n v_rsq_f64 %3, %3\n v_rsq_f64 %4, %4\n v_rsq_f64 %5, %5\n v_rsq_f64 %6, %6\n v_rsq_f64 %7, %7" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));) }
         if (OP == 8) { float f0, f1, f2, f3; REP8(asm volatile("v_cvt_f32_f64 %4, %0\n v_cvt_f32_f64 %5, %1\n v_cvt_f32_f64 %6, %2\n v_cvt_f32_f64 %7, %3\n v_cvt_f64_f32 %0, %4\n v_cvt_f64_f32 %1, %5\n v_cvt_f64_f32 %2, %6\n v_cvt_f64_f32 %3, %7" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=v"(f0), "=v"(f1), "=v"(f2), "=v"(f3));) }
         if (OP == 9) { float f0 = (float)a0, f1 = (float)a1; REP8(asm volatile("v_rcp_f32 %0, %0\n v_rcp_f32 %1, %1\n v_rcp_f32 %0, %0\n v_rcp_f32 %1, %1\n v_rcp_f32 %0, %0\n v_rcp_f32 %1, %1\n v_rcp_f32 %0, %0\n v_rcp_f32 %1, %1" : "+v"(f0), "+v"(f1));) a0 += f0; a1 += f1; }
+        if (OP == 10) { REP8(asm volatile("v_mov_b64 %0, %8\n v_mov_b64 %1, %8\n v_mov_b64 %2, %8\n v_mov_b64 %3, %8\n v_mov_b64 %4, %8\n v_mov_b64 %5, %8\n v_mov_b64 %6, %8\n v_mov_b64 %7, %8" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(m));) }
+        if (OP == 11) { REP8(asm volatile("v_lshl_add_u64 %0, %0, 0, %8\n v_lshl_add_u64 %1, %1, 0, %8\n v_lshl_add_u64 %2, %2, 0, %8\n v_lshl_add_u64 %3, %3, 0, %8\n v_lshl_add_u64 %4, %4, 0, %8\n v_lshl_add_u64 %5, %5, 0, %8\n v_lshl_add_u64 %6, %6, 0, %8\n v_lshl_add_u64 %7, %7, 0, %8" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(c));) }
+        if (OP == 12) { REP8(asm volatile("v_cmp_gt_f64 vcc, %0, %1\n v_cmp_gt_f64 vcc, %1, %2\n v_cmp_gt_f64 vcc, %2, %3\n v_cmp_gt_f64 vcc, %3, %4\n v_cmp_gt_f64 vcc, %4, %5\n v_cmp_gt_f64 vcc, %5, %6\n v_cmp_gt_f64 vcc, %6, %7\n v_cmp_gt_f64 vcc, %7, %0" :: "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5), "v"(a6), "v"(a7) : "vcc");) }
+        if (OP == 13) { REP8(asm volatile("v_cmp_gt_u32 vcc, %0, %1\n v_cmp_gt_u32 vcc, %1, %0\n v_cmp_gt_u32 vcc, %0, %1\n v_cmp_gt_u32 vcc, %1, %0\n v_cmp_gt_u32 vcc, %0, %1\n v_cmp_gt_u32 vcc, %1, %0\n v_cmp_gt_u32 vcc, %0, %1\n v_cmp_gt_u32 vcc, %1, %0" :: "v"(i0), "v"(i1) : "vcc");) }
         }
     out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + i0 + i1;
     }
@@ -68,6 +73,7 @@ int main()
         run<0>("v_fma_f64", d, w); run<1>("v_mul_f64", d, w); run<2>("v_add_f64", d, w); run<3>("v_rcp_f64", d, w);
         run<7>("v_rsq_f64", d, w); run<4>("v_cmp_f64+cndmask (x2)", d, w); run<5>("v_cndmask_b32", d, w);
         run<6>("v_fma_f32", d, w); run<8>("v_cvt f64<->f32", d, w); run<9>("v_rcp_f32", d, w);
+        run<10>("v_mov_b64", d, w); run<11>("v_lshl_add_u64", d, w); run<12>("v_cmp_gt_f64 alone", d, w); run<13>("v_cmp_gt_u32 alone", d, w);
         }
     // accuracy
     const int n = 1 << 20;
