@@ -66,7 +66,9 @@ def _check_mpcd(include_mpcd_particles):
 
 
 class _Compute:
-    """What the two compute classes share: attachment through ``sim.operations`` and the device buffers."""
+    """What the computes share: attachment through ``sim.operations``, the type masks and the device buffers. A row
+    compute has ``_row_width()`` and ``_launch(d_out)``, which queues its kernels with one row of that many 8-byte words
+    going to ``d_out``; its properties go through ``_read_row``, its recorder hands ``_launch`` a row of its table."""
 
     _coordinates = _lib.COORDINATES_CARTESIAN
 
@@ -76,6 +78,9 @@ class _Compute:
         self._sim = None
         self._bufs = None  # key -> (sums, velocity, scratch)
         self._mask = None  # (types, device tensor or None)
+        self._masks = None  # (types, mask a, mask b, device): the computes with a second filter
+        self._row = None  # the (1, _row_width()) device row of a row compute
+        self._scratch = None  # the scratch of its kernels
 
     @property
     def filter(self):
@@ -100,6 +105,57 @@ class _Compute:
             m = torch.from_numpy(self._filter.mask(st.types)).to(st.device)
             self._mask = (list(st.types), m)
         return self._mask[1]
+
+    def _type_masks(self, st):
+        """Device byte masks of ``filter`` and ``filter_b`` (a compute between two groups), None for All()."""
+        import torch
+
+        if self._masks is None or self._masks[0] != st.types or self._masks[3] != st.device:
+            m = [None if isinstance(f, All) else torch.from_numpy(f.mask(st.types)).to(st.device) for f in (self._filter, self._filter_b)]
+            self._masks = (list(st.types), m[0], m[1], st.device)
+        return self._masks[1], self._masks[2]
+
+    def _row_buffer(self, width, dtype, attr="_row"):
+        """The (1, width) device row kept in ``attr``: reused while device, width and dtype fit, else allocated."""
+        import torch
+
+        dev = self._sim.state.device
+        dtype = getattr(torch, dtype)
+        row = getattr(self, attr)
+        if row is None or row.device != dev or row.shape[1] != width or row.dtype != dtype:
+            row = torch.empty((1, width), dtype=dtype, device=dev)
+            setattr(self, attr, row)
+        return row
+
+    def _set_scratch(self, a, size_name, minimum=256):
+        """Asks ``size_name`` of libazp for the scratch the call ``a`` needs and points ``a`` at a device buffer of at
+        least that many (and ``minimum``) bytes: reused until a call asks for more or the device changes."""
+        import torch
+
+        need = C.c_uint64(0)
+        _lib.check(getattr(_lib.lib(), size_name)(C.byref(a), C.byref(need)), size_name)
+        dev = self._sim.state.device
+        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != dev:
+            self._scratch = torch.empty(max(int(need.value), minimum), dtype=torch.uint8, device=dev)
+        a.d_scratch = self._scratch.data_ptr()
+        a.scratch_bytes = self._scratch.numel()
+
+    def _read_row(self, name, dtype="int64"):
+        """One ``_launch`` on the current state into this compute's own row, which is returned: a (1, ``_row_width()``)
+        device tensor. ``name``: the property being read, for ``DataAccessError``."""
+        if not self._attached:
+            raise DataAccessError(name)
+        row = self._row_buffer(self._row_width(), dtype)
+        self._launch(row.data_ptr())
+        return row
+
+    def _reduce(self, rows):
+        """Rows of per-rank words (a (k, row width) device tensor; integer words are the uint64 of the kernels, all below
+        2^63) added over the ranks of a decomposed run, as numpy."""
+        dom = self._sim.domain
+        if dom is not None:
+            rows = _all_reduce_sum(dom, rows.clone())
+        return rows.cpu().numpy()
 
     def _velocity_field(self, num_bins, lower, upper, name):
         """Mass-averaged velocity per bin, (bins, 3) float64 numpy, at the simulation's current state."""
@@ -356,8 +412,6 @@ class ThermodynamicQuantities(_Compute):
         if not isinstance(filter, (All, Type)):
             raise _lib.AzpError("ThermodynamicQuantities: filter must be All() or Type(...), got %r" % (filter,))
         super().__init__(filter, False)
-        self._scratch = None
-        self._row = None
         self._rotation = None  # (state, any particle has a non-zero moment of inertia)
 
     # -- one launch ----------------------------------------------------------
@@ -370,10 +424,11 @@ class ThermodynamicQuantities(_Compute):
         ok = all(f._state is st and f._force is not None and f._force.shape[0] == st.N for f in forces)
         return ok, ok and all(getattr(f, "_virial_evaluated", False) for f in forces)
 
+    def _row_width(self):
+        return _lib.THERMO_NSUMS
+
     def _launch(self, d_out):
         """Queue ``azp_thermo_sums`` for the simulation's current state with the 20 doubles going to ``d_out``."""
-        import torch
-
         sim = self._sim
         st = sim.state
         integ = sim.operations.integrator
@@ -397,15 +452,9 @@ class ThermodynamicQuantities(_Compute):
         if st.N and self._reads_rotation():
             # (a rank without particles has nothing to point at; the kernel zeroes the row)
             a.d_orientation, a.d_angmom, a.d_inertia = st.orientation.data_ptr(), st.angmom.data_ptr(), st.inertia.data_ptr()
-        lib = _lib.lib()
-        need = C.c_uint64(0)
-        _lib.check(lib.azp_thermo_scratch_size(C.byref(a), C.byref(need)), "azp_thermo_scratch_size")
-        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
-            self._scratch = torch.empty(int(need.value), dtype=torch.uint8, device=st.device)
-        a.d_scratch = self._scratch.data_ptr()
-        a.scratch_bytes = self._scratch.numel()
+        self._set_scratch(a, "azp_thermo_scratch_size", minimum=0)
         a.d_out = d_out
-        _lib.check(lib.azp_thermo_sums(C.byref(a), _lib.raw_stream(st.device)), "azp_thermo_sums")
+        _lib.check(_lib.lib().azp_thermo_sums(C.byref(a), _lib.raw_stream(st.device)), "azp_thermo_sums")
 
     def _prepare(self):
         """Called by ``Simulation.run`` ahead of the first step: does any particle have a moment of inertia? Without
@@ -430,9 +479,7 @@ class ThermodynamicQuantities(_Compute):
         sim = self._sim
         st = sim.state
         dom = sim.domain
-        if dom is not None:
-            rows = _all_reduce_sum(dom, rows.clone())
-        host = rows.cpu().numpy()
+        host = self._reduce(rows)
         if dom is None:
             n_global = st.N
         elif isinstance(self._filter, All):
@@ -445,13 +492,7 @@ class ThermodynamicQuantities(_Compute):
 
     def _sums(self):
         """The row of sums of the current state, per rank, as a (1, 20) device tensor."""
-        import torch
-
-        st = self._sim.state
-        if self._row is None or self._row.device != st.device:
-            self._row = torch.empty((1, _lib.THERMO_NSUMS), dtype=torch.float64, device=st.device)
-        self._launch(self._row.data_ptr())
-        return self._row
+        return self._read_row("sums", "float64")
 
     def _get(self, name):
         if not self._attached:
@@ -475,17 +516,25 @@ for _name in THERMO_PROPERTIES:
 
 
 class _Recorder:
-    """What the recorders share: a compute of the same simulation (``_compute``), a trigger, and a device table of one
-    row per recorded timestep that the compute's kernel writes straight into -- nothing is read back and the host
-    never waits. The table grows by doubling; the copy is queued on the stream like everything else."""
+    """What the recorders share: a compute of the same simulation (``_compute``, which the subclass sets), a trigger, and
+    a device table of one row per recorded timestep that the compute's kernel writes straight into -- nothing is read
+    back and the host never waits. The table grows by doubling; the copy is queued on the stream like everything
+    else."""
 
     _dtype = "float64"
 
     def __init__(self, trigger):
         self.trigger = trigger if isinstance(trigger, Periodic) else Periodic(trigger)
+        self.reset()
+
+    def reset(self):
+        """Forget the recorded rows."""
         self._rows = None  # (capacity, row width) device tensor
         self._steps = []
         self._volumes = []  # the volume of the box each row was recorded in (host data: no synchronisation)
+
+    def _row_width(self):
+        return self._compute._row_width()
 
     def timesteps_in_run(self, t0, n):
         """The timesteps at which ``run(n)`` starting at timestep ``t0`` records: those of t0 + 1 ... t0 + n at which the
@@ -525,20 +574,14 @@ class ThermodynamicRecorder(_Recorder):
     waits. In ``run(n)`` starting at timestep t0 the trigger is evaluated at t0 + 1 ... t0 + n; the row of timestep t
     is the state after t complete steps (after step two, with the forces of that configuration). ``Simulation.run``
     runs step two of that step on its own there instead of fused with the next step one: the trajectory is the same
-    bit for bit with and without a recorder. ``timesteps`` and ``table`` are read after the run."""
+    bit for bit with and without a recorder. ``timesteps`` and ``table`` are read after the run; ``reset()`` forgets the
+    recorded rows."""
 
     def __init__(self, thermo, trigger):
         if not isinstance(thermo, ThermodynamicQuantities):
             raise _lib.AzpError("ThermodynamicRecorder: thermo must be a ThermodynamicQuantities, got %r" % (thermo,))
-        self.thermo = thermo
+        self.thermo = self._compute = thermo
         super().__init__(trigger)
-
-    @property
-    def _compute(self):
-        return self.thermo
-
-    def _row_width(self):
-        return _lib.THERMO_NSUMS
 
     @property
     def table(self):
@@ -583,6 +626,18 @@ def rdf_from_counts(counts, n_a, n_b, n_ab, volume, r_max):
 def perpendicular_widths(box):
     """Distances between opposite faces of ``box`` (a ``state.Box``; HOOMD ``BoxDim.getNearestPlaneDistance``)."""
     return box.nearest_plane_distance
+
+
+def _check_pair_range(name, box, r_max):
+    """What every compute over the pairs closer than ``r_max`` asks of the box (``name``: the class, for the message): a
+    3-D box, ``r_max`` at most half the perpendicular width of every periodic axis."""
+    widths = perpendicular_widths(box)
+    for d in range(3):
+        if not widths[d] > 0.0:
+            raise _lib.AzpError("%s: a 3-D box is needed (2-D systems are not supported), got %r" % (name, box))
+        if box.periodic[d] and r_max > 0.5 * widths[d]:
+            raise _lib.AzpError("%s: r_max = %r is larger than half the perpendicular width %r of periodic axis %d: the "
+                                "minimum image would not be unique" % (name, r_max, widths[d], d))
 
 
 def _check_rdf_filter(name, f):
@@ -630,9 +685,6 @@ class RadialDistributionFunction(_Compute):
         self.r_max = r_max
         self.num_bins = num_bins
         self.path = _lib.RDF_PATH_AUTO
-        self._masks = None    # (types, mask a, mask b)
-        self._row = None
-        self._scratch = None
 
     filter_a = _Compute.filter
 
@@ -685,15 +737,11 @@ class RadialDistributionFunction(_Compute):
         return 0.5 * (e[1:] + e[:-1])
 
     # -- one launch ----------------------------------------------------------
+    def _row_width(self):
+        return self._num_bins + 4
+
     def _check_box(self, sim):
-        box = sim.state.box
-        widths = perpendicular_widths(box)
-        for d in range(3):
-            if not widths[d] > 0.0:
-                raise _lib.AzpError("RadialDistributionFunction: a 3-D box is needed (2-D systems are not supported), got %r" % (box,))
-            if box.periodic[d] and self._r_max > 0.5 * widths[d]:
-                raise _lib.AzpError("RadialDistributionFunction: r_max = %r is larger than half the perpendicular width %r of "
-                                    "periodic axis %d: the minimum image would not be unique" % (self._r_max, widths[d], d))
+        _check_pair_range("RadialDistributionFunction", sim.state.box, self._r_max)
         dom = sim.domain
         if dom is not None:
             integ = sim.operations.integrator
@@ -704,18 +752,8 @@ class RadialDistributionFunction(_Compute):
                                     "(r_ghost = %r minus the neighbor-list buffer %r)"
                                     % (self._r_max, dom.decomp.r_ghost - buffer, dom.decomp.r_ghost, buffer))
 
-    def _type_masks(self, st):
-        import torch
-
-        if self._masks is None or self._masks[0] != st.types or self._masks[3] != st.device:
-            m = [None if isinstance(f, All) else torch.from_numpy(f.mask(st.types)).to(st.device) for f in (self._filter, self._filter_b)]
-            self._masks = (list(st.types), m[0], m[1], st.device)
-        return self._masks[1], self._masks[2]
-
     def _launch(self, d_out):
         """Queue ``azp_rdf_counts`` for the simulation's current state with the ``num_bins + 4`` words going to ``d_out``."""
-        import torch
-
         sim = self._sim
         st = sim.state
         self._check_box(sim)
@@ -733,13 +771,7 @@ class RadialDistributionFunction(_Compute):
         a.scale = self._num_bins / self._r_max
         a.path = self._path
         lib = _lib.lib()
-        need = C.c_uint64(0)
-        _lib.check(lib.azp_rdf_scratch_size(C.byref(a), C.byref(need)), "azp_rdf_scratch_size")
-        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
-            # (sized for this N, box, r_max and path: grown when any of them asks for more)
-            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
-        a.d_scratch = self._scratch.data_ptr()
-        a.scratch_bytes = self._scratch.numel()
+        self._set_scratch(a, "azp_rdf_scratch_size")  # (for this N, box, r_max and path)
         a.d_out = d_out
         kinds = self._exclusion_kinds
         if kinds and sim.domain is not None:
@@ -754,25 +786,8 @@ class RadialDistributionFunction(_Compute):
             x.d_n_excl, x.d_excl, x.excl_pitch = n_excl.data_ptr(), excl.data_ptr(), pitch
             _lib.check(lib.azp_rdf_subtract_excluded(C.byref(x), stream), "azp_rdf_subtract_excluded")
 
-    def _reduce(self, rows):
-        """Rows of per-rank words (a (k, num_bins + 4) int64 device tensor: the uint64 words of the kernel, all below
-        2^63) added over the ranks of a decomposed run, as numpy int64."""
-        dom = self._sim.domain
-        if dom is not None:
-            rows = _all_reduce_sum(dom, rows.clone())
-        return rows.cpu().numpy()
-
     def _read(self, name):
-        import torch
-
-        if not self._attached:
-            raise DataAccessError(name)
-        st = self._sim.state
-        width = self._num_bins + 4
-        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
-            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
-        self._launch(self._row.data_ptr())
-        return self._reduce(self._row)[0]
+        return self._reduce(self._read_row(name))[0]
 
     def _volume(self):
         box = self._sim.state.box
@@ -822,25 +837,13 @@ class RDFRecorder(_Recorder):
     def __init__(self, rdf, trigger):
         if not isinstance(rdf, RadialDistributionFunction):
             raise _lib.AzpError("RDFRecorder: rdf must be a RadialDistributionFunction, got %r" % (rdf,))
-        self.rdf_compute = rdf
+        self.rdf_compute = self._compute = rdf
         super().__init__(trigger)
-
-    @property
-    def _compute(self):
-        return self.rdf_compute
-
-    def _row_width(self):
-        return self.rdf_compute.num_bins + 4
-
-    def reset(self):
-        self._rows = None
-        self._steps = []
-        self._volumes = []
 
     def _table(self, name):
         k = len(self._steps)
         if k == 0:
-            return np.zeros((0, self.rdf_compute.num_bins + 4), dtype=np.int64)
+            return np.zeros((0, self._row_width()), dtype=np.int64)
         if not self.rdf_compute._attached:
             raise DataAccessError(name)
         return self.rdf_compute._reduce(self._rows[:k])
@@ -950,7 +953,6 @@ class BondedDistribution(_Compute):
             lo, hi = (0.0, np.pi) if kind == "angle" else (-np.pi, np.pi)
         self._range = (lo, hi)
         self.path = _lib.BONDED_HISTOGRAM_PATH_AUTO
-        self._row = None
 
     @property
     def kind(self):
@@ -1033,22 +1035,10 @@ class BondedDistribution(_Compute):
     def _reduce(self, rows):
         """Rows of per-rank words (a (k, row width) int64 device tensor: the uint64 words of the kernel, all below 2^63)
         added over the ranks of a decomposed run, as numpy int64 of shape (k, n_types, num_bins + 2)."""
-        dom = self._sim.domain
-        if dom is not None:
-            rows = _all_reduce_sum(dom, rows.clone())
-        return rows.cpu().numpy().reshape(rows.shape[0], -1, self._num_bins + 2)[:, :len(self._types())]
+        return super()._reduce(rows).reshape(rows.shape[0], -1, self._num_bins + 2)[:, :len(self._types())]
 
     def _read(self, name):
-        import torch
-
-        if not self._attached:
-            raise DataAccessError(name)
-        st = self._sim.state
-        width = self._row_width()
-        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
-            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
-        self._launch(self._row.data_ptr())
-        return self._reduce(self._row)[0]
+        return self._reduce(self._read_row(name))[0]
 
     @property
     def types(self):
@@ -1095,20 +1085,8 @@ class BondedDistributionRecorder(_Recorder):
     def __init__(self, dist, trigger):
         if not isinstance(dist, BondedDistribution):
             raise _lib.AzpError("BondedDistributionRecorder: dist must be a BondedDistribution, got %r" % (dist,))
-        self.dist = dist
+        self.dist = self._compute = dist
         super().__init__(trigger)
-
-    @property
-    def _compute(self):
-        return self.dist
-
-    def _row_width(self):
-        return self.dist._row_width()
-
-    def reset(self):
-        self._rows = None
-        self._steps = []
-        self._volumes = []
 
     def _table(self, name):
         k = len(self._steps)
@@ -1268,10 +1246,7 @@ class StructureFactor(_Compute):
         self.max_vectors_per_bin = max_vectors_per_bin
         self.seed = seed
         self.path = _lib.SF_PATH_AUTO
-        self._masks = None    # (types, mask a, mask b, device)
         self._set = None      # (key, m, bins, device triples, m_max)
-        self._row = None
-        self._scratch = None
 
     filter_a = _Compute.filter
 
@@ -1366,20 +1341,10 @@ class StructureFactor(_Compute):
     def _row_width(self):
         return 4 * len(self._vector_set()[0]) + 4
 
-    def _type_masks(self, st):
-        import torch
-
-        if self._masks is None or self._masks[0] != st.types or self._masks[3] != st.device:
-            m = [None if isinstance(f, All) else torch.from_numpy(f.mask(st.types)).to(st.device) for f in (self._filter, self._filter_b)]
-            self._masks = (list(st.types), m[0], m[1], st.device)
-        return self._masks[1], self._masks[2]
-
     # -- one launch ----------------------------------------------------------
     def _launch(self, d_out):
         """Queue ``azp_structure_factor_amplitudes`` for the simulation's current state with the ``4 n + 4`` doubles
         going to ``d_out``."""
-        import torch
-
         st = self._sim.state
         m, _, triples, m_max = self._vector_set()
         a = _lib.StructureFactorArgs()
@@ -1396,36 +1361,12 @@ class StructureFactor(_Compute):
         for d in range(3):
             a.m_max[d] = m_max[d]
         a.path = self._path
-        lib = _lib.lib()
-        need = C.c_uint64(0)
-        _lib.check(lib.azp_structure_factor_scratch_size(C.byref(a), C.byref(need)), "azp_structure_factor_scratch_size")
-        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
-            # (sized for this N, vector count and group pair: grown when any of them asks for more)
-            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
-        a.d_scratch = self._scratch.data_ptr()
-        a.scratch_bytes = self._scratch.numel()
+        self._set_scratch(a, "azp_structure_factor_scratch_size")  # (for this N, vector count and group pair)
         a.d_out = d_out
-        _lib.check(lib.azp_structure_factor_amplitudes(C.byref(a), _lib.raw_stream(st.device)), "azp_structure_factor_amplitudes")
-
-    def _reduce(self, rows):
-        """Rows of per-rank sums (a (k, 4 n + 4) float64 device tensor) added over the ranks of a decomposed run, as
-        numpy."""
-        dom = self._sim.domain
-        if dom is not None:
-            rows = _all_reduce_sum(dom, rows.clone())
-        return rows.cpu().numpy()
+        _lib.check(_lib.lib().azp_structure_factor_amplitudes(C.byref(a), _lib.raw_stream(st.device)), "azp_structure_factor_amplitudes")
 
     def _read(self, name):
-        import torch
-
-        if not self._attached:
-            raise DataAccessError(name)
-        st = self._sim.state
-        width = self._row_width()
-        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
-            self._row = torch.empty((1, width), dtype=torch.float64, device=st.device)
-        self._launch(self._row.data_ptr())
-        return self._reduce(self._row)[0]
+        return self._reduce(self._read_row(name, "float64"))[0]
 
     @property
     def vectors(self):
@@ -1491,16 +1432,8 @@ class StructureFactorRecorder(_Recorder):
     def __init__(self, sf, trigger):
         if not isinstance(sf, StructureFactor):
             raise _lib.AzpError("StructureFactorRecorder: sf must be a StructureFactor, got %r" % (sf,))
-        self.sf = sf
-        self._box_key = None
+        self.sf = self._compute = sf
         super().__init__(trigger)
-
-    @property
-    def _compute(self):
-        return self.sf
-
-    def _row_width(self):
-        return self.sf._row_width()
 
     def _record(self, sim, timestep):
         key = sim.state.box._key()
@@ -1511,9 +1444,7 @@ class StructureFactorRecorder(_Recorder):
         self._box_key = key
 
     def reset(self):
-        self._rows = None
-        self._steps = []
-        self._volumes = []
+        super().reset()
         self._box_key = None
 
     def _table(self, name):
@@ -1654,8 +1585,6 @@ class _BondOrder(_Compute):
         self._num_bins = int(num_bins)
         self.path = _lib.STEINHARDT_PATH_AUTO
         self._out = None      # (N, device, dict of per-particle tensors)
-        self._row = None
-        self._scratch = None
 
     @property
     def l(self):
@@ -1685,14 +1614,7 @@ class _BondOrder(_Compute):
         if sim.domain is not None:
             raise _lib.AzpError("%s: decomposed runs are not supported (the second pass would need the q_lm of the ghost "
                                 "particles)" % name)
-        box = sim.state.box
-        widths = perpendicular_widths(box)
-        for d in range(3):
-            if not widths[d] > 0.0:
-                raise _lib.AzpError("%s: a 3-D box is needed (2-D systems are not supported), got %r" % (name, box))
-            if box.periodic[d] and self._r_max > 0.5 * widths[d]:
-                raise _lib.AzpError("%s: r_max = %r is larger than half the perpendicular width %r of periodic axis %d: the "
-                                    "minimum image would not be unique" % (name, self._r_max, widths[d], d))
+        _check_pair_range(name, sim.state.box, self._r_max)
 
     def _args(self, st):
         a = _lib.SteinhardtArgs()
@@ -1744,35 +1666,21 @@ class _BondOrder(_Compute):
         a.d_order = out["order"].data_ptr()
         a.d_avg_words = out["avg_words"].data_ptr() if out["avg_words"] is not None else None
         a.d_num_connections = out["num_connections"].data_ptr() if out["num_connections"] is not None else None
-        lib = _lib.lib()
-        need = C.c_uint64(0)
-        _lib.check(lib.azp_steinhardt_scratch_size(C.byref(a), C.byref(need)), "azp_steinhardt_scratch_size")
-        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
-            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
-        a.d_scratch = self._scratch.data_ptr()
-        a.scratch_bytes = self._scratch.numel()
+        self._set_scratch(a, "azp_steinhardt_scratch_size")
         a.d_summary = d_out
-        _lib.check(lib.azp_steinhardt_compute(C.byref(a), _lib.raw_stream(st.device)), "azp_steinhardt_compute")
+        _lib.check(_lib.lib().azp_steinhardt_compute(C.byref(a), _lib.raw_stream(st.device)), "azp_steinhardt_compute")
 
     def _read(self, name):
         """One call on the current state, then ``name`` as numpy: ``summary`` (the row), ``num_neighbors``, ``qlm`` (the
         fixed-point words S, (N, words) int64), ``qlm_average`` (T), ``order`` (N, len(l)) or ``num_connections``."""
-        import torch
-
-        if not self._attached:
-            raise DataAccessError(name)
-        st = self._sim.state
-        width = self._row_width()
-        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
-            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
-        self._launch(self._row.data_ptr())
+        row = self._read_row(name)
         if name == "summary":
-            return self._row.cpu().numpy()[0]
+            return row.cpu().numpy()[0]
         key = {"qlm": "words", "qlm_average": "avg_words"}.get(name, name)
         t = self._out[2].get(key)
         if t is None:
             raise _lib.AzpError("%s: %s is not computed by this compute" % (type(self).__name__, name))
-        return t[: st.N].cpu().numpy()
+        return t[: self._sim.state.N].cpu().numpy()
 
     def _summary(self, name="summary"):
         if not self._attached:
@@ -1907,24 +1815,11 @@ class _BondOrderRecorder(_Recorder):
     def __init__(self, compute, trigger):
         if not isinstance(compute, self._kind):
             raise _lib.AzpError("%s: a %s is expected, got %r" % (type(self).__name__, self._kind.__name__, compute))
-        self._target = compute
+        self._compute = compute
         super().__init__(trigger)
 
-    @property
-    def _compute(self):
-        return self._target
-
-    def _row_width(self):
-        return self._target._row_width()
-
-    def reset(self):
-        """Forget the recorded rows."""
-        self._rows = None
-        self._steps = []
-        self._volumes = []
-
     def _table(self):
-        c = self._target
+        c = self._compute
         k = len(self._steps)
         rows = self._rows[:k].cpu().numpy() if k else np.zeros((0, self._row_width()), dtype=np.int64)
         return [steinhardt_summary(r, len(c.l), c._num_bins) for r in rows]
@@ -1949,12 +1844,12 @@ class SteinhardtRecorder(_BondOrderRecorder):
     @property
     def order(self):
         t = self._table()
-        return np.array([r["order"] for r in t]).reshape(len(t), len(self._target.l))
+        return np.array([r["order"] for r in t]).reshape(len(t), len(self._compute.l))
 
     @property
     def histogram(self):
         t = self._table()
-        c = self._target
+        c = self._compute
         return np.array([r["histogram"] for r in t], dtype=np.int64).reshape(len(t), len(c.l), c.num_bins)
 
 
@@ -2063,9 +1958,7 @@ class Cluster(_Compute):
         self.path = _lib.CLUSTER_PATH_AUTO
         self._stages = 0      # (tools/cluster_probe.py: 1 and 2 stop the call early, for timing)
         self._out = None      # (N, device, keys, sizes)
-        self._row = None
         self._solid_row = None
-        self._scratch = None
 
     @property
     def r_max(self):
@@ -2097,14 +1990,7 @@ class Cluster(_Compute):
     def _check_box(self, sim):
         if sim.domain is not None:
             raise _lib.AzpError("Cluster: decomposed runs are not supported (a cluster may span ranks)")
-        box = sim.state.box
-        widths = perpendicular_widths(box)
-        for d in range(3):
-            if not widths[d] > 0.0:
-                raise _lib.AzpError("Cluster: a 3-D box is needed (2-D systems are not supported), got %r" % (box,))
-            if box.periodic[d] and self._r_max > 0.5 * widths[d]:
-                raise _lib.AzpError("Cluster: r_max = %r is larger than half the perpendicular width %r of periodic axis %d: the "
-                                    "minimum image would not be unique" % (self._r_max, widths[d], d))
+        _check_pair_range("Cluster", sim.state.box, self._r_max)
 
     def _launch(self, d_out):
         """Queue ``azp_cluster_compute`` for the simulation's current state with the summary row going to ``d_out``
@@ -2131,15 +2017,10 @@ class Cluster(_Compute):
         a.d_tag = st.tag.data_ptr()
         mask = self._type_mask(st)
         a.d_type_mask = mask.data_ptr() if mask is not None else None
-        lib = _lib.lib()
-        need = C.c_uint64(0)
         # (every refusal of the cluster's own comes before the SolidLiquid's launch)
-        _lib.check(lib.azp_cluster_scratch_size(C.byref(a), C.byref(need)), "azp_cluster_scratch_size")
+        self._set_scratch(a, "azp_cluster_scratch_size")
         if solid is not None:
-            width = solid._row_width()
-            if self._solid_row is None or self._solid_row.device != st.device or self._solid_row.shape[1] != width:
-                self._solid_row = torch.empty((1, width), dtype=torch.int64, device=st.device)
-            solid._launch(self._solid_row.data_ptr())
+            solid._launch(self._row_buffer(solid._row_width(), "int64", "_solid_row").data_ptr())
             a.d_member = solid._out[2]["num_connections"].data_ptr()
             a.member_min = solid.solid_threshold
         if self._out is None or self._out[0] != st.N or self._out[1] != st.device:
@@ -2148,28 +2029,16 @@ class Cluster(_Compute):
                          torch.empty((n,), dtype=torch.int32, device=st.device))
         a.d_cluster_key = self._out[2].data_ptr()
         a.d_cluster_size = self._out[3].data_ptr()
-        if self._scratch is None or self._scratch.numel() < need.value or self._scratch.device != st.device:
-            self._scratch = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=st.device)
-        a.d_scratch = self._scratch.data_ptr()
-        a.scratch_bytes = self._scratch.numel()
         a.d_summary = d_out
-        _lib.check(lib.azp_cluster_compute(C.byref(a), _lib.raw_stream(st.device)), "azp_cluster_compute")
+        _lib.check(_lib.lib().azp_cluster_compute(C.byref(a), _lib.raw_stream(st.device)), "azp_cluster_compute")
 
     def _read(self, name):
         """One call on the current state, then ``name`` as numpy: ``summary`` (the row), ``cluster_keys`` or
         ``cluster_sizes`` (uint32), or ``both`` (keys, sizes) of that one call."""
-        import torch
-
-        if not self._attached:
-            raise DataAccessError(name)
-        st = self._sim.state
-        width = self._row_width()
-        if self._row is None or self._row.device != st.device or self._row.shape[1] != width:
-            self._row = torch.empty((1, width), dtype=torch.int64, device=st.device)
-        self._launch(self._row.data_ptr())
+        row = self._read_row(name)
         if name == "summary":
-            return self._row.cpu().numpy()[0]
-        keys, sizes = (t[: st.N].cpu().numpy().view(np.uint32) for t in self._out[2:])
+            return row.cpu().numpy()[0]
+        keys, sizes = (t[: self._sim.state.N].cpu().numpy().view(np.uint32) for t in self._out[2:])
         return {"cluster_keys": keys, "cluster_sizes": sizes, "both": (keys, sizes)}[name]
 
     def _summary(self, name="summary"):
@@ -2246,21 +2115,8 @@ class ClusterRecorder(_Recorder):
     def __init__(self, cluster, trigger):
         if not isinstance(cluster, Cluster):
             raise _lib.AzpError("ClusterRecorder: a Cluster is expected, got %r" % (cluster,))
-        self.cluster = cluster
+        self.cluster = self._compute = cluster
         super().__init__(trigger)
-
-    @property
-    def _compute(self):
-        return self.cluster
-
-    def _row_width(self):
-        return self.cluster._row_width()
-
-    def reset(self):
-        """Forget the recorded rows."""
-        self._rows = None
-        self._steps = []
-        self._volumes = []
 
     def _table(self):
         k = len(self._steps)

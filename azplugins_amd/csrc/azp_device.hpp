@@ -130,6 +130,15 @@ __device__ __forceinline__ bool is_interior(const BoxDev& b, double x, double y,
 // type index lives in the low 32 bits of pos.w
 __device__ __forceinline__ int type_from_w(double w) { return __double2loint(w); }
 
+// a type filter of the analysis computes: one byte per type, NULL = every particle; a type outside the table is out
+__device__ __forceinline__ bool type_in_mask(const uint8_t* mask, uint32_t ntypes, double w)
+    {
+    if (!mask)
+        return true;
+    const uint32_t t = (uint32_t)type_from_w(w);
+    return t < ntypes && mask[t] != 0;
+    }
+
 // ---------------------------------------------------------------------------
 // 16-byte loads of Scalar4 rows
 // ---------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // cell_bin.hpp -- the only place that bins particles into cells: the grid and its cell rule, and a counting sort by cell
-// (count with wave-aggregated atomics, exclusive scan, scatter through a caller's sink). azp_nlist_bin (nlist.hip) and
-// the cells path of azp_rdf_counts (rdf.hip) both run bin_particles; azp_nlist_cell_assign runs the assign kernel alone.
-// The non-template kernels are static: two translation units include this header.
+// (count with wave-aggregated atomics, exclusive scan, scatter through a caller's sink). bin_particles is run by
+// azp_nlist_bin (nlist.hip) and, through walk_bin (pair_walk.hpp), by the cells paths of azp_rdf_counts (rdf.hip),
+// azp_steinhardt_compute (steinhardt.hip) and azp_cluster_compute (cluster.hip); azp_nlist_cell_assign runs the assign
+// kernel alone. The non-template kernels are static: several translation units include this header.
 #pragma once
 
 #include "azp_device.hpp"

@@ -3,14 +3,14 @@
 // union-find over the slots of the order the pair walk works in.
 //
 // The launches of one call, all on the caller's stream:
-//   order    cells: bin_particles (cell_bin.hpp) into this call's scratch, its scatter leaves (x, y, z, flags) per slot
+//   order    cells: walk_bin (pair_walk.hpp) into this call's scratch, its scatter leaves (x, y, z, flags) per slot
 //            and the permutation slot -> row; all-pairs: the row order. Group and d_member are folded into the flag
 //            here, so the pair walk never gathers. parent[slot] = slot, min_tag = NONE, size = 0.
-//   union    the walk of the Steinhardt and RDF passes, written for this kernel: a tile of T <= 256 rows contiguous in
-//            the order, against up to 27 contiguous candidate segments staged through LDS in chunks of 256 (x, y, z as
-//            three double arrays and the candidate's slot; a candidate outside G is staged as NaN, which fails
-//            rsq < r_max^2), 256 / pow2ceil(T) lanes per row. A pair is taken where candidate slot < row slot: united
-//            once, counted once. Pairs inside the tile are united in an LDS union-find over the tile's rows; a pair
+//   union    the walk of pair_walk.hpp, the one the Steinhardt and RDF passes take: a tile of
+//            T <= 256 rows contiguous in the order, against up to 27 contiguous candidate segments staged through LDS
+//            in chunks of 256 (x, y, z as three double arrays and the candidate's slot). A pair is taken where
+//            candidate slot < row slot: united once, counted once. Pairs inside the tile are united in an LDS
+//            union-find over the tile's rows; a pair
 //            with a candidate before the tile is united in global memory at once; when the candidates are through,
 //            every row that is not the root of its LDS component is united with that root in global memory. (One
 //            cell's 300 particles, 44,850 edges: 255 + 43 such unions and 44 x 256 finds that end on one word after
@@ -36,16 +36,11 @@
 // persistent workgroup. The LDS union-find is the same code at workgroup scope.
 // What the call outputs is a function of the graph and the tags alone: the components do not depend on the order of the
 // unions, the key is the smallest tag, sizes and counts are integers.
-#include <algorithm>
-#include <cmath>
-
-#include "cell_bin.hpp"
+#include "pair_walk.hpp"
 
 namespace azp
 {
-constexpr uint32_t CL_BLOCK = 256;           // threads, rows per tile and candidates per chunk
-constexpr uint32_t CL_TARGET_BLOCKS = 2048;  // 256 CUs x 8
-constexpr uint32_t CL_MAX_CELLS = 1u << 21;
+constexpr uint32_t CL_BLOCK = WALK_BLOCK;    // threads, rows per tile and candidates per chunk
 constexpr uint32_t CL_HEAD_BYTES = 256;      // the packed maximum, zeroed per call
 constexpr uint32_t CL_LDS_BYTES = 3u * CL_BLOCK * 8u + 2u * CL_BLOCK * 4u;
 
@@ -59,7 +54,8 @@ struct ClKArgs
     BoxDev box;
     double rmaxsq;
     // the order the passes work in
-    double* sorted;            // N x 4: x, y, z, flags (1: in G)
+    double* sorted;            // N x 4: x, y, z, flag (1.0: in G, else 0.0; rows and candidates are the same set, so
+                               // this kernel keeps its one-value flag and not the two-bit word of pair_walk.hpp)
     const uint32_t* perm;      // slot -> row, NULL: the row order itself
     GridDev grid;
     uint32_t ncell, cells_per_block;
@@ -78,13 +74,7 @@ struct ClKArgs
 
 __device__ __forceinline__ bool cl_in_group(const ClKArgs& a, uint32_t p, double w)
     {
-    if (a.mask)
-        {
-        const uint32_t t = (uint32_t)type_from_w(w);
-        if (!(t < a.ntypes && a.mask[t] != 0))
-            return false;
-        }
-    return !a.member || a.member[p] >= a.member_min;
+    return type_in_mask(a.mask, a.ntypes, w) && (!a.member || a.member[p] >= a.member_min);
     }
 
 __device__ __forceinline__ void cl_init_slot(const ClKArgs& a, uint32_t slot, uint32_t p)
@@ -168,10 +158,8 @@ __device__ __forceinline__ void cl_tile(const ClKArgs& a, uint32_t slot0, uint32
     uint32_t* s_slot = reinterpret_cast<uint32_t*>(s_z + C);  // the staged candidates' slots
     uint32_t* s_par = s_slot + C;                             // the tile's own union-find, over its rows
     s_par[tid] = tid;
-    // T rows, Tp = pow2ceil(T) row slots, G = 256 / Tp lanes per row
-    const uint32_t lg = T > 1 ? 32u - (uint32_t)__builtin_clz(T - 1) : 0u;
-    const uint32_t G = CL_BLOCK >> lg;
-    const uint32_t r = tid & ((1u << lg) - 1u), sub = tid >> lg;
+    const TileLanes l = tile_lanes(T);
+    const uint32_t r = l.r;
     bool row = false;
     double xi = 0.0, yi = 0.0, zi = 0.0;
     if (r < T)
@@ -192,10 +180,7 @@ __device__ __forceinline__ void cl_tile(const ClKArgs& a, uint32_t slot0, uint32
             uint32_t slot = 0;
             if (q < M)
                 {
-                uint32_t s = 0;
-                while (q >= s_seg_end[s + 1])
-                    ++s;
-                slot = s_seg_start[s] + (q - s_seg_end[s]);
+                slot = walk_candidate_slot(q, s_seg_start, s_seg_end);
                 const double4 p = load_scalar4(a.sorted, slot);
                 if (p.w != 0.0)
                     {
@@ -208,13 +193,10 @@ __device__ __forceinline__ void cl_tile(const ClKArgs& a, uint32_t slot0, uint32
             const uint32_t n = min(C, M - cb);
             if (row)
                 {
-                for (uint32_t cc = sub; cc < n; cc += G)
+                for (uint32_t cc = l.sub; cc < n; cc += l.G)
                     {
-                    // (the acceptance rule of rdf_test: d = r_i - r_j through min_image, rsq < r_max^2)
-                    double dx = xi - s_x[cc], dy = yi - s_y[cc], dz = zi - s_z[cc];
-                    min_image(a.box, dx, dy, dz);
-                    const double rsq = dx * dx + dy * dy + dz * dz;
-                    if (!(rsq < a.rmaxsq))
+                    double dx = xi - s_x[cc], dy = yi - s_y[cc], dz = zi - s_z[cc], rsq;
+                    if (!walk_accept(a.box, a.rmaxsq, dx, dy, dz, rsq))
                         continue;
                     const uint32_t cs = s_slot[cc];
                     if (cs >= rslot)  // (the row itself, and the pair that the other row takes)
@@ -283,6 +265,8 @@ __global__ void __launch_bounds__(CL_BLOCK) cl_union_cells(const ClKArgs a)
     const uint32_t c1 = (uint32_t)std::min<uint64_t>(c0 + a.cells_per_block, a.ncell);
     const uint32_t dx = a.grid.dim[0], dy = a.grid.dim[1], dz = a.grid.dim[2];
     unsigned long long edges = 0;
+    // (the cell loop and stencil table of the walk: the same lines in rdf_cells, st_pairs_cells and cl_union_cells,
+    // pair_walk.hpp says why)
     for (uint32_t c = (uint32_t)c0; c < c1; ++c)
         {
         const uint32_t rs = a.start[c], rn = a.start[c + 1] - rs;
@@ -444,48 +428,13 @@ __global__ void cl_finish_kernel(const unsigned long long* best, long long* summ
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
-// the cell grid of the cells path, by the rule of azp_steinhardt_compute and azp_rdf_counts; false if the box does not
-// allow it
-static bool cl_make_grid(const azp_box& b, double r_max, uint32_t n, GridDev& g)
-    {
-    if (b.tilt[0] != 0.0 || b.tilt[1] != 0.0 || b.tilt[2] != 0.0)
-        return false;
-    double dim[3];
-    for (int d = 0; d < 3; ++d)
-        {
-        dim[d] = std::floor(b.L[d] / r_max);
-        if (b.periodic[d] && dim[d] < 3.0)
-            return false;
-        dim[d] = std::min(std::max(dim[d], 1.0), 1024.0);
-        }
-    const double cap = std::min<double>(CL_MAX_CELLS, std::max<double>(64.0, 2.0 * n));
-    for (int pass = 0; pass < 64 && dim[0] * dim[1] * dim[2] > cap; ++pass)
-        {
-        const double f = std::cbrt(cap / (dim[0] * dim[1] * dim[2]));
-        for (int d = 0; d < 3; ++d)
-            dim[d] = std::max(b.periodic[d] ? 3.0 : 1.0, std::floor(dim[d] * std::min(f, 0.95)));
-        }
-    if (dim[0] * dim[1] * dim[2] > (double)CL_MAX_CELLS)
-        return false;
-    for (int d = 0; d < 3; ++d)
-        {
-        g.dim[d] = (int)dim[d];
-        g.lo[d] = -0.5 * b.L[d];
-        g.winv[d] = dim[d] / b.L[d];
-        g.periodic[d] = b.periodic[d] != 0;
-        }
-    return true;
-    }
-
 struct ClPlan
     {
     int path;  // 1 all-pairs, 2 cells
     GridDev grid;
-    uint32_t ncell;
-    uint64_t off_sorted, off_parent, off_root, off_min_tag, off_size, off_cell_id, off_count, off_start, off_perm, bytes;
+    CellOrder order;  // path 2: behind the per-slot arrays
+    uint64_t off_sorted, off_parent, off_root, off_min_tag, off_size, bytes;
     };
-
-static uint64_t cl_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 
 static int cl_plan(const azp_cluster_args* a, ClPlan& p)
     {
@@ -502,27 +451,21 @@ static int cl_plan(const azp_cluster_args* a, ClPlan& p)
     for (int d = 0; d < 3; ++d)
         if (a->box.periodic[d] && a->r_max > 0.5 * w[d])
             return AZP_ERROR_INVALID_ARGUMENT;  // the minimum image would not be unique
-    const bool cells = cl_make_grid(a->box, a->r_max, a->N, p.grid);
+    const bool cells = walk_make_grid(a->box, a->r_max, a->N, p.grid);
     if (a->path == 2 && !cells)
         return AZP_ERROR_INVALID_ARGUMENT;
     p.path = (a->path == 1 || !cells) ? 1 : 2;
-    const uint64_t n = a->N, words = cl_align(n * 4);
+    const uint64_t n = a->N, words = walk_align(n * 4);
     p.off_sorted = CL_HEAD_BYTES;
-    p.off_parent = p.off_sorted + cl_align(n * 32);
+    p.off_parent = p.off_sorted + walk_align(n * 32);
     p.off_root = p.off_parent + words;
     p.off_min_tag = p.off_root + words;
     p.off_size = p.off_min_tag + words;
-    p.off_cell_id = p.off_size + words;
-    p.bytes = p.off_cell_id;
-    p.ncell = 0;
-    p.off_count = p.off_start = p.off_perm = 0;
+    p.bytes = p.off_size + words;
     if (p.path == 2)
         {
-        p.ncell = (uint32_t)p.grid.dim[0] * (uint32_t)p.grid.dim[1] * (uint32_t)p.grid.dim[2];
-        p.off_count = p.off_cell_id + words;
-        p.off_start = p.off_count + cl_align((uint64_t)p.ncell * 4);
-        p.off_perm = p.off_start + cl_align(((uint64_t)p.ncell + 1) * 4);
-        p.bytes = p.off_perm + words;
+        p.order = walk_cell_order(p.bytes, n, p.grid, true);
+        p.bytes = p.order.bytes;
         }
     return AZP_SUCCESS;
     }
@@ -597,17 +540,12 @@ extern "C" int azp_cluster_compute(const azp_cluster_args* args, void* stream)
     else
         {
         k.grid = p.grid;
-        k.ncell = p.ncell;
-        uint32_t* perm = reinterpret_cast<uint32_t*>(base + p.off_perm);
-        uint32_t* start = reinterpret_cast<uint32_t*>(base + p.off_start);
+        k.ncell = p.order.ncell;
+        uint32_t* perm = walk_words(base, p.order.off_perm);
         k.perm = perm;
-        k.start = start;
-        // (the block totals of the three-kernel scan live in the head of `sorted`, which the scatter fills only
-        // afterwards: nblk + 1 <= N words fit into N rows)
+        k.start = walk_words(base, p.order.off_start);
         const ClRowSink sink = {k, perm};
-        e = bin_particles(args->N, k.pos, k.grid, nullptr, reinterpret_cast<uint32_t*>(base + p.off_cell_id),
-                          reinterpret_cast<uint32_t*>(base + p.off_count), start, reinterpret_cast<uint32_t*>(k.sorted), sink, st);
-        if (e != hipSuccess)
+        if ((e = walk_bin(args->N, k.pos, k.grid, base, p.order, k.sorted, sink, st)) != hipSuccess)
             return (int)e;
         }
     if (args->stages == 1)
@@ -616,9 +554,7 @@ extern "C" int azp_cluster_compute(const azp_cluster_args* args, void* stream)
         hipLaunchKernelGGL(cl_union_all, per_row, block, CL_LDS_BYTES, st, k);
     else
         {
-        // (a multiple of 8 workgroups, each a contiguous range of cells: xcd_remap gives every XCD one eighth of the grid)
-        const uint32_t grid = (std::min(p.ncell, CL_TARGET_BLOCKS) + 7u) & ~7u;
-        k.cells_per_block = (p.ncell + grid - 1) / grid;
+        const uint32_t grid = walk_launch_blocks(k.ncell, k.cells_per_block);
         hipLaunchKernelGGL(cl_union_cells, dim3(grid), block, CL_LDS_BYTES, st, k);
         }
     if ((e = hipGetLastError()) != hipSuccess || args->stages == 2)

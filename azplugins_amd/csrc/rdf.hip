@@ -13,13 +13,11 @@
 //              in chunks of 256 (x, y, z as three double arrays; a candidate outside B is staged as NaN, which fails
 //              rsq < r_max^2), every lane tests every staged candidate (one LDS address per wave: a broadcast read).
 //   cells      (orthorhombic box, >= 3 cells of width >= r_max on every periodic axis; a non-periodic axis has
-//              clamped cells, as azp_cell_grid.periodic = 0). All n_total particles are binned by the counting sort of
-//              cell_bin.hpp (bin_particles, the one azp_nlist_bin runs) in this call's scratch; its scatter writes
-//              (x, y, z, flags) rows into cell order. No order is imposed inside a cell: pair counts do not
-//              depend on it. rdf_cells then gives every workgroup a contiguous range of cells (xcd_remap: one eighth of
-//              the cells per XCD); per cell, its rows are taken 256 at a time, a tile of T rows is served by
-//              256 / pow2ceil(T) lanes per row, and the members of the 27 stencil cells are staged through LDS in
-//              chunks of 256 as above (never read straight from global memory by the pair loop).
+//              clamped cells, as azp_cell_grid.periodic = 0). The walk of pair_walk.hpp over all n_total particles:
+//              binned in this call's scratch, the scatter writes (x, y, z, flags) rows into cell order (no order is
+//              imposed inside a cell: pair counts do not depend on it); rdf_cells takes a cell's rows 256 at a time
+//              and stages the members of the 27 stencil cells through LDS in chunks of 256 as above (never read
+//              straight from global memory by the pair loop).
 //
 // Accumulation is integer throughout and on chip first: one uint32 histogram of num_bins words per workgroup in LDS,
 // incremented with LDS integer atomics (ds_add_u32 without return). Overflow bound: between two flushes a bin
@@ -34,20 +32,14 @@
 // Bytes: all-pairs reads 32 B per (row tile, candidate): 32 n_total ceil(N / 256) in all. Cells: binning reads pos
 // twice (64 B per particle) and writes 36 B per particle; the pair kernel reads 32 B per staged candidate, i.e.
 // 32 x 27 x ceil(rows of the cell / 256) per particle, plus 32 B per row.
-#include <algorithm>
-#include <cmath>
-
-#include "cell_bin.hpp"
+#include "pair_walk.hpp"
 
 namespace azp
 {
-constexpr uint32_t RDF_BLOCK = 256;
+constexpr uint32_t RDF_BLOCK = WALK_BLOCK;
 constexpr uint32_t RDF_CHUNK = 256;
 constexpr uint32_t RDF_CHUNK_TESTS = RDF_BLOCK * RDF_CHUNK;       // most increments a bin gets from one staged chunk
 constexpr uint32_t RDF_FLUSH_AT = 0xFFFFFFFFu - RDF_CHUNK_TESTS;  // flush once `pending` has passed this
-constexpr uint32_t RDF_TARGET_BLOCKS = 2048;                      // 256 CUs x 8
-constexpr uint32_t RDF_MAX_CELLS = 1u << 21;
-constexpr uint32_t RDF_AUTO_CELLS_MIN_N = 0;  // path 0 takes the cells wherever they are valid
 
 struct RdfKArgs
     {
@@ -65,27 +57,18 @@ struct RdfKArgs
     // cells path
     GridDev grid;
     uint32_t ncell;
-    double* sorted;        // n_total x 4: x, y, z, flags (1: row of A below N, 2: member of B)
+    double* sorted;        // n_total x 4: x, y, z, flags (WALK_ROW: row of A below N, WALK_CANDIDATE: member of B)
     uint32_t* start;       // ncell + 1
     uint32_t cells_per_block;
     uint32_t seg_len;      // all-pairs: candidates per segment of B (a multiple of RDF_CHUNK)
     };
 
-__device__ __forceinline__ bool rdf_in_mask(const uint8_t* mask, uint32_t ntypes, double w)
-    {
-    if (!mask)
-        return true;
-    const uint32_t t = (uint32_t)type_from_w(w);
-    return t < ntypes && mask[t] != 0;
-    }
-
-// one (row, candidate) test: d = r_i - r_j before the minimum image
+// one (row, candidate) test: d = r_i - r_j before the minimum image, accepted by the rule of the walk (walk_accept)
 __device__ __forceinline__ void rdf_test(const BoxDev& b, double dx, double dy, double dz, double rmaxsq, double scale,
                                          uint32_t last_bin, uint32_t* hist)
     {
-    min_image(b, dx, dy, dz);
-    const double rsq = dx * dx + dy * dy + dz * dz;
-    if (rsq < rmaxsq)
+    double rsq;
+    if (walk_accept(b, rmaxsq, dx, dy, dz, rsq))
         {
         const double r = sqrt(rsq);  // (IEEE, correctly rounded: the bin of a pair is a property of its rsq alone)
         const uint32_t k = min((uint32_t)(r * scale), last_bin);
@@ -123,7 +106,7 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_all_pairs(const RdfKArgs a)
         {
         const double4 p = load_scalar4(a.pos, (uint32_t)i);
         xi = p.x; yi = p.y; zi = p.z;
-        row = rdf_in_mask(a.mask_a, a.ntypes, p.w);
+        row = type_in_mask(a.mask_a, a.ntypes, p.w);
         }
     const uint64_t j0 = (uint64_t)blockIdx.y * a.seg_len;
     const uint64_t j1 = std::min<uint64_t>(j0 + a.seg_len, a.n_total);
@@ -138,7 +121,7 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_all_pairs(const RdfKArgs a)
         if (j < j1)
             {
             const double4 p = load_scalar4(a.pos, (uint32_t)j);
-            if (rdf_in_mask(a.mask_b, a.ntypes, p.w))
+            if (type_in_mask(a.mask_b, a.ntypes, p.w))
                 {
                 x = p.x; y = p.y; z = p.z;
                 }
@@ -177,8 +160,8 @@ struct RdfRowSink
     __device__ void operator()(uint32_t slot, uint32_t p) const
         {
         const double4 r = load_scalar4(pos, p);
-        const uint32_t flags = ((p < N && rdf_in_mask(mask_a, ntypes, r.w)) ? 1u : 0u) | (rdf_in_mask(mask_b, ntypes, r.w) ? 2u : 0u);
-        store_scalar4(sorted, slot, r.x, r.y, r.z, (double)flags);
+        store_scalar4(sorted, slot, r.x, r.y, r.z,
+                      walk_flags(p < N && type_in_mask(mask_a, ntypes, r.w), type_in_mask(mask_b, ntypes, r.w)));
         }
     };
 
@@ -193,11 +176,12 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_cells(const RdfKArgs a)
     const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
     const uint64_t c0 = (uint64_t)b * a.cells_per_block;
     const uint32_t c1 = (uint32_t)std::min<uint64_t>(c0 + a.cells_per_block, a.ncell);
-    const uint32_t last_bin = a.num_bins - 1;
-    const double nan = __builtin_nan("");
     const uint32_t dx = a.grid.dim[0], dy = a.grid.dim[1], dz = a.grid.dim[2];
+    const uint32_t last_bin = a.num_bins - 1;
     uint32_t pending = 0;
     __syncthreads();
+    // (the cell loop and stencil table of the walk: the same lines in rdf_cells, st_pairs_cells and cl_union_cells,
+    // pair_walk.hpp says why)
     for (uint32_t c = (uint32_t)c0; c < c1; ++c)
         {
         const uint32_t rs = a.start[c], rn = a.start[c + 1] - rs;
@@ -208,7 +192,7 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_cells(const RdfKArgs a)
             const int cell[3] = {(int)(c % dx), (int)((c / dx) % dy), (int)(c / (dx * dy))};
             const int off[3] = {(int)(tid % 3) - 1, (int)((tid / 3) % 3) - 1, (int)(tid / 9) - 1};
             const int dim[3] = {(int)dx, (int)dy, (int)dz};
-            int nb[3];
+            int nbc[3];
             bool ok = true;
 #pragma unroll
             for (int d = 0; d < 3; ++d)
@@ -218,12 +202,12 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_cells(const RdfKArgs a)
                     v = v < 0 ? v + dim[d] : (v >= dim[d] ? v - dim[d] : v);
                 else if (v < 0 || v >= dim[d])
                     ok = false;
-                nb[d] = v;
+                nbc[d] = v;
                 }
             uint32_t s0 = 0, cnt = 0;
             if (ok)
                 {
-                const uint32_t nc = ((uint32_t)nb[2] * dy + (uint32_t)nb[1]) * dx + (uint32_t)nb[0];
+                const uint32_t nc = ((uint32_t)nbc[2] * dy + (uint32_t)nbc[1]) * dx + (uint32_t)nbc[0];
                 s0 = a.start[nc];
                 cnt = a.start[nc + 1] - s0;
                 }
@@ -246,43 +230,25 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_cells(const RdfKArgs a)
         const uint32_t own0 = s_seg_end[13];  // the cell's own members start here in the flat candidate list
         for (uint32_t rt = 0; rt < rn; rt += RDF_BLOCK)
             {
-            const uint32_t T = min(RDF_BLOCK, rn - rt);
-            // T rows, Tp = pow2ceil(T) row slots, G = 256 / Tp lanes per row
-            const uint32_t lg = T > 1 ? 32u - (uint32_t)__builtin_clz(T - 1) : 0u;
-            const uint32_t G = RDF_BLOCK >> lg;
-            const uint32_t r = tid & ((1u << lg) - 1u), sub = tid >> lg;
-            bool row = false;
-            double xi = 0.0, yi = 0.0, zi = 0.0;
-            if (r < T)
-                {
-                const double4 p = load_scalar4(a.sorted, rs + rt + r);
-                xi = p.x; yi = p.y; zi = p.z;
-                row = ((uint32_t)p.w & 1u) != 0;
-                }
-            const uint32_t self = own0 + rt + r;
+            const uint32_t slot0 = rs + rt, T = min(RDF_BLOCK, rn - rt);
+            const TileLanes l = tile_lanes(T);
+            double xi, yi, zi;
+            const bool row = walk_row(a.sorted, slot0, T, l.r, xi, yi, zi);
+            const uint32_t self = own0 + rt + l.r;
             if (!__syncthreads_or(row))
                 continue;
             for (uint32_t cb = 0; cb < M; cb += RDF_CHUNK)
                 {
                 const uint32_t q = cb + tid;
-                double x = nan, y = nan, z = nan;
+                double3 p = walk_no_candidate();
                 if (q < M)
-                    {
-                    uint32_t s = 0;
-                    while (q >= s_seg_end[s + 1])
-                        ++s;
-                    const double4 p = load_scalar4(a.sorted, s_seg_start[s] + (q - s_seg_end[s]));
-                    if ((uint32_t)p.w & 2u)
-                        {
-                        x = p.x; y = p.y; z = p.z;
-                        }
-                    }
-                s_x[tid] = x; s_y[tid] = y; s_z[tid] = z;
+                    p = walk_candidate(a.sorted, walk_candidate_slot(q, s_seg_start, s_seg_end));
+                s_x[tid] = p.x; s_y[tid] = p.y; s_z[tid] = p.z;
                 __syncthreads();
                 const uint32_t n = min(RDF_CHUNK, M - cb);
                 if (row)
                     {
-                    for (uint32_t cc = sub; cc < n; cc += G)
+                    for (uint32_t cc = l.sub; cc < n; cc += l.G)
                         if (cb + cc != self)
                             rdf_test(a.box, xi - s_x[cc], yi - s_y[cc], zi - s_z[cc], a.rmaxsq, a.scale, last_bin, s_hist);
                     }
@@ -311,7 +277,7 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_group_counts(const RdfKArgs a)
     for (uint64_t i = (uint64_t)blockIdx.x * RDF_BLOCK + tid; i < a.N; i += (uint64_t)gridDim.x * RDF_BLOCK)
         {
         const double w = a.pos[4ull * i + 3];
-        const bool in_a = rdf_in_mask(a.mask_a, a.ntypes, w), in_b = rdf_in_mask(a.mask_b, a.ntypes, w);
+        const bool in_a = type_in_mask(a.mask_a, a.ntypes, w), in_b = type_in_mask(a.mask_b, a.ntypes, w);
         n[0] += in_a; n[1] += in_b; n[2] += in_a && in_b;
         }
 #pragma unroll
@@ -351,7 +317,7 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_subtract_excluded(const RdfKArg
         if (n == 0)
             continue;
         const double4 p = load_scalar4(a.pos, (uint32_t)i);
-        if (!rdf_in_mask(a.mask_a, a.ntypes, p.w))
+        if (!type_in_mask(a.mask_a, a.ntypes, p.w))
             continue;
         for (uint32_t s = 0; s < n; ++s)
             {
@@ -359,7 +325,7 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_subtract_excluded(const RdfKArg
             if (j >= a.n_total || j == i)
                 continue;
             const double4 q = load_scalar4(a.pos, j);
-            if (rdf_in_mask(a.mask_b, a.ntypes, q.w))
+            if (type_in_mask(a.mask_b, a.ntypes, q.w))
                 rdf_test(a.box, p.x - q.x, p.y - q.y, p.z - q.z, a.rmaxsq, a.scale, last_bin, s_hist);
             }
         }
@@ -384,49 +350,13 @@ __global__ void __launch_bounds__(RDF_BLOCK) rdf_subtract_excluded(const RdfKArg
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
-// the cell grid of the cells path; false if the box does not allow it (winv = dim / L, filled here: make_grid_dev's
-// 1 / (L / dim) may differ in the last bit)
-static bool rdf_make_grid(const azp_box& b, double r_max, uint32_t n_total, GridDev& g)
-    {
-    if (b.tilt[0] != 0.0 || b.tilt[1] != 0.0 || b.tilt[2] != 0.0)
-        return false;
-    double dim[3];
-    for (int d = 0; d < 3; ++d)
-        {
-        dim[d] = std::floor(b.L[d] / r_max);
-        if (b.periodic[d] && dim[d] < 3.0)
-            return false;
-        dim[d] = std::min(std::max(dim[d], 1.0), 1024.0);
-        }
-    // (a sparse system: no more cells than a few per particle, at most RDF_MAX_CELLS; wider cells stay valid)
-    const double cap = std::min<double>(RDF_MAX_CELLS, std::max<double>(64.0, 2.0 * n_total));
-    for (int pass = 0; pass < 64 && dim[0] * dim[1] * dim[2] > cap; ++pass)
-        {
-        const double f = std::cbrt(cap / (dim[0] * dim[1] * dim[2]));
-        for (int d = 0; d < 3; ++d)
-            dim[d] = std::max(b.periodic[d] ? 3.0 : 1.0, std::floor(dim[d] * std::min(f, 0.95)));
-        }
-    if (dim[0] * dim[1] * dim[2] > (double)RDF_MAX_CELLS)
-        return false;
-    for (int d = 0; d < 3; ++d)
-        {
-        g.dim[d] = (int)dim[d];
-        g.lo[d] = -0.5 * b.L[d];
-        g.winv[d] = dim[d] / b.L[d];
-        g.periodic[d] = b.periodic[d] != 0;
-        }
-    return true;
-    }
-
 struct RdfPlan
     {
     int path;  // 1 all-pairs, 2 cells
     GridDev grid;
-    uint32_t ncell;
-    uint64_t off_cell_id, off_count, off_start, bytes;
+    CellOrder order;  // behind `sorted`, which heads the scratch
+    uint64_t bytes;
     };
-
-static uint64_t rdf_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 
 static int rdf_plan(const azp_rdf_args* a, RdfPlan& p)
     {
@@ -443,20 +373,34 @@ static int rdf_plan(const azp_rdf_args* a, RdfPlan& p)
     for (int d = 0; d < 3; ++d)
         if (a->box.periodic[d] && a->r_max > 0.5 * w[d])
             return AZP_ERROR_INVALID_ARGUMENT;  // the minimum image would not be unique
-    const bool cells = rdf_make_grid(a->box, a->r_max, a->n_total, p.grid);
+    const bool cells = walk_make_grid(a->box, a->r_max, a->n_total, p.grid);
     if (a->path == 2 && !cells)
         return AZP_ERROR_INVALID_ARGUMENT;
-    p.path = (a->path == 1 || !cells || (a->path == 0 && a->n_total < RDF_AUTO_CELLS_MIN_N)) ? 1 : 2;
+    p.path = (a->path == 1 || !cells) ? 1 : 2;  // (path 0 takes the cells wherever they are valid)
     p.bytes = 0;
     if (p.path == 2)
         {
-        p.ncell = (uint32_t)p.grid.dim[0] * (uint32_t)p.grid.dim[1] * (uint32_t)p.grid.dim[2];
-        p.off_cell_id = rdf_align((uint64_t)a->n_total * 32);
-        p.off_count = p.off_cell_id + rdf_align((uint64_t)a->n_total * 4);
-        p.off_start = p.off_count + rdf_align((uint64_t)p.ncell * 4);
-        p.bytes = p.off_start + rdf_align(((uint64_t)p.ncell + 1) * 4);
+        p.order = walk_cell_order(walk_align((uint64_t)a->n_total * 32), a->n_total, p.grid, false);
+        p.bytes = p.order.bytes;
         }
     return AZP_SUCCESS;
+    }
+
+static RdfKArgs rdf_kernel_args(const azp_rdf_args* args)
+    {
+    RdfKArgs k = {};
+    k.pos = args->d_pos;
+    k.mask_a = args->d_type_mask_a;
+    k.mask_b = args->d_type_mask_b;
+    k.out = reinterpret_cast<unsigned long long*>(args->d_out);
+    k.box = make_box_dev(args->box);
+    k.rmaxsq = args->r_max * args->r_max;
+    k.scale = args->scale;
+    k.N = args->N;
+    k.n_total = args->n_total;
+    k.ntypes = args->ntypes;
+    k.num_bins = args->num_bins;
+    return k;
     }
 
 } // namespace azp
@@ -489,18 +433,7 @@ extern "C" int azp_rdf_counts(const azp_rdf_args* args, void* stream)
     hipError_t e = hipMemsetAsync(args->d_out, 0, ((uint64_t)args->num_bins + 4) * sizeof(uint64_t), st);
     if (e != hipSuccess || args->N == 0)
         return (int)e;
-    RdfKArgs k = {};
-    k.pos = args->d_pos;
-    k.mask_a = args->d_type_mask_a;
-    k.mask_b = args->d_type_mask_b;
-    k.out = reinterpret_cast<unsigned long long*>(args->d_out);
-    k.box = make_box_dev(args->box);
-    k.rmaxsq = args->r_max * args->r_max;
-    k.scale = args->scale;
-    k.N = args->N;
-    k.n_total = args->n_total;
-    k.ntypes = args->ntypes;
-    k.num_bins = args->num_bins;
+    RdfKArgs k = rdf_kernel_args(args);
     const uint32_t n_tiles = (args->N + RDF_BLOCK - 1) / RDF_BLOCK;
     hipLaunchKernelGGL(rdf_group_counts, dim3(std::min(n_tiles, 1024u)), dim3(RDF_BLOCK), 0, st, k);
     if ((e = hipGetLastError()) != hipSuccess)
@@ -509,28 +442,21 @@ extern "C" int azp_rdf_counts(const azp_rdf_args* args, void* stream)
     if (p.path == 1)
         {
         const uint32_t n_chunks = (uint32_t)(((uint64_t)args->n_total + RDF_CHUNK - 1) / RDF_CHUNK);
-        uint32_t n_seg = std::min(n_chunks, std::max(1u, RDF_TARGET_BLOCKS / n_tiles));
+        uint32_t n_seg = std::min(n_chunks, std::max(1u, WALK_TARGET_BLOCKS / n_tiles));
         const uint32_t chunks_per_seg = (n_chunks + n_seg - 1) / n_seg;
         n_seg = (n_chunks + chunks_per_seg - 1) / chunks_per_seg;
         k.seg_len = chunks_per_seg * RDF_CHUNK;
         hipLaunchKernelGGL(rdf_all_pairs, dim3(n_tiles, n_seg), dim3(RDF_BLOCK), lds, st, k);
         return (int)hipGetLastError();
         }
-    char* base = static_cast<char*>(args->d_scratch);
     k.grid = p.grid;
-    k.ncell = p.ncell;
-    k.sorted = reinterpret_cast<double*>(base);
-    k.start = reinterpret_cast<uint32_t*>(base + p.off_start);
-    // (the block totals of the three-kernel scan live in the head of `sorted`, which the scatter fills only afterwards:
-    // nblk + 1 <= n_total words fit into n_total rows)
+    k.ncell = p.order.ncell;
+    k.sorted = static_cast<double*>(args->d_scratch);
+    k.start = walk_words(args->d_scratch, p.order.off_start);
     const RdfRowSink sink = {k.pos, k.mask_a, k.mask_b, k.sorted, k.N, k.ntypes};
-    e = bin_particles(args->n_total, k.pos, k.grid, nullptr, reinterpret_cast<uint32_t*>(base + p.off_cell_id),
-                      reinterpret_cast<uint32_t*>(base + p.off_count), k.start, reinterpret_cast<uint32_t*>(base), sink, st);
-    if (e != hipSuccess)
+    if ((e = walk_bin(args->n_total, k.pos, k.grid, args->d_scratch, p.order, k.sorted, sink, st)) != hipSuccess)
         return (int)e;
-    // (a multiple of 8 workgroups, each a contiguous range of cells: xcd_remap gives every XCD one eighth of the grid)
-    const uint32_t grid = (std::min(p.ncell, RDF_TARGET_BLOCKS) + 7u) & ~7u;
-    k.cells_per_block = (p.ncell + grid - 1) / grid;
+    const uint32_t grid = walk_launch_blocks(k.ncell, k.cells_per_block);
     hipLaunchKernelGGL(rdf_cells, dim3(grid), dim3(RDF_BLOCK), lds, st, k);
     return (int)hipGetLastError();
     }
@@ -553,20 +479,9 @@ extern "C" int azp_rdf_subtract_excluded(const azp_rdf_exclusion_args* xargs, vo
         return AZP_SUCCESS;
     if (!xargs->d_n_excl || !xargs->d_excl || xargs->excl_pitch < args->N)
         return AZP_ERROR_INVALID_ARGUMENT;
-    RdfKArgs k = {};
-    k.pos = args->d_pos;
-    k.mask_a = args->d_type_mask_a;
-    k.mask_b = args->d_type_mask_b;
-    k.out = reinterpret_cast<unsigned long long*>(args->d_out);
-    k.box = make_box_dev(args->box);
-    k.rmaxsq = args->r_max * args->r_max;
-    k.scale = args->scale;
-    k.N = args->N;
-    k.n_total = args->n_total;
-    k.ntypes = args->ntypes;
-    k.num_bins = args->num_bins;
+    RdfKArgs k = rdf_kernel_args(args);
     const uint32_t n_tiles = (args->N + RDF_BLOCK - 1) / RDF_BLOCK;
-    hipLaunchKernelGGL(rdf_subtract_excluded, dim3(std::min(n_tiles, RDF_TARGET_BLOCKS)), dim3(RDF_BLOCK),
+    hipLaunchKernelGGL(rdf_subtract_excluded, dim3(std::min(n_tiles, WALK_TARGET_BLOCKS)), dim3(RDF_BLOCK),
                        args->num_bins * sizeof(uint32_t), static_cast<hipStream_t>(stream), k, xargs->d_n_excl, xargs->d_excl,
                        xargs->excl_pitch);
     return (int)hipGetLastError();

@@ -2,14 +2,14 @@
 // DESIGN 4.28): per particle the fixed-point sums S_lm of the spherical harmonics of its bonds, q_l from them, the
 // neighbour average (Lechner-Dellago) and the solid-bond count (ten Wolde-Frenkel), and one summary row.
 //
-// Every pass over the pairs is the same walk: a tile of T <= `tile` rows that are contiguous in the order the pass works
-// in, against a flat list of M candidates made of up to 27 contiguous segments of that order, staged through LDS in
-// chunks (x, y, z as three double arrays; a candidate outside the group is staged as NaN, which fails rsq < r_max^2).
-// Tp = pow2ceil(T) row slots, 256 / Tp lanes per row, lane `sub` of a row takes the staged candidates sub, sub + G, ...
-//   cells      the order is the cell order of cell_bin.hpp (bin_particles in this call's scratch; its scatter leaves
-//              (x, y, z, flags) rows and the permutation); a workgroup walks a contiguous range of cells, a cell's rows
-//              `tile` at a time against the members of its 27 stencil cells. What the first pass leaves (S, N_b, then
-//              q_lm as fixed point or normalised) stays in cell order, so the second pass stages it the same way.
+// Every pass over the pairs is the walk of pair_walk.hpp: a tile of T <= `tile` rows that are contiguous
+// in the order the pass works in, against a flat list of M candidates made of up to 27 contiguous segments of that
+// order, staged through LDS in chunks (x, y, z as three double arrays), the lanes split over the rows by tile_lanes, a
+// pair accepted by walk_accept.
+//   cells      the order is the cell order (walk_bin in this call's scratch; the scatter leaves (x, y, z, flags) rows
+//              and the permutation); st_pairs_cells takes a cell's rows `tile` at a time against the members of its 27
+//              stencil cells. What the first pass leaves (S, N_b, then q_lm as fixed point or normalised) stays in cell
+//              order, so the second pass stages it the same way.
 //   all-pairs  the order is the row order, the candidates are the one segment [0, N); a workgroup per tile.
 // Three passes (template MODE): 0 the terms, 1 the neighbour average, 2 the solid bonds.
 //
@@ -21,19 +21,14 @@
 // words. First pass: chunk 256, tile = min(256, pow2floor(ST_ROW_BYTES / (8 words))), 64 rows for l = (4, 6): 18.5 KB, so
 // that eight workgroups share a CU (with 48 KB of rows and two per CU the pass took 1.7 times as long at N = 2^20,
 // profiles/steinhardt.md). Second passes: tile = chunk = min(128, pow2floor(ST_ROW_BYTES_2 / (8 words))).
-#include <algorithm>
-#include <cmath>
-
-#include "cell_bin.hpp"
+#include "pair_walk.hpp"
 #include "steinhardt_device.hpp"
 
 namespace azp
 {
-constexpr uint32_t ST_BLOCK = 256;
+constexpr uint32_t ST_BLOCK = WALK_BLOCK;
 constexpr uint32_t ST_ROW_BYTES = 12288;    // the rows of a first-pass tile
 constexpr uint32_t ST_ROW_BYTES_2 = 24576;  // the rows of a second-pass tile, and as much again for a chunk's candidates
-constexpr uint32_t ST_TARGET_BLOCKS = 2048;  // 256 CUs x 8
-constexpr uint32_t ST_MAX_CELLS = 1u << 21;
 
 struct StKArgs
     {
@@ -46,7 +41,7 @@ struct StKArgs
     uint32_t words;            // terms.words
     uint32_t tile, chunk;      // rows per tile and candidates per chunk of the pass being launched
     // the order the passes work in
-    double* sorted;            // N x 4: x, y, z, flags (1: a row of G, 2: a candidate of G)
+    double* sorted;            // N x 4: x, y, z, flags (WALK_ROW | WALK_CANDIDATE: in G)
     const uint32_t* perm;      // slot -> row, NULL: the row order itself
     GridDev grid;
     uint32_t ncell, cells_per_block;
@@ -67,12 +62,13 @@ struct StKArgs
     unsigned long long* summary;
     };
 
-__device__ __forceinline__ bool st_in_group(const uint8_t* mask, uint32_t ntypes, double w)
+// particle p's row of `sorted` at `slot`
+__device__ __forceinline__ void st_init_slot(const double* pos, const uint8_t* mask, uint32_t ntypes, double* sorted, uint32_t slot,
+                                             uint32_t p)
     {
-    if (!mask)
-        return true;
-    const uint32_t t = (uint32_t)type_from_w(w);
-    return t < ntypes && mask[t] != 0;
+    const double4 r = load_scalar4(pos, p);
+    const bool in = type_in_mask(mask, ntypes, r.w);
+    store_scalar4(sorted, slot, r.x, r.y, r.z, walk_flags(in, in));
     }
 
 // the rows in row order (the all-pairs path)
@@ -80,10 +76,7 @@ __global__ void __launch_bounds__(ST_BLOCK) st_rows_kernel(const StKArgs a)
     {
     const uint32_t p = blockIdx.x * ST_BLOCK + threadIdx.x;
     if (p < a.N)
-        {
-        const double4 r = load_scalar4(a.pos, p);
-        store_scalar4(a.sorted, p, r.x, r.y, r.z, st_in_group(a.mask, a.ntypes, r.w) ? 3.0 : 0.0);
-        }
+        st_init_slot(a.pos, a.mask, a.ntypes, a.sorted, p, p);
     }
 
 // the rows in cell order: what bin_particles' scatter leaves at a particle's slot
@@ -96,8 +89,7 @@ struct StRowSink
     uint32_t ntypes;
     __device__ void operator()(uint32_t slot, uint32_t p) const
         {
-        const double4 r = load_scalar4(pos, p);
-        store_scalar4(sorted, slot, r.x, r.y, r.z, st_in_group(mask, ntypes, r.w) ? 3.0 : 0.0);
+        st_init_slot(pos, mask, ntypes, sorted, slot, p);
         perm[slot] = p;
         }
     };
@@ -138,20 +130,11 @@ __device__ __forceinline__ void st_tile(const StKArgs& a, uint32_t slot0, uint32
         }
     if (tid < T)
         s_cnt[tid] = 0;
-    // T rows, Tp = pow2ceil(T) row slots, G = 256 / Tp lanes per row
-    const uint32_t lg = T > 1 ? 32u - (uint32_t)__builtin_clz(T - 1) : 0u;
-    const uint32_t G = ST_BLOCK >> lg;
-    const uint32_t r = tid & ((1u << lg) - 1u), sub = tid >> lg;
-    bool row = false;
-    double xi = 0.0, yi = 0.0, zi = 0.0;
-    if (r < T)
-        {
-        const double4 p = load_scalar4(a.sorted, slot0 + r);
-        xi = p.x; yi = p.y; zi = p.z;
-        row = ((uint32_t)p.w & 1u) != 0;
-        }
+    const TileLanes l = tile_lanes(T);
+    const uint32_t r = l.r;
+    double xi, yi, zi;
+    const bool row = walk_row(a.sorted, slot0, T, r, xi, yi, zi);
     const uint32_t self = self0 + r;
-    const double nan = __builtin_nan("");
     if (__syncthreads_or(row))
         {
         for (uint32_t cb = 0; cb < M; cb += C)
@@ -159,18 +142,11 @@ __device__ __forceinline__ void st_tile(const StKArgs& a, uint32_t slot0, uint32
             const uint32_t q = cb + tid;
             if (tid < C)
                 {
-                double x = nan, y = nan, z = nan;
+                double3 c = walk_no_candidate();
                 if (q < M)
                     {
-                    uint32_t s = 0;
-                    while (q >= s_seg_end[s + 1])
-                        ++s;
-                    const uint32_t slot = s_seg_start[s] + (q - s_seg_end[s]);
-                    const double4 p = load_scalar4(a.sorted, slot);
-                    if ((uint32_t)p.w & 2u)
-                        {
-                        x = p.x; y = p.y; z = p.z;
-                        }
+                    const uint32_t slot = walk_candidate_slot(q, s_seg_start, s_seg_end);
+                    c = walk_candidate(a.sorted, slot);
                     if (MODE == 1)
                         for (uint32_t k = 0; k < W; ++k)
                             s_cand[(uint64_t)tid * W + k] = (unsigned long long)a.Q[(uint64_t)slot * W + k];
@@ -178,21 +154,18 @@ __device__ __forceinline__ void st_tile(const StKArgs& a, uint32_t slot0, uint32
                         for (uint32_t k = 0; k < W; ++k)
                             s_candq[(uint64_t)tid * W + k] = a.qhat[(uint64_t)slot * W + k];
                     }
-                s_x[tid] = x; s_y[tid] = y; s_z[tid] = z;
+                s_x[tid] = c.x; s_y[tid] = c.y; s_z[tid] = c.z;
                 }
             __syncthreads();
             const uint32_t n = min(C, M - cb);
             if (row)
                 {
-                for (uint32_t cc = sub; cc < n; cc += G)
+                for (uint32_t cc = l.sub; cc < n; cc += l.G)
                     {
                     if (MODE != 1 && cb + cc == self)
                         continue;
-                    // (the acceptance rule of rdf_test: d = r_i - r_j through min_image, rsq < r_max^2)
-                    double dx = xi - s_x[cc], dy = yi - s_y[cc], dz = zi - s_z[cc];
-                    min_image(a.box, dx, dy, dz);
-                    const double rsq = dx * dx + dy * dy + dz * dz;
-                    if (!(rsq < a.rmaxsq))
+                    double dx = xi - s_x[cc], dy = yi - s_y[cc], dz = zi - s_z[cc], rsq;
+                    if (!walk_accept(a.box, a.rmaxsq, dx, dy, dz, rsq))
                         continue;
                     if (MODE == 0)
                         {
@@ -262,6 +235,8 @@ __global__ void __launch_bounds__(ST_BLOCK) st_pairs_cells(const StKArgs a)
     const uint64_t c0 = (uint64_t)b * a.cells_per_block;
     const uint32_t c1 = (uint32_t)std::min<uint64_t>(c0 + a.cells_per_block, a.ncell);
     const uint32_t dx = a.grid.dim[0], dy = a.grid.dim[1], dz = a.grid.dim[2];
+    // (the cell loop and stencil table of the walk: the same lines in rdf_cells, st_pairs_cells and cl_union_cells,
+    // pair_walk.hpp says why)
     for (uint32_t c = (uint32_t)c0; c < c1; ++c)
         {
         const uint32_t rs = a.start[c], rn = a.start[c + 1] - rs;
@@ -380,7 +355,7 @@ __global__ void __launch_bounds__(ST_BLOCK) st_summary_kernel(const StKArgs a)
     long long sum_q[ST_MAX_TERMS] = {0, 0, 0, 0};
     for (uint64_t p = (uint64_t)blockIdx.x * ST_BLOCK + tid; p < a.N; p += (uint64_t)gridDim.x * ST_BLOCK)
         {
-        if (!st_in_group(a.mask, a.ntypes, a.pos[4ull * p + 3]))
+        if (!type_in_mask(a.mask, a.ntypes, a.pos[4ull * p + 3]))
             continue;
         const uint32_t nb = a.out_nb[p];
         head[0] += 1;
@@ -420,49 +395,15 @@ __global__ void __launch_bounds__(ST_BLOCK) st_summary_kernel(const StKArgs a)
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
-// the cell grid of the cells path, by the rule of azp_rdf_counts (rdf.hip rdf_make_grid); false if the box does not
-// allow it
-static bool st_make_grid(const azp_box& b, double r_max, uint32_t n, GridDev& g)
-    {
-    if (b.tilt[0] != 0.0 || b.tilt[1] != 0.0 || b.tilt[2] != 0.0)
-        return false;
-    double dim[3];
-    for (int d = 0; d < 3; ++d)
-        {
-        dim[d] = std::floor(b.L[d] / r_max);
-        if (b.periodic[d] && dim[d] < 3.0)
-            return false;
-        dim[d] = std::min(std::max(dim[d], 1.0), 1024.0);
-        }
-    const double cap = std::min<double>(ST_MAX_CELLS, std::max<double>(64.0, 2.0 * n));
-    for (int pass = 0; pass < 64 && dim[0] * dim[1] * dim[2] > cap; ++pass)
-        {
-        const double f = std::cbrt(cap / (dim[0] * dim[1] * dim[2]));
-        for (int d = 0; d < 3; ++d)
-            dim[d] = std::max(b.periodic[d] ? 3.0 : 1.0, std::floor(dim[d] * std::min(f, 0.95)));
-        }
-    if (dim[0] * dim[1] * dim[2] > (double)ST_MAX_CELLS)
-        return false;
-    for (int d = 0; d < 3; ++d)
-        {
-        g.dim[d] = (int)dim[d];
-        g.lo[d] = -0.5 * b.L[d];
-        g.winv[d] = dim[d] / b.L[d];
-        g.periodic[d] = b.periodic[d] != 0;
-        }
-    return true;
-    }
-
 struct StPlan
     {
     int path;  // 1 all-pairs, 2 cells
     SteinhardtTerms terms;
     GridDev grid;
-    uint32_t ncell, tile, tile2;
-    uint64_t off_S, off_nb, off_Q, off_qhat, off_cell_id, off_count, off_start, off_perm, bytes;
+    CellOrder order;  // path 2: behind the per-slot arrays
+    uint32_t tile, tile2;
+    uint64_t off_S, off_nb, off_Q, off_qhat, bytes;
     };
-
-static uint64_t st_align(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 
 static int st_plan(const azp_steinhardt_args* a, StPlan& p)
     {
@@ -484,7 +425,7 @@ static int st_plan(const azp_steinhardt_args* a, StPlan& p)
     for (int d = 0; d < 3; ++d)
         if (a->box.periodic[d] && a->r_max > 0.5 * w[d])
             return AZP_ERROR_INVALID_ARGUMENT;  // the minimum image would not be unique
-    const bool cells = st_make_grid(a->box, a->r_max, a->N, p.grid);
+    const bool cells = walk_make_grid(a->box, a->r_max, a->N, p.grid);
     if (a->path == 2 && !cells)
         return AZP_ERROR_INVALID_ARGUMENT;
     p.path = (a->path == 1 || !cells) ? 1 : 2;
@@ -495,21 +436,16 @@ static int st_plan(const azp_steinhardt_args* a, StPlan& p)
     p.tile2 = ST_BLOCK / 2;
     while ((uint64_t)p.tile2 * W * 8 > ST_ROW_BYTES_2)
         p.tile2 >>= 1;
-    const uint64_t n = a->N, row_words = st_align(n * W * 8);
-    p.off_S = st_align(n * 32);
+    const uint64_t n = a->N, row_words = walk_align(n * W * 8);
+    p.off_S = walk_align(n * 32);
     p.off_nb = p.off_S + row_words;
-    p.off_Q = p.off_nb + st_align(n * 4);
+    p.off_Q = p.off_nb + walk_align(n * 4);
     p.off_qhat = p.off_Q + ((a->flags & AZP_STEINHARDT_AVERAGE) ? row_words : 0);
-    p.off_cell_id = p.off_qhat + ((a->flags & AZP_STEINHARDT_CONNECTIONS) ? row_words : 0);
-    p.bytes = p.off_cell_id;
-    p.ncell = 0;
+    p.bytes = p.off_qhat + ((a->flags & AZP_STEINHARDT_CONNECTIONS) ? row_words : 0);
     if (p.path == 2)
         {
-        p.ncell = (uint32_t)p.grid.dim[0] * (uint32_t)p.grid.dim[1] * (uint32_t)p.grid.dim[2];
-        p.off_count = p.off_cell_id + st_align(n * 4);
-        p.off_start = p.off_count + st_align((uint64_t)p.ncell * 4);
-        p.off_perm = p.off_start + st_align(((uint64_t)p.ncell + 1) * 4);
-        p.bytes = p.off_perm + st_align(n * 4);
+        p.order = walk_cell_order(p.bytes, n, p.grid, true);
+        p.bytes = p.order.bytes;
         }
     return AZP_SUCCESS;
     }
@@ -530,9 +466,7 @@ static hipError_t st_launch_pairs(const StPlan& p, StKArgs& k, hipStream_t st)
         hipLaunchKernelGGL(st_pairs_all<MODE>, dim3((k.N + k.tile - 1) / k.tile), dim3(ST_BLOCK), lds, st, k);
     else
         {
-        // (a multiple of 8 workgroups, each a contiguous range of cells: xcd_remap gives every XCD one eighth of the grid)
-        const uint32_t grid = (std::min(p.ncell, ST_TARGET_BLOCKS) + 7u) & ~7u;
-        k.cells_per_block = (p.ncell + grid - 1) / grid;
+        const uint32_t grid = walk_launch_blocks(k.ncell, k.cells_per_block);
         hipLaunchKernelGGL(st_pairs_cells<MODE>, dim3(grid), dim3(ST_BLOCK), lds, st, k);
         }
     return hipGetLastError();
@@ -605,17 +539,12 @@ extern "C" int azp_steinhardt_compute(const azp_steinhardt_args* args, void* str
     else
         {
         k.grid = p.grid;
-        k.ncell = p.ncell;
-        uint32_t* perm = reinterpret_cast<uint32_t*>(base + p.off_perm);
-        uint32_t* start = reinterpret_cast<uint32_t*>(base + p.off_start);
+        k.ncell = p.order.ncell;
+        uint32_t* perm = walk_words(base, p.order.off_perm);
         k.perm = perm;
-        k.start = start;
-        // (the block totals of the three-kernel scan live in the head of `sorted`, which the scatter fills only
-        // afterwards: nblk + 1 <= N words fit into N rows)
+        k.start = walk_words(base, p.order.off_start);
         const StRowSink sink = {k.pos, k.mask, k.sorted, perm, k.ntypes};
-        e = bin_particles(args->N, k.pos, k.grid, nullptr, reinterpret_cast<uint32_t*>(base + p.off_cell_id),
-                          reinterpret_cast<uint32_t*>(base + p.off_count), start, reinterpret_cast<uint32_t*>(base), sink, st);
-        if (e != hipSuccess)
+        if ((e = walk_bin(args->N, k.pos, k.grid, base, p.order, k.sorted, sink, st)) != hipSuccess)
             return (int)e;
         }
     if ((e = st_launch_pairs<0>(p, k, st)) != hipSuccess)

@@ -80,14 +80,6 @@ struct SfKArgs
     uint32_t ne;    // powers path: entries of one particle's table row
     };
 
-__device__ __forceinline__ bool sf_in_mask(const uint8_t* mask, uint32_t ntypes, double w)
-    {
-    if (!mask)
-        return true;
-    const uint32_t t = (uint32_t)type_from_w(w);
-    return t < ntypes && mask[t] != 0;
-    }
-
 __device__ __forceinline__ double2 sf_cmul(const double2& a, const double2& b)
     {
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -148,8 +140,8 @@ template<uint32_t NS, bool POWERS> __global__ void __launch_bounds__(SF_BLOCK) s
             {
             const double4 p = load_scalar4(a.pos, (uint32_t)(base + tid));
             f = fractional(a.frac, p.x, p.y, p.z);
-            const bool in_a = sf_in_mask(a.mask_a, a.ntypes, p.w);
-            const bool in_b = NS == 2 ? in_a : sf_in_mask(a.mask_b, a.ntypes, p.w);
+            const bool in_a = type_in_mask(a.mask_a, a.ntypes, p.w);
+            const bool in_b = NS == 2 ? in_a : type_in_mask(a.mask_b, a.ntypes, p.w);
             flag = (in_a ? 1u : 0u) | (in_b ? 2u : 0u);
             n_a += in_a;
             n_b += in_b;

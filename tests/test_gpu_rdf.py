@@ -191,8 +191,8 @@ def test_two_cells_on_an_axis():
 
 
 def _grid_rule(L, periodic, r_max, n_total):
-    """rdf_make_grid (csrc/rdf.hip) restated: floor(L / r_max) cells per axis, at least 1 and at most 1024 (fewer than
-    3 on a periodic axis: no grid); while there are more cells than max(64, 2 n_total) (at most 2^21), every axis is
+    """walk_make_grid (csrc/pair_walk.hpp) restated: floor(L / r_max) cells per axis, at least 1 and at most 1024 (fewer
+    than 3 on a periodic axis: no grid); while there are more cells than max(64, 2 n_total) (at most 2^21), every axis is
     scaled by min(cbrt(cap / cells), 0.95), rounded down, not below 3 (periodic) or 1."""
     dim = [np.floor(L[d] / r_max) for d in range(3)]
     if any(periodic[d] and dim[d] < 3 for d in range(3)):
