@@ -417,6 +417,27 @@ class ClusterArgs(C.Structure):
         ("d_summary", C.c_void_p),
         ("d_scratch", C.c_void_p),
         ("scratch_bytes", C.c_uint64),
+        ("d_cluster_rep", C.c_void_p),
+    ]
+
+
+CLUSTER_PROPERTIES_ROW = 16
+CLUSTER_PROPERTIES_SUMMARY = 20
+
+
+class ClusterPropertiesArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("N", C.c_uint32),
+        ("min_size", C.c_uint32),
+        ("box", Box),
+        ("d_cluster_rep", C.c_void_p),
+        ("d_cluster_key", C.c_void_p),
+        ("d_cluster_size", C.c_void_p),
+        ("d_table", C.c_void_p),
+        ("d_summary", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
     ]
 
 
@@ -828,6 +849,8 @@ SYMBOLS = {
     "azp_steinhardt_compute": (C.c_int, [C.POINTER(SteinhardtArgs), _VP]),
     "azp_cluster_scratch_size": (C.c_int, [C.POINTER(ClusterArgs), C.POINTER(C.c_uint64)]),
     "azp_cluster_compute": (C.c_int, [C.POINTER(ClusterArgs), _VP]),
+    "azp_cluster_properties_scratch_size": (C.c_int, [C.POINTER(ClusterPropertiesArgs), C.POINTER(C.c_uint64)]),
+    "azp_cluster_properties": (C.c_int, [C.POINTER(ClusterPropertiesArgs), _VP]),
     "azp_wall_lj93_params_make": (C.c_int, [_D] * 4 + [C.c_int, _PD]),
     "azp_wall_colloid_params_make": (C.c_int, [_D] * 5 + [C.c_int, _PD]),
     "azp_wall_forces_lj93": (C.c_int, [C.POINTER(WallArgs), _VP]),

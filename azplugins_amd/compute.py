@@ -32,6 +32,10 @@ as integers in units of 2^-40 (``csrc/steinhardt.hip``; this project's, DESIGN 4
 ``Cluster`` is the connected components of the particles of a group closer than ``r_max`` (optionally of those a
 ``SolidLiquid`` marks solid), labelled by a concurrent union-find on the device (``csrc/cluster.hip``; this project's,
 DESIGN 4.29); ``ClusterRecorder`` appends its summary row to a device table inside ``Simulation.run``.
+
+``ClusterProperties`` is the centre, the gyration tensor and the extent of every cluster of a ``Cluster``, from sums over
+the cluster labels kept as integers (``csrc/cluster_properties.hip``; this project's, DESIGN 4.30);
+``ClusterPropertiesRecorder`` appends the number of clusters and the row of the largest one inside ``Simulation.run``.
 """
 
 import ctypes as C
@@ -1959,6 +1963,8 @@ class Cluster(_Compute):
         self._stages = 0      # (tools/cluster_probe.py: 1 and 2 stop the call early, for timing)
         self._out = None      # (N, device, keys, sizes)
         self._solid_row = None
+        self._want_rep = False  # (a ClusterProperties asks for the representative rows: allocated on request)
+        self._rep = None
 
     @property
     def r_max(self):
@@ -2029,6 +2035,10 @@ class Cluster(_Compute):
                          torch.empty((n,), dtype=torch.int32, device=st.device))
         a.d_cluster_key = self._out[2].data_ptr()
         a.d_cluster_size = self._out[3].data_ptr()
+        if self._want_rep:
+            if self._rep is None or self._rep.shape[0] != max(st.N, 1) or self._rep.device != st.device:
+                self._rep = torch.empty((max(st.N, 1),), dtype=torch.int32, device=st.device)
+            a.d_cluster_rep = self._rep.data_ptr()
         a.d_summary = d_out
         _lib.check(_lib.lib().azp_cluster_compute(C.byref(a), _lib.raw_stream(st.device)), "azp_cluster_compute")
 
@@ -2148,7 +2158,239 @@ class ClusterRecorder(_Recorder):
         return self._table()[:, 6:].copy()
 
 
-__all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute", "Cluster", "ClusterRecorder",
+# ---------------------------------------------------------------------------
+# cluster properties
+# ---------------------------------------------------------------------------
+def _gyration_matrix(words):
+    """(..., 6) words xx, xy, xz, yy, yz, zz -> (..., 3, 3) symmetric."""
+    w = np.asarray(words, dtype=np.float64)
+    return w[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(w.shape[:-1] + (3, 3))
+
+
+def _properties_row(row):
+    """One table row of ``azp_cluster_properties`` (16 float64) as a dict."""
+    return dict(key=int(row[0]), size=int(row[1]), center=row[2:5].copy(), gyration=_gyration_matrix(row[5:11]),
+                radius_of_gyration=float(np.sqrt(max(row[11], 0.0))), compact=bool(row[12] != 0.0), extent=row[13:16].copy())
+
+
+def cluster_properties_table(table, summary):
+    """The table and the summary of ``azp_cluster_properties`` (float64, (rows >= summary[0], 16) and (20,)) as a dict of
+    numpy arrays in freud's order of the clusters -- descending size, then ascending key: ``keys`` (C,) int64, ``sizes``
+    (C,) int64, ``centers`` (C, 3), ``gyrations`` (C, 3, 3), ``radii_of_gyration`` (C,), ``compact`` (C,) bool,
+    ``extents`` (C, 3); and ``num_clusters``, ``num_particles``, ``shift`` and ``largest`` (the summary's row as a dict,
+    key -1 where there is no cluster)."""
+    table = np.asarray(table, dtype=np.float64)
+    summary = np.asarray(summary, dtype=np.float64).reshape(-1)
+    if summary.shape[0] != _lib.CLUSTER_PROPERTIES_SUMMARY or table.ndim != 2 or table.shape[1] != _lib.CLUSTER_PROPERTIES_ROW:
+        raise _lib.AzpError("cluster_properties_table: a (rows, %d) table and a summary of %d words are expected, got %r and %r"
+                            % (_lib.CLUSTER_PROPERTIES_ROW, _lib.CLUSTER_PROPERTIES_SUMMARY, table.shape, summary.shape))
+    rows = int(summary[0])
+    if rows > table.shape[0]:
+        raise _lib.AzpError("cluster_properties_table: the summary counts %d rows, the table has %d" % (rows, table.shape[0]))
+    t = table[:rows]
+    t = t[np.lexsort((t[:, 0], -t[:, 1]))]  # by size, largest first, then by key
+    return dict(num_clusters=rows, num_particles=int(summary[1]), shift=int(summary[2]),
+                keys=t[:, 0].astype(np.int64), sizes=t[:, 1].astype(np.int64), centers=t[:, 2:5].copy(),
+                gyrations=_gyration_matrix(t[:, 5:11]), radii_of_gyration=np.sqrt(np.maximum(t[:, 11], 0.0)),
+                compact=t[:, 12] != 0.0, extents=t[:, 13:16].copy(), largest=_properties_row(summary[4:]))
+
+
+class ClusterProperties(_Compute):
+    """The centre and the gyration tensor of every cluster of ``cluster`` (a ``Cluster`` in ``computes`` of the same
+    simulation) with at least ``min_size`` particles; freud's ``cluster.ClusterProperties`` on the device, every
+    particle with weight 1 (semantics: ``include/azp.h`` "cluster properties"). Every read queues the
+    ``Cluster``'s own call and then ``azp_cluster_properties`` on its per-row keys, sizes and representative rows;
+    nothing goes through the host.
+
+    A cluster is unwrapped about the circular mean of its fractional coordinates. ``compact`` is True where it extends
+    over less than half the box on every periodic axis; its centre and tensor are then exact. For any other cluster
+    (one that wraps round the box is never compact) the same formulas are evaluated: reproducible, but what they mean is
+    the caller's business. All sums are integers in units of 2^-``shift``: two reads, the two paths of the ``Cluster`` and
+    a sorted state give the same bits per key.
+
+    In freud's order of the clusters (descending size, then ascending key; with ``min_size == 1`` index k is
+    ``cluster_idx == k``): ``keys``, ``sizes`` (C,), ``centers`` (C, 3), ``gyrations`` (C, 3, 3), ``radii_of_gyration``
+    (C,), ``compact`` (C,) bool, ``extents`` (C, 3) fractional, ``principal_moments`` (C, 3) descending,
+    ``relative_shape_anisotropy`` (C,); ``num_clusters``; ``largest``, a dict of the largest cluster's row. Refused with
+    ``AzpError``: a ``cluster`` that is not a ``Cluster``, a ``min_size`` that is not an integer >= 1; when read: not
+    attached, a ``Cluster`` of another simulation, a decomposed run."""
+
+    def __init__(self, cluster, min_size=1):
+        if not isinstance(cluster, Cluster):
+            raise _lib.AzpError("ClusterProperties: cluster must be a Cluster, got %r" % (cluster,))
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or not 1 <= int(min_size) < (1 << 32):
+            raise _lib.AzpError("ClusterProperties: min_size must be an integer >= 1, got %r" % (min_size,))
+        super().__init__(None, False)
+        self._cluster = cluster
+        self._min_size = int(min_size)
+        self._cluster_row = None
+        self._table = None
+        self._own_only = False  # (tools/cluster_properties_probe.py: the properties call alone, on the labels of the last call)
+
+    @property
+    def cluster(self):
+        return self._cluster
+
+    @property
+    def min_size(self):
+        return self._min_size
+
+    def _row_width(self):
+        return _lib.CLUSTER_PROPERTIES_SUMMARY
+
+    def _launch(self, d_out):
+        """Queue the ``Cluster``'s call and ``azp_cluster_properties`` for the simulation's current state with the summary
+        going to ``d_out``; the table goes to this compute's own buffer."""
+        import torch
+
+        sim = self._sim
+        if sim.domain is not None:
+            raise _lib.AzpError("ClusterProperties: decomposed runs are not supported (a cluster may span ranks)")
+        cl = self._cluster
+        if cl._sim is not sim or not cl._attached:
+            raise _lib.AzpError("ClusterProperties: cluster must be in sim.operations.computes of the same simulation")
+        st = sim.state
+        a = _lib.ClusterPropertiesArgs()
+        a.N = st.N
+        a.min_size = self._min_size
+        a.box = st.box.to_c()
+        a.d_pos = st.pos.data_ptr()
+        # (every refusal of this compute's own comes before the Cluster's launch)
+        self._set_scratch(a, "azp_cluster_properties_scratch_size")
+        if self._own_only:
+            if cl._rep is None or cl._out is None or cl._out[0] != st.N or cl._rep.device != st.device:
+                raise _lib.AzpError("ClusterProperties: the properties call alone needs the labels of an earlier whole call on this state")
+        else:
+            cl._want_rep = True  # (for this call only: a Cluster read on its own writes no representative rows)
+            try:
+                cl._launch(self._row_buffer(cl._row_width(), "int64", "_cluster_row").data_ptr())
+            finally:
+                cl._want_rep = False
+        rows = max(st.N // self._min_size, 1)
+        if self._table is None or self._table.shape[0] != rows or self._table.device != st.device:
+            self._table = torch.empty((rows, _lib.CLUSTER_PROPERTIES_ROW), dtype=torch.float64, device=st.device)
+        a.d_cluster_rep = cl._rep.data_ptr()
+        a.d_cluster_key = cl._out[2].data_ptr()
+        a.d_cluster_size = cl._out[3].data_ptr()
+        a.d_table = self._table.data_ptr()
+        a.d_summary = d_out
+        _lib.check(_lib.lib().azp_cluster_properties(C.byref(a), _lib.raw_stream(st.device)), "azp_cluster_properties")
+
+    def _read(self, name="table"):
+        """One call on the current state: ``cluster_properties_table`` of its table and summary."""
+        row = self._read_row(name, "float64").cpu().numpy()[0]
+        return cluster_properties_table(self._table[: int(row[0])].cpu().numpy(), row)
+
+    @property
+    def num_clusters(self):
+        return int(self._read_row("num_clusters", "float64").cpu().numpy()[0, 0])
+
+    @property
+    def keys(self):
+        """numpy int64 (C,): the clusters' keys (``Cluster.cluster_keys``)."""
+        return self._read("keys")["keys"]
+
+    @property
+    def sizes(self):
+        return self._read("sizes")["sizes"]
+
+    @property
+    def centers(self):
+        """numpy float64 (C, 3): the mean position of the unwrapped cluster, wrapped into the box."""
+        return self._read("centers")["centers"]
+
+    @property
+    def gyrations(self):
+        """numpy float64 (C, 3, 3): the covariance of the positions of the unwrapped cluster."""
+        return self._read("gyrations")["gyrations"]
+
+    @property
+    def radii_of_gyration(self):
+        return self._read("radii_of_gyration")["radii_of_gyration"]
+
+    @property
+    def compact(self):
+        return self._read("compact")["compact"]
+
+    @property
+    def extents(self):
+        """numpy float64 (C, 3): the extent of the unwrapped cluster along each lattice vector, as a fraction of it."""
+        return self._read("extents")["extents"]
+
+    @property
+    def principal_moments(self):
+        """numpy float64 (C, 3): the eigenvalues of ``gyrations``, descending."""
+        g = self._read("principal_moments")["gyrations"]
+        return np.linalg.eigvalsh(g)[:, ::-1] if g.shape[0] else np.zeros((0, 3))
+
+    @property
+    def relative_shape_anisotropy(self):
+        """numpy float64 (C,): 1 - 3 (l1 l2 + l2 l3 + l3 l1) / (l1 + l2 + l3)^2 of the principal moments, 0 where Rg^2 = 0."""
+        g = self._read("relative_shape_anisotropy")["gyrations"]
+        if not g.shape[0]:
+            return np.zeros(0)
+        lam = np.linalg.eigvalsh(g)
+        tr = lam.sum(axis=1)
+        pairs = lam[:, 0] * lam[:, 1] + lam[:, 1] * lam[:, 2] + lam[:, 2] * lam[:, 0]
+        return np.where(tr > 0.0, 1.0 - 3.0 * np.divide(pairs, tr * tr, out=np.zeros_like(tr), where=tr > 0.0), 0.0)
+
+    @property
+    def largest(self):
+        """dict: ``key`` (-1 where there is no cluster), ``size``, ``center``, ``gyration``, ``radius_of_gyration``,
+        ``compact``, ``extent`` of the largest cluster (among equal sizes the smallest key)."""
+        return _properties_row(self._read_row("largest", "float64").cpu().numpy()[0, 4:])
+
+
+class ClusterPropertiesRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) for a ``ClusterProperties`` in ``computes`` of the same simulation: its summary
+    (20 float64: the number of clusters and the row of the largest one) appended to a device table at the timesteps the
+    trigger fires inside ``Simulation.run`` -- the call's last kernel writes row k itself, nothing is read back, the host
+    does not wait, and the trajectory is the same bit for bit with and without the recorder. Read after the run:
+    ``timesteps``, ``num_clusters``, ``largest_cluster_size``, ``largest_cluster_key`` (frames,), ``largest_center``
+    (frames, 3), ``largest_gyration`` (frames, 3, 3), ``largest_radius_of_gyration``, ``largest_compact`` (frames,);
+    ``reset()`` forgets the frames."""
+
+    def __init__(self, props, trigger):
+        if not isinstance(props, ClusterProperties):
+            raise _lib.AzpError("ClusterPropertiesRecorder: a ClusterProperties is expected, got %r" % (props,))
+        self.props = self._compute = props
+        super().__init__(trigger)
+
+    def _table(self):
+        k = len(self._steps)
+        return self._rows[:k].cpu().numpy() if k else np.zeros((0, self._row_width()))
+
+    @property
+    def num_clusters(self):
+        return self._table()[:, 0].astype(np.int64)
+
+    @property
+    def largest_cluster_size(self):
+        return self._table()[:, 5].astype(np.int64)
+
+    @property
+    def largest_cluster_key(self):
+        return self._table()[:, 4].astype(np.int64)
+
+    @property
+    def largest_center(self):
+        return self._table()[:, 6:9].copy()
+
+    @property
+    def largest_gyration(self):
+        return _gyration_matrix(self._table()[:, 9:15])
+
+    @property
+    def largest_radius_of_gyration(self):
+        return np.sqrt(np.maximum(self._table()[:, 15], 0.0))
+
+    @property
+    def largest_compact(self):
+        return self._table()[:, 16] != 0.0
+
+
+__all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute", "Cluster", "ClusterProperties",
+           "ClusterPropertiesRecorder", "ClusterRecorder", "cluster_properties_table",
            "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder", "cluster_indices", "cluster_summary", "distribution_from_counts",
            "RadialDistributionFunction", "SolidLiquid", "SolidLiquidRecorder", "Steinhardt", "SteinhardtRecorder",
            "StructureFactor", "StructureFactorRecorder", "ThermodynamicQuantities",

@@ -18,7 +18,8 @@
 //   flatten  a later launch, so everything the union pass wrote is visible to plain loads: root[slot] = find(slot),
 //            then per wave and distinct root one atomicMin of the smallest tag and one atomicAdd of the number of its
 //            lanes at the root (32-bit integer atomics).
-//   relabel  cluster_key / cluster_size of the row of each slot, through the permutation.
+//   relabel  cluster_key / cluster_size of the row of each slot, through the permutation; where the caller asks for it
+//            also cluster_rep, the row of the slot's root (what cluster_properties.hip indexes its table by).
 //   summary  over the roots of G: counts, sum of squares and histogram through LDS into the row with 64-bit integer
 //            atomics; the largest cluster as one 64-bit atomicMax of size << 32 | ~key in the scratch head.
 //   finish   one thread unpacks that maximum into words [2] and [3] (-1 for an empty G). (An atomicMax cannot leave two
@@ -69,6 +70,7 @@ struct ClKArgs
     // per row
     uint32_t* out_key;
     uint32_t* out_size;
+    uint32_t* out_rep;         // may be NULL: the row of the root slot
     unsigned long long* summary;
     };
 
@@ -368,6 +370,8 @@ __global__ void __launch_bounds__(CL_BLOCK) cl_relabel_kernel(const ClKArgs a)
     const bool in = root != AZP_CLUSTER_NONE;
     a.out_key[p] = in ? a.min_tag[root] : AZP_CLUSTER_NONE;
     a.out_size[p] = in ? a.size[root] : 0u;
+    if (a.out_rep)  // (azp_cluster_properties needs a row per cluster: tags are not bounded by N, rows are)
+        a.out_rep[p] = in ? (a.perm ? a.perm[root] : root) : AZP_CLUSTER_NONE;
     }
 
 // the summary row from the roots: the workgroup's counts in LDS first (integer LDS atomics), then its non-zero words
@@ -529,6 +533,7 @@ extern "C" int azp_cluster_compute(const azp_cluster_args* args, void* stream)
     k.size = reinterpret_cast<uint32_t*>(base + p.off_size);
     k.out_key = args->d_cluster_key;
     k.out_size = args->d_cluster_size;
+    k.out_rep = args->d_cluster_rep;
     k.summary = reinterpret_cast<unsigned long long*>(args->d_summary);
     const dim3 per_row((args->N + CL_BLOCK - 1) / CL_BLOCK), block(CL_BLOCK);
     if (p.path == 1)

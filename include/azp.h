@@ -1771,10 +1771,66 @@ typedef struct azp_cluster_args
     int64_t* d_summary;           /* 6 + size_bins */
     void* d_scratch;
     uint64_t scratch_bytes;
+    uint32_t* d_cluster_rep;      /* N, may be NULL: the row that represents the row's cluster (below) */
     } azp_cluster_args;
 
 int azp_cluster_scratch_size(const azp_cluster_args* args, uint64_t* bytes);
 int azp_cluster_compute(const azp_cluster_args* args, void* stream);
+
+/* ---- cluster properties (compute.ClusterProperties) ----
+ * Not part of the reference; the semantics are DEFINED HERE: the centre and the gyration tensor of every
+ * cluster of an azp_cluster_compute call that has at least min_size particles. Every particle has weight 1.
+ * Inputs: d_pos and box of that call and its outputs d_cluster_key, d_cluster_size and d_cluster_rep.
+ * d_cluster_rep (the optional output of azp_cluster_compute, NULL there changes nothing): for a row of the group the
+ * index of the ROW that represents its cluster (the row of the union-find's root slot): equal for all rows of a cluster,
+ * rep[rep[i]] == rep[i]; AZP_CLUSTER_NONE outside the group. Which row represents a cluster is unspecified. (Tags are
+ * not bounded by N, so a key cannot index a table: the representative row can.)
+ * With H the lattice matrix (columns (Lx, 0, 0), (xy Ly, Ly, 0), (xz Lz, yz Lz, Lz)), origin = -H (1/2, 1/2, 1/2) and
+ * s_i = H^-1 (r_i - origin) the fractional coordinate the tilted cell list bins by, in [0, 1) for a wrapped particle:
+ *   reference point  periodic axis k: C_k = sum cos(2 pi s_ik), S_k = sum sin(2 pi s_ik) (sincospi of 2 s),
+ *                    s0_k = atan2(S_k, C_k) / (2 pi) brought into [0, 1), 0 where both sums are 0;
+ *                    non-periodic axis: s0_k = 1/2
+ *   unwrapping       ds_i = s_i - s0, on periodic axes minus rint(ds): |ds| <= 1/2
+ *   moments          M1 = sum ds, M2 = sum ds (x) ds, per axis min and max of ds
+ *   results          m = M1 / n; centre = origin + H (s0 + m), wrapped into the box on periodic axes;
+ *                    G = H (M2 / n - m m^T) H^T; Rg^2 = tr G; extent_k = max ds_k - min ds_k;
+ *                    compact = 1 where extent_k < 1/2 on every periodic axis
+ * compact == 1 exactly when the cluster, unwrapped along its edges, extends over less than half the box on every
+ * periodic axis; centre and G are then exact. Otherwise the same formulas are written: reproducible, their meaning
+ * the caller's business (a cluster that wraps round the box is never compact).
+ * All sums are integers in units of 2^-shift, shift = min(52, 61 - ceil(log2(max(N, 2)))): every term (|term| <= 1)
+ * goes through a round-to-nearest conversion of term * 2^shift and is added with 64-bit integer atomics, so the row of
+ * a key is bit-identical between two calls, the two paths of azp_cluster_compute and a re-ordered state.
+ * d_table: floor(N / min_size) rows of AZP_CLUSTER_PROPERTIES_ROW = 16 doubles (always enough), in the order of the
+ * representatives' rows (unspecified): [0] key [1] size [2..4] centre [5..10] G as xx, xy, xz, yy, yz, zz [11] Rg^2
+ * [12] compact [13..15] fractional extents. Rows behind summary [0] are not written.
+ * d_summary: AZP_CLUSTER_PROPERTIES_SUMMARY = 20 doubles, OVERWRITTEN: [0] the number of table rows [1] the particles
+ * in them [2] shift [3] 0 [4..19] the table row of the largest cluster, among equal sizes the smallest key (as summary
+ * [3] of azp_cluster_compute); no rows: zeros with key -1.
+ * Asynchronous on `stream`: nothing is read back. d_scratch: azp_cluster_properties_scratch_size bytes.
+ * AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written: NULL args; min_size == 0; N > AZP_CLUSTER_MAX_N;
+ * a box length that is not positive; a NULL d_summary; with N > 0 a NULL d_pos, d_cluster_rep, d_cluster_key,
+ * d_cluster_size, d_table or too small a scratch. */
+#define AZP_CLUSTER_PROPERTIES_ROW 16
+#define AZP_CLUSTER_PROPERTIES_SUMMARY 20
+
+typedef struct azp_cluster_properties_args
+    {
+    const double* d_pos;              /* N x 4 */
+    uint32_t N;
+    uint32_t min_size;                /* >= 1 */
+    azp_box box;
+    const uint32_t* d_cluster_rep;    /* N */
+    const uint32_t* d_cluster_key;    /* N */
+    const uint32_t* d_cluster_size;   /* N */
+    double* d_table;                  /* floor(N / min_size) x 16 */
+    double* d_summary;                /* 20 */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_cluster_properties_args;
+
+int azp_cluster_properties_scratch_size(const azp_cluster_properties_args* args, uint64_t* bytes);
+int azp_cluster_properties(const azp_cluster_properties_args* args, void* stream);
 
 /* ---- wall potentials (azplugins_amd.wall) ----
  * Replace the reference's legacy wall evaluators src/WallEvaluatorLJ93.h:50-150 and
