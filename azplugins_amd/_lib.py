@@ -489,6 +489,51 @@ class StructureFactorArgs(C.Structure):
     ]
 
 
+DISPLACEMENT_MAX_ORIGINS = 64
+DISPLACEMENT_NSUMS = 12
+
+
+class DisplacementOriginArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("N", C.c_uint32),
+        ("slot", C.c_uint32),
+        ("n_slots", C.c_uint32),
+        ("build_rtag", C.c_uint32),
+        ("d_origin_pos", C.c_void_p),
+        ("d_origin_image", C.c_void_p),
+        ("d_rtag", C.c_void_p),
+    ]
+
+
+class DisplacementArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_image", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("d_rtag", C.c_void_p),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("box", Box),
+        ("d_type_mask", C.c_void_p),
+        ("d_origin_pos", C.c_void_p),
+        ("d_origin_image", C.c_void_p),
+        ("n_origins", C.c_uint32),
+        ("num_bins", C.c_uint32),
+        ("active_mask", C.c_uint64),
+        ("r_max", C.c_double),
+        ("d_displacements", C.c_void_p),
+        ("n_vectors", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("d_vectors", C.c_void_p),
+        ("d_out", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 FLOW_CONSTANT = 0
 FLOW_PARABOLIC = 1
 
@@ -845,6 +890,11 @@ SYMBOLS = {
     "azp_bonded_histogram": (C.c_int, [C.POINTER(BondedHistogramArgs), _VP]),
     "azp_structure_factor_scratch_size": (C.c_int, [C.POINTER(StructureFactorArgs), C.POINTER(C.c_uint64)]),
     "azp_structure_factor_amplitudes": (C.c_int, [C.POINTER(StructureFactorArgs), _VP]),
+    "azp_displacement_origin": (C.c_int, [C.POINTER(DisplacementOriginArgs), _VP]),
+    "azp_displacement_moments_scratch_size": (C.c_int, [C.POINTER(DisplacementArgs), C.POINTER(C.c_uint64)]),
+    "azp_displacement_moments": (C.c_int, [C.POINTER(DisplacementArgs), _VP]),
+    "azp_self_scattering_scratch_size": (C.c_int, [C.POINTER(DisplacementArgs), C.POINTER(C.c_uint64)]),
+    "azp_self_scattering": (C.c_int, [C.POINTER(DisplacementArgs), _VP]),
     "azp_steinhardt_scratch_size": (C.c_int, [C.POINTER(SteinhardtArgs), C.POINTER(C.c_uint64)]),
     "azp_steinhardt_compute": (C.c_int, [C.POINTER(SteinhardtArgs), _VP]),
     "azp_cluster_scratch_size": (C.c_int, [C.POINTER(ClusterArgs), C.POINTER(C.c_uint64)]),

@@ -36,6 +36,16 @@ DESIGN 4.29); ``ClusterRecorder`` appends its summary row to a device table insi
 ``ClusterProperties`` is the centre, the gyration tensor and the extent of every cluster of a ``Cluster``, from sums over
 the cluster labels kept as integers (``csrc/cluster_properties.hip``; this project's, DESIGN 4.30);
 ``ClusterPropertiesRecorder`` appends the number of clusters and the row of the largest one inside ``Simulation.run``.
+
+``MeanSquaredDisplacement`` and ``SelfIntermediateScattering`` measure dynamics: the moments of the displacement of a
+group since a time origin (msd, its tensor, the fourth moment, the self part of the van Hove function) and F_s(q, t) on
+the vector set of ``StructureFactor``. An origin is the wrapped position and the image of every particle stored BY TAG;
+every sum runs in tag order in the reproducible reduction, so a result is bit-identical between two reads and under
+the particle sorter (``csrc/displacement.hip``; this project's). ``MeanSquaredDisplacementRecorder`` and
+``SelfIntermediateScatteringRecorder`` keep a ring of time origins on the device and write the rows of all of them with
+one launch inside ``Simulation.run``; ``average_over_origins`` is their lag average.
+``intermediate_scattering_from_amplitudes`` (``StructureFactorRecorder.intermediate_scattering``) is the collective
+F(q, t) from the amplitudes that recorder already keeps, on the host.
 """
 
 import ctypes as C
@@ -540,6 +550,10 @@ class _Recorder:
     def _row_width(self):
         return self._compute._row_width()
 
+    def _launch_row(self, d_out):
+        """Queue the kernels that write one row of the table at ``d_out``."""
+        self._compute._launch(d_out)
+
     def timesteps_in_run(self, t0, n):
         """The timesteps at which ``run(n)`` starting at timestep ``t0`` records: those of t0 + 1 ... t0 + n at which the
         trigger fires."""
@@ -561,7 +575,7 @@ class _Recorder:
             if k:
                 grown[:k].copy_(rows[:k])
             self._rows = rows = grown
-        self._compute._launch(rows.data_ptr() + k * width * 8)
+        self._launch_row(rows.data_ptr() + k * width * 8)
         self._steps.append(int(timestep))
         self._volumes.append(st.box.volume)  # (an update.BoxResize may change the box before the row is read)
 
@@ -1490,6 +1504,14 @@ class StructureFactorRecorder(_Recorder):
             return np.full(nb, np.nan)
         return spherical_average(s.mean(axis=0), self.sf._vector_set()[1], nb)[0]
 
+    @property
+    def intermediate_scattering(self):
+        """``(lags, F)``: the collective intermediate scattering function F_AB(m, tau) of the recorded frames, numpy int64
+        (lags,) and float64 (lags, n) (``intermediate_scattering_from_amplitudes`` with each frame's own group sizes)."""
+        t = self._table("intermediate_scattering")
+        n = (t.shape[1] - 4) // 4
+        return intermediate_scattering_from_amplitudes(self.amplitudes, self.timesteps, t[:, 4 * n:4 * n + 2])
+
 
 # ---------------------------------------------------------------------------
 # bond-orientational order
@@ -2389,7 +2411,652 @@ class ClusterPropertiesRecorder(_Recorder):
         return self._table()[:, 16] != 0.0
 
 
-__all__ = ["BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute", "Cluster", "ClusterProperties",
+# ---------------------------------------------------------------------------
+# displacements between two times: mean squared displacement, self scattering
+# ---------------------------------------------------------------------------
+def average_over_origins(steps, origin_steps, rows):
+    """The lag average behind the recorders of this section: ``steps`` (R,) the timestep of every recorded row,
+    ``origin_steps`` (R, K) the timestep of the origin that slot held when the row was recorded (negative: the slot was
+    not filled), ``rows`` (R, K, W) the SUMS of every (row, slot). Returns ``(lags, samples, sums)``: the distinct lags
+    ``steps[r] - origin_steps[r, s]`` of the filled pairs in ascending order, how many pairs have each lag, and the rows
+    of equal lag added, (lags, W), in the dtype of ``rows`` -- sums are added first, the caller normalises afterwards, so
+    that pairs with different group sizes weigh by their particles. Pure host code."""
+    steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+    origin_steps = np.asarray(origin_steps, dtype=np.int64)
+    rows = np.asarray(rows)
+    if origin_steps.ndim != 2 or rows.ndim != 3 or origin_steps.shape[0] != len(steps) or rows.shape[:2] != origin_steps.shape:
+        raise _lib.AzpError("average_over_origins: steps (R,), origin_steps (R, K) and rows (R, K, W) are expected, got %r, %r and %r"
+                            % (steps.shape, origin_steps.shape, rows.shape))
+    filled = origin_steps >= 0
+    lag = (steps[:, None] - origin_steps)[filled]
+    lags = np.unique(lag)
+    where = np.searchsorted(lags, lag)
+    sums = np.zeros((len(lags), rows.shape[2]), dtype=rows.dtype)
+    np.add.at(sums, where, rows[filled])
+    return lags, np.bincount(where, minlength=len(lags)).astype(np.int64), sums
+
+
+def displacement_moments(sums):
+    """The properties of ``MeanSquaredDisplacement`` from the 12 doubles of ``azp_displacement_moments`` (N_g, S_x, S_y,
+    S_z, S_xx, S_yy, S_zz, S_xy, S_xz, S_yz, S_4, 0; leading axes are kept): a dict of ``num_particles``,
+    ``mean_displacement`` (.., 3), ``msd``, ``msd_components`` (.., 3), ``msd_tensor`` (.., 3, 3), ``msd_drift_removed``,
+    ``fourth_moment`` and ``non_gaussian`` = 3 <d^4> / (5 <d^2>^2) - 1 (NaN where ``msd`` is 0). An empty group gives
+    zeros. The compute, the recorders and the tests all go through here."""
+    s = np.asarray(sums, dtype=np.float64)
+    n = s[..., 0]
+    inv = np.divide(1.0, n, out=np.zeros_like(n), where=n > 0.0)
+    mean = s[..., 1:4] * inv[..., None]
+    comp = s[..., 4:7] * inv[..., None]
+    msd = ((s[..., 4] + s[..., 5]) + s[..., 6]) * inv
+    xy, xz, yz = (s[..., 7 + c] * inv for c in range(3))
+    tensor = np.stack([np.stack([comp[..., 0], xy, xz], axis=-1), np.stack([xy, comp[..., 1], yz], axis=-1),
+                       np.stack([xz, yz, comp[..., 2]], axis=-1)], axis=-2)
+    fourth = s[..., 10] * inv
+    ngp = np.full(np.shape(msd), np.nan)
+    np.divide(3.0 * fourth, 5.0 * msd * msd, out=ngp, where=msd != 0.0)
+    ngp = np.where(msd != 0.0, ngp - 1.0, np.nan)
+    return {"num_particles": np.asarray(n).astype(np.int64), "mean_displacement": mean, "msd": msd, "msd_components": comp,
+            "msd_tensor": tensor, "msd_drift_removed": msd - ((mean[..., 0] ** 2 + mean[..., 1] ** 2) + mean[..., 2] ** 2),
+            "fourth_moment": fourth, "non_gaussian": ngp}
+
+
+def van_hove_from_counts(counts, n_g, r_max):
+    """The self part of the van Hove function from the integer histogram of |d|: counts / (N_g x shell volume), so that
+    sum_k van_hove[k] V_k = 1 - outside / N_g; zeros for an empty group. Leading axes are kept."""
+    counts = np.asarray(counts, dtype=np.float64)
+    nb = counts.shape[-1]
+    n_g = np.asarray(n_g, dtype=np.float64)[..., None]
+    if nb == 0:
+        return np.zeros(counts.shape)
+    return np.divide(counts, n_g * _shell_volumes(nb, r_max), out=np.zeros(counts.shape), where=n_g > 0.0)
+
+
+def self_scattering_from_row(row, n_vectors):
+    """(Re rho_s / N_g, Im rho_s / N_g) per vector from rows of ``azp_self_scattering`` (2 n + 2 doubles: Re[n], Im[n],
+    N_g, bad_tags; leading axes are kept); zeros for an empty group."""
+    row = np.asarray(row, dtype=np.float64)
+    n = int(n_vectors)
+    n_g = row[..., 2 * n:2 * n + 1]
+    inv = np.divide(1.0, n_g, out=np.zeros_like(n_g), where=n_g > 0.0)
+    return row[..., :n] * inv, row[..., n:2 * n] * inv
+
+
+def intermediate_scattering_from_amplitudes(amplitudes, timesteps, group_sizes=None):
+    """The collective intermediate scattering function from density amplitudes of several times (what
+    ``StructureFactorRecorder.amplitudes`` holds: complex (frames, 2, n), rho_A and rho_B) and their ``timesteps``:
+    ``(lags, F)`` with F (lags, n),
+
+        F(m, tau) = <Re[rho_A(m, t + tau) conj(rho_B(m, t))]>_t / sqrt(N_A N_B)
+
+    over all pairs of frames t + tau >= t, every frame serving as a time origin, with the lag averaging of
+    ``average_over_origins``: the products of equal lag are added, then divided by the added sqrt(N_A(t + tau) N_B(t)).
+    ``group_sizes``: (N_A, N_B) or one pair per frame (frames, 2); None leaves the mean product unnormalised. F(m, 0) is
+    the static S_AB(m) averaged over the frames. Host code: the collective counterpart of F_s costs no kernel."""
+    amp = np.asarray(amplitudes, dtype=np.complex128)
+    steps = np.asarray(timesteps, dtype=np.int64).reshape(-1)
+    if amp.ndim != 3 or amp.shape[1] != 2 or amp.shape[0] != len(steps):
+        raise _lib.AzpError("intermediate_scattering_from_amplitudes: amplitudes must be (frames, 2, n) with one timestep per "
+                            "frame, got %r and %d timesteps" % (amp.shape, len(steps)))
+    frames, n = amp.shape[0], amp.shape[2]
+    if group_sizes is None:
+        sizes = np.ones((frames, 2))
+    else:
+        sizes = np.broadcast_to(np.asarray(group_sizes, dtype=np.float64), (frames, 2))
+    origin_steps = np.where(steps[None, :] <= steps[:, None], steps[None, :], -1)  # (row r, origin s): s no later than r
+    rows = np.zeros((frames, frames, n + 1))
+    for r in range(frames):
+        rows[r, :, :n] = (amp[r, 0][None, :] * np.conj(amp[:, 1])).real
+        rows[r, :, n] = np.sqrt(sizes[r, 0] * sizes[:, 1])
+    lags, _, sums = average_over_origins(steps, origin_steps, rows)
+    norm = sums[:, n:]
+    return lags, np.divide(sums[:, :n], norm, out=np.zeros((len(lags), n)), where=norm > 0.0)
+
+
+class _TwoTimeCompute(_Compute):
+    """What ``MeanSquaredDisplacement`` and ``SelfIntermediateScattering`` share: the time origin (wrapped positions and
+    images BY TAG, ``csrc/displacement.hip``), the reverse-tag table and the refusals."""
+
+    _needs_periodic = False
+
+    def __init__(self, filter):
+        name = type(self).__name__
+        if not isinstance(filter, (All, Type)):
+            raise _lib.AzpError("%s: filter must be All() or Type(...), got %r" % (name, filter))
+        super().__init__(filter, False)
+        self._origin = None  # (state, box key, timestep, positions (1, N, 4), images (1, N, 3))
+        self._rtag = None    # (state, order generation, N, device tensor)
+
+    def _state(self, name):
+        """The state, after the refusals that every read and every record makes."""
+        if not self._attached:
+            raise DataAccessError(name)
+        cls = type(self).__name__
+        sim = self._sim
+        if sim.domain is not None:
+            raise _lib.AzpError("%s: decomposed runs are not supported (an origin is stored by tag on one device)" % cls)
+        box = sim.state.box
+        if not (box.Lx > 0.0 and box.Ly > 0.0 and box.Lz > 0.0):
+            raise _lib.AzpError("%s: a 3-D box is needed (2-D systems are not supported), got %r" % (cls, box))
+        if self._needs_periodic and not all(box.periodic):
+            raise _lib.AzpError("%s: the box has to be periodic on all three axes (the wavevectors are those of its lattice), "
+                                "got periodic = %r" % (cls, box.periodic))
+        return sim.state
+
+    def _reverse_tags(self, st):
+        """(device table rtag[tag[i]] = i, stale): cached on (state, order_generation, N); a stale table is rebuilt by the
+        next ``_scatter`` call, which the caller makes."""
+        import torch
+
+        c = self._rtag
+        if c is not None and c[0] is st and c[1] == st.order_generation and c[2] == st.N and c[3].device == st.device:
+            return c[3], False
+        self._rtag = (st, st.order_generation, st.N, torch.empty(max(st.N, 1), dtype=torch.int32, device=st.device))
+        return self._rtag[3], True
+
+    def _scatter(self, st, pos0=None, image0=None, slot=0):
+        """Queue ``azp_displacement_origin``: the current state into slot ``slot`` of the store (``pos0`` (K, N, 4),
+        ``image0`` (K, N, 3); None: no origin is taken) and, where it is stale, the reverse-tag table. Returns the table."""
+        rtag, stale = self._reverse_tags(st)
+        if pos0 is None and not stale:
+            return rtag
+        a = _lib.DisplacementOriginArgs()
+        a.d_pos, a.d_image, a.d_tag, a.N = st.pos.data_ptr(), st.image.data_ptr(), st.tag.data_ptr(), st.N
+        a.slot, a.n_slots = int(slot), 1 if pos0 is None else pos0.shape[0]
+        a.build_rtag = 1 if stale else 0
+        if pos0 is not None:
+            a.d_origin_pos, a.d_origin_image = pos0.data_ptr(), image0.data_ptr()
+        a.d_rtag = rtag.data_ptr()
+        _lib.check(_lib.lib().azp_displacement_origin(C.byref(a), _lib.raw_stream(st.device)), "azp_displacement_origin")
+        return rtag
+
+    @staticmethod
+    def _store(st, n_slots):
+        import torch
+
+        return (torch.empty((n_slots, max(st.N, 1), 4), dtype=torch.float64, device=st.device),
+                torch.empty((n_slots, max(st.N, 1), 3), dtype=torch.int32, device=st.device))
+
+    def set_origin(self):
+        """Take the time origin from the current state: the wrapped position and the image of every particle, by tag."""
+        st = self._state("set_origin")
+        o = self._origin
+        if o is None or o[0] is not st or o[3].shape[1] != max(st.N, 1) or o[3].device != st.device:
+            pos0, image0 = self._store(st, 1)
+        else:
+            pos0, image0 = o[3], o[4]
+        self._scatter(st, pos0, image0, 0)
+        self._origin = (st, st.box._key(), int(self._sim.timestep), pos0, image0)
+
+    @property
+    def origin_timestep(self):
+        """The timestep the origin was taken at; None without an origin (none taken yet, or the state was replaced)."""
+        o = self._origin
+        if o is None or self._sim is None or o[0] is not self._sim.state:
+            return None
+        return o[2]
+
+    def _check_box(self, st, key, what="the origin"):
+        if key != st.box._key():
+            raise _lib.AzpError("%s: the box changed since %s was taken (%r now): a displacement across a box change is not "
+                                "defined here; take a new origin (set_origin(), or reset() of the recorder)"
+                                % (type(self).__name__, what, st.box))
+
+    def _current_origin(self, name):
+        """(state, origin positions, origin images): the origin is taken now if there is none for this state."""
+        st = self._state(name)
+        if self._origin is None or self._origin[0] is not st:
+            self.set_origin()
+        o = self._origin
+        self._check_box(st, o[1])
+        return st, o[3], o[4]
+
+    def _args(self, st, pos0, image0, n_origins, active):
+        a = _lib.DisplacementArgs()
+        a.d_pos, a.d_image, a.d_tag, a.N = st.pos.data_ptr(), st.image.data_ptr(), st.tag.data_ptr(), st.N
+        a.d_rtag = self._scatter(st).data_ptr()
+        a.ntypes = len(st.types)
+        a.box = st.box.to_c()
+        mask = self._type_mask(st)
+        a.d_type_mask = mask.data_ptr() if mask is not None else None
+        a.d_origin_pos, a.d_origin_image = pos0.data_ptr(), image0.data_ptr()
+        a.n_origins, a.active_mask = int(n_origins), int(active)
+        return a
+
+    def _launch(self, d_out):
+        """One row against this compute's own origin."""
+        st, pos0, image0 = self._current_origin("row")
+        self._launch_slots(d_out, st, pos0, image0, 1, 1)
+
+    @staticmethod
+    def _refuse_bad_tags(name, bad):
+        if np.any(np.asarray(bad) != 0):
+            raise _lib.AzpError("%s: %d tag slot(s) without a particle: the tags of the state are not a permutation of "
+                                "0 .. N-1 (a tag >= N, a duplicate)" % (name, int(np.max(bad))))
+
+
+class MeanSquaredDisplacement(_TwoTimeCompute):
+    """Mean squared displacement of a group since a time origin, with the moments around it, by one deterministic pass
+    over the particles (``csrc/displacement.hip``). Not part of the reference (freud's ``msd.MSD`` is the model in
+    spirit); the semantics are this project's (``include/azp.h``).
+
+    ``set_origin()`` stores the wrapped position r0 and the image n0 of every particle BY TAG; it is also taken by the
+    first read without one, and dropped when the state is replaced. The displacement of a particle is
+    d = (r - r0) + H (n - n0) with the images subtracted as integers first, H the lattice matrix of the box. A particle
+    belongs to the group (``filter``: ``All()`` or ``Type(...)``) by its CURRENT type. Properties, computed when read:
+    ``num_particles`` N_g, ``mean_displacement`` <d>, ``msd`` <|d|^2>, ``msd_components``, ``msd_tensor`` <d_a d_b>,
+    ``msd_drift_removed`` = msd - |<d>|^2, ``fourth_moment`` <|d|^4>, ``non_gaussian`` = 3 <d^4> / (5 <d^2>^2) - 1 (NaN
+    where msd is 0), with ``num_bins`` > 0 the self part of the van Hove function on [0, ``r_max``):
+    ``van_hove_counts``, ``outside``, ``van_hove`` = counts / (N_g x shell volume), ``bin_edges``, ``bin_centers``; and
+    ``displacements`` (N, 3) by tag, of every particle. An empty group gives zeros.
+
+    All sums run in TAG order in the reproducible reduction of ``csrc/azp_reduce.hpp``: two reads agree bit for bit, a
+    ``ParticleSorter.sort`` between them changes no bit, and ``tests/reduction_ref.tree_sum`` over the terms in tag
+    order reproduces them. Refused with ``AzpError``: a filter that is not ``All()`` or ``Type(...)``, ``num_bins``
+    outside [0, 8192], ``num_bins`` > 0 without a positive ``r_max`` (at construction); when read: a decomposed run, a
+    2-D box, a box other than the origin's ("take a new origin"), tags that are not a permutation of 0 .. N-1."""
+
+    def __init__(self, filter=None, num_bins=0, r_max=None):
+        super().__init__(All() if filter is None else filter)
+        if isinstance(num_bins, bool) or int(num_bins) != num_bins or not 0 <= int(num_bins) <= _lib.RDF_MAX_BINS:
+            raise _lib.AzpError("MeanSquaredDisplacement: num_bins must be an integer in [0, %d], got %r" % (_lib.RDF_MAX_BINS, num_bins))
+        self._num_bins = int(num_bins)
+        if self._num_bins and (r_max is None or not (float(r_max) > 0.0 and np.isfinite(float(r_max)))):
+            raise _lib.AzpError("MeanSquaredDisplacement: num_bins = %d needs a positive r_max, got %r" % (self._num_bins, r_max))
+        self._r_max = None if r_max is None else float(r_max)
+        self._disp = None
+
+    @property
+    def num_bins(self):
+        return self._num_bins
+
+    @property
+    def r_max(self):
+        return self._r_max
+
+    @property
+    def bin_edges(self):
+        """numpy.ndarray: the ``num_bins + 1`` edges of the |d| bins."""
+        return np.linspace(0.0, self._r_max or 0.0, self._num_bins + 1)
+
+    @property
+    def bin_centers(self):
+        e = self.bin_edges
+        return 0.5 * (e[1:] + e[:-1])
+
+    def _row_width(self):
+        return _lib.DISPLACEMENT_NSUMS + 2 + self._num_bins
+
+    def _launch_slots(self, d_out, st, pos0, image0, n_origins, active, d_displacements=None):
+        """Queue ``azp_displacement_moments``: ``n_origins`` rows of ``_row_width()`` words to ``d_out``, one per slot of the
+        store (``pos0``, ``image0``); a slot whose bit in ``active`` is clear gives zeros."""
+        a = self._args(st, pos0, image0, n_origins, active)
+        a.num_bins = self._num_bins
+        a.r_max = self._r_max if self._num_bins else 0.0
+        a.d_displacements = d_displacements
+        self._set_scratch(a, "azp_displacement_moments_scratch_size")
+        a.d_out = d_out
+        _lib.check(_lib.lib().azp_displacement_moments(C.byref(a), _lib.raw_stream(st.device)), "azp_displacement_moments")
+
+    def _read(self, name):
+        """The row of the current state against the origin as int64 numpy (the first 12 words are doubles)."""
+        row = self._read_row(name, "int64").cpu().numpy()[0]
+        self._refuse_bad_tags("MeanSquaredDisplacement", row[_lib.DISPLACEMENT_NSUMS])
+        return row
+
+    def _moments(self, name):
+        return displacement_moments(self._read(name)[:_lib.DISPLACEMENT_NSUMS].view(np.float64))[name]
+
+    @property
+    def num_particles(self):
+        return int(self._moments("num_particles"))
+
+    @property
+    def msd(self):
+        return float(self._moments("msd"))
+
+    @property
+    def msd_drift_removed(self):
+        return float(self._moments("msd_drift_removed"))
+
+    @property
+    def fourth_moment(self):
+        return float(self._moments("fourth_moment"))
+
+    @property
+    def non_gaussian(self):
+        return float(self._moments("non_gaussian"))
+
+    @property
+    def mean_displacement(self):
+        return self._moments("mean_displacement")
+
+    @property
+    def msd_components(self):
+        return self._moments("msd_components")
+
+    @property
+    def msd_tensor(self):
+        return self._moments("msd_tensor")
+
+    @property
+    def van_hove_counts(self):
+        """numpy int64 (num_bins,): particles of the group with |d| in each bin."""
+        return self._read("van_hove_counts")[_lib.DISPLACEMENT_NSUMS + 2:].copy()
+
+    @property
+    def outside(self):
+        """int: particles of the group with |d| >= r_max."""
+        return int(self._read("outside")[_lib.DISPLACEMENT_NSUMS + 1])
+
+    @property
+    def van_hove(self):
+        row = self._read("van_hove")
+        return van_hove_from_counts(row[_lib.DISPLACEMENT_NSUMS + 2:], row[:1].view(np.float64)[0], self._r_max)
+
+    @property
+    def displacements(self):
+        """numpy float64 (N, 3): d of EVERY particle (in the group or not), indexed by tag."""
+        import torch
+
+        st, pos0, image0 = self._current_origin("displacements")
+        if self._disp is None or self._disp.shape[0] != max(st.N, 1) or self._disp.device != st.device:
+            self._disp = torch.empty((max(st.N, 1), 3), dtype=torch.float64, device=st.device)
+        row = self._row_buffer(self._row_width(), "int64")
+        self._launch_slots(row.data_ptr(), st, pos0, image0, 1, 1, self._disp.data_ptr())
+        self._refuse_bad_tags("MeanSquaredDisplacement", row.cpu().numpy()[0, _lib.DISPLACEMENT_NSUMS])
+        return self._disp[: st.N].cpu().numpy()
+
+
+class SelfIntermediateScattering(_TwoTimeCompute):
+    """Self intermediate scattering function F_s(q, t) of a group since a time origin on the reciprocal-lattice vectors
+    of the box (``csrc/displacement.hip``; this project's): rho_s(m) = sum_j exp(-2 pi i m . (f_j - f0_j))
+    over the group, f the fractional coordinates of the wrapped positions -- on the reciprocal lattice the images drop
+    out exactly. The vector set, its thinning and the |q| bins are those of ``StructureFactor`` with the same arguments
+    (``structure_factor_vectors``). ``set_origin()``, ``origin_timestep`` as ``MeanSquaredDisplacement``. Properties,
+    computed when read: ``vectors``, ``q``, ``vectors_per_bin``, ``num_particles``, ``vector_scattering`` = Re rho_s / N_g,
+    ``scattering`` (its mean per |q| bin, NaN in an empty bin) and ``imaginary`` (the mean of Im rho_s / N_g per bin: the
+    odd part, which shows a drift). The sums run in tag order in a fixed shape: bit-identical between two reads and
+    under a sort. Refused as ``StructureFactor`` refuses its arguments; when read: a decomposed run, a 2-D or not fully
+    periodic box, a box other than the origin's, an empty vector set, tags that are not a permutation."""
+
+    _needs_periodic = True
+
+    def __init__(self, filter, q_max, num_bins, max_vectors_per_bin=None, seed=0):
+        super().__init__(filter)
+        try:  # (the argument checks of StructureFactor, which also keeps the values)
+            self._sf = StructureFactor(filter, filter, q_max, num_bins, max_vectors_per_bin, seed)
+        except _lib.AzpError as e:
+            raise _lib.AzpError(str(e).replace("StructureFactor", "SelfIntermediateScattering")) from None
+        self._set = None
+
+    q_max = property(lambda self: self._sf.q_max)
+    num_bins = property(lambda self: self._sf.num_bins)
+    max_vectors_per_bin = property(lambda self: self._sf.max_vectors_per_bin)
+    seed = property(lambda self: self._sf.seed)
+    bin_edges = property(lambda self: self._sf.bin_edges)
+    bin_centers = property(lambda self: self._sf.bin_centers)
+
+    def _vector_set(self, name="vectors"):
+        """(m, bins, device triples) for the current box, rebuilt when the box changed."""
+        import torch
+
+        st = self._state(name)
+        sf = self._sf
+        key = (st.box._key(), st.device)
+        if self._set is None or self._set[0] != key:
+            m, bins = structure_factor_vectors(st.box, sf.q_max, sf.num_bins, sf.max_vectors_per_bin, sf.seed)
+            if len(m) == 0:
+                raise _lib.AzpError("SelfIntermediateScattering: q_max = %r is below the smallest |q| of the box: no wavevector" % (sf.q_max,))
+            self._set = (key, m, bins, torch.from_numpy(np.ascontiguousarray(m, dtype=np.int32)).to(st.device))
+        return self._set[1:]
+
+    def _row_width(self):
+        return 2 * len(self._vector_set()[0]) + 2
+
+    def _launch_slots(self, d_out, st, pos0, image0, n_origins, active):
+        """Queue ``azp_self_scattering``: ``n_origins`` rows of ``2 n + 2`` doubles to ``d_out``."""
+        m, _, triples = self._vector_set()
+        a = self._args(st, pos0, image0, n_origins, active)
+        a.n_vectors = len(m)
+        a.d_vectors = triples.data_ptr()
+        self._set_scratch(a, "azp_self_scattering_scratch_size")
+        a.d_out = d_out
+        _lib.check(_lib.lib().azp_self_scattering(C.byref(a), _lib.raw_stream(st.device)), "azp_self_scattering")
+
+    def _read(self, name):
+        row = self._read_row(name, "float64").cpu().numpy()[0]
+        self._refuse_bad_tags("SelfIntermediateScattering", row[-1])
+        return row
+
+    @property
+    def vectors(self):
+        """numpy int64 (n, 3): the integer triples m = (h, k, l), ordered by (l, k, h)."""
+        return self._vector_set("vectors")[0].copy()
+
+    @property
+    def q(self):
+        """numpy float64 (n,): the lengths |q(m)|."""
+        v = reciprocal_vectors(self._sim.state.box, self._vector_set("q")[0])
+        return np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+
+    @property
+    def vectors_per_bin(self):
+        return np.bincount(self._vector_set("vectors_per_bin")[1], minlength=self.num_bins).astype(np.int64)
+
+    @property
+    def num_particles(self):
+        return int(self._read("num_particles")[-2])
+
+    @property
+    def vector_scattering(self):
+        """numpy float64 (n,): Re rho_s(m) / N_g of every vector."""
+        row = self._read("vector_scattering")
+        return self_scattering_from_row(row, (len(row) - 2) // 2)[0]
+
+    def _binned(self, name, part):
+        row = self._read(name)
+        return spherical_average(self_scattering_from_row(row, (len(row) - 2) // 2)[part], self._vector_set()[1], self.num_bins)[0]
+
+    @property
+    def scattering(self):
+        """numpy float64 (num_bins,): F_s per |q| bin, the mean of Re rho_s / N_g over the bin's vectors (NaN: none)."""
+        return self._binned("scattering", 0)
+
+    @property
+    def imaginary(self):
+        """numpy float64 (num_bins,): the mean of Im rho_s / N_g per |q| bin (zero without a drift)."""
+        return self._binned("imaginary", 1)
+
+
+class _TwoTimeRecorder(_Recorder):
+    """The recorders of this section: a ring of ``origins`` = K <= 64 time origins on the device, filled by the recorder.
+    The first firing, and then every ``origin_every``-th firing (None: no further one), first scatters the current
+    state into slot (origins taken so far) mod K, overwriting the oldest; then ONE launch writes the rows of all K slots
+    into row k of the table (K x the compute's row width; a slot not yet filled gives zeros). Which origin timestep each
+    slot held at each row is host data like the timesteps: nothing is read back, the host never waits, and the
+    trajectory is the same bit for bit with and without the recorder. An origin taken and compared in the same firing
+    is lag 0. All rows and origins belong to ONE box and one state: a record in another box raises ``AzpError``;
+    ``reset()`` forgets rows and origins."""
+
+    def __init__(self, compute, trigger, origins=1, origin_every=None):
+        name = type(self).__name__
+        if isinstance(origins, bool) or int(origins) != origins or not 1 <= int(origins) <= _lib.DISPLACEMENT_MAX_ORIGINS:
+            raise _lib.AzpError("%s: origins must be an integer in [1, %d], got %r" % (name, _lib.DISPLACEMENT_MAX_ORIGINS, origins))
+        if origin_every is not None and (isinstance(origin_every, bool) or int(origin_every) != origin_every or int(origin_every) < 1):
+            raise _lib.AzpError("%s: origin_every must be None or a positive integer, got %r" % (name, origin_every))
+        self._compute = compute
+        self.origins = int(origins)
+        self.origin_every = None if origin_every is None else int(origin_every)
+        super().__init__(trigger)
+
+    def reset(self):
+        super().reset()
+        self._ring = None           # (state, box key, positions (K, N, 4), images (K, N, 3))
+        self._slot_steps = [-1] * getattr(self, "origins", 1)
+        self._taken = 0
+        self._origin_steps = []     # per row: the origin timestep of every slot (-1: not filled)
+
+    def _row_width(self):
+        return self.origins * self._compute._row_width()
+
+    def _record(self, sim, timestep):
+        c = self._compute
+        name = type(self).__name__
+        st = c._state(name)
+        if self._ring is not None and (self._ring[0] is not st or self._ring[2].shape[1] != max(st.N, 1)):
+            raise _lib.AzpError("%s: the state was replaced with rows recorded; call reset() first" % name)
+        if self._ring is not None and self._ring[1] != st.box._key():
+            raise _lib.AzpError("%s: the box changed with rows recorded (%r now): the origins of the ring belong to another "
+                                "box; call reset() first" % (name, st.box))
+        if self._ring is None:
+            self._ring = (st, st.box._key()) + c._store(st, self.origins)
+        k = len(self._steps)
+        if k == 0 or (self.origin_every is not None and k % self.origin_every == 0):
+            slot = self._taken % self.origins
+            c._scatter(st, self._ring[2], self._ring[3], slot)
+            self._slot_steps[slot] = int(timestep)
+            self._taken += 1
+        super()._record(sim, timestep)
+        self._origin_steps.append(list(self._slot_steps))
+
+    def _launch_row(self, d_out):
+        st = self._ring[0]
+        active = sum(1 << s for s, t in enumerate(self._slot_steps) if t >= 0)
+        self._compute._launch_slots(d_out, st, self._ring[2], self._ring[3], self.origins, active)
+
+    @property
+    def origin_timesteps(self):
+        """numpy int64 (rows, origins): the timestep of the origin every slot held at every row, -1 where not filled."""
+        return np.array(self._origin_steps, dtype=np.int64).reshape(len(self._steps), self.origins)
+
+    def _host_rows(self, dtype):
+        """The table as numpy (rows, origins, row width of the compute) in ``dtype`` (8-byte words)."""
+        k = len(self._steps)
+        w = self._compute._row_width() if k else 0
+        if k == 0:
+            return np.zeros((0, self.origins, w), dtype=dtype)
+        return self._rows[:k].cpu().numpy().view(dtype).reshape(k, self.origins, w)
+
+    def _lag_sums(self, rows):
+        return average_over_origins(self._steps, self.origin_timesteps, rows)
+
+    @property
+    def lags(self):
+        """numpy int64: the distinct lags (row timestep - origin timestep) recorded, ascending."""
+        return self._lag_sums(np.zeros((len(self._steps), self.origins, 0)))[0]
+
+    @property
+    def samples_per_lag(self):
+        """numpy int64: the (row, slot) pairs behind every lag."""
+        return self._lag_sums(np.zeros((len(self._steps), self.origins, 0)))[1]
+
+
+class MeanSquaredDisplacementRecorder(_TwoTimeRecorder):
+    """Writer (``sim.operations.writers``) for a ``MeanSquaredDisplacement`` in ``computes`` of the same simulation, with
+    a ring of ``origins`` time origins (see ``_TwoTimeRecorder`` for the ring, ``origin_every`` and the guarantees).
+    Read after the run: ``timesteps``, ``origin_timesteps``, ``table`` (per row and slot the properties of the compute;
+    an unfilled slot gives zeros, NaN for ``non_gaussian``) and the lag averages ``lags``, ``samples_per_lag``, ``msd``,
+    ``msd_components``, ``non_gaussian`` and ``van_hove`` (lags, num_bins): over all (row, slot) pairs of equal lag the
+    SUMS are added and then normalised (``average_over_origins``)."""
+
+    def __init__(self, msd, trigger, origins=1, origin_every=None):
+        if not isinstance(msd, MeanSquaredDisplacement):
+            raise _lib.AzpError("MeanSquaredDisplacementRecorder: msd must be a MeanSquaredDisplacement, got %r" % (msd,))
+        self.msd_compute = msd
+        super().__init__(msd, trigger, origins, origin_every)
+
+    def _words(self):
+        rows = self._host_rows(np.int64)
+        self._compute._refuse_bad_tags("MeanSquaredDisplacementRecorder", rows[..., _lib.DISPLACEMENT_NSUMS] if rows.size else 0)
+        return rows
+
+    @property
+    def table(self):
+        """dict of numpy arrays (rows, origins, ...) keyed by the property names of ``MeanSquaredDisplacement``."""
+        rows = self._words()
+        ns = _lib.DISPLACEMENT_NSUMS
+        sums = np.ascontiguousarray(rows[..., :ns]).view(np.float64)
+        out = displacement_moments(sums)
+        out["van_hove_counts"] = rows[..., ns + 2:].copy()
+        out["outside"] = rows[..., ns + 1].copy()
+        out["van_hove"] = van_hove_from_counts(rows[..., ns + 2:], sums[..., 0], self._compute.r_max)
+        return out
+
+    def _averaged(self):
+        rows = self._words()
+        ns = _lib.DISPLACEMENT_NSUMS
+        _, _, sums = self._lag_sums(np.ascontiguousarray(rows[..., :ns]).view(np.float64))
+        _, _, words = self._lag_sums(rows[..., ns:])
+        return sums, words
+
+    @property
+    def msd(self):
+        """numpy float64 (lags,): the sums of |d|^2 of equal lag added, over the added N_g."""
+        return displacement_moments(self._averaged()[0])["msd"]
+
+    @property
+    def msd_components(self):
+        return displacement_moments(self._averaged()[0])["msd_components"]
+
+    @property
+    def non_gaussian(self):
+        return displacement_moments(self._averaged()[0])["non_gaussian"]
+
+    @property
+    def van_hove(self):
+        sums, words = self._averaged()
+        return van_hove_from_counts(words[:, 2:], sums[:, 0], self._compute.r_max)
+
+
+class SelfIntermediateScatteringRecorder(_TwoTimeRecorder):
+    """Writer (``sim.operations.writers``) for a ``SelfIntermediateScattering`` in ``computes`` of the same simulation,
+    with a ring of ``origins`` time origins (see ``_TwoTimeRecorder``). Read after the run: ``timesteps``,
+    ``origin_timesteps``, ``table`` (``num_particles`` (rows, origins), ``vector_scattering`` and ``vector_imaginary``
+    (rows, origins, n)) and the lag averages ``lags``, ``samples_per_lag``, ``vector_scattering_per_lag`` (lags, n) and
+    ``scattering`` (lags, num_bins): Re rho_s of equal lag added over the added N_g, then the mean over each bin's
+    vectors."""
+
+    def __init__(self, fs, trigger, origins=1, origin_every=None):
+        if not isinstance(fs, SelfIntermediateScattering):
+            raise _lib.AzpError("SelfIntermediateScatteringRecorder: fs must be a SelfIntermediateScattering, got %r" % (fs,))
+        self.fs = fs
+        super().__init__(fs, trigger, origins, origin_every)
+
+    def _words(self):
+        rows = self._host_rows(np.float64)
+        self._compute._refuse_bad_tags("SelfIntermediateScatteringRecorder", rows[..., -1] if rows.size else 0)
+        return rows
+
+    @property
+    def table(self):
+        rows = self._words()
+        n = (rows.shape[2] - 2) // 2 if rows.shape[2] else 0
+        re, im = self_scattering_from_row(rows, n) if rows.shape[2] else (rows, rows)
+        return {"num_particles": rows[..., 2 * n].astype(np.int64) if rows.shape[2] else np.zeros(rows.shape[:2], dtype=np.int64),
+                "vector_scattering": re, "vector_imaginary": im}
+
+    @property
+    def vector_scattering_per_lag(self):
+        rows = self._words()
+        _, _, sums = self._lag_sums(rows)
+        n = (sums.shape[1] - 2) // 2 if sums.shape[1] else 0
+        return self_scattering_from_row(sums, n)[0] if sums.shape[1] else sums
+
+    @property
+    def scattering(self):
+        """numpy float64 (lags, num_bins): F_s(|q|, lag), NaN in a bin without vectors."""
+        per = self.vector_scattering_per_lag
+        nb = self.fs.num_bins
+        if per.shape[0] == 0:
+            return np.zeros((0, nb))
+        bins = self.fs._vector_set()[1]
+        return np.stack([spherical_average(r, bins, nb)[0] for r in per])
+
+
+__all__ = ["MeanSquaredDisplacement", "MeanSquaredDisplacementRecorder", "SelfIntermediateScattering",
+           "SelfIntermediateScatteringRecorder", "average_over_origins", "displacement_moments",
+           "intermediate_scattering_from_amplitudes", "self_scattering_from_row", "van_hove_from_counts",
+           "BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute", "Cluster", "ClusterProperties",
            "ClusterPropertiesRecorder", "ClusterRecorder", "cluster_properties_table",
            "CylindricalVelocityFieldCompute", "DataAccessError", "RDFRecorder", "cluster_indices", "cluster_summary", "distribution_from_counts",
            "RadialDistributionFunction", "SolidLiquid", "SolidLiquidRecorder", "Steinhardt", "SteinhardtRecorder",

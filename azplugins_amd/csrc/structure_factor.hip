@@ -41,31 +41,14 @@
 
 #include "azp_reduce.hpp"
 #include "cell_bin.hpp"
+#include "sf_shape.hpp"
 
 namespace azp
 {
-constexpr uint32_t SF_BLOCK = 256;
+// (SF_BLOCK, the chunk targets and sf_shape: sf_shape.hpp, shared with displacement.hip)
 constexpr uint32_t SF_SUB = 32;             // particles per table sub-stage of the powers path
-constexpr uint32_t SF_TARGET_BLOCKS = 4096; // 256 CUs x 16
-constexpr uint32_t SF_MIN_CHUNKS = 16, SF_MAX_CHUNKS = 512;
 // path 0: the powers path wherever its tables fit (profiles/structure_factor.md)
 constexpr bool SF_AUTO_TAKES_POWERS = true;
-
-struct SfShape
-    {
-    uint32_t stages, n_chunks;
-    };
-
-static SfShape sf_shape(uint32_t N, uint32_t n_vectors)
-    {
-    const uint32_t vblocks = (n_vectors + SF_BLOCK - 1) / SF_BLOCK;
-    const uint32_t target = std::min(std::max(SF_TARGET_BLOCKS / std::max(vblocks, 1u), SF_MIN_CHUNKS), SF_MAX_CHUNKS);
-    const uint32_t n_stages = (uint32_t)(((uint64_t)N + SF_BLOCK - 1) / SF_BLOCK);
-    SfShape s;
-    s.stages = std::max(1u, (n_stages + target - 1) / target);
-    s.n_chunks = std::max(1u, (n_stages + s.stages - 1) / s.stages);
-    return s;
-    }
 
 struct SfKArgs
     {

@@ -1905,8 +1905,111 @@ int azp_wall_net_forces_scratch_size(const azp_wall_args* args, uint64_t* bytes)
 int azp_wall_net_forces_lj93(const azp_wall_args* args, double* d_out, void* d_scratch, uint64_t scratch_bytes, void* stream);
 int azp_wall_net_forces_colloid(const azp_wall_args* args, double* d_out, void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- displacements between two times (compute.MeanSquaredDisplacement, compute.SelfIntermediateScattering) ----
+ * Not part of the reference; the semantics are DEFINED HERE. Single-domain states in a 3-D box (tilts
+ * included) that does not change between the two times.
+ * TIME ORIGIN. azp_displacement_origin copies the wrapped position (all four words of the row) and the image of every
+ * row i < N into slot `slot` of an origin store, INDEXED BY TAG: d_origin_pos[(slot N + tag_i) 4 ..], d_origin_image[(slot
+ * N + tag_i) 3 ..]. The store holds n_slots origins: n_slots x N x 4 doubles and n_slots x N x 3 int32. The tags of a
+ * single-domain state are a permutation of 0 .. N-1; a row with a tag >= N is not copied (the kernels below report
+ * it). build_rtag != 0: d_rtag is first filled with 0xFFFFFFFF and then d_rtag[tag_i] = i (the reverse-tag table the
+ * kernels below gather through; it has to be rebuilt whenever the rows are re-indexed). d_origin_pos == NULL with
+ * build_rtag != 0 builds the table alone.
+ * DISPLACEMENT of the particle with tag g, row i = d_rtag[g], with plain IEEE operations in exactly this order (no
+ * contraction into FMAs), h_xy = xy Ly, h_xz = xz Lz, h_yz = yz Lz rounded once on the host:
+ *   dn = n_i - n0_g                                   (int32, subtracted as integers first: a particle that crossed
+ *                                                      the box a thousand times loses nothing to cancellation)
+ *   dx = (x_i - x0_g) + ((Lx dn_x + h_xy dn_y) + h_xz dn_z)
+ *   dy = (y_i - y0_g) + (Ly dn_y + h_yz dn_z)
+ *   dz = (z_i - z0_g) + Lz dn_z
+ * A particle belongs to the group by its CURRENT type (the type bits of pos_i.w against d_type_mask, NULL = all).
+ * A tag slot g is BAD when d_rtag[g] >= N or d_tag[d_rtag[g]] != g (a forged or duplicated tag, a stale table): it
+ * adds 1 to the bad_tags word and nothing else.
+ * azp_displacement_moments OVERWRITES, for every origin slot s < n_origins, one row of 14 + num_bins 8-byte words at
+ * d_out + s (14 + num_bins):
+ *   doubles  0 N_g | 1-3 S_x S_y S_z (sums of dx, dy, dz) | 4-9 S_xx S_yy S_zz S_xy S_xz S_yz (dx dx, ... one product
+ *            each) | 10 S_4 = sum r2 r2 with r2 = (dx dx + dy dy) + dz dz | 11 zero
+ *   uint64   12 bad_tags | 13 outside | 14 .. counts[num_bins]: the self part of the van Hove function. With
+ *            r = sqrt(r2): r >= r_max counts in `outside`, else bin min(int(r (num_bins / r_max)), num_bins - 1), the
+ *            scale num_bins / r_max rounded once on the host. num_bins == 0: no histogram work, outside stays 0.
+ * A slot whose bit in active_mask (bit s) is clear has not been filled: its row is all zeros.
+ * d_displacements (may be NULL): N x 3 doubles by tag, (dx, dy, dz) of EVERY particle (in the group or not) against
+ * origin slot 0; zeros for a bad slot. Written only when bit 0 of active_mask is set.
+ * ORDER OF SUMMATION: in TAG order, the reproducible sum of csrc/azp_reduce.hpp with (per_lane, n_blocks) =
+ * reduce_shape(N): thread t of workgroup b takes the tags b 256 per_lane + j 256 + t, j < per_lane, reads the origin
+ * coalesced and gathers the current row through d_rtag. A particle outside the group adds nothing. No floating-point
+ * atomics: the result does not depend on the order of the rows (a sort changes no bit), two calls agree bit for bit,
+ * and tests/reduction_ref.tree_sum over the per-particle terms in tag order reproduces it. Every term goes straight
+ * into its lane's accumulator: ADDITION DEPTH per_lane + 6 + 3 + ceil(n_blocks / 64) + 6 (72 up to N = 2^24). The
+ * integer words are counted in LDS per workgroup (uint32) and added with 64-bit integer atomics. The origins are a grid
+ * dimension: workgroup (b, s) reads the current rows of its tags again for every slot.
+ * d_scratch: azp_displacement_moments_scratch_size bytes = n_origins x 12 x n_blocks doubles.
+ * azp_self_scattering: for n_vectors integer triples m (compute.structure_factor_vectors) and every origin slot,
+ *   rho_s(m) = sum over the group of exp(-2 pi i m . (f_i - f0_g)),
+ * f = fractional() of csrc/cell_bin.hpp of the WRAPPED positions at the two times. On the reciprocal lattice
+ * q(m) . H dn = 2 pi m . dn is a multiple of 2 pi, so the images drop out exactly and are not read. df = f - f0 is one
+ * subtraction per axis, t = h df_x + k df_y + l df_z (FMA-contracted, left to right), the term (c, -s) of
+ * sincospi(2 t). One lane per vector, 256 tags per stage staged through LDS in tag order, shape, fold and depth those
+ * of azp_structure_factor_amplitudes' direct path: D = 256 + stages + ceil(n_chunks / 64) + 6. Row per slot, 2 n + 2
+ * doubles at d_out + s (2 n + 2): Re[n], Im[n], N_g, bad_tags; zeros for a slot that is not active. Error of a component:
+ * N_g 2^-52 (c |m|_1 + 4 + D) with c = pi (2 e_f + 4) (tests/displacement_ref.py). The box has to be periodic on all
+ * three axes. d_scratch: azp_self_scattering_scratch_size bytes = n_origins (2 n + 2) n_chunks doubles.
+ * All three calls are asynchronous on `stream`: no host synchronisation, no readback.
+ * AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written: NULL args or a NULL array the call reads or
+ * writes (with N > 0); n_origins outside [1, 64]; slot >= n_slots; num_bins > AZP_RDF_MAX_BINS; num_bins > 0 with
+ * r_max not positive and finite; n_vectors outside [1, AZP_SF_MAX_VECTORS]; a mask with ntypes == 0; a box length that
+ * is not positive and finite (for azp_self_scattering: a non-periodic axis); too small a scratch. N == 0: the rows
+ * are zeroed. */
+#define AZP_DISPLACEMENT_MAX_ORIGINS 64
+#define AZP_DISPLACEMENT_NSUMS 12
+
+typedef struct azp_displacement_origin_args
+    {
+    const double* d_pos;       /* N x 4 at least */
+    const int32_t* d_image;    /* N x 3 at least */
+    const uint32_t* d_tag;     /* N at least */
+    uint32_t N;
+    uint32_t slot;             /* < n_slots */
+    uint32_t n_slots;          /* origins the store holds */
+    uint32_t build_rtag;
+    double* d_origin_pos;      /* n_slots x N x 4, by tag; NULL: the reverse-tag table alone */
+    int32_t* d_origin_image;   /* n_slots x N x 3, by tag */
+    uint32_t* d_rtag;          /* N; written when build_rtag != 0 */
+    } azp_displacement_origin_args;
+
+typedef struct azp_displacement_args
+    {
+    const double* d_pos;            /* N x 4 at least (x, y, z, type bits) */
+    const int32_t* d_image;         /* N x 3 at least (azp_self_scattering: not read) */
+    const uint32_t* d_tag;          /* N at least */
+    const uint32_t* d_rtag;         /* N: row of every tag */
+    uint32_t N;
+    uint32_t ntypes;
+    azp_box box;
+    const uint8_t* d_type_mask;     /* ntypes bytes, may be NULL */
+    const double* d_origin_pos;     /* n_origins x N x 4 at least, by tag */
+    const int32_t* d_origin_image;  /* n_origins x N x 3 at least, by tag (azp_self_scattering: not read) */
+    uint32_t n_origins;             /* 1 .. 64: rows written */
+    uint32_t num_bins;              /* moments: 0 .. AZP_RDF_MAX_BINS */
+    uint64_t active_mask;           /* bit s: slot s holds an origin */
+    double r_max;                   /* moments, with num_bins > 0 */
+    double* d_displacements;        /* moments: N x 3 by tag against slot 0, may be NULL */
+    uint32_t n_vectors;             /* scattering: 1 .. AZP_SF_MAX_VECTORS */
+    uint32_t _pad;
+    const int32_t* d_vectors;       /* scattering: n_vectors x 3 */
+    void* d_out;                    /* n_origins rows, overwritten */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_displacement_args;
+
+int azp_displacement_origin(const azp_displacement_origin_args* args, void* stream);
+int azp_displacement_moments_scratch_size(const azp_displacement_args* args, uint64_t* bytes);
+int azp_displacement_moments(const azp_displacement_args* args, void* stream);
+int azp_self_scattering_scratch_size(const azp_displacement_args* args, uint64_t* bytes);
+int azp_self_scattering(const azp_displacement_args* args, void* stream);
+
 /* ---- misc ---- */
-int azp_version(void);                    /* major * 1000 + minor       */
+int azp_version(void);                   /* major * 1000 + minor       */
 const char* azp_status_string(int status);
 /* Resolved launch configuration of the last pair-force call on this thread
  * (for benchmarks / profiling reports). */
