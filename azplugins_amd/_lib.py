@@ -327,6 +327,37 @@ class ThermoArgs(C.Structure):
     ]
 
 
+THERMO_FIELD_NSUMS = 18
+THERMO_FIELD_NO_BIN = 0x7FFFFFFF
+THERMO_FIELD_HEADS, THERMO_FIELD_LEVELS = 1, 2  # ThermoFieldArgs.phases, for timing alone (0: everything)
+
+
+class ThermoFieldArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_vel", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("d_type_mask", C.c_void_p),
+        ("d_force", C.c_void_p * THERMO_MAX_FORCES),
+        ("d_virial", C.c_void_p * THERMO_MAX_FORCES),
+        ("d_keys", C.c_void_p),
+        ("d_sorted_keys", C.c_void_p),
+        ("d_order", C.c_void_p),
+        ("d_out", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+        ("box", Box),
+        ("lower", C.c_double * 3),
+        ("upper", C.c_double * 3),
+        ("num_bins", C.c_uint32 * 3),
+        ("coordinates", C.c_uint32),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("n_forces", C.c_uint32),
+        ("phases", C.c_uint32),
+    ]
+
+
 RDF_MAX_BINS = 8192
 RDF_PATH_AUTO, RDF_PATH_ALL_PAIRS, RDF_PATH_CELLS = 0, 1, 2
 
@@ -884,6 +915,9 @@ SYMBOLS = {
     "azp_velocity_field_normalize": (C.c_int, [_VP, C.c_uint64, _VP, _VP]),
     "azp_thermo_scratch_size": (C.c_int, [C.POINTER(ThermoArgs), C.POINTER(C.c_uint64)]),
     "azp_thermo_sums": (C.c_int, [C.POINTER(ThermoArgs), _VP]),
+    "azp_thermo_field_scratch_size": (C.c_int, [C.POINTER(ThermoFieldArgs), C.POINTER(C.c_uint64)]),
+    "azp_thermo_field_keys": (C.c_int, [C.POINTER(ThermoFieldArgs), _VP]),
+    "azp_thermo_field_sums": (C.c_int, [C.POINTER(ThermoFieldArgs), _VP]),
     "azp_rdf_scratch_size": (C.c_int, [C.POINTER(RdfArgs), C.POINTER(C.c_uint64)]),
     "azp_rdf_counts": (C.c_int, [C.POINTER(RdfArgs), _VP]),
     "azp_rdf_subtract_excluded": (C.c_int, [C.POINTER(RdfExclusionArgs), _VP]),

@@ -12,6 +12,12 @@ of a group from one deterministic pass over the particles (``csrc/thermo.hip``);
 sums of that pass to a device table at the timesteps its trigger fires inside ``Simulation.run``, without a host
 synchronisation.
 
+``CartesianThermodynamicField`` / ``CylindricalThermodynamicField`` are the spatial profiles of density, temperature
+and (per-atom) stress on the grid of the velocity fields: the particles are keyed by (bin, tag), sorted, and every bin is
+summed in a fixed 64-ary tree over its members in tag order (``csrc/thermo_field.hip``; this project's, DESIGN 4.32);
+``ThermodynamicFieldRecorder`` appends the raw rows to a device table inside ``Simulation.run`` and
+``thermo_field_quantities`` turns raw rows into the quantities.
+
 ``RadialDistributionFunction`` is g(r) between two groups from exact integer pair counts (``csrc/rdf.hip``; not part of
 the reference: azplugins had ``analyze.rdf`` in its HOOMD-2 line, the semantics are this project's, DESIGN 4.14);
 ``RDFRecorder`` appends the counts to a device table inside ``Simulation.run`` in the same way.
@@ -616,6 +622,291 @@ class ThermodynamicRecorder(_Recorder):
         # (each row with the volume of the box it was recorded in, not the box of this moment)
         rows = [thermo_quantities(host[i], ctx[0], self._volumes[i], *ctx[2:]) for i in range(k)]
         return {name: np.array([r[name] for r in rows]) for name in THERMO_PROPERTIES}
+
+
+# ---------------------------------------------------------------------------
+# thermodynamic field
+# ---------------------------------------------------------------------------
+THERMO_FIELD_PROPERTIES = ("counts", "num_particles", "bin_volumes", "number_density", "mass_density", "velocities",
+                           "kinetic_temperature", "pressure_tensor", "pressure", "potential_energy_density", "sums")
+_THERMO_FIELD_NEEDS_VOLUME = ("bin_volumes", "number_density", "mass_density", "pressure_tensor", "pressure",
+                              "potential_energy_density")
+_TENSOR_PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))  # xx, xy, xz, yy, yz, zz
+RECORDER_MAX_BYTES = 2**30
+
+
+def thermo_field_quantities(rows, bin_volumes, streaming):
+    """The quantities of ``THERMO_FIELD_PROPERTIES`` from raw rows of ``azp_thermo_field_sums``: ``rows`` has shape
+    (..., 18 + ntypes) (slots n, M, P, K, W, U, counts per type; added over the ranks of a decomposed run),
+    ``bin_volumes`` the shape of ``rows`` without its last axis (or one that broadcasts to it), or ``None``: the
+    quantities that divide by a volume are then left out. ``streaming``: ``"subtract"`` (K'_ab = K_ab - P_a P_b / M,
+    ``kinetic_temperature`` = tr K' / (3 n - 3), 0 for n < 2) or ``"keep"`` (K' = K, tr K / (3 n), 0 for n = 0). Plain
+    numpy in a fixed order: the properties, the recorder's ``table`` and ``mean()`` go through here and agree bit for
+    bit."""
+    if streaming not in ("subtract", "keep"):
+        raise _lib.AzpError("streaming must be 'subtract' or 'keep', got %r" % (streaming,))
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.shape[-1] < _lib.THERMO_FIELD_NSUMS:
+        raise _lib.AzpError("thermo_field_quantities: a row has at least %d words, got %d" % (_lib.THERMO_FIELD_NSUMS, rows.shape[-1]))
+    n, mass = rows[..., 0], rows[..., 1]
+    mom, kin, vir, pot = rows[..., 2:5], rows[..., 5:11], rows[..., 11:17], rows[..., 17]
+    has_mass = mass > 0.0
+    safe_mass = np.where(has_mass, mass, 1.0)
+    vel = np.where(has_mass[..., None], mom / safe_mass[..., None], 0.0)
+    if streaming == "subtract":
+        flow = np.stack([mom[..., a] * mom[..., b] / safe_mass for a, b in _TENSOR_PAIRS], axis=-1)
+        kin = kin - np.where(has_mass[..., None], flow, 0.0)
+        dof = 3.0 * n - 3.0
+        counted = n >= 2.0
+    else:
+        dof = 3.0 * n
+        counted = n >= 1.0
+    trace = kin[..., 0] + kin[..., 3] + kin[..., 5]
+    out = dict(counts=np.rint(rows[..., _lib.THERMO_FIELD_NSUMS:]).astype(np.int64), num_particles=np.rint(n).astype(np.int64),
+               velocities=vel, kinetic_temperature=np.where(counted, trace / np.where(counted, dof, 1.0), 0.0), sums=rows)
+    if bin_volumes is not None:
+        vol = np.broadcast_to(np.asarray(bin_volumes, dtype=np.float64), n.shape)
+        p = (kin + vir) / vol[..., None]
+        out.update(bin_volumes=vol, number_density=out["counts"] / vol[..., None], mass_density=mass / vol, pressure_tensor=p,
+                   pressure=(p[..., 0] + p[..., 3] + p[..., 5]) / 3.0, potential_energy_density=pot / vol)
+    return out
+
+
+class ThermodynamicField(VelocityFieldCompute):
+    """Density, temperature and stress per bin (this project's). Use a derived type.
+
+    ``num_bins`` / ``lower_bounds`` / ``upper_bounds`` / ``coordinates`` are those of ``VelocityFieldCompute``: 0 bins
+    means the coordinate is not binned, particles outside the bounds are not counted, ghosts never are. ``filter``:
+    ``All()`` or ``Type(...)``. Per bin, with n the particle count, M = sum m, P = sum m v, K_ab = sum m v_a v_b, W_ab the
+    sum of the per-particle virials of every force of the integrator, U the sum of the per-particle energies and V_bin
+    the volume of the bin:
+
+    - ``counts`` (int64, trailing axis: the state's types; exact), ``num_particles`` = n, ``bin_volumes``,
+      ``number_density`` = counts / V_bin per type, ``mass_density`` = M / V_bin;
+    - ``velocities`` = P / M, 0 in a bin without mass (``VelocityFieldCompute.velocities``; in the cylindrical field in
+      the local (r, theta, z) basis, computed by that compute's kernel);
+    - ``streaming="subtract"``: K'_ab = K_ab - P_a P_b / M and ``kinetic_temperature`` = tr K' / (3 n - 3), 0 for
+      n < 2; ``"keep"``: K' = K and tr K / (3 n);
+    - ``pressure_tensor`` = (K'_ab + W_ab) / V_bin in the order xx, xy, xz, yy, yz, zz, ``pressure`` a third of its
+      trace, ``potential_energy_density`` = U / V_bin;
+    - ``sums``: the raw row (bins..., 18 + types) of ``azp_thermo_field_sums``.
+
+    THE STRESS IS THE PER-ATOM (IK1) PROFILE: the virial of a pair is shared in halves between its two particles and
+    counted in the bins they sit in. It is not the Irving-Kirkwood contour integral (method of planes); the two differ
+    where the density varies over the range of the forces. In the cylindrical field P, K and W stay Cartesian.
+
+    V_bin: Cartesian, V_box times the product over the binned axes of width_d / L_d (also in a tilted box);
+    cylindrical, (r1^2 - r0^2) / 2 x dtheta x dz with dtheta = 2 pi and dz = Lz where theta / z are not binned -- r must
+    be binned, else every property that divides by a volume raises.
+
+    While a ``ThermodynamicField`` is in ``sim.operations.computes``, ``Simulation.run`` turns ``compute_virial`` on for
+    every force, as for ``ThermodynamicQuantities``; ``pressure*`` and ``potential_energy_density`` need the forces
+    evaluated that way (``sim.run(0)``). At most 8 forces. Every property is computed when it is read. The sum of a bin
+    is a fixed 64-ary tree over its members in tag order: two reads of a state, and reads before and after a
+    reordering of the rows that carries the tags (``ParticleSorter``), agree bit for bit (single domain)."""
+
+    def __init__(self, num_bins, lower_bounds, upper_bounds, filter=None, streaming="subtract"):
+        filter = All() if filter is None else filter
+        if not isinstance(filter, (All, Type)):
+            raise _lib.AzpError("%s: filter must be All() or Type(...), got %r" % (type(self).__name__, filter))
+        super().__init__(num_bins, lower_bounds, upper_bounds, filter, False)
+        self.streaming = streaming
+        self._keys = None
+
+    @property
+    def streaming(self):
+        return self._streaming
+
+    @streaming.setter
+    def streaming(self, value):
+        if value not in ("subtract", "keep"):
+            raise _lib.AzpError("streaming must be 'subtract' or 'keep', got %r" % (value,))
+        self._streaming = value
+
+    _forces_evaluated = ThermodynamicQuantities._forces_evaluated
+
+    def _row_width(self):
+        return _total_bins(self._num_bins) * (_lib.THERMO_FIELD_NSUMS + len(self._sim.state.types))
+
+    def _launch(self, d_out):
+        """Queue the key kernel, the sort and ``azp_thermo_field_sums`` for the current state, the row going to
+        ``d_out``."""
+        import torch
+
+        self._check_bounds()
+        sim = self._sim
+        st = sim.state
+        integ = sim.operations.integrator
+        forces = list(integ.forces) if integ is not None else []
+        if len(forces) > _lib.THERMO_MAX_FORCES:
+            raise _lib.AzpError("%s sums at most %d forces, the integrator has %d"
+                                % (type(self).__name__, _lib.THERMO_MAX_FORCES, len(forces)))
+        a = _lib.ThermoFieldArgs()
+        a.d_pos, a.d_vel, a.d_tag = st.pos.data_ptr(), st.vel.data_ptr(), st.tag.data_ptr()
+        a.N = st.N
+        a.coordinates = self._coordinates
+        a.box = st.box.to_c()
+        for d in range(3):
+            a.num_bins[d], a.lower[d], a.upper[d] = self._num_bins[d], self._lower_bounds[d], self._upper_bounds[d]
+        mask = self._type_mask(st)
+        a.ntypes = len(st.types)
+        a.d_type_mask = mask.data_ptr() if mask is not None else None
+        if self._forces_evaluated()[0]:
+            a.n_forces = len(forces)
+            for k, f in enumerate(forces):
+                a.d_force[k] = f._force.data_ptr()
+                a.d_virial[k] = f._virial.data_ptr() if getattr(f, "_virial_evaluated", False) else None
+        self._set_scratch(a, "azp_thermo_field_scratch_size")
+        a.d_out = d_out
+        stream = _lib.raw_stream(st.device)
+        if st.N:
+            if self._keys is None or self._keys.shape[0] != st.N or self._keys.device != st.device:
+                self._keys = torch.empty(st.N, dtype=torch.int64, device=st.device)
+            a.d_keys = self._keys.data_ptr()
+            _lib.check(_lib.lib().azp_thermo_field_keys(C.byref(a), stream), "azp_thermo_field_keys")
+            # (the keys are unique: any sort gives the one order, by bin and then by tag; queued on the stream)
+            keys, order = torch.sort(self._keys)
+            a.d_sorted_keys, a.d_order = keys.data_ptr(), order.data_ptr()
+        _lib.check(_lib.lib().azp_thermo_field_sums(C.byref(a), stream), "azp_thermo_field_sums")
+
+    def _bin_volumes(self, box):
+        """Volume of every bin in ``box`` (raveled, float64), or None where it is not defined (no r binning)."""
+        raise NotImplementedError
+
+    def _shape_rows(self, host):
+        """(k, row width) host rows as (k, bins, 18 + types)."""
+        return host.reshape(host.shape[0], _total_bins(self._num_bins), -1)
+
+    def _get(self, name):
+        if not self._attached:
+            raise DataAccessError(name)
+        self._check_bounds()
+        energies, virials = self._forces_evaluated()
+        if name == "potential_energy_density" and not energies:
+            raise _lib.AzpError("%s: the forces have not been evaluated on this state; call sim.run(0)" % name)
+        if name in ("pressure", "pressure_tensor") and not virials:
+            raise _lib.AzpError("%s: the last force evaluation ran without virials; call sim.run(0) with this compute in "
+                                "sim.operations.computes" % name)
+        vol = self._bin_volumes(self._sim.state.box)
+        if vol is None and name in _THERMO_FIELD_NEEDS_VOLUME:
+            raise _lib.AzpError("%s: the volume of a cylindrical bin needs the r coordinate binned" % name)
+        shape = tuple(self._compact_shape)
+        if name == "bin_volumes":
+            return vol.reshape(shape)
+        if name == "velocities" and self._coordinates == _lib.COORDINATES_CYLINDRICAL:
+            v = self._velocity_field(self._num_bins, self._lower_bounds, self._upper_bounds, name)
+            return v.reshape(shape + (3,))
+        rows = self._shape_rows(self._reduce(self._read_row(name, "float64")))[0]
+        value = thermo_field_quantities(rows, vol, self._streaming)[name]
+        return value.reshape(shape + value.shape[1:])
+
+
+def _thermo_field_property(name):
+    return property(lambda self: self._get(name), doc="``%s`` of every bin at the current state." % name)
+
+
+for _name in THERMO_FIELD_PROPERTIES:
+    setattr(ThermodynamicField, _name, _thermo_field_property(_name))
+
+
+class CartesianThermodynamicField(ThermodynamicField):
+    """``ThermodynamicField`` binned in (x, y, z)."""
+
+    _coordinates = _lib.COORDINATES_CARTESIAN
+
+    def _bin_volumes(self, box):
+        v = box.volume
+        for n, lo, hi, length in zip(self._num_bins, self._lower_bounds, self._upper_bounds, (box.Lx, box.Ly, box.Lz)):
+            if n > 0:
+                v *= ((hi - lo) / n) / length
+        return np.full(_total_bins(self._num_bins), v, dtype=np.float64)
+
+
+class CylindricalThermodynamicField(ThermodynamicField):
+    """``ThermodynamicField`` binned in (r, theta, z), 0 <= theta < 2 pi. The sums stay Cartesian; ``velocities`` is in
+    the local (r, theta, z) basis, as ``CylindricalVelocityFieldCompute`` gives it."""
+
+    _coordinates = _lib.COORDINATES_CYLINDRICAL
+
+    def _bin_volumes(self, box):
+        nr, nt, nz = self._num_bins
+        if nr == 0:
+            return None
+        edges = np.linspace(self._lower_bounds[0], self._upper_bounds[0], nr + 1)
+        area = 0.5 * (edges[1:] ** 2 - edges[:-1] ** 2)
+        dtheta = (self._upper_bounds[1] - self._lower_bounds[1]) / nt if nt > 0 else 2.0 * np.pi
+        dz = (self._upper_bounds[2] - self._lower_bounds[2]) / nz if nz > 0 else box.Lz
+        return np.repeat(area * dtheta * dz, max(nt, 1) * max(nz, 1))
+
+
+class ThermodynamicFieldRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) that appends the raw row of ``field`` (a ``ThermodynamicField`` in
+    ``computes`` of the same simulation) to a device table at the timesteps ``trigger`` fires, as
+    ``ThermodynamicRecorder`` does: the kernels write row k of the table, nothing is read back, and the trajectory is
+    the same bit for bit with and without it. A row is bins x (18 + types) words: a ``_record`` that would grow the table
+    beyond 2^30 bytes raises. ``table`` is the dict of ``thermo_field_quantities`` with a leading axis of recorded
+    timesteps, every row normalised with the bin volumes of the box it was recorded in (the local-basis ``velocities``
+    of a cylindrical field is not in the rows: ``velocities`` is the Cartesian P / M here); ``mean()`` the same
+    quantities from the rows SUMMED FIRST and then normalised with the summed volumes (the convention of
+    ``average_over_origins``: with ``streaming="subtract"`` the streaming velocity is that of the summed momentum and
+    three degrees of freedom are removed once). On a decomposed run the rows of all ranks are added in one reduction."""
+
+    def __init__(self, field, trigger):
+        if not isinstance(field, ThermodynamicField):
+            raise _lib.AzpError("ThermodynamicFieldRecorder: field must be a ThermodynamicField, got %r" % (field,))
+        self.field = self._compute = field
+        super().__init__(trigger)
+
+    def reset(self):
+        super().reset()
+        self._bin_volumes = []  # per row: the bin volumes in the box it was recorded in (host data)
+
+    @staticmethod
+    def _grown_bytes(k, capacity, width):
+        """Bytes of the table after row k is recorded into a table of ``capacity`` rows of ``width`` words (the base
+        class grows it by doubling, to at least 64 rows)."""
+        rows = capacity if k < capacity else max(64, 2 * k)
+        return rows * width * 8
+
+    def _record(self, sim, timestep):
+        k = len(self._steps)
+        width = self._row_width()
+        fits = self._rows is not None and self._rows.shape[1] == width and self._rows.device == sim.state.device
+        need = self._grown_bytes(k, self._rows.shape[0] if fits else 0, width)
+        if need > RECORDER_MAX_BYTES:
+            raise _lib.AzpError("%s: recording row %d of %d words would grow the table to %d bytes, more than 2^30; record "
+                                "fewer bins or reset() more often" % (type(self).__name__, k, width, need))
+        super()._record(sim, timestep)
+        self._bin_volumes.append(self.field._bin_volumes(sim.state.box))
+
+    def _host_rows(self, name):
+        k = len(self._steps)
+        if not self.field._attached:
+            raise DataAccessError(name)
+        rows = self.field._shape_rows(self.field._reduce(self._rows[:k]))
+        vol = None if any(v is None for v in self._bin_volumes) else np.array(self._bin_volumes, dtype=np.float64).reshape(k, -1)
+        return rows, vol
+
+    def _shaped(self, q, lead):
+        shape = lead + tuple(self.field._compact_shape)
+        return {name: v.reshape(shape + v.shape[len(lead) + 1:]) for name, v in q.items()}
+
+    @property
+    def table(self):
+        """dict of numpy arrays keyed by ``THERMO_FIELD_PROPERTIES``, shape (rows, bins..., trailing axis)."""
+        k = len(self._steps)
+        if k == 0:
+            return {}
+        rows, vol = self._host_rows("table")
+        return self._shaped(thermo_field_quantities(rows, vol, self.field.streaming), (k,))
+
+    def mean(self):
+        """dict of the same quantities from the sum of the recorded rows and the sum of their bin volumes."""
+        if len(self._steps) == 0:
+            return {}
+        rows, vol = self._host_rows("mean")
+        return self._shaped(thermo_field_quantities(rows.sum(axis=0), None if vol is None else vol.sum(axis=0),
+                                                    self.field.streaming), ())
 
 
 # ---------------------------------------------------------------------------

@@ -211,9 +211,9 @@ class Simulation:
                 f._attach(self)
                 if f not in self._attached:
                     self._attached.append(f)
-        if self._has_thermo() or self._barostat(integ) is not None:
-            # (a ThermodynamicQuantities and a ConstantPressure read the per-particle virials: the virial pass of every
-            # force runs every step)
+        if self._has_thermo() or self._has_thermo_field() or self._barostat(integ) is not None:
+            # (a ThermodynamicQuantities, a ThermodynamicField and a ConstantPressure read the per-particle virials: the
+            # virial pass of every force runs every step)
             for f in integ.forces:
                 f.compute_virial = True
             for c in self._thermo_computes():
@@ -232,6 +232,11 @@ class Simulation:
     def _has_thermo(self):
         return bool(self.operations.computes) and bool(self._thermo_computes())
 
+    def _has_thermo_field(self):
+        from .compute import ThermodynamicField
+
+        return any(isinstance(c, ThermodynamicField) for c in self.operations.computes)
+
     def _check_writers(self):
         """A recorder reads its compute through this simulation's state: the compute has to be in ``computes``."""
         for w in self.operations.writers:
@@ -239,9 +244,10 @@ class Simulation:
                 raise _lib.AzpError("%s: its %s is not in sim.operations.computes of this simulation"
                                     % (type(w).__name__, type(w._compute).__name__))
         integ = self.operations.integrator
-        if integ is not None and len(integ.forces) > _lib.THERMO_MAX_FORCES and self._has_thermo():
-            raise _lib.AzpError("ThermodynamicQuantities sums at most %d forces, the integrator has %d"
-                                % (_lib.THERMO_MAX_FORCES, len(integ.forces)))
+        if integ is not None and len(integ.forces) > _lib.THERMO_MAX_FORCES and (self._has_thermo() or self._has_thermo_field()):
+            raise _lib.AzpError("%s sums at most %d forces, the integrator has %d"
+                                % ("ThermodynamicQuantities" if self._has_thermo() else "ThermodynamicField",
+                                   _lib.THERMO_MAX_FORCES, len(integ.forces)))
 
     def _writers_due(self):
         return [w for w in self.operations.writers if w.trigger(self.timestep)]

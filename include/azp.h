@@ -1446,6 +1446,75 @@ typedef struct azp_thermo_args
 int azp_thermo_scratch_size(const azp_thermo_args* args, uint64_t* bytes);
 int azp_thermo_sums(const azp_thermo_args* args, void* stream);
 
+/* ---- thermodynamic sums per bin (compute.ThermodynamicField) ----
+ * Not part of the reference: the semantics are DEFINED HERE. The particles of rows [0, N) that
+ * d_type_mask selects (NULL: every particle) are wrapped into the box and binned exactly as azp_velocity_field_sums
+ * bins them (same triple num_bins / lower / upper, same coordinate systems, same arithmetic: csrc/field_bin.hpp; in
+ * the cylindrical system only the BIN is cylindrical, every summed quantity stays Cartesian). Per bin the row holds
+ * AZP_THERMO_FIELD_NSUMS + ntypes doubles:
+ *   0      n, the particle count
+ *   1      M = sum m
+ *   2-4    P = sum m v
+ *   5-10   K = sum m v_a v_b, order xx, xy, xz, yy, yz, zz
+ *   11-16  W = sum over the particles of (the per-particle virials of the force arrays with a non-NULL d_virial entry,
+ *          added in the order of the arrays starting from +0.0), same order
+ *   17     U = sum over the particles of (the .w of the force arrays, added in the same way)
+ *   18...  the count per type (types outside [0, ntypes) are counted in slot 0 only): exact integers stored as doubles
+ * d_out (n_bins x (AZP_THERMO_FIELD_NSUMS + ntypes) doubles, bin-major, any 8-byte aligned device address) is
+ * OVERWRITTEN, the empty bins with +0.0.
+ *
+ * Three steps. azp_thermo_field_keys writes d_keys[i] = (bin << 32) | d_tag[i] for the N rows (a row that is not
+ * counted gets the bin AZP_THERMO_FIELD_NO_BIN, which sorts last). The caller sorts the keys as signed or unsigned
+ * 64-bit integers (they are unique and below 2^63) and hands d_sorted_keys and d_order (int64: d_sorted_keys[p] =
+ * d_keys[d_order[p]]) to azp_thermo_field_sums, which finds the non-empty bins and sums each of them in a fixed
+ * 64-ary tree: the terms of a bin in tag order are padded with +0.0 to a multiple of 64, every run of 64 is replaced
+ * by its balanced pairwise sum ((x0 + x1) + (x2 + x3)) + ..., and this repeats until one value remains. The tree is a
+ * function of the members of the bin in tag order and of nothing else: not of N, of the other bins or of the order of
+ * the rows. The terms are plain IEEE operations, no contraction: p_a = m v_a, K_ab = p_a v_b. No floating-point
+ * atomics. The number of kernel launches depends on N alone (ceil(log64 N) tree levels, at least 1); nothing is read
+ * back. All calls are asynchronous on `stream`.
+ * The scratch (azp_thermo_field_scratch_size bytes: depends on N, ntypes and the bin count) is used by
+ * azp_thermo_field_sums alone.
+ * AZP_ERROR_TOO_MANY_BINS: more than 2^31 - 1 bins. AZP_ERROR_INVALID_ARGUMENT, before anything is launched or
+ * written: NULL args, upper <= lower in a binned dimension, an unknown coordinate system, more than
+ * AZP_THERMO_MAX_FORCES forces or a NULL listed force array, a NULL array the call uses, too small a scratch, phases
+ * above 3. N == 0: d_out is zeroed. */
+#define AZP_THERMO_FIELD_NSUMS 18
+#define AZP_THERMO_FIELD_NO_BIN 0x7fffffffu
+#define AZP_THERMO_FIELD_HEADS 1u
+#define AZP_THERMO_FIELD_LEVELS 2u
+
+typedef struct azp_thermo_field_args
+    {
+    const double* d_pos;       /* N x 4 (x, y, z, type bits) */
+    const double* d_vel;       /* N x 4 (vx, vy, vz, mass) */
+    const uint32_t* d_tag;     /* N */
+    const uint8_t* d_type_mask; /* ntypes bytes, may be NULL */
+    const double* d_force[AZP_THERMO_MAX_FORCES];  /* n_forces arrays, N x 4 */
+    const double* d_virial[AZP_THERMO_MAX_FORCES]; /* per force: 6 rows of pitch N, or NULL (no virial) */
+    int64_t* d_keys;           /* N, written by azp_thermo_field_keys */
+    const int64_t* d_sorted_keys; /* N, read by azp_thermo_field_sums */
+    const int64_t* d_order;    /* N, read by azp_thermo_field_sums */
+    double* d_out;             /* bins x (AZP_THERMO_FIELD_NSUMS + ntypes), overwritten */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    azp_box box;               /* global box */
+    double lower[3];
+    double upper[3];
+    uint32_t num_bins[3];      /* Cartesian (x, y, z) or cylindrical (r, theta, z); 0: not binned */
+    uint32_t coordinates;      /* azp_coordinates */
+    uint32_t N;
+    uint32_t ntypes;           /* entries of d_type_mask and per-type count slots */
+    uint32_t n_forces;
+    uint32_t phases;           /* 0: all of azp_thermo_field_sums. For timing alone (tools/thermo_field_probe.py):
+                                * AZP_THERMO_FIELD_HEADS runs the segment heads only, AZP_THERMO_FIELD_LEVELS zeroes d_out
+                                * and runs the tree on the heads that an earlier call left in the scratch */
+    } azp_thermo_field_args;
+
+int azp_thermo_field_scratch_size(const azp_thermo_field_args* args, uint64_t* bytes);
+int azp_thermo_field_keys(const azp_thermo_field_args* args, void* stream);
+int azp_thermo_field_sums(const azp_thermo_field_args* args, void* stream);
+
 /* ---- radial distribution function (compute.RadialDistributionFunction) ----
  * Not part of the reference (azplugins had analyze.rdf in its HOOMD-2 line): the semantics are DEFINED HERE
  * (DESIGN 4.14). For two groups A and B (d_type_mask_a / d_type_mask_b: one byte per type, NULL = every particle; the
