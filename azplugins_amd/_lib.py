@@ -386,6 +386,51 @@ class RdfExclusionArgs(C.Structure):
     _fields_ = [("rdf", RdfArgs), ("d_n_excl", C.c_void_p), ("d_excl", C.c_void_p), ("excl_pitch", C.c_uint64)]
 
 
+PRESSURE_PROFILE_MAX_BINS = 8192
+PRESSURE_PROFILE_LDS_BINS = 1024
+# azp_pressure_profile_evaluator
+PP_EVALUATORS = dict(PerturbedLennardJones=0, Hertz=1, ExpandedYukawa=2, Colloid=3, DPDConservativeGeneralWeight=4, PairTable=5,
+                     DoubleWell=16, Quartic=17, BondTable=18, SpecialPairLJ=19)
+
+
+class PressureProfileArgs(C.Structure):
+    _fields_ = [
+        ("d_pos", C.c_void_p),
+        ("d_tag", C.c_void_p),
+        ("N", C.c_uint32),
+        ("ntypes", C.c_uint32),
+        ("box", Box),
+        ("axis", C.c_uint32),
+        ("num_bins", C.c_uint32),
+        ("lower", C.c_double),
+        ("scale", C.c_double),
+        ("max_term", C.c_double),
+        ("wrap", C.c_uint32),
+        ("shift", C.c_uint32),
+        ("d_rcutsq", C.c_void_p),
+        ("d_ronsq", C.c_void_p),
+        ("r_max", C.c_double),
+        ("shift_mode", C.c_uint32),
+        ("path", C.c_uint32),
+        ("d_out", C.c_void_p),
+        ("d_scratch", C.c_void_p),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
+class PressureProfileListArgs(C.Structure):
+    _fields_ = [
+        ("profile", PressureProfileArgs),
+        ("d_table", C.c_void_p),
+        ("d_counts", C.c_void_p),
+        ("pitch", C.c_uint64),
+        ("n_types", C.c_uint32),
+        ("evaluator", C.c_uint32),
+        ("sign", C.c_int32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 STEINHARDT_MAX_TERMS = 4
 STEINHARDT_MAX_L = 12
 STEINHARDT_MAX_BINS = 1024
@@ -922,6 +967,15 @@ SYMBOLS = {
     "azp_rdf_counts": (C.c_int, [C.POINTER(RdfArgs), _VP]),
     "azp_rdf_subtract_excluded": (C.c_int, [C.POINTER(RdfExclusionArgs), _VP]),
     "azp_bonded_histogram": (C.c_int, [C.POINTER(BondedHistogramArgs), _VP]),
+    "azp_pressure_profile_scratch_size": (C.c_int, [C.POINTER(PressureProfileArgs), C.POINTER(C.c_uint64)]),
+    "azp_pressure_profile_begin": (C.c_int, [C.POINTER(PressureProfileArgs), _VP]),
+    "azp_pressure_profile_pairs_perturbed_lennard_jones": (C.c_int, [C.POINTER(PressureProfileArgs), _VP, _VP]),
+    "azp_pressure_profile_pairs_hertz": (C.c_int, [C.POINTER(PressureProfileArgs), _VP, _VP]),
+    "azp_pressure_profile_pairs_expanded_yukawa": (C.c_int, [C.POINTER(PressureProfileArgs), _VP, _VP]),
+    "azp_pressure_profile_pairs_colloid": (C.c_int, [C.POINTER(PressureProfileArgs), _VP, _VP]),
+    "azp_pressure_profile_pairs_dpd_conservative": (C.c_int, [C.POINTER(PressureProfileArgs), _VP, _VP]),
+    "azp_pressure_profile_pairs_table": (C.c_int, [C.POINTER(PressureProfileArgs), _VP, _VP]),
+    "azp_pressure_profile_listed": (C.c_int, [C.POINTER(PressureProfileListArgs), _VP, _VP]),
     "azp_structure_factor_scratch_size": (C.c_int, [C.POINTER(StructureFactorArgs), C.POINTER(C.c_uint64)]),
     "azp_structure_factor_amplitudes": (C.c_int, [C.POINTER(StructureFactorArgs), _VP]),
     "azp_displacement_origin": (C.c_int, [C.POINTER(DisplacementOriginArgs), _VP]),

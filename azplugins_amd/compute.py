@@ -18,6 +18,11 @@ summed in a fixed 64-ary tree over its members in tag order (``csrc/thermo_field
 ``ThermodynamicFieldRecorder`` appends the raw rows to a device table inside ``Simulation.run`` and
 ``thermo_field_quantities`` turns raw rows into the quantities.
 
+``PressureProfile`` is the pressure tensor in slabs along one axis with every pair's virial spread along the line between
+its two particles (the Irving-Kirkwood contour; ``csrc/pressure_profile.hip``; this project's): the pair
+and two-body bonded forces are evaluated pair by pair and accumulated as integers; ``PressureProfileRecorder`` appends the
+raw rows inside ``Simulation.run`` and ``pressure_profile_quantities`` turns raw rows into the quantities.
+
 ``RadialDistributionFunction`` is g(r) between two groups from exact integer pair counts (``csrc/rdf.hip``; not part of
 the reference: azplugins had ``analyze.rdf`` in its HOOMD-2 line, the semantics are this project's, DESIGN 4.14);
 ``RDFRecorder`` appends the counts to a device table inside ``Simulation.run`` in the same way.
@@ -3344,7 +3349,438 @@ class SelfIntermediateScatteringRecorder(_TwoTimeRecorder):
         return np.stack([spherical_average(r, bins, nb)[0] for r in per])
 
 
-__all__ = ["MeanSquaredDisplacement", "MeanSquaredDisplacementRecorder", "SelfIntermediateScattering",
+# ---------------------------------------------------------------------------
+# pressure profile (Irving-Kirkwood contour)
+# ---------------------------------------------------------------------------
+PRESSURE_PROFILE_PROPERTIES = ("configurational_pressure_tensor", "kinetic_pressure_tensor", "pressure_tensor", "normal_pressure",
+                               "tangential_pressure", "bin_volumes", "num_pairs", "num_terms", "overflow")
+_AXES = {"x": 0, "y": 1, "z": 2}
+_DIAGONAL = (0, 3, 5)  # xx, yy, zz among xx, xy, xz, yy, yz, zz
+
+
+def pressure_profile_shift(n_particles, max_term):
+    """The shift of ``azp_pressure_profile_args`` for N particles: terms are kept in units of 2^-shift, the largest
+    shift (at most 52) at which ``max_term * 2^shift * 2^pair_bits <= 2^63``, ``pair_bits = ceil(log2 N) + 8`` -- the sum
+    of a word cannot wrap while fewer than 2^pair_bits pairs are evaluated. Returns ``(shift, pair_bits)``; ``AzpError``
+    where ``max_term`` leaves no shift >= 0."""
+    max_term = float(max_term)
+    if not (max_term > 0.0 and np.isfinite(max_term)):
+        raise _lib.AzpError("PressureProfile: max_term must be positive and finite, got %r" % (max_term,))
+    pair_bits = max(int(n_particles) - 1, 1).bit_length() + 8
+    m = int(np.ceil(np.log2(max_term)))
+    while 2.0 ** m < max_term:  # (log2 rounded down at a power of two's neighbour)
+        m += 1
+    shift = min(52, 63 - pair_bits - m)
+    if shift < 0:
+        raise _lib.AzpError("PressureProfile: max_term = %r is too large for %d particles (no integer scale is left)"
+                            % (max_term, n_particles))
+    return shift, pair_bits
+
+
+def pressure_profile_quantities(row, kinetic_rows, bin_volumes, axis, bin_width, streaming="subtract", interfaces=2, shift=None):
+    """The quantities of ``compute.PressureProfile`` from raw rows. ``row``: (..., 6 bins + 4) int64 of
+    ``azp_pressure_profile_*`` (a sum of rows where ``shift`` is given: the shift word of a sum is meaningless);
+    ``kinetic_rows``: (..., bins, 18 + types) raw rows of ``azp_thermo_field_sums`` on the same bins (their W slots are
+    not read); ``bin_volumes``: (..., bins) or one that broadcasts; ``axis``: 0, 1, 2; ``bin_width``: the width of a bin
+    along the axis. Returns a dict: ``configurational_pressure_tensor`` = sums 2^-shift / V_k, ``kinetic_pressure_tensor``
+    = K'_ab / V_k (``streaming`` as ``thermo_field_quantities``), ``pressure_tensor`` their sum (all (..., bins, 6), xx,
+    xy, xz, yy, yz, zz), ``normal_pressure`` the axis' diagonal component, ``tangential_pressure`` the mean of the other
+    two, ``surface_tension`` = (1 / interfaces) sum_k (P_N - P_T)_k bin_width, ``bin_volumes``, ``num_pairs``,
+    ``num_terms`` and ``overflow``. Plain numpy in a fixed order: the properties and the recorder go through here."""
+    if axis not in (0, 1, 2):
+        raise _lib.AzpError("pressure_profile_quantities: axis must be 0, 1 or 2, got %r" % (axis,))
+    if isinstance(interfaces, bool) or int(interfaces) != interfaces or int(interfaces) < 1:
+        raise _lib.AzpError("pressure_profile_quantities: interfaces must be a positive integer, got %r" % (interfaces,))
+    row = np.asarray(row, dtype=np.int64)
+    if row.shape[-1] < 10 or (row.shape[-1] - 4) % 6:
+        raise _lib.AzpError("pressure_profile_quantities: a row has 6 bins + 4 words, got %d" % row.shape[-1])
+    nb = (row.shape[-1] - 4) // 6
+    if shift is None:
+        shift = row[..., -1]
+    scale = np.ldexp(1.0, -np.asarray(shift, dtype=np.int64))
+    sums = row[..., : 6 * nb].reshape(row.shape[:-1] + (nb, 6)).astype(np.float64) * np.asarray(scale)[..., None, None]
+    kin = np.asarray(kinetic_rows, dtype=np.float64).copy()
+    if kin.shape[-2] != nb:
+        raise _lib.AzpError("pressure_profile_quantities: %d kinetic rows for %d bins" % (kin.shape[-2], nb))
+    kin[..., 11:17] = 0.0  # (the field's W is the per-atom virial: not this compute's)
+    vol = np.broadcast_to(np.asarray(bin_volumes, dtype=np.float64), sums.shape[:-1])
+    p_conf = sums / vol[..., None]
+    p_kin = thermo_field_quantities(kin, vol, streaming)["pressure_tensor"]
+    p = p_kin + p_conf
+    others = [d for d in range(3) if d != axis]
+    p_n = p[..., _DIAGONAL[axis]]
+    p_t = 0.5 * (p[..., _DIAGONAL[others[0]]] + p[..., _DIAGONAL[others[1]]])
+    gamma = ((p_n - p_t) * np.asarray(bin_width, dtype=np.float64)[..., None]).sum(axis=-1) / float(interfaces)
+    return dict(configurational_pressure_tensor=p_conf, kinetic_pressure_tensor=p_kin, pressure_tensor=p, normal_pressure=p_n,
+                tangential_pressure=p_t, surface_tension=gamma, bin_volumes=vol, num_pairs=row[..., -4].copy(),
+                num_terms=row[..., -3].copy(), overflow=row[..., -2].copy())
+
+
+def _pressure_profile_force(f):
+    """How ``PressureProfile`` takes the force ``f``: ``("pair", libazp entry, evaluator)``, ``("bond" | "pair group",
+    evaluator)`` for the bonds and special pairs, ``None`` for a one-body force; ``AzpError`` for the others."""
+    from . import angle, bond, dihedral, external, pair, special_pair, wall
+
+    name = type(f).__name__
+    if isinstance(f, pair.DPDGeneralWeight):
+        raise _lib.AzpError("PressureProfile: %s is a thermostat: its pair force depends on the velocities and on random "
+                            "numbers, which the contour integral of a configuration does not hold" % name)
+    if isinstance(f, pair.TwoPatchMorse):
+        raise _lib.AzpError("PressureProfile: %s is anisotropic: its force is not along the line between the particles" % name)
+    if isinstance(f, (angle.Angle, dihedral.Dihedral)):
+        raise _lib.AzpError("PressureProfile: %s is a many-body force: its contour is not a single segment (out of scope)" % name)
+    pairs = {pair.PerturbedLennardJones: "perturbed_lennard_jones", pair.Hertz: "hertz", pair.ExpandedYukawa: "expanded_yukawa",
+             pair.Colloid: "colloid", pair.DPDConservativeGeneralWeight: "dpd_conservative", pair.Table: "table"}
+    names = {pair.Table: "PairTable", bond.Table: "BondTable", special_pair.LJ: "SpecialPairLJ"}
+    for cls, entry in pairs.items():
+        if type(f) is cls:
+            return ("pair", "azp_pressure_profile_pairs_" + entry, _lib.PP_EVALUATORS[names.get(cls, cls.__name__)])
+    for cls in (bond.DoubleWell, bond.Quartic, bond.Table, special_pair.LJ):
+        if type(f) is cls:
+            return ("group", f._kind, _lib.PP_EVALUATORS[names.get(cls, cls.__name__)])
+    if isinstance(f, (external.HarmonicBarrier, wall._WallPotential)):
+        return None
+    raise _lib.AzpError("PressureProfile: %s is not a force this compute knows how to spread over a contour" % name)
+
+
+class _KineticField(ThermodynamicField):
+    """The ``CartesianThermodynamicField`` a ``PressureProfile`` owns: counts, M, P and K on its bins; no force is read."""
+
+    _coordinates = _lib.COORDINATES_CARTESIAN
+
+    def _forces_evaluated(self):
+        return False, False
+
+
+class PressureProfile(_Compute):
+    """The pressure tensor along one Cartesian axis by the Irving-Kirkwood contour (this project's):
+    ``num_bins`` equal slabs on [``lower``, ``upper``) along ``axis`` ("x", "y" or "z"; default range: the whole box
+    length). The virial of every pair is spread along the straight line between the two particles: a slab receives the
+    fraction of the line's extent along the axis that lies in it. Unlike the per-atom profile of
+    ``ThermodynamicField`` its normal component is constant across a flat interface at equilibrium, and
+    ``surface_tension`` is the mechanical route, gamma = (1 / interfaces) sum_k (P_N - P_T)_k delta.
+
+    ``forces``: the forces that count, default every force of the integrator. The isotropic pair potentials
+    (``Colloid``, ``ExpandedYukawa``, ``Hertz``, ``PerturbedLennardJones``, ``DPDConservativeGeneralWeight``,
+    ``pair.Table``; with their ``r_cut``, ``r_on`` and ``mode``, less the pairs their neighbor list's ``exclusions``
+    name) and the two-body bonded forces (``bond.DoubleWell``, ``bond.Quartic``, ``bond.Table``, ``special_pair.LJ``) are
+    evaluated pair by pair with the evaluators the force kernels use; barriers and walls are one-body and skipped; the
+    DPD thermostat, ``TwoPatchMorse``, angles, dihedrals and anything else are refused with an ``AzpError``. The forces
+    themselves are not read: ``compute_virial`` is neither needed nor turned on, but the forces must be attached
+    (``sim.run(0)``).
+
+    Pairs, weights and integer accumulation are stated in ``include/azp.h`` ("pressure profile"). A term of magnitude
+    ``max_term`` or more (two particles nearly on top of each other) is not added but counted in ``overflow``; reading a
+    profile then raises and names ``max_term``, as it does when more pairs were evaluated than the integer scale was
+    chosen for (2^(ceil(log2 N) + 8)). The raw row is the same bits between two reads, between the paths, under the
+    particle sorter and with or without a recorder.
+
+    The range wraps (bin indices modulo ``num_bins``) where ``lower`` and ``upper`` are both left None and the axis is
+    periodic; then a tilt that shears the axis (xy, xz for "x"; yz for "y") is refused. With explicit bounds the parts of
+    a line outside the range are dropped. V_k = V_box delta / L_axis. The kinetic part K'_ab / V_k and the counts come
+    from a ``CartesianThermodynamicField`` on the same bins that this compute owns (``All()``, the same
+    ``streaming``). ``path``: 0 automatic, 1 all-pairs (any box), 2 cells (orthorhombic, three cells of the largest
+    ``r_cut`` on every periodic axis), as ``RadialDistributionFunction.path``. Single-domain states only: a pair that
+    straddles two ranks would need its line cut at the boundary. At most 8 forces in the integrator (the owned field's
+    limit)."""
+
+    def __init__(self, axis, num_bins, forces=None, lower=None, upper=None, streaming="subtract", max_term=1024.0):
+        super().__init__(All(), False)
+        if axis not in _AXES:
+            raise _lib.AzpError("PressureProfile: axis must be 'x', 'y' or 'z', got %r" % (axis,))
+        self._axis = _AXES[axis]
+        if isinstance(num_bins, bool) or int(num_bins) != num_bins or not 1 <= int(num_bins) <= _lib.PRESSURE_PROFILE_MAX_BINS:
+            raise _lib.AzpError("PressureProfile: num_bins must be an integer in [1, %d], got %r"
+                                % (_lib.PRESSURE_PROFILE_MAX_BINS, num_bins))
+        self._num_bins = int(num_bins)
+        if (lower is None) != (upper is None):
+            raise _lib.AzpError("PressureProfile: give both lower and upper, or neither")
+        if lower is not None:
+            lower, upper = float(lower), float(upper)
+            if not (np.isfinite(lower) and np.isfinite(upper) and upper > lower):
+                raise _lib.AzpError("PressureProfile: upper = %r must be larger than lower = %r" % (upper, lower))
+        self._lower, self._upper = lower, upper
+        if streaming not in ("subtract", "keep"):
+            raise _lib.AzpError("streaming must be 'subtract' or 'keep', got %r" % (streaming,))
+        self._streaming = streaming
+        pressure_profile_shift(2, max_term)
+        self._max_term = float(max_term)
+        self.forces = None if forces is None else list(forces)
+        if self.forces is not None:
+            for f in self.forces:
+                _pressure_profile_force(f)
+        self.path = _lib.RDF_PATH_AUTO
+        bins = [0, 0, 0]
+        bins[self._axis] = self._num_bins
+        self._field = _KineticField(bins, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), All(), streaming)
+
+    axis = property(lambda self: "xyz"[self._axis])
+    num_bins = property(lambda self: self._num_bins)
+    streaming = property(lambda self: self._streaming)
+    max_term = property(lambda self: self._max_term)
+
+    @property
+    def path(self):
+        return self._path
+
+    @path.setter
+    def path(self, value):
+        if value not in (_lib.RDF_PATH_AUTO, _lib.RDF_PATH_ALL_PAIRS, _lib.RDF_PATH_CELLS):
+            raise _lib.AzpError("PressureProfile: path must be 0 (auto), 1 (all-pairs) or 2 (cells), got %r" % (value,))
+        self._path = int(value)
+
+    def _range(self, box):
+        """(lower, upper, wrap) in ``box``."""
+        length = (box.Lx, box.Ly, box.Lz)[self._axis]
+        if self._lower is None:
+            return -0.5 * length, 0.5 * length, bool(box.periodic[self._axis])
+        return self._lower, self._upper, False
+
+    def _edges(self):
+        if self._lower is None and not self._attached:
+            raise DataAccessError("bin_edges")
+        lo, hi, _ = self._range(self._sim.state.box) if self._lower is None else (self._lower, self._upper, False)
+        return np.linspace(lo, hi, self._num_bins + 1)
+
+    @property
+    def bin_edges(self):
+        """numpy.ndarray: the ``num_bins + 1`` edges of the slabs (of the current box where the range is the default)."""
+        return self._edges()
+
+    @property
+    def bin_centers(self):
+        e = self._edges()
+        return 0.5 * (e[1:] + e[:-1])
+
+    def _bin_width(self, box):
+        lo, hi, _ = self._range(box)
+        return (hi - lo) / self._num_bins
+
+    def _bin_volumes(self, box):
+        length = (box.Lx, box.Ly, box.Lz)[self._axis]
+        return np.full(self._num_bins, box.volume * (self._bin_width(box) / length), dtype=np.float64)
+
+    # -- one launch ----------------------------------------------------------
+    def _kinetic_width(self):
+        return self._num_bins * (_lib.THERMO_FIELD_NSUMS + len(self._sim.state.types))
+
+    def _row_width(self):
+        """6 bins + 4 integer words, then the kinetic field's row (float64 bits in the same 8-byte words)."""
+        return 6 * self._num_bins + 4 + self._kinetic_width()
+
+    def _forces(self):
+        integ = self._sim.operations.integrator
+        forces = self.forces if self.forces is not None else (list(integ.forces) if integ is not None else [])
+        out = []
+        for f in forces:
+            how = _pressure_profile_force(f)
+            if how is not None:
+                if f._state is not self._sim.state:
+                    raise _lib.AzpError("PressureProfile: %s is not attached to this simulation's state; call sim.run(0)"
+                                        % type(f).__name__)
+                out.append((f, how))
+        return out
+
+    def _launch(self, d_out):
+        """Queue the kernels of every force and the kinetic field for the current state, the row going to ``d_out``."""
+        sim = self._sim
+        st = sim.state
+        if sim.domain is not None:
+            raise _lib.AzpError("PressureProfile: decomposed runs are not supported (the line of a pair that straddles two "
+                                "ranks would have to be cut at the boundary)")
+        box = st.box
+        lo, hi, wrap = self._range(box)
+        if wrap and ((self._axis == 0 and (box.xy != 0.0 or box.xz != 0.0)) or (self._axis == 1 and box.yz != 0.0)):
+            raise _lib.AzpError("PressureProfile: axis %r of %r is sheared by a tilt: its slabs are not periodic images of "
+                                "themselves; profile along z, or give lower and upper" % ("xyz"[self._axis], box))
+        shift, _ = pressure_profile_shift(st.N, self._max_term)
+        a = _lib.PressureProfileArgs()
+        a.d_pos, a.d_tag = st.pos.data_ptr(), st.tag.data_ptr()
+        a.N = st.N
+        a.ntypes = len(st.types)
+        a.box = box.to_c()
+        a.axis, a.num_bins = self._axis, self._num_bins
+        a.lower = lo
+        a.scale = self._num_bins / (hi - lo)
+        a.max_term = self._max_term
+        a.wrap, a.shift = int(wrap), shift
+        a.path = self._path
+        a.d_out = d_out
+        lib = _lib.lib()
+        stream = _lib.raw_stream(st.device)
+        forces = self._forces()
+        _lib.check(lib.azp_pressure_profile_begin(C.byref(a), stream), "azp_pressure_profile_begin")
+        for f, how in forces:
+            if f._tables is None:
+                f._build_tables()
+            if how[0] == "pair":
+                r_max = float(np.max(f._r_cut_matrix()))
+                if not r_max > 0.0:
+                    continue
+                _check_pair_range("PressureProfile (%s)" % type(f).__name__, box, r_max)
+                a.d_rcutsq, a.d_ronsq = f._tables["rcutsq"].data_ptr(), f._tables["ronsq"].data_ptr()
+                a.r_max = r_max
+                a.shift_mode = {"none": 0, "shift": 1, "xplor": 2}[f.mode]
+                params = f._tables["params"].data_ptr()
+                if self._path == _lib.RDF_PATH_CELLS and box.is_triclinic:
+                    raise _lib.AzpError("PressureProfile: path 2 (cells) needs an orthorhombic box, got %r" % (box,))
+                self._set_scratch(a, "azp_pressure_profile_scratch_size")
+                _lib.check(getattr(lib, how[1])(C.byref(a), params, stream), how[1])
+                kinds = f.nlist._exclusion_kinds
+                if kinds and any(g.n for g in st.groups.values()):
+                    x = _lib.PressureProfileListArgs()
+                    x.profile = a
+                    n_excl, excl, pitch = st.merged_exclusion_table(kinds)
+                    x.d_table, x.d_counts, x.pitch = excl.data_ptr(), n_excl.data_ptr(), pitch
+                    x.evaluator, x.sign = how[2], -1
+                    _lib.check(lib.azp_pressure_profile_listed(C.byref(x), params, stream), "azp_pressure_profile_listed")
+            else:
+                kind = how[1]
+                if not st.groups[kind].n:
+                    continue
+                tab = st.group_table(kind)
+                x = _lib.PressureProfileListArgs()
+                x.profile = a
+                x.profile.d_rcutsq = x.profile.d_ronsq = None
+                x.profile.shift_mode = 0
+                x.d_table, x.d_counts, x.pitch = tab["table"].data_ptr(), tab["n_%ss" % kind].data_ptr(), tab["pitch"]
+                x.n_types = max(len(f._types()), 1)
+                x.evaluator, x.sign = how[2], 1
+                _lib.check(lib.azp_pressure_profile_listed(C.byref(x), f._tables.data_ptr(), stream), "azp_pressure_profile_listed")
+        field = self._field
+        field._sim = sim
+        lower, upper = [0.0, 0.0, 0.0], [1.0, 1.0, 1.0]
+        lower[self._axis], upper[self._axis] = lo, hi
+        field.lower_bounds, field.upper_bounds = lower, upper
+        field._launch(d_out + (6 * self._num_bins + 4) * 8)
+
+    # -- results -------------------------------------------------------------
+    def _split(self, host):
+        """(k, row width) int64 host rows as the integer rows and the kinetic rows (k, bins, 18 + types)."""
+        n = 6 * self._num_bins + 4
+        return host[:, :n], np.ascontiguousarray(host[:, n:]).view(np.float64).reshape(host.shape[0], self._num_bins, -1)
+
+    def _check_rows(self, rows, n_particles, what):
+        """Raise where a row cannot be trusted: refused terms, or more pairs than the scale was chosen for."""
+        for r, n in zip(rows, n_particles):
+            _, pair_bits = pressure_profile_shift(n, self._max_term)
+            if int(r[-2]) != 0:
+                raise _lib.AzpError("PressureProfile.%s: %d terms were not finite or reached max_term = %r and were left out "
+                                    "(particles nearly on top of each other?); raise max_term" % (what, int(r[-2]), self._max_term))
+            if int(r[-4]) >= 2 ** pair_bits:
+                raise _lib.AzpError("PressureProfile.%s: %d pairs were evaluated, the integer scale chosen from max_term = %r "
+                                    "holds fewer than 2^%d; lower max_term" % (what, int(r[-4]), self._max_term, pair_bits))
+
+    def _read(self, name):
+        return self._read_row(name).cpu().numpy()
+
+    @property
+    def row(self):
+        """numpy int64 (6 num_bins + 4,): the raw integer row (bins x {xx, xy, xz, yy, yz, zz} in units of 2^-shift, then
+        pairs evaluated, terms added, terms refused, shift)."""
+        return self._split(self._read("row"))[0][0].copy()
+
+    def _get(self, name, interfaces=2):
+        host = self._read(name)
+        box = self._sim.state.box
+        ints, kin = self._split(host)
+        if name not in ("num_pairs", "num_terms", "overflow"):
+            self._check_rows(ints, [self._sim.state.N], name)
+        q = pressure_profile_quantities(ints[0], kin[0], self._bin_volumes(box), self._axis, self._bin_width(box), self._streaming,
+                                        interfaces)
+        v = q[name]
+        return int(v) if name in ("num_pairs", "num_terms", "overflow") else v
+
+    def surface_tension(self, interfaces=2):
+        """float: (1 / ``interfaces``) sum_k (P_N - P_T)_k delta; a slab of liquid in a periodic box has two interfaces."""
+        return float(self._get("surface_tension", interfaces))
+
+
+def _pressure_profile_property(name):
+    return property(lambda self: self._get(name), doc="``%s`` at the current state (``pressure_profile_quantities``)." % name)
+
+
+for _name in PRESSURE_PROFILE_PROPERTIES:
+    setattr(PressureProfile, _name, _pressure_profile_property(_name))
+
+
+class PressureProfileRecorder(_Recorder):
+    """Writer (``sim.operations.writers``) that appends the raw row of ``profile`` (a ``PressureProfile`` in ``computes``
+    of the same simulation: the integer row and the kinetic field's row) to a device table at the timesteps ``trigger``
+    fires, as ``ThermodynamicFieldRecorder`` does: the kernels write row k of the table, nothing is read back, and the
+    trajectory is the same bit for bit with and without it. ``rows`` are the integer rows, ``table`` the dict of
+    ``pressure_profile_quantities`` with a leading axis of recorded timesteps, every row with the bin volumes of the box
+    it was recorded in; ``mean()`` the same quantities from the rows SUMMED and normalised with the summed volumes."""
+
+    _dtype = "int64"
+
+    def __init__(self, profile, trigger):
+        if not isinstance(profile, PressureProfile):
+            raise _lib.AzpError("PressureProfileRecorder: profile must be a PressureProfile, got %r" % (profile,))
+        self.profile = self._compute = profile
+        super().__init__(trigger)
+
+    def reset(self):
+        super().reset()
+        self._bin_volumes = []  # per row, host data: the bin volumes, the bin width and N when it was recorded
+        self._bin_widths = []
+        self._n = []
+
+    def _record(self, sim, timestep):
+        k = len(self._steps)
+        width = self._row_width()
+        need = ThermodynamicFieldRecorder._grown_bytes(k, self._rows.shape[0] if self._rows is not None and self._rows.shape[1] == width
+                                                       else 0, width)
+        if need > RECORDER_MAX_BYTES:
+            raise _lib.AzpError("%s: recording row %d of %d words would grow the table to %d bytes, more than 2^30; record "
+                                "fewer bins or reset() more often" % (type(self).__name__, k, width, need))
+        super()._record(sim, timestep)
+        box = sim.state.box
+        self._bin_volumes.append(self.profile._bin_volumes(box))
+        self._bin_widths.append(self.profile._bin_width(box))
+        self._n.append(sim.state.N)
+
+    def _host(self, name):
+        k = len(self._steps)
+        if not self.profile._attached:
+            raise DataAccessError(name)
+        ints, kin = self.profile._split(self._rows[:k].cpu().numpy())
+        return ints, kin
+
+    @property
+    def rows(self):
+        """numpy int64 (rows, 6 num_bins + 4): the raw integer rows."""
+        if len(self._steps) == 0:
+            return np.zeros((0, 6 * self.profile.num_bins + 4), dtype=np.int64)
+        return self._host("rows")[0].copy()
+
+    def table(self, interfaces=2):
+        """dict of numpy arrays, one leading entry per recorded timestep."""
+        if len(self._steps) == 0:
+            return {}
+        ints, kin = self._host("table")
+        p = self.profile
+        p._check_rows(ints, self._n, "table")
+        return pressure_profile_quantities(ints, kin, np.array(self._bin_volumes), p._axis, np.array(self._bin_widths), p.streaming,
+                                           interfaces)
+
+    def mean(self, interfaces=2):
+        """dict of the same quantities from the sum of the recorded rows and the sum of their bin volumes (the bin width
+        is the mean of the recorded widths)."""
+        if len(self._steps) == 0:
+            return {}
+        ints, kin = self._host("mean")
+        p = self.profile
+        p._check_rows(ints, self._n, "mean")
+        if np.any(ints[:, -1] != ints[0, -1]):
+            raise _lib.AzpError("PressureProfileRecorder.mean: the rows were recorded with different integer scales (the number "
+                                "of particles changed); use table()")
+        return pressure_profile_quantities(ints.sum(axis=0), kin.sum(axis=0), np.array(self._bin_volumes).sum(axis=0), p._axis,
+                                           np.mean(self._bin_widths), p.streaming, interfaces, shift=int(ints[0, -1]))
+
+
+__all__ = ["PressureProfile", "PressureProfileRecorder", "pressure_profile_quantities", "pressure_profile_shift",
+           "MeanSquaredDisplacement", "MeanSquaredDisplacementRecorder", "SelfIntermediateScattering",
            "SelfIntermediateScatteringRecorder", "average_over_origins", "displacement_moments",
            "intermediate_scattering_from_amplitudes", "self_scattering_from_row", "van_hove_from_counts",
            "BondedDistribution", "BondedDistributionRecorder", "CartesianVelocityFieldCompute", "Cluster", "ClusterProperties",

@@ -2077,8 +2077,116 @@ int azp_displacement_moments(const azp_displacement_args* args, void* stream);
 int azp_self_scattering_scratch_size(const azp_displacement_args* args, uint64_t* bytes);
 int azp_self_scattering(const azp_displacement_args* args, void* stream);
 
+/* ---- pressure profile (compute.PressureProfile) ----
+ * Not part of the reference; the semantics are DEFINED HERE. The configurational part of the
+ * Irving-Kirkwood contour stress along one Cartesian axis (0, 1, 2 = x, y, z), in num_bins equal bins on
+ * [lower, lower + num_bins / scale): scale = num_bins / (upper - lower) is computed once by the caller and passed in.
+ *
+ * A pair. Every unordered pair (i, j) that the force acts on is taken ONCE, with i the member with the smaller tag:
+ *   d = minimum image of r_i - r_j (the image code of the force kernels), rsq = d.x d.x + d.y d.y + d.z d.z as
+ *   walk_accept writes it; force_divr from the force's evaluator (E::prepare / E::eval with the force's r_cut^2 and
+ *   r_on^2 tables and shift_mode, xplor through apply_xplor, exactly as the pair kernels call them); a pair that the
+ *   evaluator does not evaluate (beyond its r_cut, a bond that its evaluator rejects) contributes nothing and is not
+ *   counted. The six virial words are w = {fx d.x, fx d.y, fx d.z, fy d.y, fy d.z, fz d.z} with fx = force_divr d.x,
+ *   fy = force_divr d.y, fz = force_divr d.z.
+ * The weights. With z1 = the stored coordinate of i along the axis and da = d[axis], every operation rounded once (no
+ * contraction):
+ *   s1 = (z1 - lower) * scale;  s0 = ((z1 - da) - lower) * scale;  lo = min(s0, s1);  hi = max(s0, s1);
+ *   if floor(lo) == floor(hi): the one bin k = floor(lo) gets lambda = 1 (da = 0 is this case);
+ *   else for every integer k from floor(lo) to floor(hi): lambda_k = (min(hi, k + 1) - max(lo, k)) / (hi - lo), and a
+ *   bin with lambda_k <= 0 (an end point exactly on an edge) gets nothing.
+ *   wrap != 0 (the range is the whole box length of a periodic axis): k is taken modulo num_bins; wrap == 0: a k
+ *   outside [0, num_bins) is dropped. |lo| or |hi| >= 1e9 or not finite: the pair's six words count as overflow.
+ * A term is t = lambda_k * w[c]. If t is not finite or |t| >= max_term it is NOT added and the overflow word counts it;
+ * else q = round-to-nearest-even(t * 2^shift) is added to word 6 k + c of the row with a 64-bit integer atomic (in
+ * LDS first where num_bins <= AZP_PRESSURE_PROFILE_LDS_BINS, else straight into the row). Integers only: a row is the
+ * same bits between two calls, between the paths, and under a reordering of the rows that carries the tags.
+ *
+ * The row at d_out is 6 num_bins + 4 int64 words: the bins (xx, xy, xz, yy, yz, zz each), then pairs evaluated, terms
+ * added, terms refused (overflow), shift. azp_pressure_profile_begin zeroes it on the stream and writes the shift;
+ * every other call ADDS to it, so the forces of an integrator are summed by calling one after the other:
+ *   azp_pressure_profile_pairs_<potential>  all pairs closer than r_max (the largest r_cut of the force), by the walk
+ *       of azp_rdf_counts: path 0 = automatic, 1 = all-pairs (any box), 2 = cells (orthorhombic, at least three cells
+ *       of width r_max on every periodic axis; refused elsewhere, never silently replaced). d_scratch:
+ *       azp_pressure_profile_scratch_size bytes (0 for all-pairs). r_max beyond half a perpendicular width of a
+ *       periodic axis is refused. Table and the conservative DPD force take shift_mode AZP_SHIFT_NONE only.
+ *   azp_pressure_profile_listed  the pairs of a per-particle table (entry s of row i at s * pitch + i, s < d_counts[i]),
+ *       each taken from the row with the smaller tag, multiplied by sign (+1 / -1; a pass with -1 also counts the
+ *       summary words down). A pair evaluator (AZP_PP_PERTURBED_LENNARD_JONES .. AZP_PP_PAIR_TABLE): d_table holds
+ *       uint32 partner rows, the symmetric exclusion table of a neighbor list; with sign -1 behind the walk it takes
+ *       out exactly what the walk added, because a pair's terms are a function of the pair alone. A bond evaluator
+ *       (AZP_PP_BOND_DOUBLE_WELL .. AZP_PP_SPECIAL_PAIR_LJ): d_table holds azp_bond_entry (the bond table, which the
+ *       special pairs share), d_params n_types parameter structs; d_rcutsq, d_ronsq, r_max are not read.
+ *   An entry that names a row >= N, the row itself or a type >= n_types is skipped.
+ * Single-domain states only (N rows, no ghosts). AZP_ERROR_INVALID_ARGUMENT, before anything is launched or written:
+ * NULL args or a NULL array the call reads; axis > 2; num_bins < 1 or > AZP_PRESSURE_PROFILE_MAX_BINS; scale or max_term
+ * not positive and finite; shift > 52; ntypes == 0; and per call what is said above. AZP_ERROR_TOO_MANY_TYPES: the
+ * coefficient table does not fit beside the histogram. N == 0: success. Asynchronous on `stream`. */
+#define AZP_PRESSURE_PROFILE_MAX_BINS 8192
+#define AZP_PRESSURE_PROFILE_LDS_BINS 1024
+
+typedef enum azp_pressure_profile_evaluator
+    {
+    AZP_PP_PERTURBED_LENNARD_JONES = 0,
+    AZP_PP_HERTZ = 1,
+    AZP_PP_EXPANDED_YUKAWA = 2,
+    AZP_PP_COLLOID = 3,
+    AZP_PP_DPD_CONSERVATIVE = 4,
+    AZP_PP_PAIR_TABLE = 5,
+    AZP_PP_BOND_DOUBLE_WELL = 16,
+    AZP_PP_BOND_QUARTIC = 17,
+    AZP_PP_BOND_TABLE = 18,
+    AZP_PP_SPECIAL_PAIR_LJ = 19
+    } azp_pressure_profile_evaluator;
+
+typedef struct azp_pressure_profile_args
+    {
+    const double* d_pos;      /* N x 4 (x, y, z, type bits) */
+    const uint32_t* d_tag;    /* N */
+    uint32_t N;
+    uint32_t ntypes;
+    azp_box box;
+    uint32_t axis;            /* 0, 1, 2 */
+    uint32_t num_bins;
+    double lower;
+    double scale;             /* num_bins / (upper - lower) */
+    double max_term;
+    uint32_t wrap;            /* bin indices modulo num_bins */
+    uint32_t shift;           /* terms in units of 2^-shift */
+    const double* d_rcutsq;   /* ntypes x ntypes (pair evaluators) */
+    const double* d_ronsq;    /* ntypes x ntypes (AZP_SHIFT_XPLOR) */
+    double r_max;             /* the radius of the walk: the largest r_cut */
+    uint32_t shift_mode;      /* azp_shift_mode */
+    uint32_t path;            /* 0 auto, 1 all-pairs, 2 cells */
+    int64_t* d_out;           /* 6 num_bins + 4 */
+    void* d_scratch;
+    uint64_t scratch_bytes;
+    } azp_pressure_profile_args;
+
+typedef struct azp_pressure_profile_list_args
+    {
+    azp_pressure_profile_args profile; /* path, d_scratch and scratch_bytes are not looked at */
+    const void* d_table;
+    const uint32_t* d_counts;          /* N */
+    uint64_t pitch;
+    uint32_t n_types;                  /* bond evaluators: parameter structs at d_params */
+    uint32_t evaluator;                /* azp_pressure_profile_evaluator */
+    int32_t sign;                      /* +1 or -1 */
+    uint32_t _pad;
+    } azp_pressure_profile_list_args;
+
+int azp_pressure_profile_scratch_size(const azp_pressure_profile_args* args, uint64_t* bytes);
+int azp_pressure_profile_begin(const azp_pressure_profile_args* args, void* stream);
+int azp_pressure_profile_pairs_perturbed_lennard_jones(const azp_pressure_profile_args* args, const azp_plj_params* d_params, void* stream);
+int azp_pressure_profile_pairs_hertz(const azp_pressure_profile_args* args, const azp_hertz_params* d_params, void* stream);
+int azp_pressure_profile_pairs_expanded_yukawa(const azp_pressure_profile_args* args, const azp_yukawa_params* d_params, void* stream);
+int azp_pressure_profile_pairs_colloid(const azp_pressure_profile_args* args, const azp_colloid_params* d_params, void* stream);
+int azp_pressure_profile_pairs_dpd_conservative(const azp_pressure_profile_args* args, const azp_dpd_params* d_params, void* stream);
+int azp_pressure_profile_pairs_table(const azp_pressure_profile_args* args, const azp_table_params* d_params, void* stream);
+int azp_pressure_profile_listed(const azp_pressure_profile_list_args* args, const void* d_params, void* stream);
+
 /* ---- misc ---- */
-int azp_version(void);                   /* major * 1000 + minor       */
+int azp_version(void);                  /* major * 1000 + minor       */
 const char* azp_status_string(int status);
 /* Resolved launch configuration of the last pair-force call on this thread
  * (for benchmarks / profiling reports). */
